@@ -13,9 +13,14 @@ random-init weights and synthetic text/depth inputs (no network for checkpoints 
 
 N>1: one process per GPU; the 6-8 views of a mesh shard one per rank (weak scaling: every rank denoises its
 own view, no data-path collective inside the denoise loop); value = total steps of all ranks / max time.
-The line also carries `sec_per_mesh`: ONE measured ConTEXTure.paint (6 views over the job's ranks, both
-all-reduces inside).  `--mode mesh` makes that the timed quantity (a step = one mesh; strong scaling).
+`--mode mesh` makes ONE ConTEXTure.paint the timed quantity (a step = one mesh of 6 views over the job's ranks, both
+all-reduces inside; strong scaling).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds the side measurements, each outside
+the timed region: live per-kernel roofline timing, VAE decode, two views in flight, the measured `sec_per_mesh` (one
+ConTEXTure.paint), the atlas all-reduce (N>1) and the fp32 CPU baseline; `--vae 0`, `--mesh 0`, ... drop single legs.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy in float32.
 """
 import argparse
 import ctypes as C
@@ -37,6 +42,11 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--latent", type=int, default=96, help="latent side (96 = 768^2 image; 64 = 512^2)")
     p.add_argument("--guidance", type=float, default=10.0)
+    p.add_argument("--full", action="store_true",
+                   help="steps mode: also run the side measurements (roofline, VAE decode, views in flight, sec/mesh, atlas all-reduce, "
+                        "CPU baseline); --cpu-baseline / --vae / --two-views / --mesh 0 leave single ones out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32, rank 0)")
     p.add_argument("--cpu-baseline", type=int, default=1)
     p.add_argument("--cpu-latent", type=int, default=0, help="latent side of the CPU sample (0 = auto)")
     p.add_argument("--vae", type=int, default=1, help="also time the once-per-view VAE decode (outside the step loop)")
@@ -50,7 +60,18 @@ def parse():
     p.add_argument("--in-flight", type=int, default=3, help="views a rank keeps in its denoise loop at once (optim.views_in_flight)")
     p.add_argument("--per-eval", type=int, default=6, help="mesh leg: views a rank denoises in lockstep as ONE UNet evaluation of batch 2 x this "
                                                             "(optim.views_per_eval; 0 / 1: --in-flight streams of batch 2 instead)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:                       # a plain run measures the headline only
+        a.cpu_baseline = a.vae = a.two_views = a.mesh = 0
+    return a
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy in float32 for every (name, tensor): what the timed path handed back in its last step."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def make_painter(a, dev, unet):
@@ -178,6 +199,7 @@ def main():
             x = torch.cat([torch.cat([lat] * 2), depth2], dim=1)                      # [2,5,S,S]
             eps = net(x, float(t), encoder_hidden_states=text_z)['sample']           # K14
             state["lat"] = sched.step_cfg(eps, a.guidance, t, lat)['prev_sample']   # K15+K16 fused
+            state["eps"] = eps
             state["i"] += 1
         return step, state
 
@@ -185,6 +207,8 @@ def main():
         # strong scaling: ONE mesh, its views sharded over the ranks, measured wall time per mesh
         tr = make_painter(a, dev, unet)
         el, cover = timed_paints(tr, a.steps, max(1, a.warmup), dist, dev)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"atlas": tr.atlas, "atlas_coverage": tr.atlas_coverage})
         if rank == 0:
             print(json.dumps({
                 "metric": "sec/mesh full texture (6 views, 50 PLMS steps)", "value": round(el / a.steps, 4), "unit": "s/mesh",
@@ -218,22 +242,27 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(state["lat"]).all(), "non-finite latents"
+    if a.dump_outputs and rank == 0:
+        # the last timed step's results: the UNet's (uncond, text) noise prediction and the updated latents
+        dump_outputs(a.dump_outputs, {"noise_pred": state["eps"], "latents": state["lat"]})
+
+    fl = unet.flops(2, S, S, 77)
+    total_fl = sum(v[1] for v in fl.values())
 
     # ---- live per-kernel timing (outside the timed region): dominant kernel = fp16 MFMA GEMM / implicit conv ------
-    fl = unet.flops(2, S, S, 77)
-    L.check(lib.ctx_profile_begin())
-    step()
-    torch.cuda.synchronize()
-    prof = {}
-    for k, name in ((0, "gemm_conv"), (1, "attention")):
-        ms, n = C.c_double(), C.c_int64()
-        L.check(lib.ctx_profile_end(k, C.byref(ms), C.byref(n)))
-        prof[name] = (ms.value, n.value)
-    gemm_ms, gemm_n = prof["gemm_conv"]
-    att_ms, att_n = prof["attention"]
-    gemm_fl = fl["gemm_conv"][1]
-    achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    total_fl = sum(v[1] for v in fl.values())
+    if a.full:
+        L.check(lib.ctx_profile_begin())
+        step()
+        torch.cuda.synchronize()
+        prof = {}
+        for k, name in ((0, "gemm_conv"), (1, "attention")):
+            ms, n = C.c_double(), C.c_int64()
+            L.check(lib.ctx_profile_end(k, C.byref(ms), C.byref(n)))
+            prof[name] = (ms.value, n.value)
+        gemm_ms, gemm_n = prof["gemm_conv"]
+        att_ms, att_n = prof["attention"]
+        gemm_fl = fl["gemm_conv"][1]
+        achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
 
     # once-per-view tail of img2img_step: VAE decode of the denoised latents (stable_diffusion_depth.py:567), timed outside
     # the step loop
@@ -277,7 +306,7 @@ def main():
 
     # multi-GPU exchange step of the path (once per mesh, not per denoise step): atlas all-reduce, timed separately
     atlas_ms = None
-    if dist is not None:
+    if dist is not None and a.full:
         atlas = torch.zeros(4, 1024, 1024, device=dev)
         dist.all_reduce(atlas); torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -319,7 +348,7 @@ def main():
     traffic, traffic_src = None, None
     import glob
     tfs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_traffic.json")))      # newest round's PMC pass
-    tf = tfs[-1] if tfs else ""
+    tf = tfs[-1] if tfs and a.full else ""
     if tf:
         try:
             tj = json.load(open(tf))
@@ -340,32 +369,35 @@ def main():
                        "latent": S, "cfg_batch": 2, "ctx_len": 77, "views_per_rank": 1, "parallelism": f"view-shard x{world}"},
             "tflops_per_step": round(total_fl / 1e12, 4),
             "step_tflops_per_s": round(total_fl / 1e12 / (elapsed / a.steps), 2),
-            "vae_decode_ms": round(vae_ms, 3) if vae_ms is not None else None,
-            "vae_decode_tflop": round(vae_tflop, 3) if vae_tflop is not None else None,
-            "sec_per_view": round((51 * ms_per_step + (vae_ms or 0.0)) / 1e3, 3),
-            "sec_per_mesh_6_views_est": round(-(-6 // world) * (51 * ms_per_step + (vae_ms or 0.0)) / 1e3, 3),
-            "roofline": {"bound": "mfma", "kernel": "k_gemm144 + k_gemm_pipe<...> + k_gemm8 (+ k_splitk_reduce): fp16 MFMA GEMM / implicit-GEMM conv3x3 of the UNet",
-                         "achieved": round(achieved, 2), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(achieved / 2500.0, 4),
-                         "traffic": traffic, "traffic_source": traffic_src, "launches_per_step": gemm_n, "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_n, 1), 2),
-                         "flops_per_launch_avg": round(gemm_fl / max(gemm_n, 1) / 1e9, 3), "kernel_ms_per_step": round(gemm_ms, 3)},
-            "attention": {"kernel": "k_attention_dma", "achieved": round(fl["attention"][1] / (att_ms * 1e-3) / 1e12, 2) if att_ms > 0 else 0.0,
-                          "unit": "TFLOP/s", "launches_per_step": att_n, "kernel_ms_per_step": round(att_ms, 3)},
         }
-        out["sec_per_mesh"] = round(mesh_s, 3) if mesh_s is not None else None
-        out["sec_per_mesh_note"] = (f"{'MEASURED' if mesh_s is not None else 'NOT MEASURED (' + str(mesh_cover) + ')'}: one ConTEXTure.paint of {a.mesh_path}, {a.mesh_views} views over {world} rank(s), "
-                                    + (f"full groups of {a.per_eval} views per lockstep evaluation (batch {2 * a.per_eval}), the rest " if a.per_eval > 1 else "")
-                                    + f"{a.in_flight} views in flight per rank, 1200^2 render, 51 UNet evals + VAE decode per view, "
-                                    + f"view weights, UV scatter, atlas merge; coverage {mesh_cover}")
-        if two is not None:
-            out["views_in_flight"] = two
-            out["sec_per_mesh_6_views_est_2_in_flight"] = round(-(-6 // world) * (51 * two["2"]["ms_per_step_per_view"] + (vae_ms or 0.0)) / 1e3, 3)
-        if atlas_ms is not None:
-            out["atlas_allreduce_ms"] = round(atlas_ms, 3)
-        if world == 1 and a.cpu_baseline:
-            try:
-                out["cpu_baseline"] = cpu_baseline(S, forced=a.cpu_latent)
-            except Exception as e:                      # never lose the GPU line to a host-side failure
-                out["cpu_baseline"] = {"value": None, "unit": "steps/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
+        if a.full:
+            out.update({
+                "vae_decode_ms": round(vae_ms, 3) if vae_ms is not None else None,
+                "vae_decode_tflop": round(vae_tflop, 3) if vae_tflop is not None else None,
+                "sec_per_view": round((51 * ms_per_step + (vae_ms or 0.0)) / 1e3, 3),
+                "sec_per_mesh_6_views_est": round(-(-6 // world) * (51 * ms_per_step + (vae_ms or 0.0)) / 1e3, 3),
+                "roofline": {"bound": "mfma", "kernel": "k_gemm144 + k_gemm_pipe<...> + k_gemm8 (+ k_splitk_reduce): fp16 MFMA GEMM / implicit-GEMM conv3x3 of the UNet",
+                             "achieved": round(achieved, 2), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(achieved / 2500.0, 4),
+                             "traffic": traffic, "traffic_source": traffic_src, "launches_per_step": gemm_n, "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_n, 1), 2),
+                             "flops_per_launch_avg": round(gemm_fl / max(gemm_n, 1) / 1e9, 3), "kernel_ms_per_step": round(gemm_ms, 3)},
+                "attention": {"kernel": "k_attention_dma", "achieved": round(fl["attention"][1] / (att_ms * 1e-3) / 1e12, 2) if att_ms > 0 else 0.0,
+                              "unit": "TFLOP/s", "launches_per_step": att_n, "kernel_ms_per_step": round(att_ms, 3)},
+            })
+            out["sec_per_mesh"] = round(mesh_s, 3) if mesh_s is not None else None
+            out["sec_per_mesh_note"] = (f"{'MEASURED' if mesh_s is not None else 'NOT MEASURED (' + str(mesh_cover) + ')'}: one ConTEXTure.paint of {a.mesh_path}, {a.mesh_views} views over {world} rank(s), "
+                                        + (f"full groups of {a.per_eval} views per lockstep evaluation (batch {2 * a.per_eval}), the rest " if a.per_eval > 1 else "")
+                                        + f"{a.in_flight} views in flight per rank, 1200^2 render, 51 UNet evals + VAE decode per view, "
+                                        + f"view weights, UV scatter, atlas merge; coverage {mesh_cover}")
+            if two is not None:
+                out["views_in_flight"] = two
+                out["sec_per_mesh_6_views_est_2_in_flight"] = round(-(-6 // world) * (51 * two["2"]["ms_per_step_per_view"] + (vae_ms or 0.0)) / 1e3, 3)
+            if atlas_ms is not None:
+                out["atlas_allreduce_ms"] = round(atlas_ms, 3)
+            if world == 1 and a.cpu_baseline:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(S, forced=a.cpu_latent)
+                except Exception as e:                      # never lose the GPU line to a host-side failure
+                    out["cpu_baseline"] = {"value": None, "unit": "steps/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
         print(json.dumps(out), flush=True)
     # A rank whose mesh leg never came back sits in a collective (a GPU / RCCL hang): that is a FAILURE of the run, not a clean
     # one.  The steps/s line above is already out; every rank now learns through the rendezvous store (not through the process

@@ -30,7 +30,7 @@ def load(d, counter):
 
 
 f, w = load(sys.argv[1], 'FETCH_SIZE'), load(sys.argv[2], 'WRITE_SIZE')
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --steps 2 --warmup 1 --cpu-baseline 0 --vae 0` (4 UNet evaluations)",
+out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --steps 2 --warmup 1` (3 UNet evaluations)",
        "correction": "FETCH_SIZE x2 (gfx950 counts 128-B requests at 64 B); WRITE_SIZE as reported; KiB -> bytes", "families": {}}
 for k in f:
     n = f[k][0]

@@ -4,6 +4,7 @@
 # Usage: ROUND=r03 PART=A tools/refresh_profiles.sh ; ROUND=r03 PART=B tools/refresh_profiles.sh
 set -x
 R=${ROUND:-r03}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_refresh
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
@@ -11,12 +12,12 @@ if [ "${PART:-A}" = "A" ]; then
 bash tools/pmc_traffic.sh prof_refresh/traffic > /dev/null 2>&1
 cp gpurun_out/prof_refresh/traffic.json profiles/${R}_pmc_traffic.json      # so that the default bench line below can quote it
 bash tools/pmc_mfma.sh prof_refresh/mfma > /dev/null 2>&1
-timeout -k 10 400 python3 bench.py > $OUT/bench_default.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_default.log 2>&1
 tail -1 $OUT/bench_default.log > $OUT/${R}_bench_default.json
 timeout -k 10 300 python3 bench.py --mode mesh --steps 2 --warmup 1 > $OUT/bench_mesh.log 2>&1
 tail -1 $OUT/bench_mesh.log > $OUT/${R}_bench_mesh_mode.json
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/unet -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --cpu-baseline 0 --vae 0 --two-views 0 --mesh 0 > $OUT/unet.log 2>&1
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/unet -- python3 $REPO/bench.py --steps 5 --warmup 2 --full --cpu-baseline 0 --vae 0 --two-views 0 --mesh 0 > $OUT/unet.log 2>&1
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/geom -- python3 $GRAFT_REPO_ROOT/tools/bench_geometry.py > $OUT/geom.log 2>&1
 cd $GRAFT_REPO_ROOT
 python3 tools/prof_summary.py $OUT/unet 8 70 > $OUT/${R}_bench_by_kernel_and_grid.txt 2>&1
