@@ -6,11 +6,12 @@ Work items are (mesh, view) pairs in mesh-major order; item k goes to rank k mod
 mesh m+1 start on the ranks mesh m leaves idle and every rank ends up with the same number of denoise loops (48 items / 8 ranks).
 Exchange steps, both over RCCL, one of each per mesh:
   phase A  all-reduce(MAX) of the per-face view-weight maxima [F]    (before painting: the masks gate the scatter)
-  phase B  each rank paints its items, `views_in_flight` denoise loops at a time (items of different meshes may share a group)
+  phase B  each rank paints its items wave by wave (stable_diffusion_depth.plan_waves; items of different meshes may share a group)
   phase C  all-reduce(SUM) of the atlas contribution [3+1, T, T] as int64 fixed-point sums (bit-identical for any world size)
 Every rank calls the collectives of every mesh in mesh order, whether or not it holds views of that mesh."""
 import torch
 from . import dist as D
+from .stable_diffusion_depth import plan_waves
 
 
 def schedule(n_meshes, n_views, world):
@@ -43,30 +44,18 @@ class MeshBatchPainter:
             tr.define_view_weights(ids)
             for j, vid in enumerate(ids):
                 slot[(m, vid)] = j
-        # phase B: denoise loops, `views_in_flight` at a time across mesh boundaries
+        # phase B: the rank's items wave by wave as plan_waves lays them out (a group may span mesh boundaries); only the
+        # current wave's renders are held
         T = self.trainers[0].cfg.guide.texture_resolution
         contrib = [torch.zeros(4, T, T, dtype=torch.int64, device=self.device) for _ in self.trainers]   # 2^-32 fixed point
-        diffusion = self.trainers[0].diffusion
-        infl = max(1, int(getattr(self.trainers[0].cfg.optim, 'views_in_flight', 3)))
-        vpe = int(getattr(self.trainers[0].cfg.optim, 'views_per_eval', 0))
-        if vpe > 1 and hasattr(diffusion, 'img2img_step_batched'):
-            infl = 2 * vpe if len(mine) >= 2 * vpe else vpe          # lockstep groups of vpe views (batch 2 x vpe), two groups in flight
-        if not hasattr(diffusion, 'img2img_step_multi'):
-            infl = 1
-        for j in range(0, len(mine), infl):
-            grp = mine[j:j + infl]
-            preps = []
-            for (m, v) in grp:
-                tr = self.trainers[m]
-                preps.append(tr._paint_prepare(tr.train_views[self.view_ids[v]], image_size, num_inference_steps))
-            if len(grp) > 1 and vpe > 1 and hasattr(diffusion, 'img2img_step_batched'):
-                outs = diffusion.img2img_step_batched([p[0] for p in preps], views_per_eval=vpe)
-            elif len(grp) > 1:
-                outs = diffusion.img2img_step_multi([p[0] for p in preps])
-            else:
-                kw = dict(preps[0][0])
-                outs = [diffusion.img2img_step(kw.pop('text_embeddings'), kw.pop('inputs'), kw.pop('original_depth_mask'), **kw)]
-            for (m, v), (kw, ctx), (rgb, _) in zip(grp, preps, outs):
+        optim = self.trainers[0].cfg.optim
+        vpe, infl = int(optim.views_per_eval), int(optim.views_in_flight)
+        for wave in plan_waves(len(mine), vpe, infl):
+            items = [mine[k] for grp in wave for k in grp]
+            preps = [self.trainers[m]._paint_prepare(self.trainers[m].train_views[self.view_ids[v]], image_size, num_inference_steps)
+                     for (m, v) in items]
+            outs = self.trainers[0].diffusion.img2img_steps([kw for kw, _ in preps], views_per_eval=vpe, views_in_flight=infl)
+            for (m, v), (_, ctx), (rgb, _) in zip(items, preps, outs):
                 tr = self.trainers[m]
                 rgb_output, obj_mask = tr._paint_finish(ctx, rgb)
                 k = slot[(m, self.view_ids[v])]

@@ -22,6 +22,22 @@ from .vae import AutoencoderKL
 from .utils import seed_everything
 
 
+def plan_waves(n, views_per_eval, views_in_flight, groups_in_flight=2, batchable=True):
+    """How a rank denoises its n views (the one place that decides it): -> waves, each a list of GROUPS that run concurrently,
+    one lane each; a group is a list of view indices evaluated as ONE UNet batch of 2 x len(group) per step.
+    2 <= views_per_eval <= 8 and batchable: consecutive full groups of views_per_eval views, groups_in_flight of them per wave;
+    the n mod views_per_eval views left over form one last wave of single-view groups, all in flight (a padded batch would
+    multiply their work).  Otherwise: single-view groups, views_in_flight per wave."""
+    G = int(views_per_eval)
+    if batchable and 2 <= G <= 8:
+        nfull, gif = n - n % G, max(1, int(groups_in_flight))
+        full = [list(range(g0, g0 + G)) for g0 in range(0, nfull, G)]
+        rest = [[[k] for k in range(nfull, n)]] if nfull < n else []
+        return [full[w:w + gif] for w in range(0, len(full), gif)] + rest
+    infl = max(1, int(views_in_flight))
+    return [[[k] for k in range(w, min(w + infl, n))] for w in range(0, n, infl)]
+
+
 class StableDiffusion:
     def __init__(self, device, model_name='stabilityai/stable-diffusion-2-depth', concept_name=None, concept_path=None,
                  latent_mode=True, min_timestep=0.02, max_timestep=0.98, no_noise=False, use_inpaint=False,
@@ -69,6 +85,7 @@ class StableDiffusion:
         self.scheduler = PNDMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                        num_train_timesteps=self.num_train_timesteps, steps_offset=1, skip_prk_steps=True)
         self.alphas = self.scheduler.alphas_cumprod.to(self.device)
+        self._lane_pool = []                          # (engine clone, side stream) per extra lane of _run_wave
 
     @property
     def inpaint_unet(self):
@@ -131,14 +148,15 @@ class StableDiffusion:
 
     class _Denoise:
         """The inner `sample` loop of img2img_step (stable_diffusion_depth.py:297-516) as a resumable job: construction does
-        what precedes the loop, advance() is one loop body (CFG-batched UNet evaluation + fused CFG / PLMS update)."""
+        what precedes the loop, model_input() / apply() bracket one loop body's UNet evaluation (CFG pair in, fused CFG / PLMS
+        update out); the evaluation itself is the lane runner's (`_run_wave`)."""
 
-        def __init__(self, sd, unet, scheduler, text_embeddings, latents, depth_mask, strength, num_inference_steps, update_mask,
+        def __init__(self, sd, scheduler, text_embeddings, latents, depth_mask, strength, num_inference_steps, update_mask,
                      fixed_seed, guidance_scale):
-            self.sd, self.unet, self.scheduler = sd, unet, scheduler
+            self.scheduler = scheduler
             self.text_embeddings, self.guidance_scale = text_embeddings, guidance_scale
             scheduler.set_timesteps(num_inference_steps)
-            shape = (text_embeddings.shape[0] // 2, unet.in_channels - 1, depth_mask.shape[2], depth_mask.shape[3])
+            shape = (text_embeddings.shape[0] // 2, sd.unet.in_channels - 1, depth_mask.shape[2], depth_mask.shape[3])
             noise = None                                                 # `noise` of the reference's sample(): stays None when latents is None
             if latents is None:
                 latents = torch.randn(shape, device=sd.device)
@@ -176,10 +194,6 @@ class StableDiffusion:
             self.latents = self.scheduler.step_cfg(noise_pred, self.guidance_scale, int(t), self.latents)['prev_sample']
             self.i += 1
 
-        def advance(self):
-            x, t = self.model_input()
-            self.apply(self.unet(x, float(t), encoder_hidden_states=self.text_embeddings)['sample'], t)
-
     def _prepare(self, inputs, original_depth_mask, update_mask, latent_mode, image_size):
         depth_mask = F.interpolate(original_depth_mask, size=(image_size // 8, image_size // 8), mode='bicubic', align_corners=False)
         if inputs is None:
@@ -198,23 +212,27 @@ class StableDiffusion:
         depth_mask = 2.0 * (depth_mask - depth_mask.min()) / (depth_mask.max() - depth_mask.min()) - 1.0
         return latents, depth_mask, update_mask
 
+    def _job(self, kw):
+        """img2img_step's keyword arguments -> its _Denoise job (everything the reference does before the loop), with its own
+        scheduler; `vis` collects the intermediate images when the call asks for them."""
+        latent_mode, image_size = kw.get('latent_mode', False), kw.get('image_size', 512)
+        latents, depth_mask, update_mask = self._prepare(kw['inputs'], kw['original_depth_mask'], kw.get('update_mask'), latent_mode, image_size)
+        job = StableDiffusion._Denoise(self, self._new_scheduler(), kw['text_embeddings'], latents, depth_mask, kw.get('strength', 0.5),
+                                       kw.get('num_inference_steps', 50), update_mask, kw.get('fixed_seed'), kw.get('guidance_scale', 100))
+        job.latent_mode, job.vis = latent_mode, []
+        if kw.get('intermediate_vis'):
+            job.on_step = lambda t, lat, noise: job.vis.append(self._vis_step(t, lat, noise))
+        return job
+
     def img2img_step(self, text_embeddings, inputs, original_depth_mask, guidance_scale=100, strength=0.5,
                      num_inference_steps=50, update_mask=None, latent_mode=False, fixed_seed=None, intermediate_vis=False,
                      view_dir=None, front_image=None, phi=None, theta=None, condition_guidance_scales=None, image_size=512):
-        intermediate_results = []
-        latents, depth_mask, update_mask = self._prepare(inputs, original_depth_mask, update_mask, latent_mode, image_size)
-        with torch.no_grad():
-            job = StableDiffusion._Denoise(self, self.unet, self.scheduler, text_embeddings, latents, depth_mask, strength,
-                                           num_inference_steps, update_mask, fixed_seed, guidance_scale)
-            if intermediate_vis:
-                job.on_step = lambda t, lat, noise: intermediate_results.append(self._vis_step(t, lat, noise))
-            while not job.done():
-                job.advance()
-            target_latents = job.latents
-            target_rgb = self.decode_latents(target_latents)
-        if latent_mode:
-            return target_rgb, target_latents
-        return target_rgb, intermediate_results
+        """One view: (rgb, latents) with latent_mode, else (rgb, intermediate images).  view_dir ... condition_guidance_scales
+        are the reference's call contract and are not read."""
+        return self.img2img_steps([dict(text_embeddings=text_embeddings, inputs=inputs, original_depth_mask=original_depth_mask,
+                                        guidance_scale=guidance_scale, strength=strength, num_inference_steps=num_inference_steps,
+                                        update_mask=update_mask, latent_mode=latent_mode, fixed_seed=fixed_seed,
+                                        intermediate_vis=intermediate_vis, image_size=image_size)])[0]
 
     def _vis_step(self, t, latents, noise):
         """`intermediate_vis` of img2img_step (stable_diffusion_depth.py:500-511, LogConfig.vis_diffusion_steps): the x0 estimate
@@ -228,139 +246,69 @@ class StableDiffusion:
         image = image.cpu().permute(0, 2, 3, 1).numpy()
         return Image.fromarray((image[0] * 255).round().astype("uint8"))
 
-    def img2img_step_multi(self, calls):
-        """Several img2img_step calls (views of one mesh) with their denoise loops in flight together: one HIP stream, one
-        engine (UNet2DConditionModel.clone_shared: all over ONE weight blob) and one scheduler per call.  `calls` = dicts of
-        img2img_step keyword arguments.  Each result is what img2img_step(**call) returns on its own (same seeds, same
-        deterministic kernels); two in flight finish ~1.25x sooner, three ~1.3x, because the deep UNet levels do not fill the chip."""
-        n = len(calls)
-        if n == 1:
-            kw = dict(calls[0])
-            return [self.img2img_step(kw.pop('text_embeddings'), kw.pop('inputs'), kw.pop('original_depth_mask'), **kw)]
-        engines = getattr(self, '_engines', None)
-        if engines is None:
-            engines = self._engines = [self.unet]
-        while len(engines) < n:
-            engines.append(self.unet.clone_shared())
-        streams = getattr(self, '_multi_streams', None)
-        if streams is None:
-            streams = self._multi_streams = []
-        while len(streams) < n:
-            streams.append(torch.cuda.Stream(self.device))
-        main = torch.cuda.current_stream(self.device)
-        jobs, metas = [], []
-        with torch.no_grad():
-            for k, kw in enumerate(calls):
-                kw = dict(kw)
-                image_size = kw.get('image_size', 512)
-                latent_mode = kw.get('latent_mode', False)
-                latents, depth_mask, update_mask = self._prepare(kw['inputs'], kw['original_depth_mask'], kw.get('update_mask'),
-                                                                 latent_mode, image_size)
-                jobs.append(StableDiffusion._Denoise(self, engines[k], self._new_scheduler(), kw['text_embeddings'], latents, depth_mask,
-                                                     kw.get('strength', 0.5), kw.get('num_inference_steps', 50), update_mask,
-                                                     kw.get('fixed_seed'), kw.get('guidance_scale', 100)))
-                metas.append(latent_mode)
-            for st in streams[:n]:
-                st.wait_stream(main)
-            while not all(j.done() for j in jobs):
-                for k in range(n):
-                    if not jobs[k].done():
-                        with torch.cuda.stream(streams[k]):
-                            jobs[k].advance()
-            for st in streams[:n]:
-                main.wait_stream(st)
-            outs = []
-            for k in range(n):
-                jobs[k].latents.record_stream(main)
-                rgb = self.decode_latents(jobs[k].latents)
-                outs.append((rgb, jobs[k].latents) if metas[k] else (rgb, []))
-        return outs
-
-    def img2img_step_batched(self, calls, views_per_eval=6, groups_in_flight=2):
-        """Several img2img_step calls (views, possibly of different meshes) denoised in LOCKSTEP as ONE UNet evaluation of batch
-        2 x views_per_eval per step: rows [u_0, c_0, u_1, c_1, ...] (every view keeps its own text embeddings, depth, seed, scheduler
-        state and fused CFG / PLMS update).  At M = views x 2 x h x w rows every layer is a large GEMM (no split-K slabs, full tiles),
-        which one view at CFG batch 2 cannot offer: 155 view-steps/s against 145 for three streams of batch 2 and 116 for one (latent 96,
-        plan table tuned for batch 12).
-        Only FULL groups of views_per_eval views are batched; the remaining views (fewer than a group: a rank of a multi-GPU job that
-        owns one or two views) go through img2img_step_multi — streams of batch 2 — because a padded batch would multiply their work.
-        The executor's plan depends on the row count only and every row's arithmetic is independent of the other rows, so inside
-        full groups a view's result does not depend on which views share its batch nor on its position (tested).  It is NOT
-        bit-identical to the batch-2 loop: other tile / split-K plans sum in another order (same tolerance against the oracle).
-        All calls must share image_size and num_inference_steps / strength (one timestep schedule); otherwise everything falls back
-        to img2img_step_multi.
-        groups_in_flight: with two or more full groups (a mesh batch), that many lockstep evaluations run concurrently on their own
-        HIP streams and engine clones (one weight blob): 34.0 instead of 36.9 ms per batch-12 evaluation with two in flight
-        (tools/bench_concurrent.py 96 6 12); a group's arithmetic does not depend on what runs beside it, so results are unchanged."""
-        n, G = len(calls), int(views_per_eval)
+    def img2img_steps(self, calls, views_per_eval=0, views_in_flight=3, groups_in_flight=2):
+        """Several img2img_step calls (views, possibly of different meshes) evaluated wave by wave as `plan_waves` lays them out.
+        `calls` = dicts of img2img_step keyword arguments; returns, per call and in order, what img2img_step(**call) returns.
+        Every view keeps its own text embeddings, depth, seed, scheduler state and fused CFG / PLMS update.  A group of V views is
+        ONE UNet evaluation of batch 2V per step: the executor's plan depends on the row count only and rows are arithmetically
+        independent, so a view's bits depend on the size of its group, not on its mates, its position or what runs beside it.
+        Calls that differ in image size, step count, strength or latent mode are not batched; a call with intermediate_vis runs
+        as its own one-lane wave on the current stream."""
         key = lambda kw: (kw.get('image_size', 512), kw.get('num_inference_steps', 50), kw.get('strength', 0.5), kw.get('latent_mode', False))
-        if n < G or G < 2 or 2 * G > 16 or any(key(kw) != key(calls[0]) for kw in calls) or any(kw.get('intermediate_vis') for kw in calls):
-            return self.img2img_step_multi(calls)
-        nfull = (n // G) * G
-        jobs, metas = [], []
+        vis = [bool(kw.get('intermediate_vis')) for kw in calls]
+        batchable = not any(vis) and all(key(kw) == key(calls[0]) for kw in calls)
+        outs = [None] * len(calls)
         with torch.no_grad():
-            for kw in calls[:nfull]:
-                image_size, latent_mode = kw.get('image_size', 512), kw.get('latent_mode', False)
-                latents, depth_mask, update_mask = self._prepare(kw['inputs'], kw['original_depth_mask'], kw.get('update_mask'),
-                                                                 latent_mode, image_size)
-                jobs.append(StableDiffusion._Denoise(self, self.unet, self._new_scheduler(), kw['text_embeddings'], latents, depth_mask,
-                                                     kw.get('strength', 0.5), kw.get('num_inference_steps', 50), update_mask,
-                                                     kw.get('fixed_seed'), kw.get('guidance_scale', 100)))
-                metas.append(latent_mode)
-            groups = [jobs[g0:g0 + G] for g0 in range(0, nfull, G)]
-            steps = len(jobs[0].timesteps)
-            if any(len(j.timesteps) != steps or not torch.equal(j.timesteps, jobs[0].timesteps) for j in jobs):
-                raise L.CtxError("img2img_step_batched: the views of one evaluation must share their timestep schedule")
-            F = max(1, min(int(groups_in_flight), len(groups)))
-
-            def one_step(engine, grp, ctx):
-                xs, t = [], None
-                for j in grp:
-                    x, t = j.model_input()
-                    xs.append(x)
-                noise = engine(torch.cat(xs), float(t), encoder_hidden_states=ctx)['sample']
-                for v, j in enumerate(grp):
-                    j.apply(noise[2 * v:2 * v + 2], t)
-
-            if F == 1:
-                for grp in groups:
-                    ctx = torch.cat([j.text_embeddings for j in grp])
-                    for _ in range(steps):
-                        one_step(self.unet, grp, ctx)
-            else:
-                engines = getattr(self, '_engines', None)
-                if engines is None:
-                    engines = self._engines = [self.unet]
-                while len(engines) < F:
-                    engines.append(self.unet.clone_shared())
-                streams = getattr(self, '_multi_streams', None)
-                if streams is None:
-                    streams = self._multi_streams = []
-                while len(streams) < F:
-                    streams.append(torch.cuda.Stream(self.device))
-                main = torch.cuda.current_stream(self.device)
-                for c0 in range(0, len(groups), F):
-                    chunk = groups[c0:c0 + F]
-                    ctxs = [torch.cat([j.text_embeddings for j in grp]) for grp in chunk]
-                    for st in streams[:len(chunk)]:
-                        st.wait_stream(main)
-                    for _ in range(steps):
-                        for k, grp in enumerate(chunk):
-                            with torch.cuda.stream(streams[k]):
-                                one_step(engines[k], grp, ctxs[k])
-                    for st in streams[:len(chunk)]:
-                        main.wait_stream(st)
-                    for grp in chunk:
-                        for j in grp:
-                            j.latents.record_stream(main)
-            outs = []
-            for j, lm in zip(jobs, metas):
-                rgb = self.decode_latents(j.latents)
-                outs.append((rgb, j.latents) if lm else (rgb, []))
-        if nfull < n:
-            outs += self.img2img_step_multi(calls[nfull:])
+            for wave in plan_waves(len(calls), views_per_eval, views_in_flight, groups_in_flight, batchable):
+                for part in [[g] for g in wave if vis[g[0]]] + [[g for g in wave if not vis[g[0]]]]:
+                    if not part:
+                        continue
+                    jobs = [[self._job(calls[k]) for k in g] for g in part]
+                    for grp in jobs:
+                        if any(not torch.equal(j.timesteps, grp[0].timesteps) for j in grp):
+                            raise L.CtxError("img2img_steps: the views of one evaluation must share their timestep schedule")
+                    self._run_wave(jobs)
+                    for g, grp in zip(part, jobs):
+                        for k, j in zip(g, grp):
+                            rgb = self.decode_latents(j.latents)
+                            outs[k] = (rgb, j.latents) if j.latent_mode else (rgb, j.vis)
         return outs
 
-    def img2img_step_pair(self, calls):
-        assert len(calls) == 2
-        return self.img2img_step_multi(calls)
+    def _lanes(self, n):
+        """-> n (engine, stream) lanes.  Lane 0 is self.unet on the current stream; lane k >= 1 is pooled engine clone k
+        (UNet2DConditionModel.clone_shared: the same weight blob, its own workspace) on pooled side stream k, made once."""
+        pool = self._lane_pool
+        while len(pool) < n - 1:
+            pool.append((self.unet.clone_shared(), torch.cuda.Stream(self.device)))
+        return [(self.unet, torch.cuda.current_stream(self.device))] + pool[:n - 1]
+
+    def _run_wave(self, groups):
+        """Denoise one wave: `groups` = lists of _Denoise jobs, one lane each, stepped round-robin one loop body at a time.  The
+        deep UNet levels do not fill the chip, so evaluations in flight together finish sooner than back to back (two lockstep
+        groups of 6: 34.0 instead of 36.9 ms per batch-12 evaluation, tools/bench_concurrent.py)."""
+        lanes = self._lanes(len(groups))
+        main = lanes[0][1]
+        ctxs = [grp[0].text_embeddings if len(grp) == 1 else torch.cat([j.text_embeddings for j in grp]) for grp in groups]
+        for (_, st), grp, ctx in zip(lanes[1:], groups[1:], ctxs[1:]):
+            st.wait_stream(main)
+            # made on the current stream, read on this lane: record_stream keeps the allocator from reusing their blocks on the
+            # current stream before the lane is done with them (the first step frees the initial latents)
+            for t in [ctx] + [x for j in grp for x in (j.latents, j.depth2, j.text_embeddings)]:
+                t.record_stream(st)
+        while not all(grp[0].done() for grp in groups):
+            for (unet, st), grp, ctx in zip(lanes, groups, ctxs):
+                if grp[0].done():
+                    continue
+                with torch.cuda.stream(st):
+                    if len(grp) == 1:
+                        x, t = grp[0].model_input()
+                    else:
+                        xs = [j.model_input() for j in grp]
+                        x, t = torch.cat([x_ for x_, _ in xs]), xs[0][1]
+                    noise = unet(x, float(t), encoder_hidden_states=ctx)['sample']
+                    for v, j in enumerate(grp):
+                        j.apply(noise[2 * v:2 * v + 2], t)
+        for (_, st), grp in zip(lanes[1:], groups[1:]):
+            main.wait_stream(st)
+            for j in grp:
+                j.latents.record_stream(main)             # made on the lane, decoded on the current stream

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import dist as D
 from . import utils, view_weights
+from .batch import MeshBatchPainter
 from .run_nerf_helpers import get_embedder, NeRF2D
 from .textured_mesh import TexturedMeshModel
 from .views_dataset import Zero123PlusDataset, MultiviewDataset
@@ -138,7 +139,6 @@ class ConTEXTure:
         min_h, min_w, max_h, max_w = ctx['box']
         rgb_output = ctx['rgb_render'].clone()
         rgb_output[:, :, min_h:max_h, min_w:max_w] = cropped_rgb_output
-        self._last = dict(render_cache=ctx['render_cache'], z_normals=ctx['z_normals'])
         return rgb_output, ctx['object_mask']
 
     def paint_viewpoint(self, data, should_project_back=True, image_size=None, num_inference_steps=None):
@@ -154,24 +154,6 @@ class ConTEXTure:
             self.fitted_pred_rgb = self.project_back(render_cache=ctx['render_cache'], background=ctx['background'], rgb_output=rgb_output,
                                                      object_mask=object_mask, update_mask=object_mask, z_normals=z, z_normals_cache=None)
         return rgb_output, object_mask
-
-    def paint_viewpoints_multi(self, datas, image_size=None, num_inference_steps=None):
-        """Several views painted with their denoise loops in flight together (StableDiffusion.img2img_step_multi): same result
-        per view as paint_viewpoint.  Returns [(rgb_output, object_mask, last)] per view."""
-        preps = [self._paint_prepare(d, image_size, num_inference_steps) for d in datas]
-        vpe = int(getattr(self.cfg.optim, 'views_per_eval', 0))
-        if vpe > 1 and hasattr(self.diffusion, 'img2img_step_batched'):
-            outs = self.diffusion.img2img_step_batched([p[0] for p in preps], views_per_eval=vpe)
-        else:
-            outs = self.diffusion.img2img_step_multi([p[0] for p in preps])
-        res = []
-        for (kw, ctx), (rgb, _) in zip(preps, outs):
-            rgb_output, mask = self._paint_finish(ctx, rgb)
-            res.append((rgb_output, mask, self._last))
-        return res
-
-    def paint_viewpoints_pair(self, data_a, data_b, image_size=None, num_inference_steps=None):
-        return self.paint_viewpoints_multi([data_a, data_b], image_size, num_inference_steps)
 
     # ---- north_star "UV back-projection" (absent in the reference, SURVEY R6 / §8f n1) ----------------------------
     def project_back_scatter(self, render_cache, rgb_output, weight_mask, acc=None):
@@ -406,34 +388,10 @@ class ConTEXTure:
         return log
 
     def paint(self, image_size=None, num_inference_steps=None):
-        """Per-view paint loop with views sharded one per rank and one atlas all-reduce at the end."""
-        n = len(self.train_views)
-        mine = D.shard_views(n, self.rank, self.world)
-        T = self.cfg.guide.texture_resolution
-        contrib = torch.zeros(4, T, T, dtype=torch.int64, device=self.device)      # 2^-32 fixed point: see project_back_scatter
-        masks = self.define_view_weights(mine)          # an idle rank (no views of this mesh) still joins the all-reduce(MAX)
-        # a rank that owns several views keeps `views_in_flight` of them (default 3) in the denoise loop at once
-        infl = max(1, int(getattr(self.cfg.optim, 'views_in_flight', 3)))
-        if int(getattr(self.cfg.optim, 'views_per_eval', 0)) > 1:
-            infl = int(self.cfg.optim.views_per_eval)                # one lockstep evaluation per group of that many views
-        if not hasattr(self.diffusion, 'img2img_step_multi'):
-            infl = 1
-        j = 0
-        while j < len(mine):
-            grp = mine[j:j + infl]
-            if len(grp) > 1:
-                res = self.paint_viewpoints_multi([self.train_views[k] for k in grp], image_size=image_size,
-                                                  num_inference_steps=num_inference_steps)
-                for o, (rgb, obj_mask, last) in enumerate(res):
-                    self.project_back_scatter(last['render_cache'], rgb, masks[j + o:j + o + 1] & (obj_mask > 0), acc=contrib)
-            else:
-                rgb, obj_mask = self.paint_viewpoint(self.train_views[grp[0]], should_project_back=False, image_size=image_size,
-                                                     num_inference_steps=num_inference_steps)
-                self.project_back_scatter(self._last['render_cache'], rgb, masks[j:j + 1] & (obj_mask > 0), acc=contrib)
-            j += len(grp)
-        atlas, coverage = D.merge_atlas(contrib, self.group)
-        self.atlas, self.atlas_coverage = atlas, coverage
-        return atlas, coverage
+        """Per-view paint loop: views sharded over the ranks (view k -> rank k mod world, as D.shard_views), one all-reduce(MAX)
+        of the view-weight maxima and one atlas all-reduce(SUM); an idle rank joins both.  It is the one-mesh MeshBatchPainter."""
+        painter = MeshBatchPainter([self], view_ids=list(range(len(self.train_views))), group=self.group)
+        return painter.paint_all(image_size, num_inference_steps)[0]
 
     def export(self, path=None):
         """The outputs the reference writes after painting (src/training/trainer.py:954-968 -> export_mesh): mesh.obj / mesh.mtl /

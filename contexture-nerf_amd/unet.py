@@ -48,6 +48,7 @@ class UNet2DConditionModel:
         self._ws = None
         self._ws_key = None
         self._t = None
+        self._res32 = False
         if self.device.type == 'cuda':
             self._weights = torch.empty(self._lib.ctx_unet_weight_bytes(self._h), dtype=torch.uint8, device=self.device)
             self._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
@@ -76,8 +77,10 @@ class UNet2DConditionModel:
         o._h = o._create_handle()
         o._weights = self._weights                      # shared, read-only during forward
         o._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
-        o._ws_key, o._t = None, None
+        o._ws_key, o._t, o._res32 = None, None, False
         o._bind()
+        if self._res32:                                 # handle-level switches live in the C handle: re-apply them
+            o.set_residual_fp32(True)
         return o
 
     def __del__(self):
@@ -194,6 +197,7 @@ class UNet2DConditionModel:
     def set_residual_fp32(self, on=True):
         """Precision experiment: keep the residual stream in fp32 (fp16 operands and weights unchanged)."""
         L.check(self._lib.ctx_unet_set_residual_fp32(self._h, int(bool(on))))
+        self._res32 = bool(on)
         self._ws_key = None
         return self
 

@@ -53,6 +53,18 @@ class FakeLib:
         return b""
 
 
+class FakeDiffusion:
+    """The runner seam of StableDiffusion: one result per call, in order; the "image" is the call's view id, which the fake
+    _paint_finish checks before it hands back the painted view.  `waves` records how many calls each paint wave passed."""
+
+    def __init__(self):
+        self.waves = []
+
+    def img2img_steps(self, calls, views_per_eval=0, views_in_flight=3, groups_in_flight=2):
+        self.waves.append(len(calls))
+        return [(kw['vid'], []) for kw in calls]
+
+
 def fake_view(vid):
     """Deterministic synthetic raster of view `vid`: face_idx [H,W], face z-normals [F], uv [H,W,2], painted rgb [3,H,W]."""
     rng = np.random.default_rng(1000 + vid)
@@ -89,29 +101,18 @@ def make_trainer(rank, world, n_views, key=0):
     tr.paint_step, tr.group, tr.rank, tr.world, tr.device = 0, None, rank, world, torch.device('cpu')
     tr.mesh_model = FakeMeshModel(key)
     tr.train_views = [dict(theta=1.0, phi=v / 100.0, radius=1.5, vid=v) for v in range(n_views)]
-    tr.view_weights, tr.text_z, tr.diffusion = None, None, types.SimpleNamespace(img2img_step_multi=None)
+    tr.view_weights, tr.text_z, tr.diffusion = None, None, FakeDiffusion()
 
     def prep(data, image_size=None, num_inference_steps=None):
         fi, fnz, uv, rgb = fake_view(key + data['vid'])
         rc = dict(uv_features=torch.from_numpy(uv)[None], face_idx=torch.from_numpy(fi)[None])
-        return dict(text_embeddings=None, inputs=None, original_depth_mask=None, vid=data['vid']), dict(render_cache=rc, rgb=torch.from_numpy(rgb)[None], object_mask=torch.from_numpy((fi >= 0).astype(np.float32))[None, None])
+        return dict(text_embeddings=None, inputs=None, original_depth_mask=None, vid=data['vid']), dict(vid=data['vid'], render_cache=rc, rgb=torch.from_numpy(rgb)[None], object_mask=torch.from_numpy((fi >= 0).astype(np.float32))[None, None])
     tr._paint_prepare = prep
-    tr._paint_finish = lambda ctx, rgb: (ctx['rgb'], ctx['object_mask'])
 
-    def multi(datas, image_size=None, num_inference_steps=None):
-        out = []
-        for d in datas:
-            kw, ctx = prep(d)
-            out.append((ctx['rgb'], ctx['object_mask'], dict(render_cache=ctx['render_cache'])))
-        return out
-    tr.paint_viewpoints_multi = multi
-
-    def single(data, should_project_back=True, image_size=None, num_inference_steps=None):
-        assert should_project_back is False                # paint() scatters itself
-        kw, ctx = prep(data)
-        tr._last = dict(render_cache=ctx['render_cache'])
+    def finish(ctx, rgb):
+        assert rgb == ctx['vid']                           # the runner's results come back in call order
         return ctx['rgb'], ctx['object_mask']
-    tr.paint_viewpoint = single
+    tr._paint_finish = finish
     return tr
 
 
@@ -185,6 +186,7 @@ def _worker(rank, world, port, tmp):
     assert np.array_equal(cov.numpy(), want_contrib[3])
     assert np.array_equal(atlas.numpy(), _atlas(want_contrib))
     assert np.array_equal(tr.view_weights[:, 0].numpy(), want_masks[mine])
+    assert tr.diffusion.waves == ([2, 1] if rank == 0 else [2])                      # optim.views_in_flight = 2
 
     # 3. one view, two ranks: rank 1 is idle and must still join both collectives
     calls.clear()
@@ -198,10 +200,6 @@ def _worker(rank, world, port, tmp):
     # 4. BASELINE configs[3] driver: 3 meshes x 3 views over 2 ranks; items of different meshes share a group in flight
     calls.clear()
     trs = [make_trainer(rank, world, 4, key=100 * m) for m in range(3)]
-    for t_ in trs:
-        t_.diffusion = types.SimpleNamespace(
-            img2img_step_multi=lambda kws: [(None, []) for _ in kws],
-            img2img_step=lambda te, inp, dm, **k: (None, []))
     bp = MeshBatchPainter(trs, view_ids=[1, 2, 3])
     assert bp.plan == schedule(3, 3, 2) and sorted(sum(bp.plan, [])) == [(m, v) for m in range(3) for v in range(3)]
     assert [len(p) for p in schedule(8, 6, 8)] == [6] * 8 and schedule(8, 6, 8)[6][0] == (1, 0)     # mesh 1 starts on the rank mesh 0 leaves idle

@@ -548,3 +548,34 @@ def test_mjpeg_avi_muxer_round_trip(tmp_path):
         write_mjpeg_avi(tmp_path / "bad.avi", [np.zeros((4, 4, 3), np.uint8), np.zeros((5, 4, 3), np.uint8)])
     with pytest.raises(ValueError):
         write_mjpeg_avi(tmp_path / "bad.avi", [])
+
+
+def test_plan_waves_pins_the_multi_view_schedule():
+    """stable_diffusion_depth.plan_waves: the one place that decides how a rank denoises its views (waves of concurrent groups;
+    a group = one UNet batch of 2 x len(group)).  A view's bits depend on the size of its group, so these partitions are the
+    ones the atlases of bench.py and tools/ were recorded with."""
+    from contexture_nerf_amd.stable_diffusion_depth import plan_waves
+    g = lambda a, b: list(range(a, b))
+    assert plan_waves(6, 6, 3) == [[g(0, 6)]]                                       # bench.py --mode mesh --per-eval 6
+    w = plan_waves(48, 6, 3, groups_in_flight=2)                                    # configs[3] on one rank
+    assert w == [[g(12 * i, 12 * i + 6), g(12 * i + 6, 12 * i + 12)] for i in range(4)]
+    assert plan_waves(6, 0, 3) == [[[0], [1], [2]], [[3], [4], [5]]]
+    assert plan_waves(6, 1, 3) == plan_waves(6, 0, 3)
+    assert plan_waves(5, 3, 3) == [[[0, 1, 2]], [[3], [4]]]                          # left-overs: single views, all in flight
+    assert plan_waves(14, 6, 3) == [[g(0, 6), g(6, 12)], [[12], [13]]]
+    assert plan_waves(20, 6, 3) == [[g(0, 6), g(6, 12)], [g(12, 18)], [[18], [19]]]
+    assert plan_waves(2, 3, 3) == [[[0], [1]]]
+    assert plan_waves(48, 6, 3, groups_in_flight=1) == [[g(6 * i, 6 * i + 6)] for i in range(8)]
+    assert plan_waves(9, 9, 4) == [[[0], [1], [2], [3]], [[4], [5], [6], [7]], [[8]]]   # views_per_eval 9: not batched
+    assert plan_waves(16, 8, 3) == [[g(0, 8), g(8, 16)]]                                # 8: batch 16, the largest batched
+    assert plan_waves(7, 6, 2, batchable=False) == [[[0], [1]], [[2], [3]], [[4], [5]], [[6]]]
+    assert plan_waves(0, 6, 3) == [] and plan_waves(3, 0, 0) == [[[0]], [[1]], [[2]]]
+    # a paint loop hands the runner one wave at a time, and the runner re-plans it: every wave must plan to itself
+    for n in range(0, 30):
+        for vpe in (0, 1, 2, 3, 6, 8, 9):
+            for infl in (1, 2, 3):
+                waves = plan_waves(n, vpe, infl)
+                assert sorted(k for w in waves for grp in w for k in grp) == list(range(n))
+                for w in waves:
+                    k0 = w[0][0]
+                    assert plan_waves(sum(map(len, w)), vpe, infl) == [[[k - k0 for k in grp] for grp in w]]

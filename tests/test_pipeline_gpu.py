@@ -106,7 +106,9 @@ def test_trainer_view_weights_paint_and_atlas(dev, meshes):
     assert rgb.shape == (1, 3, 160, 160) and obj.shape == (1, 1, 160, 160) and torch.isfinite(rgb).all()
     # two views in flight (two streams, two engines over one weight blob) == the same two views one after the other
     rgb1, obj1 = tr.paint_viewpoint(tr.train_views[1])
-    pair = tr.paint_viewpoints_pair(tr.train_views[0], tr.train_views[1])
+    preps = [tr._paint_prepare(tr.train_views[k]) for k in (0, 1)]
+    outs = sd.img2img_steps([kw for kw, _ in preps], views_in_flight=2)
+    pair = [tr._paint_finish(ctx, rgb_) for (_, ctx), (rgb_, _) in zip(preps, outs)]
     assert torch.equal(pair[0][0], rgb) and torch.equal(pair[1][0], rgb1) and torch.equal(pair[1][1], obj1)
     atlas, cov = tr.paint()
     assert atlas.shape == (3, 128, 128) and torch.isfinite(atlas).all()
@@ -126,49 +128,59 @@ def test_trainer_view_weights_paint_and_atlas(dev, meshes):
         assert struct.unpack('>II', raw[16:24]) == (128, 128) and os.path.exists(os.path.join(p, 'mesh.mtl'))
 
 
-def test_img2img_step_batched_lockstep_views(dev):
-    """StableDiffusion.img2img_step_batched: V views denoised in lockstep as ONE UNet evaluation of batch 2V per step.
-    (a) Inside full groups a view's result does not depend on which other views share its batch, nor on its position in it: the
-        executor's plan depends on the row count only and rows are arithmetically independent  -> torch.equal.
-    (b) Views left over after the full groups go through the batch-2 streams and equal img2img_step bit for bit.
+def test_img2img_steps_lockstep_views(dev):
+    """StableDiffusion.img2img_steps with views_per_eval V: groups of V views denoised in lockstep as ONE UNet evaluation of batch
+    2V per step.
+    (a) Inside full groups a view's result does not depend on which other views share its batch, nor on its position in it, nor
+        on its lane: the executor's plan depends on the row count only and rows are arithmetically independent  -> torch.equal.
+    (b) Views left over after the full groups run as single views and equal img2img_step bit for bit.
     (c) Against the batch-2 loop (other tile / split-K plans -> another summation order) the batched latents agree to the fp16
-        tolerance of the parity tests, not bit for bit."""
+        tolerance of the parity tests, not bit for bit.
+    (d) Two lockstep groups in flight (lane 1 = an engine clone on a side stream) equal the same groups back to back, and
+        views_per_eval 0 (three single-view lanes per wave) equals the serial img2img_step, bit for bit."""
     sd, _, cfg = _tiny_sd(dev)
     g = torch.Generator().manual_seed(9)
     calls = []
-    for v in range(5):
+    for v in range(8):
         calls.append(dict(text_embeddings=torch.randn(2, 9, cfg['cross_attention_dim'], generator=g).to(dev),
                           inputs=torch.rand(1, 3, 72, 72, generator=g).to(dev), original_depth_mask=torch.rand(1, 1, 72, 72, generator=g).to(dev),
                           guidance_scale=10.0, strength=1.0, num_inference_steps=4, update_mask=torch.ones(1, 1, 72, 72, device=dev),
                           latent_mode=False, fixed_seed=11 + v, image_size=128))
     lat = lambda kw: dict(kw, latent_mode=True, inputs=torch.zeros(1, 4, 16, 16, device=dev))
-    serial = []
-    for k in range(5):
-        kw = lat(calls[k])
-        serial.append(sd.img2img_step(kw['text_embeddings'], kw['inputs'], kw['original_depth_mask'],
-                                      **{kk: vv for kk, vv in kw.items() if kk not in ('text_embeddings', 'inputs', 'original_depth_mask')}))
-    a = sd.img2img_step_batched([lat(c) for c in calls[:3]], views_per_eval=3)
-    b = sd.img2img_step_batched([lat(calls[2]), lat(calls[4]), lat(calls[0])], views_per_eval=3)      # other mates, other positions
-    d = sd.img2img_step_batched([lat(c_) for c_ in calls], views_per_eval=3)                        # one full group + two left over
+    serial = [sd.img2img_step(**lat(c)) for c in calls]
+    a = sd.img2img_steps([lat(c) for c in calls[:3]], views_per_eval=3)
+    b = sd.img2img_steps([lat(calls[2]), lat(calls[4]), lat(calls[0])], views_per_eval=3)      # other mates, other positions
+    d = sd.img2img_steps([lat(c_) for c_ in calls], views_per_eval=3)          # two full groups in flight + two left over
     assert torch.equal(a[0][1], b[2][1]) and torch.equal(a[2][1], b[0][1]) and torch.equal(a[0][0], b[2][0])
     assert all(torch.equal(a[k][1], d[k][1]) for k in range(3))
-    assert torch.equal(d[3][1], serial[3][1]) and torch.equal(d[4][1], serial[4][1])                # the remainder: batch-2 streams
-    for k in range(3):
+    assert torch.equal(b[1][1], d[4][1])                                        # lane 0 alone == lane 1 beside lane 0
+    assert torch.equal(d[6][1], serial[6][1]) and torch.equal(d[7][1], serial[7][1])                # the remainder: single views
+    for k in range(6):
         rel = float((d[k][1] - serial[k][1]).norm() / serial[k][1].norm())
         assert rel < 4e-3 and torch.isfinite(d[k][0]).all(), (k, rel)         # 0 on this tiny net (the same plans at batch 6); ~1e-3 at full size
     assert not torch.equal(d[0][1], d[1][1])
-    # fewer views than a group: everything takes the stream path; image-mode calls return (rgb, []) like img2img_step
-    e = sd.img2img_step_batched([lat(calls[0]), lat(calls[1])], views_per_eval=3)
+    d1 = sd.img2img_steps([lat(c_) for c_ in calls], views_per_eval=3, groups_in_flight=1)
+    assert all(torch.equal(d[k][0], d1[k][0]) and torch.equal(d[k][1], d1[k][1]) for k in range(8))
+    s = sd.img2img_steps([lat(c_) for c_ in calls], views_per_eval=0, views_in_flight=3)
+    assert all(torch.equal(s[k][0], serial[k][0]) and torch.equal(s[k][1], serial[k][1]) for k in range(8))
+    # fewer views than a group: single views; image-mode calls return (rgb, []) like img2img_step
+    e = sd.img2img_steps([lat(calls[0]), lat(calls[1])], views_per_eval=3)
     assert torch.equal(e[0][1], serial[0][1]) and torch.equal(e[1][1], serial[1][1])
-    f = sd.img2img_step_batched(calls[:2], views_per_eval=2)
+    f = sd.img2img_steps(calls[:2], views_per_eval=2)
     assert f[0][0].shape == (1, 3, 128, 128) and f[0][1] == []
+    # intermediate_vis: that call runs on its own and returns its per-step images (5 PLMS steps for 4 inference steps)
+    v = sd.img2img_steps([dict(calls[0], intermediate_vis=True), calls[1]], views_in_flight=2)
+    assert len(v[0][1]) == 5 and v[0][1][0].size == (128, 128) and v[1][1] == []
+    assert torch.equal(v[0][0], sd.img2img_step(**calls[0])[0]) and torch.equal(v[1][0], sd.img2img_step(**calls[1])[0])
 
 
-def test_mesh_batch_painter_configs3_on_the_hip_path(dev):
+@pytest.mark.parametrize("views_per_eval", [0, 3])
+def test_mesh_batch_painter_configs3_on_the_hip_path(dev, views_per_eval):
     """BASELINE configs[3] on the HIP path: the 8-mesh batch (the 6 bundled shapes + 2 repeats), 6 views each, through
-    MeshBatchPainter.paint_all (3 denoise loops in flight, groups spanning mesh boundaries) with a tiny random-init UNet on a small
-    grid.  Every mesh's atlas and coverage must be BIT-IDENTICAL to that mesh's own ConTEXTure.paint over the same six views
-    (serial loop): the denoise loops in flight are bit-reproducible per view and the UV scatter sums integers."""
+    MeshBatchPainter.paint_all with a tiny random-init UNet on a small grid: views_per_eval 0 = 3 denoise loops in flight, groups
+    spanning mesh boundaries; 3 = two lockstep groups of 3 views in flight.  Every mesh's atlas and coverage must be BIT-IDENTICAL
+    to that mesh's own ConTEXTure.paint over the same six views with the same views_per_eval (a serial loop at 0; two groups in
+    flight at 3): the denoise loops in flight are bit-reproducible per view and the UV scatter sums integers."""
     from contexture_nerf_amd import config as CFG
     from contexture_nerf_amd.trainer import ConTEXTure
     from contexture_nerf_amd.batch import MeshBatchPainter, schedule
@@ -185,6 +197,7 @@ def test_mesh_batch_painter_configs3_on_the_hip_path(dev):
         cfg.guide.num_inference_steps = 2
         cfg.render.train_grid_size = 160
         cfg.optim.views_in_flight = in_flight
+        cfg.optim.views_per_eval = views_per_eval
         tr = ConTEXTure(cfg, device=dev, diffusion=sd)
         tr.text_z = sd.get_text_embeds([cfg.guide.text])
         return tr

@@ -837,3 +837,21 @@ def test_unet_fp32_residual_stream(dev):
         assert _rel(net(x.to(dev), 333.0, ctx.to(dev))['sample'], want) == r16            # switches back cleanly
         print(f"residual stream fp16 {r16:.3e} vs fp32 {r32:.3e} (rel L2 vs the fp32 oracle, channels {cfg['block_out_channels']})")
         assert r32 < 2.5e-3 and r32 <= r16 * 1.05
+
+
+def test_clone_shared_keeps_residual_fp32(dev):
+    """clone_shared re-applies the parent's handle-level switches: with set_residual_fp32(True) on the parent, a clone (the engine
+    of a second lane of StableDiffusion.img2img_steps) computes at the parent's precision, bit for bit."""
+    from contexture_nerf_amd.unet import UNet2DConditionModel
+    from oracle import unet_ref
+    cfg = unet_ref.tiny_config()
+    torch.manual_seed(8)
+    ref = unet_ref.randomize_affine(unet_ref.UNet2DConditionModelRef(cfg)).eval()
+    net = UNet2DConditionModel(cfg, device=dev, init=False); net.load_state_dict(ref.state_dict())
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(2, 5, 16, 16, generator=g).to(dev); ctx = torch.randn(2, 11, cfg['cross_attention_dim'], generator=g).to(dev)
+    y16 = net(x, 333.0, ctx)['sample'].clone()
+    net.set_residual_fp32(True)
+    y32 = net(x, 333.0, ctx)['sample'].clone()
+    assert not torch.equal(y16, y32)                                                   # the switch changes this net's output
+    assert torch.equal(net.clone_shared()(x, 333.0, ctx)['sample'], y32)
