@@ -11,6 +11,7 @@ Exchange steps, both over RCCL, one of each per mesh:
 Every rank calls the collectives of every mesh in mesh order, whether or not it holds views of that mesh."""
 import torch
 from . import dist as D
+from .config import validate
 from .stable_diffusion_depth import plan_waves
 
 
@@ -65,5 +66,8 @@ class MeshBatchPainter:
         for m, tr in enumerate(self.trainers):
             atlas, cov = D.merge_atlas(contrib[m], self.group)
             tr.atlas, tr.atlas_coverage = atlas, cov
+            tr.atlas_filled = tr.atlas_fill_src = None
+            if validate(tr.cfg).guide.atlas_fill == 'nearest':      # every rank holds the same merged atlas: no collective
+                tr.complete_atlas()
             res.append((atlas, cov))
         return res

@@ -56,6 +56,10 @@ class GuideConfig:
     zero123plus_model_dir: Optional[str] = None      # LOCAL directory in the zero123plus pipeline layout (vision_encoder/, feature_extractor_clip/,
                                                      # tokenizer/, text_encoder/, model_index.json, optionally unet/ vae/ controlnet/): the condition
                                                      # path of src/zero123plus.py:772-803; nothing is fetched by name
+    atlas_fill: str = 'none'         # 'none': uncovered texels keep the texture field's colour (the outputs of earlier builds, byte for byte);
+                                     # 'nearest': after the atlas merge every uncovered chart texel copies its nearest covered texel and the
+                                     # charts are padded outward (ConTEXTure.complete_atlas, csrc/atlasfill.hip)
+    atlas_pad: int = 8               # texels of chart-edge padding of atlas_fill = 'nearest' (0: hole fill only)
 
 
 @dataclass
@@ -129,6 +133,20 @@ def _apply(obj, key, value):
         setattr(obj, key, _coerce(value, hints[key]))
 
 
+ATLAS_FILL_MODES = ('none', 'nearest')
+
+
+def validate(cfg):
+    """Value checks of the fields this build adds (the types are coerced by _apply)."""
+    guide = getattr(cfg, 'guide', None)
+    if guide is not None:
+        if guide.atlas_fill not in ATLAS_FILL_MODES:
+            raise ValueError(f"guide.atlas_fill={guide.atlas_fill!r}: expected one of {ATLAS_FILL_MODES}")
+        if guide.atlas_pad < 0:
+            raise ValueError(f"guide.atlas_pad={guide.atlas_pad}: expected >= 0")
+    return cfg
+
+
 def parse(config_class=TrainConfig, argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     cfg = config_class()
@@ -152,7 +170,7 @@ def parse(config_class=TrainConfig, argv=None):
         for p in parts[:-1]:
             obj = getattr(obj, p)
         _apply(obj, parts[-1], v)
-    return cfg
+    return validate(cfg)
 
 
 def dump(cfg, path):

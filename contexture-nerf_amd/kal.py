@@ -200,6 +200,44 @@ def fixed_to_float(acc, frac_bits=SCATTER_FRAC_BITS, out=None):
     return out
 
 
+def _fill_ws(lib, T, device):
+    n = lib.ctx_atlas_fill_ws_bytes(T)
+    if n < 0:
+        raise L.CtxError(f"atlas fill: T={T} outside [1, 4096]")
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def nearest_seed(seed):
+    """seed [T,T] uint8 (non-zero = seed) -> (src [T,T] int32, d2 [T,T] int32): per texel the seed minimising (d2, sy, sx), exact
+    integer Euclidean; src = sy*T + sx; both -1 everywhere when there is no seed."""
+    lib = L.load()
+    if seed.dim() != 2 or seed.shape[0] != seed.shape[1]:
+        raise L.CtxError(f"nearest_seed: seed must be [T,T], got {tuple(seed.shape)}")
+    T = seed.shape[0]
+    p_seed = L.ptr(seed, torch.uint8, "seed")
+    ws, n = _fill_ws(lib, T, seed.device)
+    src = torch.empty(T, T, dtype=torch.int32, device=seed.device)
+    d2 = torch.empty(T, T, dtype=torch.int32, device=seed.device)
+    L.check(lib.ctx_nearest_seed(p_seed, T, L.ptr(src), L.ptr(d2), L.ptr(ws), n, L.stream()))
+    return src, d2
+
+
+def atlas_fill(atlas, coverage, chart, pad):
+    """Atlas completion: (filled [C,T,T] f32, src [T,T] int32).  Uncovered chart texels take the colour of their nearest covered
+    texel, then texels within `pad` of chart | covered take the colour of the nearest of those; src is the flat index of the
+    covered texel a colour was copied from (-1 = untouched).  atlas [C,T,T] f32, coverage [T,T] f32, chart [T,T] uint8."""
+    lib = L.load()
+    if atlas.dim() != 3 or atlas.shape[1] != atlas.shape[2] or tuple(coverage.shape) != tuple(atlas.shape[1:]) or tuple(chart.shape) != tuple(atlas.shape[1:]):
+        raise L.CtxError(f"atlas_fill: want atlas [C,T,T], coverage [T,T], chart [T,T]; got {tuple(atlas.shape)}, {tuple(coverage.shape)}, {tuple(chart.shape)}")
+    C, T = atlas.shape[0], atlas.shape[1]
+    p_atlas, p_cov, p_chart = L.ptr(atlas, torch.float32, "atlas"), L.ptr(coverage, torch.float32, "coverage"), L.ptr(chart, torch.uint8, "chart")
+    ws, n = _fill_ws(lib, T, atlas.device)
+    filled = torch.empty_like(atlas)
+    src = torch.empty(T, T, dtype=torch.int32, device=atlas.device)
+    L.check(lib.ctx_atlas_fill(p_atlas, p_cov, p_chart, C, T, int(pad), L.ptr(filled), L.ptr(src), L.ptr(ws), n, L.stream()))
+    return filled, src
+
+
 class _TextureMapping(torch.autograd.Function):
     @staticmethod
     def forward(ctx, uv, tex, mode, mask_idx):

@@ -51,6 +51,18 @@ def _chart_atlas_memo(v_np, f_np, resolution):
     return vt.clone(), ft.clone()
 
 
+def uv_chart_mask(face_uv, T):
+    """face_uv [1,F,3,2] (vt[ft]) -> [T,T] uint8, 1 where the texel centre lies inside a UV triangle, in the texel convention of
+    texture_mapping and of the UV scatter (row y = (1 - v) * T; atlas.rasterize_uv_counts has the other row order).  The UV
+    triangles are drawn with the rasteriser at T x T: vt * 2 - 1 is the image position whose pixel centres are the texel
+    centres, depth is constant, and the face index it returns is the mask."""
+    with torch.no_grad():
+        xy = (face_uv.detach().to(torch.float32) * 2 - 1).contiguous()
+        z = torch.full(xy.shape[:3], -1.0, device=xy.device)
+        _, idx = kal.render.mesh.rasterize(T, T, z, xy, z.unsqueeze(-1).contiguous())
+        return (idx[0] >= 0).to(torch.uint8).contiguous()
+
+
 class TexturedMeshModel(torch.nn.Module):
     def __init__(self, opt, render_grid_size=1024, texture_resolution=1024, initial_texture_path=None, cache_path=None,
                  device=torch.device('cuda'), augmentations=False, augment_prob=0.5, fovyangle=np.pi / 3,
@@ -126,6 +138,14 @@ class TexturedMeshModel(torch.nn.Module):
     def get_texture_map(self):
         """-> (texture [1,3,res,res] in [0,1], mlp_output [res*res,3]); uv grid, embedding, MLP and (tanh+1)/2 fused."""
         return self.texture_mlp.texture_map(self.texture_resolution)
+
+    def chart_mask(self):
+        """uv_chart_mask of this mesh's UV triangles at the texture resolution.  Depends on vt, ft and T only, so it is built once."""
+        T = int(self.texture_resolution)
+        cached = getattr(self, '_chart_mask', None)
+        if cached is None or cached.shape[0] != T:
+            cached = self._chart_mask = uv_chart_mask(self.face_attributes, T)
+        return cached
 
     def export_mesh(self, path, texture=None):
         """src/models/textured_mesh.py:418-474: albedo.png + mesh.obj + mesh.mtl.  texture (optional [1,3,T,T] in [0,1]): the

@@ -40,6 +40,7 @@ class ConTEXTure:
         ds = Zero123PlusDataset if self.cfg.guide.use_zero123plus else MultiviewDataset
         self.train_views = list(ds(self.cfg.render, self.device))
         self.view_weights = None
+        self.atlas_filled = self.atlas_fill_src = None                                  # set by complete_atlas (guide.atlas_fill = 'nearest')
         self.back_im = torch.full((3, 64, 64), 0.5, device=self.device)
         self.view_dirs = ['front', 'left', 'back', 'right', 'overhead', 'bottom']       # trainer.py:138
         self.text_string = None
@@ -223,8 +224,26 @@ class ConTEXTure:
                 outputs['depth'].permute(0, 2, 3, 1).contiguous(), z_normals)
 
     def _painted_texture(self, base):
+        if getattr(self, 'atlas_filled', None) is not None:
+            cov = (self.atlas_fill_src >= 0)[None, None].to(base.dtype)
+            return base * (1 - cov) + self.atlas_filled[None, :3] * cov
         cov = (self.atlas_coverage > 0)[None, None].to(base.dtype)
         return base * (1 - cov) + self.atlas[None, :3] * cov
+
+    def complete_atlas(self, pad=None):
+        """Atlas completion after the merge (guide.atlas_fill = 'nearest'): every uncovered chart texel copies the colour of its
+        nearest covered texel, then the charts are padded outward by `pad` (default guide.atlas_pad) texels.  Sets
+        self.atlas_filled [3,T,T] and self.atlas_fill_src [T,T] int32 (flat index of the covered texel each colour came from,
+        -1 = untouched); atlas and atlas_coverage are left as they are.  The merged atlas is identical on every rank and the
+        fill is integer-exact, so every rank computes the same result without a collective."""
+        from . import kal
+        if getattr(self, 'atlas', None) is None:
+            raise RuntimeError("complete_atlas: no merged atlas yet (paint first)")
+        pad = int(self.cfg.guide.atlas_pad if pad is None else pad)
+        with torch.no_grad():
+            self.atlas_filled, self.atlas_fill_src = kal.atlas_fill(self.atlas[:3].contiguous(), self.atlas_coverage.contiguous(),
+                                                                    self.mesh_model.chart_mask(), pad)
+        return self.atlas_filled, self.atlas_fill_src
 
     @torch.no_grad()
     def evaluate(self, dataloader, save_path, save_as_video=False):
@@ -395,13 +414,12 @@ class ConTEXTure:
 
     def export(self, path=None):
         """The outputs the reference writes after painting (src/training/trainer.py:954-968 -> export_mesh): mesh.obj / mesh.mtl /
-        albedo.png with the painted atlas (rank 0 only; uncovered texels keep the texture field's colour)."""
+        albedo.png with the painted atlas (rank 0 only; uncovered texels keep the texture field's colour, unless complete_atlas
+        has filled them)."""
         if D.dist.is_initialized() and D.dist.get_rank(self.group) != 0:
             return None
         path = str(self.cfg.log.exp_dir / 'mesh') if path is None else str(path)
         with torch.no_grad():
-            base = self.mesh_model.get_texture_map()[0]
-            cov = (self.atlas_coverage > 0)[None, None].to(base.dtype)
-            tex = base * (1 - cov) + self.atlas[None, :3] * cov
+            tex = self._painted_texture(self.mesh_model.get_texture_map()[0])
         self.mesh_model.export_mesh(path, texture=tex)
         return path

@@ -103,6 +103,25 @@ int32_t ctx_uv_scatter_fixed(const float *values, const float *uv, const int64_t
                              const void *plan, int32_t frac_bits, int64_t *acc, ctx_stream_t stream);
 int32_t ctx_fixed_to_float(const int64_t *acc, int64_t n, int32_t frac_bits, int32_t accumulate, float *out, ctx_stream_t stream);
 
+/* Atlas completion (atlasfill.hip): the step after the scatter above.  The scatter is a forward one, so texels no screen pixel
+   reaches stay empty; the call site it completes is src/training/trainer.py:1076-1090 (project_back, which has no body upstream).
+   Colours are copied, never computed, so the result is defined by an integer source map:
+     nearest seed of texel (y, x) = the seed (sy, sx) minimising (d2, sy, sx) lexicographically, d2 = (y-sy)^2 + (x-sx)^2 (exact).
+   ctx_nearest_seed: seed [T,T] u8 (non-zero = seed) -> src [T,T] int32 = sy*T + sx and d2 [T,T] int32; a seed maps to itself with
+   d2 = 0; with no seed at all src = d2 = -1 everywhere.
+   ctx_atlas_fill: atlas [C,T,T] f32, coverage [T,T] f32, chart [T,T] u8, pad >= 0 -> filled [C,T,T] f32, src [T,T] int32 (outputs and ws must not overlap
+   the inputs or each other).
+     stage A  seeds = coverage > 0: every texel with chart & ~seed takes the colour of its nearest seed (no distance limit);
+     stage B  seeds = chart | coverage > 0: every other texel whose nearest stage-B seed has d2 <= pad*pad takes that seed's
+              stage-A colour (pad = 0 skips it).
+   src[p] = flat index of the COVERED texel whose colour p ends up with (p itself when covered), -1 = untouched, so
+   filled[c][p] == atlas[c][src[p]] bit for bit where src[p] >= 0 and filled[c][p] == atlas[c][p] elsewhere.  Nothing covered:
+   filled == atlas, src == -1.  1 <= T <= 4096 (d2 < 2^25).  ws: ctx_atlas_fill_ws_bytes(T) bytes, for either entry. */
+int64_t ctx_atlas_fill_ws_bytes(int32_t T);
+int32_t ctx_nearest_seed(const uint8_t *seed, int32_t T, int32_t *src, int32_t *d2, void *ws, int64_t ws_bytes, ctx_stream_t stream);
+int32_t ctx_atlas_fill(const float *atlas, const float *coverage, const uint8_t *chart, int32_t C, int32_t T, int32_t pad, float *filled, int32_t *src,
+                       void *ws, int64_t ws_bytes, ctx_stream_t stream);
+
 /* Texel-interleaved forward for C <= 4 and one texture shared by the batch (the reference's texture_img.expand(B, ...),
    render.py:133-135): ctx_texture_pack4 repacks [C,T,T] into [T,T,4] once, ctx_texture_mapping_packed_fwd then gathers one
    16-byte texel per bilinear tap.  Results are bit-identical to ctx_texture_mapping_fwd. */

@@ -30,8 +30,16 @@ def main(cfg: cfgmod.TrainConfig):
         return
     atlas, coverage = trainer.paint()
     if trainer.rank == 0:
-        torch.save({'atlas': atlas.cpu(), 'coverage': coverage.cpu()}, os.path.join(exp, 'atlas.pt'))
-        print(f"painted {len(trainer.train_views)} views -> {exp}/atlas.pt  coverage {float((coverage > 0).float().mean()):.3f}")
+        saved = {'atlas': atlas.cpu(), 'coverage': coverage.cpu()}
+        line = f"painted {len(trainer.train_views)} views -> {exp}/atlas.pt  coverage {float((coverage > 0).float().mean()):.3f}"
+        if getattr(trainer, 'atlas_filled', None) is not None:              # guide.atlas_fill = 'nearest'
+            saved.update({'filled': trainer.atlas_filled.cpu(), 'fill_src': trainer.atlas_fill_src.cpu()})
+            chart = trainer.mesh_model.chart_mask() > 0
+            n = float(chart.sum().clamp_min(1))
+            line += (f"  in-chart coverage {float(((coverage > 0) & chart).sum()) / n:.3f} -> "
+                     f"{float(((trainer.atlas_fill_src >= 0) & chart).sum()) / n:.3f} after fill (pad {cfg.guide.atlas_pad})")
+        torch.save(saved, os.path.join(exp, 'atlas.pt'))
+        print(line)
     if cfg.log.save_mesh:                               # src/training/trainer.py:962-968: mesh.obj / mesh.mtl / albedo.png
         out = trainer.export()
         if out:
