@@ -77,6 +77,9 @@ class OptimConfig:
                                      # two groups in flight; left-over views all in flight as single views (stable_diffusion_depth.plan_waves)
     sds_iterations: int = 0          # 0: the per-view paint loop (north_star).  > 0: the reference's live paint() = paint_zero123plus
                                      # with that many SDS iterations (the reference hard-codes 5000, src/training/trainer.py:662)
+    consistency_weight: float = 0.0  # > 0: the SDS loop back-propagates loss - weight * view consistency of the six rendered views
+                                     # (src/training/trainer.py:856-863, where upstream fixed the weight at 500 and then switched the term
+                                     # off); 0.0: the kernel is not called and the loop computes what it computed before
 
 
 @dataclass
@@ -89,6 +92,7 @@ class LogConfig:
     save_mesh: bool = True
     vis_diffusion_steps: bool = False
     log_images: bool = True
+    eval_consistency: bool = False   # full_eval also writes results/view_consistency.json (ConTEXTure.view_consistency of the train views)
 
     @property
     def exp_dir(self) -> Path:
@@ -144,6 +148,9 @@ def validate(cfg):
             raise ValueError(f"guide.atlas_fill={guide.atlas_fill!r}: expected one of {ATLAS_FILL_MODES}")
         if guide.atlas_pad < 0:
             raise ValueError(f"guide.atlas_pad={guide.atlas_pad}: expected >= 0")
+    optim = getattr(cfg, 'optim', None)
+    if optim is not None and not optim.consistency_weight >= 0:
+        raise ValueError(f"optim.consistency_weight={optim.consistency_weight}: expected >= 0")
     return cfg
 
 

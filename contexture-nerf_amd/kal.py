@@ -238,6 +238,83 @@ def atlas_fill(atlas, coverage, chart, pad):
     return filled, src
 
 
+# ---- multi-view consistency (src/training/trainer.py:429-531) ------------------------------------------
+VIEW_ROWS = {'reference': 0, 'image': 1}      # 'reference': upstream's rows (row 0 at Y = -1); 'image': the raster's (row 0 at Y = +1)
+
+
+def _vc_args(views, faces, face_idx, fvi):
+    p = (L.ptr(views, torch.float32, "views"), L.ptr(faces, torch.int64, "faces"), L.ptr(face_idx, torch.int64, "face_idx"),
+         L.ptr(fvi, torch.float32, "face_vertices_image"))
+    if views.dim() != 4 or face_idx.dim() != 3 or faces.dim() != 2 or faces.shape[1] != 3 or fvi.dim() != 4:
+        raise L.CtxError(f"view_consistency: want views [V,C,h,w], faces [F,3], face_idx [V,h,w], face_vertices_image [V,F,3,2]; got "
+                         f"{tuple(views.shape)}, {tuple(faces.shape)}, {tuple(face_idx.shape)}, {tuple(fvi.shape)}")
+    V, C, h, w = views.shape
+    F = faces.shape[0]
+    if tuple(face_idx.shape) != (V, h, w) or tuple(fvi.shape) != (V, F, 3, 2):
+        raise L.CtxError(f"view_consistency: face_idx {tuple(face_idx.shape)} / face_vertices_image {tuple(fvi.shape)} do not match views "
+                         f"{tuple(views.shape)} and faces {tuple(faces.shape)}")
+    return p, (V, C, h, w, F)
+
+
+class _ViewConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, views, faces, face_idx, fvi, rows, seen, build):
+        lib = L.load()
+        (p_views, p_faces, p_idx, p_fvi), (V, C, h, w, F) = _vc_args(views, faces, face_idx, fvi)
+        dev = views.device
+        n_vertices = seen.shape[1]
+        pair_sum = torch.empty(V, V, dtype=torch.int64, device=dev)
+        pair_count = torch.empty(V, V, dtype=torch.int64, device=dev)
+        n_outside = torch.empty((), dtype=torch.int64, device=dev)
+        mean = torch.empty((), dtype=torch.float32, device=dev)
+        L.check(lib.ctx_view_consistency_fwd(p_views, p_faces, p_idx, p_fvi, V, C, h, w, F, n_vertices, rows, int(build),
+                                             L.ptr(seen, torch.uint8, "seen"), seen.numel(), L.ptr(pair_sum), L.ptr(pair_count), L.ptr(n_outside),
+                                             L.ptr(mean), L.stream()))
+        ctx.save_for_backward(views, faces, face_idx, fvi, seen, pair_count)
+        ctx.meta = (V, C, h, w, F, n_vertices, rows)
+        ctx.mark_non_differentiable(pair_sum, pair_count, n_outside)
+        return mean, pair_sum, pair_count, n_outside
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        views, faces, face_idx, fvi, seen, pair_count = ctx.saved_tensors
+        V, C, h, w, F, n_vertices, rows = ctx.meta
+        lib = L.load()
+        g = L.f32c(g)
+        sign_count = torch.empty(views.shape, dtype=torch.int32, device=views.device)
+        grad = torch.empty_like(views)
+        L.check(lib.ctx_view_consistency_bwd(L.ptr(views), L.ptr(faces), L.ptr(face_idx), L.ptr(fvi), L.ptr(seen), V, C, h, w, F, n_vertices, rows,
+                                             L.ptr(pair_count), L.ptr(g, torch.float32, "grad_mean"), L.ptr(sign_count), L.ptr(grad), L.stream()))
+        return grad, None, None, None, None, None, None
+
+
+def view_consistency(views, faces, face_idx, face_vertices_image, rows='image', seen=None, stats=False, n_vertices=None):
+    """Mean colour agreement of V rendered views over the pixels that show a shared vertex (trainer.py:429-531): a f32 device
+    scalar, differentiable with respect to `views`, no host sync.  views [V,C,h,w] f32, faces [F,3] i64, face_idx [V,h,w] i64
+    (-1 = background), face_vertices_image [V,F,3,2] f32.  rows: 'image' looks the source pixel up in the raster's row convention,
+    'reference' in upstream's (vertically mirrored) one.  seen [V, n_vertices] u8: the seen-vertex map a previous call on the SAME
+    raster returned (stats['seen']); it depends on faces and face_idx only, so the SDS loop builds it once.  n_vertices: the mesh's
+    vertex count; without it (and without `seen`) it is read from faces.max(), which syncs.  stats=True: -> (mean, dict(pair_sum
+    [V,V] i64 in units of 2^-32 indexed [source, target], pair_count [V,V] i64, n_outside i64, seen))."""
+    if rows not in VIEW_ROWS:
+        raise L.CtxError(f"view_consistency: rows={rows!r}, expected one of {tuple(VIEW_ROWS)}")
+    (_, (V, C, h, w, F)) = _vc_args(views, faces, face_idx, face_vertices_image)
+    build = seen is None
+    if build:
+        n_vertices = int(faces.max()) + 1 if n_vertices is None else int(n_vertices)
+        if L.load().ctx_view_consistency_ws_bytes(V, n_vertices) < 0:
+            raise L.CtxError(f"view_consistency: V={V} outside [1, 16] or n_vertices={n_vertices} < 1")
+        seen = torch.empty(V, n_vertices, dtype=torch.uint8, device=views.device)
+    else:
+        L.ptr(seen, torch.uint8, "seen")
+        if seen.dim() != 2 or seen.shape[0] != V:
+            raise L.CtxError(f"view_consistency: seen must be [V={V}, n_vertices] uint8, got {tuple(seen.shape)}")
+    mean, pair_sum, pair_count, n_outside = _ViewConsistency.apply(views, faces, face_idx, face_vertices_image, VIEW_ROWS[rows], seen, build)
+    if stats:
+        return mean, dict(pair_sum=pair_sum, pair_count=pair_count, n_outside=n_outside, seen=seen)
+    return mean
+
+
 class _TextureMapping(torch.autograd.Function):
     @staticmethod
     def forward(ctx, uv, tex, mode, mask_idx):

@@ -246,6 +246,27 @@ class ConTEXTure:
         return self.atlas_filled, self.atlas_fill_src
 
     @torch.no_grad()
+    def view_consistency(self, images=None, view_ids=None, rows='image'):
+        """How well the train views agree where they show the same surface (trainer.py:429-531, kal.view_consistency): the
+        evaluation entry, it syncs and does not run unless called.  images [V,3,G,G]: painted or rendered views of `view_ids`
+        (default: all train views) at train_grid_size; None renders them from the current texture.  rows: 'image' (the raster's
+        row convention) | 'reference' (upstream's).  -> dict(mean, pair_mean [V][V] indexed [source][target] (0 where no pair),
+        pair_count [V][V], n_outside) as Python values."""
+        from . import kal
+        ids = list(range(len(self.train_views))) if view_ids is None else list(view_ids)
+        mm = self.mesh_model
+        out = mm.render(theta=[self.train_views[i]['theta'] for i in ids], phi=[self._offset_phi(self.train_views[i]['phi']) for i in ids],
+                        radius=[float(self.train_views[i]['radius']) for i in ids], background=torch.tensor([0.5, 0.5, 0.5], device=self.device))
+        rc = out['render_cache']
+        views = out['image'] if images is None else images.to(self.device)
+        mean, st = kal.view_consistency(views.detach().float().contiguous(), mm.mesh.faces.contiguous(), rc['face_idx'].contiguous(),
+                                        rc['face_vertices_image'].contiguous(), rows=rows, stats=True, n_vertices=int(mm.mesh.vertices.shape[0]))
+        cnt = st['pair_count'].cpu()
+        pair_mean = (st['pair_sum'].cpu().double() / 4294967296.0 / cnt.clamp_min(1).double()) * (cnt > 0)
+        return dict(mean=float(mean), pair_mean=pair_mean.tolist(), pair_count=cnt.tolist(), n_outside=int(st['n_outside']), rows=rows,
+                    view_ids=ids)
+
+    @torch.no_grad()
     def evaluate(self, dataloader, save_path, save_as_video=False):
         """trainer.py:913-952: one rgb frame (+ normal map) per eval view and the texture atlas, under the reference's file names.
         `save_as_video`: the reference muxes `eval:constructed_video:all_rendered_rgb_<seed>.mp4` with imageio / ffmpeg (neither is
@@ -284,6 +305,10 @@ class ConTEXTure:
             return None
         out = self.cfg.log.exp_dir / 'results' if output_dir is None else output_dir
         n = self.evaluate(ViewsDataset(self.cfg.render, self.device, size=size or self.cfg.log.full_eval_size), out, save_as_video=True)
+        if self.cfg.log.eval_consistency:
+            import json
+            with open(os.path.join(str(out), 'view_consistency.json'), 'w') as fh:
+                json.dump(self.view_consistency(), fh)
         if self.cfg.log.save_mesh:
             if getattr(self, 'atlas', None) is not None:
                 self.export(str(self.cfg.log.exp_dir / 'mesh') if output_dir is None else str(output_dir) + '/mesh')
@@ -348,7 +373,9 @@ class ConTEXTure:
         depth ControlNet, CFG 10) -> v target -> `targets = z0 - grad`, 0.5 * sum-MSE on one random latent tile, backward through
         the VAE encoder / resize / texture_mapping / texture field, Adam(lr 1e-5, betas (0.9, 0.99), eps 1e-15).
         Host syncs of the reference's loop body that are hoisted out of it: the six crop boxes (the masks do not change) and the
-        DreamTime table (rebuilt every iteration there).  -> list of per-iteration dicts (loss, t, fisher, grad_norm)."""
+        DreamTime table (rebuilt every iteration there).  -> list of per-iteration dicts (loss, t, fisher, grad_norm).
+        optim.consistency_weight > 0 adds the term upstream wrote and switched off (:856-863): the loss that is back-propagated is
+        `loss - weight * kal.view_consistency(six views)`; the record's `loss` stays the SDS term and gains `consistency`."""
         from . import sds
         from .scheduler import DDPMScheduler
         if getattr(self, 'zero123plus', None) is None:
@@ -385,6 +412,11 @@ class ConTEXTure:
         alphas_cumprod = train_sched.alphas_cumprod.to(self.device)
         dream = utils.DreamTimeScheduler(alphas_cumprod, iterations, m=500, s=125)
         ikl, log = None, []
+        cw = float(self.cfg.optim.consistency_weight)
+        if cw > 0:
+            from . import kal
+            faces, n_vertices, vc_seen = self.mesh_model.mesh.faces.contiguous(), int(self.mesh_model.mesh.vertices.shape[0]), None
+            vc_idx, vc_fvi = render_cache['face_idx'][1:].contiguous(), render_cache['face_vertices_image'][1:].contiguous()
         for i in range(iterations):
             t = dream.get_t(i)
             optimizer.zero_grad()
@@ -396,10 +428,19 @@ class ConTEXTure:
                                   train_sched.alphas_cumprod, train_sched.add_noise, guidance_scale=10.0, grad_scale=0.2,
                                   ikl_running_avg=ikl)
             ikl = r['ikl_running_avg']
-            r['loss'].backward()
+            if cw > 0:
+                # trainer.py:856-863 (`loss = sds_loss - 500 * consistency_reward`, switched off upstream): the seen-vertex map
+                # depends on the cached raster only, so it is built by the first iteration and handed back to the others
+                reward, vc = kal.view_consistency(six.contiguous(), faces, vc_idx, vc_fvi, seen=vc_seen, stats=True, n_vertices=n_vertices)
+                vc_seen = vc['seen']
+                (r['loss'] - cw * reward).backward()
+            else:
+                r['loss'].backward()
             gn = torch.linalg.norm(torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None]))
             optimizer.step()
             rec = dict(i=i, t=int(t), loss=float(r['loss'].detach()), fisher=r['fisher'], ikl_running_avg=ikl, grad_norm=float(gn), index=r['index'])
+            if cw > 0:
+                rec['consistency'] = float(reward.detach())
             log.append(rec)
             if on_iteration is not None:
                 on_iteration(rec)

@@ -122,6 +122,30 @@ int32_t ctx_nearest_seed(const uint8_t *seed, int32_t T, int32_t *src, int32_t *
 int32_t ctx_atlas_fill(const float *atlas, const float *coverage, const uint8_t *chart, int32_t C, int32_t T, int32_t pad, float *filled, int32_t *src,
                        void *ws, int64_t ws_bytes, ctx_stream_t stream);
 
+/* ---- multi-view consistency (src/training/trainer.py:429-531; the reward of :856-863, switched off upstream) ------- */
+/* views [V,C,h,w] f32, faces [F,3] i64, face_idx [V,h,w] i64 (-1 = background), face_vertices_image [V,F,3,2] f32 in [-1, 1].
+   Vertex k is seen in view j when it is a corner of a face owning a pixel of face_idx[j].  For target view i, pixel (y, x) with
+   f = face_idx[i,y,x] >= 0 and source j != i: c = first corner of faces[f] seen in j (none: no pair), (X, Y) = face_vertices_image[j,f,c],
+   sx = trunc(((X + 1) / 2) * w), sy = trunc(((Y + 1) / 2) * h) for rows = 0 (upstream's rows) or trunc(((1 - Y) / 2) * h) for rows = 1
+   (the raster's rows).  (sy, sx) outside the image: counted in n_outside, nothing else.  d = 1 - (|t0 - s0| + |t1 - s1| + ..) / C in f32,
+   t = views[i,:,y,x], s = views[j,:,sy,sx]; the pair counts when d >= 0: pair_sum[j,i] += floor(d * 2^32), pair_count[j,i] += 1 (both
+   [V,V] i64, written, not accumulated).  mean = sum(pair_sum) / 2^32 / sum(pair_count) in f64 rounded to f32; 0 when nothing counts.
+   Integer sums: the results do not depend on the launch geometry or the stream.  1 <= V <= 16, 1 <= C <= 4.
+   seen [V, n_vertices] u8 of ctx_view_consistency_ws_bytes(V, n_vertices) bytes: built when build_seen != 0, else read as a
+   previous call on the same face_idx left it (trainer.py:429-531 rebuilds it on every call). */
+int64_t ctx_view_consistency_ws_bytes(int32_t V, int32_t n_vertices);
+int32_t ctx_view_consistency_fwd(const float *views, const int64_t *faces, const int64_t *face_idx, const float *face_vertices_image,
+                                 int32_t V, int32_t C, int32_t h, int32_t w, int32_t F, int32_t n_vertices, int32_t rows, int32_t build_seen,
+                                 uint8_t *seen, int64_t seen_bytes, int64_t *pair_sum, int64_t *pair_count, int64_t *n_outside, float *mean,
+                                 ctx_stream_t stream);
+/* Gradient of that mean (trainer.py:429-531 under autograd) with respect to views: per counted pair sign_count[i,c,y,x] -= sign(t_c - s_c)
+   and sign_count[j,c,sy,sx] += sign(t_c - s_c), sign(0) = 0; sign_count [V,C,h,w] i32 (written); then
+   grad_views = float(sign_count) * (u * grad_mean[0]), u = (1 / float(N)) / C, N = sum(pair_count) of the forward.  pair_count and
+   grad_mean are device memory: no host sync. */
+int32_t ctx_view_consistency_bwd(const float *views, const int64_t *faces, const int64_t *face_idx, const float *face_vertices_image,
+                                 const uint8_t *seen, int32_t V, int32_t C, int32_t h, int32_t w, int32_t F, int32_t n_vertices, int32_t rows,
+                                 const int64_t *pair_count, const float *grad_mean, int32_t *sign_count, float *grad_views, ctx_stream_t stream);
+
 /* Texel-interleaved forward for C <= 4 and one texture shared by the batch (the reference's texture_img.expand(B, ...),
    render.py:133-135): ctx_texture_pack4 repacks [C,T,T] into [T,T,4] once, ctx_texture_mapping_packed_fwd then gathers one
    16-byte texel per bilinear tap.  Results are bit-identical to ctx_texture_mapping_fwd. */
