@@ -1,0 +1,104 @@
+// Engine core (engine.h): table accessors, bind, the parameter repack kernels and the GEMM launch sequence.
+#include "engine.h"
+
+int32_t engine_param_count(const Engine *e) { return e ? (int32_t)e->params.size() : 0; }
+const char *engine_param_name(const Engine *e, int32_t i)
+{
+    return (e && i >= 0 && i < (int)e->params.size()) ? e->params[i].name.c_str() : "";
+}
+int32_t engine_param_shape(const Engine *e, int32_t i, int64_t shape4[4])
+{
+    if (!e || i < 0 || i >= (int)e->params.size()) return 0;
+    for (int k = 0; k < 4; ++k) shape4[k] = e->params[i].shape[k];
+    return e->params[i].ndim;
+}
+int64_t engine_weight_bytes(const Engine *e) { return e ? (int64_t)e->wtop * 2 + 256 : 0; }
+
+int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace_bytes, const char *who)
+{
+    CTX_REQUIRE(e && weights && workspace && workspace_bytes > 0, "%s: bad args", who);
+    CTX_REQUIRE(((uintptr_t)weights & 255) == 0 && ((uintptr_t)workspace & 255) == 0, "%s: blobs must be 256-byte aligned", who);
+    e->W = (f16 *)weights; e->ws = (char *)workspace; e->ws_cap = (size_t)workspace_bytes;
+    return CTX_OK;
+}
+
+void engine_gemm(Engine &e, GemmArgs &a, bool conv)
+{
+    size_t mark = e.top;
+    ctx_gemm_plan(a, conv);
+    if (a.zins) a.use8 = 0;        // the zero-inserted grid is an addressing mode of gemm.hip only
+    if (a.splitk > 1) a.part = (float *)e.alloc((size_t)a.splitk * a.M * a.N * 4);
+    ENGINE_RUN(&e, ctx_gemm_dispatch(a, conv, e.s));
+    e.top = mark;
+}
+
+// ---- parameter repack kernels ----------------------------------------------------------------------
+__global__ void k_pack_copy(const float *__restrict__ s, int64_t n, f16 *__restrict__ d)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d[i] = (f16)s[i];
+}
+// [Cout,Cin,3,3] -> [Cout][3][3][Cinp] (Cinp = Cin, or 8 for conv_in)
+__global__ void k_pack_conv3(const float *__restrict__ s, int Cout, int Cin, int Cinp, f16 *__restrict__ d)
+{
+    int64_t n = (int64_t)Cout * 9 * Cinp;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        int c = (int)(i % Cinp);
+        int tap = (int)((i / Cinp) % 9);
+        int o = (int)(i / ((int64_t)Cinp * 9));
+        d[i] = c < Cin ? (f16)s[((int64_t)o * Cin + c) * 9 + tap] : (f16)0.f;
+    }
+}
+// GEGLU rows: packed row p (of 2*C4) <- source row  (w<32 ? blk*32+w : C4 + blk*32 + w-32), blk=p/64, w=p%64
+__global__ void k_pack_geglu(const float *__restrict__ s, int C4, int K, f16 *__restrict__ d)
+{
+    int64_t n = (int64_t)2 * C4 * (K > 0 ? K : 1);
+    int kk = K > 0 ? K : 1;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        int k = (int)(i % kk);
+        int p = (int)(i / kk);
+        int blk = p / 64, w = p % 64;
+        int src = w < 32 ? blk * 32 + w : C4 + blk * 32 + (w - 32);
+        d[i] = (f16)s[(int64_t)src * kk + k];
+    }
+}
+// backward packs: conv3 [Cout,Cin,3,3] -> [Cin][t' = 3 (2-ky) + (2-kx)][pad] (zero beyond Cout); matrix [out,in] -> [in][ld] at column col
+__global__ void k_pack_conv3_T(const float *__restrict__ s, int Cout, int Cin, int pad, f16 *__restrict__ d)
+{
+    int64_t n = (int64_t)Cin * 9 * pad;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        int o = (int)(i % pad), tp = (int)((i / pad) % 9), c = (int)(i / ((int64_t)pad * 9));
+        int ky = 2 - tp / 3, kx = 2 - tp % 3;
+        d[i] = o < Cout ? (f16)s[(((int64_t)o * Cin + c) * 3 + ky) * 3 + kx] : (f16)0.f;
+    }
+}
+__global__ void k_pack_mat_T(const float *__restrict__ s, int out, int in, int ld, int col, f16 *__restrict__ d)
+{
+    int64_t n = (int64_t)out * in;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        int c = (int)(i % in), o = (int)(i / in);
+        d[(int64_t)c * ld + col + o] = (f16)s[i];
+    }
+}
+
+int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t stream, const char *who)
+{
+    CTX_REQUIRE(e && e->W && src && i >= 0 && i < (int)e->params.size(), "%s: bad args / not bound", who);
+    const Param &p = e->params[i];
+    hipStream_t s = (hipStream_t)stream;
+    int64_t n = 1;
+    for (int k = 0; k < p.ndim; ++k) n *= p.shape[k];
+    f16 *d = e->W + p.dst;
+    int64_t nbk = cdiv64(n, 256);
+    unsigned nb = (unsigned)(nbk > 4096 ? 4096 : nbk);
+    switch (p.kind) {
+    case PK_COPY: hipLaunchKernelGGL(k_pack_copy, dim3(nb), dim3(256), 0, s, src, n, d); break;
+    case PK_CONV3: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b, d); break;
+    case PK_CONVIN: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b > 8 ? 16 : 8, d); break;
+    case PK_GEGLU_W: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, p.b, d); break;
+    case PK_GEGLU_B: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, 0, d); break;
+    }
+    if (p.kind2 == 1) hipLaunchKernelGGL(k_pack_conv3_T, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.pad2, e->W + p.dst2);
+    else if (p.kind2 == 2) hipLaunchKernelGGL(k_pack_mat_T, dim3(nb), dim3(256), 0, s, src, (int)p.shape[0], (int)p.shape[1], p.ld2, p.col2, e->W + p.dst2);
+    CTX_CHECK_LAUNCH(who);
+    return CTX_OK;
+}

@@ -8,22 +8,8 @@
 // lives in the same lane as its value, all time_emb_proj layers concatenated into one GEMV) and one
 // workspace arena (bump allocator with mark/release; sized by a dry run of the same code path).
 // Activations are NHWC fp16; statistics, softmax and accumulators are fp32.
-#include "common.h"
-#include "kernels.h"
-#include <string>
-#include <vector>
+#include "engine.h"
 #include <string.h>
-
-enum PackKind { PK_COPY = 0, PK_CONV3 = 1, PK_CONVIN = 2, PK_GEGLU_W = 3, PK_GEGLU_B = 4 };
-
-struct Param {
-    std::string name;
-    int ndim;
-    int64_t shape[4];
-    int kind;
-    size_t dst;      // element offset into the fp16 weight blob
-    int a, b;        // kind-specific dims
-};
 
 struct ResP {
     int cin, cout;
@@ -43,10 +29,8 @@ struct LevelP {
     int sc = 0;
 };
 
-struct ctx_unet {
+struct ctx_unet : Engine {
     ctx_unet_config_t cfg;
-    std::vector<Param> params;
-    size_t wtop = 0;           // elements
     // parameter offsets
     size_t ciw, cib, t1w, t1b, t2w, t2b, tpw, tpb, cng, cnb, cow, cob;
     int temb_dim = 0, temb_rows = 0;
@@ -55,15 +39,6 @@ struct ctx_unet {
     int kv_rows_total = 0, kv_rows = 0;
     std::vector<LevelP> down, up;
     LevelP mid;
-    // bound memory
-    f16 *W = nullptr;
-    char *ws = nullptr;
-    size_t ws_cap = 0;
-    // arena state
-    size_t top = 0, peak = 0;
-    bool dry = false;
-    hipStream_t s = nullptr;
-    int rc = 0;
     // stats
     int64_t launches[3] = {0, 0, 0};
     double flops[3] = {0, 0, 0};
@@ -110,27 +85,6 @@ struct ctx_unet {
         if (!dry && rc == 0 && tap_cursor + n <= tap_cap) (void)hipMemcpyAsync(tap_buf + tap_cursor, x, n * 2, hipMemcpyDeviceToDevice, s);
         tap_cursor += n;
     }
-
-    size_t walloc(size_t n) { size_t o = wtop; wtop += (n + 127) / 128 * 128; return o; }
-    size_t add(const std::string &name, std::vector<int64_t> shp, int kind, size_t dst, int a = 0, int b = 0)
-    {
-        Param p; p.name = name; p.ndim = (int)shp.size(); p.kind = kind; p.dst = dst; p.a = a; p.b = b;
-        for (int i = 0; i < 4; ++i) p.shape[i] = i < p.ndim ? shp[i] : 1;
-        params.push_back(p);
-        return dst;
-    }
-    size_t vec(const std::string &name, int n) { return add(name, {n}, PK_COPY, walloc(n)); }
-    size_t lin(const std::string &name, int out, int in) { return add(name, {out, in}, PK_COPY, walloc((size_t)out * in)); }
-
-    void *alloc(size_t bytes)
-    {
-        size_t o = (top + 255) / 256 * 256;
-        top = o + bytes;
-        if (top > peak) peak = top;
-        if (!dry && top > ws_cap) { rc = CTX_E_STATE; ctx_set_error("unet: workspace too small (%zu > %zu)", top, ws_cap); return ws; }
-        return dry ? nullptr : (void *)(ws + o);
-    }
-    f16 *allocH(size_t n) { return (f16 *)alloc(n * 2); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -196,6 +150,7 @@ static ctx_unet_t *unet_create_impl(const ctx_unet_config_t *cfg, bool controlne
             return nullptr;
         }
     ctx_unet *u = new ctx_unet();
+    u->tag = "unet";
     u->cfg = *cfg;
     const int n = cfg->n_levels, lpb = cfg->layers_per_block;
     const int *ch = cfg->block_out_channels;
@@ -329,76 +284,17 @@ extern "C" ctx_unet_t *ctx_controlnet_create(const ctx_unet_config_t *cfg, int32
     return unet_create_impl(cfg, true, cond_channels);
 }
 extern "C" void ctx_unet_destroy(ctx_unet_t *u) { delete u; }
-extern "C" int32_t ctx_unet_param_count(const ctx_unet_t *u) { return u ? (int32_t)u->params.size() : 0; }
-extern "C" const char *ctx_unet_param_name(const ctx_unet_t *u, int32_t i)
-{
-    return (u && i >= 0 && i < (int)u->params.size()) ? u->params[i].name.c_str() : "";
-}
-extern "C" int32_t ctx_unet_param_shape(const ctx_unet_t *u, int32_t i, int64_t shape4[4])
-{
-    if (!u || i < 0 || i >= (int)u->params.size()) return 0;
-    for (int k = 0; k < 4; ++k) shape4[k] = u->params[i].shape[k];
-    return u->params[i].ndim;
-}
-extern "C" int64_t ctx_unet_weight_bytes(const ctx_unet_t *u) { return u ? (int64_t)u->wtop * 2 + 256 : 0; }
-
+extern "C" int32_t ctx_unet_param_count(const ctx_unet_t *u) { return engine_param_count(u); }
+extern "C" const char *ctx_unet_param_name(const ctx_unet_t *u, int32_t i) { return engine_param_name(u, i); }
+extern "C" int32_t ctx_unet_param_shape(const ctx_unet_t *u, int32_t i, int64_t shape4[4]) { return engine_param_shape(u, i, shape4); }
+extern "C" int64_t ctx_unet_weight_bytes(const ctx_unet_t *u) { return engine_weight_bytes(u); }
 extern "C" int32_t ctx_unet_bind(ctx_unet_t *u, void *weights, void *workspace, int64_t workspace_bytes)
 {
-    CTX_REQUIRE(u && weights && workspace && workspace_bytes > 0, "unet_bind: bad args");
-    CTX_REQUIRE(((uintptr_t)weights & 255) == 0 && ((uintptr_t)workspace & 255) == 0, "unet_bind: blobs must be 256-byte aligned");
-    u->W = (f16 *)weights; u->ws = (char *)workspace; u->ws_cap = (size_t)workspace_bytes;
-    return CTX_OK;
+    return engine_bind(u, weights, workspace, workspace_bytes, "unet_bind");
 }
-
-// ---- parameter repack kernels ----------------------------------------------------------------------
-__global__ void k_pack_copy(const float *__restrict__ s, int64_t n, f16 *__restrict__ d)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d[i] = (f16)s[i];
-}
-// [Cout,Cin,3,3] -> [Cout][3][3][Cinp] (Cinp = Cin, or 8 for conv_in)
-__global__ void k_pack_conv3(const float *__restrict__ s, int Cout, int Cin, int Cinp, f16 *__restrict__ d)
-{
-    int64_t n = (int64_t)Cout * 9 * Cinp;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        int c = (int)(i % Cinp);
-        int tap = (int)((i / Cinp) % 9);
-        int o = (int)(i / ((int64_t)Cinp * 9));
-        d[i] = c < Cin ? (f16)s[((int64_t)o * Cin + c) * 9 + tap] : (f16)0.f;
-    }
-}
-// GEGLU rows: packed row p (of 2*C4) <- source row  (w<32 ? blk*32+w : C4 + blk*32 + w-32), blk=p/64, w=p%64
-__global__ void k_pack_geglu(const float *__restrict__ s, int C4, int K, f16 *__restrict__ d)
-{
-    int64_t n = (int64_t)2 * C4 * (K > 0 ? K : 1);
-    int kk = K > 0 ? K : 1;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        int k = (int)(i % kk);
-        int p = (int)(i / kk);
-        int blk = p / 64, w = p % 64;
-        int src = w < 32 ? blk * 32 + w : C4 + blk * 32 + (w - 32);
-        d[i] = (f16)s[(int64_t)src * kk + k];
-    }
-}
-
 extern "C" int32_t ctx_unet_set_param(ctx_unet_t *u, int32_t i, const float *src, ctx_stream_t stream)
 {
-    CTX_REQUIRE(u && u->W && src && i >= 0 && i < (int)u->params.size(), "unet_set_param: bad args / not bound");
-    const Param &p = u->params[i];
-    hipStream_t s = (hipStream_t)stream;
-    int64_t n = 1;
-    for (int k = 0; k < p.ndim; ++k) n *= p.shape[k];
-    f16 *d = u->W + p.dst;
-    int64_t nbk = cdiv64(n, 256);
-    unsigned nb = (unsigned)(nbk > 4096 ? 4096 : nbk);
-    switch (p.kind) {
-    case PK_COPY: hipLaunchKernelGGL(k_pack_copy, dim3(nb), dim3(256), 0, s, src, n, d); break;
-    case PK_CONV3: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b, d); break;
-    case PK_CONVIN: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b > 8 ? 16 : 8, d); break;
-    case PK_GEGLU_W: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, p.b, d); break;
-    case PK_GEGLU_B: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, 0, d); break;
-    }
-    CTX_CHECK_LAUNCH("unet_set_param");
-    return CTX_OK;
+    return engine_set_param(u, i, src, stream, "unet_set_param");
 }
 
 // 3x3 convolution (pad 1, stride 1 | 2) for the few-channel layers of ControlNet's conditioning embedding (3 -> 16 -> 16 -> 32
@@ -469,7 +365,7 @@ __global__ __launch_bounds__(256) void k_add_scaled_f16(f16 *__restrict__ dst, c
 
 // ---- op wrappers (skip launches on a dry run, keep accounting identical) ---------------------------------
 static void note(ctx_unet *u, int klass, double fl, int n = 1) { u->launches[klass] += n; u->flops[klass] += fl; }
-#define RUN(expr) do { if (!u->dry && u->rc == 0) { int r__ = (expr); if (r__ != 0) u->rc = r__; } } while (0)
+#define RUN(expr) ENGINE_RUN(u, expr)
 
 // res / out are residual-stream tensors (fp32 when u->res32) iff res_s / out_s
 static void op_gemm(ctx_unet *u, const f16 *X, size_t w, size_t bias, bool has_bias, const void *res, int M, int N, int K, void *out,
@@ -480,11 +376,7 @@ static void op_gemm(ctx_unet *u, const f16 *X, size_t w, size_t bias, bool has_b
     a.M = M; a.N = N; a.K = K; a.ldc = epi == 1 ? N / 2 : N; a.ldr = N; a.rows_per_batch = 1; a.ldrb = N; a.epi = epi;
     a.res32 = (u->res32 && res_s && res) ? 1 : 0; a.out32 = (u->res32 && out_s) ? 1 : 0;
     note(u, 0, 2.0 * M * N * K);
-    size_t mark = u->top;
-    ctx_gemm_plan(a, false);
-    if (a.splitk > 1) a.part = (float *)u->alloc((size_t)a.splitk * M * N * 4);
-    RUN(ctx_gemm_dispatch(a, false, u->s));
-    u->top = mark;
+    engine_gemm(*u, a, false);
 }
 static void op_conv(ctx_unet *u, const f16 *x, size_t w, size_t bias, const f16 *rowbias, int ldrb, const void *res, int B, int H,
                     int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false)
@@ -497,11 +389,7 @@ static void op_conv(ctx_unet *u, const f16 *x, size_t w, size_t bias, const f16 
     a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.ups = ups;
     a.res32 = (u->res32 && res_s && res) ? 1 : 0; a.out32 = (u->res32 && out_s) ? 1 : 0;
     note(u, 0, 2.0 * a.M * a.N * a.K);
-    size_t mark = u->top;
-    ctx_gemm_plan(a, true);
-    if (a.splitk > 1) a.part = (float *)u->alloc((size_t)a.splitk * a.M * a.N * 4);
-    RUN(ctx_gemm_dispatch(a, true, u->s));
-    u->top = mark;
+    engine_gemm(*u, a, true);
 }
 // x_s: x is a residual-stream tensor
 static void op_gn(ctx_unet *u, const void *x, size_t g, size_t b, int B, int HW, int C, float eps, int silu, f16 *y, void *stats, bool x_s = true)

@@ -5,23 +5,14 @@
 // Reuses the UNet's fp16 MFMA conv / GEMM and GroupNorm kernels; the single-head (dim 512) mid-block attention is run
 // as two GEMMs around a row softmax (scores are materialised: it is one call per painted view, not per denoise step).
 // Parameter names follow the diffusers AutoencoderKL state_dict ("decoder.up_blocks.2.resnets.0.conv1.weight", ...).
-#include "common.h"
-#include "kernels.h"
+#include "engine.h"
 #include <algorithm>
-#include <string>
-#include <vector>
 
-struct VParam { std::string name; int ndim; int64_t shape[4]; int kind; size_t dst; int a, b;   // kind: 0 copy, 1 conv3, 2 convin
-                // second pack for the encoder's backward (input gradients): kind2 1 = conv3 [Cout,Cin,3,3] -> [Cin][2-ky][2-kx][pad2 >= Cout]
-                // (the data-gradient of a 3x3 convolution is a 3x3 convolution with this matrix), 2 = [out,in] -> [in][ld2] at column col2
-                int kind2 = 0; size_t dst2 = 0; int pad2 = 0, ld2 = 0, col2 = 0; };
 struct VRes { int cin, cout; size_t n1g, n1b, c1w, c1b, n2g, n2b, c2w, c2b, scw, scb; size_t c1wT = 0, c2wT = 0, scwT = 0; };
 struct VAttn { size_t ng, nb, qkv, qkvb, ow, ob; size_t qkvT = 0, owT = 0; };
 
-struct ctx_vae {
+struct ctx_vae : Engine {
     ctx_vae_config_t cfg;
-    std::vector<VParam> params;
-    size_t wtop = 0;
     size_t pqw, pqb, ciw, cib, cng, cnb, cow, cob;
     VAttn att;
     VRes mid[2];
@@ -34,8 +25,6 @@ struct ctx_vae {
     std::vector<std::vector<VRes>> up;
     std::vector<size_t> upw, upb;
     std::vector<int> upc;
-    f16 *W = nullptr; char *ws = nullptr; size_t ws_cap = 0, top = 0, peak = 0;
-    bool dry = false; hipStream_t s = nullptr; int rc = 0;
     double flops = 0;
     int n_dec_params = 0;
     // encoder backward: transposed packs + the tape of the last training forward (pointers into the workspace)
@@ -49,36 +38,17 @@ struct ctx_vae {
         const f16 *attn_in = nullptr, *qkv = nullptr, *norm_out_in = nullptr;
     } tape;
     bool train = false;
-
-    size_t walloc(size_t n) { size_t o = wtop; wtop += (n + 127) / 128 * 128; return o; }
-    size_t add(const std::string &name, std::vector<int64_t> shp, int kind, size_t dst, int a = 0, int b = 0)
-    {
-        VParam p; p.name = name; p.ndim = (int)shp.size(); p.kind = kind; p.dst = dst; p.a = a; p.b = b;
-        for (int i = 0; i < 4; ++i) p.shape[i] = i < p.ndim ? shp[i] : 1;
-        params.push_back(p);
-        return dst;
-    }
-    size_t vec(const std::string &n, int c) { return add(n, {c}, 0, walloc(c)); }
-    void *alloc(size_t bytes)
-    {
-        size_t o = (top + 255) / 256 * 256;
-        top = o + bytes;
-        if (top > peak) peak = top;
-        if (!dry && top > ws_cap) { rc = CTX_E_STATE; ctx_set_error("vae: workspace too small (%zu > %zu)", top, ws_cap); return ws; }
-        return dry ? nullptr : (void *)(ws + o);
-    }
-    f16 *allocH(size_t n) { return (f16 *)alloc(n * 2); }
 };
 
 static void vadd_bwd_conv3(ctx_vae *v, size_t &dstT, int cout, int cin, int pad)
 {
     dstT = v->walloc((size_t)cin * 9 * pad);
-    VParam &q = v->params.back();
+    Param &q = v->params.back();
     q.kind2 = 1; q.dst2 = dstT; q.pad2 = pad;
 }
 static void vadd_bwd_mat(ctx_vae *v, size_t dstT, int ld, int col)
 {
-    VParam &q = v->params.back();
+    Param &q = v->params.back();
     q.kind2 = 2; q.dst2 = dstT; q.ld2 = ld; q.col2 = col;
 }
 
@@ -123,6 +93,7 @@ extern "C" ctx_vae_t *ctx_vae_create(const ctx_vae_config_t *cfg)
     for (int i = 0; i < cfg->n_levels; ++i)
         if (cfg->block_out_channels[i] % 64 || cfg->block_out_channels[i] % cfg->groups) { ctx_set_error("vae_create: channels must be multiples of 64 and of groups"); return nullptr; }
     ctx_vae *v = new ctx_vae();
+    v->tag = "vae";
     v->cfg = *cfg;
     const int n = cfg->n_levels, L = cfg->latent_channels;
     const int *ch = cfg->block_out_channels;
@@ -183,69 +154,19 @@ extern "C" ctx_vae_t *ctx_vae_create(const ctx_vae_config_t *cfg)
 }
 
 extern "C" void ctx_vae_destroy(ctx_vae_t *v) { delete v; }
-extern "C" int32_t ctx_vae_param_count(const ctx_vae_t *v) { return v ? (int32_t)v->params.size() : 0; }
+extern "C" int32_t ctx_vae_param_count(const ctx_vae_t *v) { return engine_param_count(v); }
 /* the first ctx_vae_decoder_param_count entries are post_quant_conv + decoder, the rest encoder + quant_conv */
 extern "C" int32_t ctx_vae_decoder_param_count(const ctx_vae_t *v) { return v ? v->n_dec_params : 0; }
-extern "C" const char *ctx_vae_param_name(const ctx_vae_t *v, int32_t i) { return (v && i >= 0 && i < (int)v->params.size()) ? v->params[i].name.c_str() : ""; }
-extern "C" int32_t ctx_vae_param_shape(const ctx_vae_t *v, int32_t i, int64_t shape4[4])
-{
-    if (!v || i < 0 || i >= (int)v->params.size()) return 0;
-    for (int k = 0; k < 4; ++k) shape4[k] = v->params[i].shape[k];
-    return v->params[i].ndim;
-}
-extern "C" int64_t ctx_vae_weight_bytes(const ctx_vae_t *v) { return v ? (int64_t)v->wtop * 2 + 256 : 0; }
+extern "C" const char *ctx_vae_param_name(const ctx_vae_t *v, int32_t i) { return engine_param_name(v, i); }
+extern "C" int32_t ctx_vae_param_shape(const ctx_vae_t *v, int32_t i, int64_t shape4[4]) { return engine_param_shape(v, i, shape4); }
+extern "C" int64_t ctx_vae_weight_bytes(const ctx_vae_t *v) { return engine_weight_bytes(v); }
 extern "C" int32_t ctx_vae_bind(ctx_vae_t *v, void *weights, void *workspace, int64_t workspace_bytes)
 {
-    CTX_REQUIRE(v && weights && workspace && workspace_bytes > 0, "vae_bind: bad args");
-    v->W = (f16 *)weights; v->ws = (char *)workspace; v->ws_cap = (size_t)workspace_bytes;
-    return CTX_OK;
+    return engine_bind(v, weights, workspace, workspace_bytes, "vae_bind");
 }
-
-__global__ void k_vpack_copy(const float *__restrict__ s, int64_t n, f16 *__restrict__ d)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d[i] = (f16)s[i];
-}
-__global__ void k_vpack_conv3(const float *__restrict__ s, int Cout, int Cin, int Cinp, f16 *__restrict__ d)
-{
-    int64_t n = (int64_t)Cout * 9 * Cinp;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        int c = (int)(i % Cinp), tap = (int)((i / Cinp) % 9), o = (int)(i / ((int64_t)Cinp * 9));
-        d[i] = c < Cin ? (f16)s[((int64_t)o * Cin + c) * 9 + tap] : (f16)0.f;
-    }
-}
-// backward packs: conv3 [Cout,Cin,3,3] -> [Cin][t' = 3 (2-ky) + (2-kx)][pad] (zero beyond Cout); matrix [out,in] -> [in][ld] at column col
-__global__ void k_vpack_conv3_T(const float *__restrict__ s, int Cout, int Cin, int pad, f16 *__restrict__ d)
-{
-    int64_t n = (int64_t)Cin * 9 * pad;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        int o = (int)(i % pad), tp = (int)((i / pad) % 9), c = (int)(i / ((int64_t)pad * 9));
-        int ky = 2 - tp / 3, kx = 2 - tp % 3;
-        d[i] = o < Cout ? (f16)s[(((int64_t)o * Cin + c) * 3 + ky) * 3 + kx] : (f16)0.f;
-    }
-}
-__global__ void k_vpack_mat_T(const float *__restrict__ s, int out, int in, int ld, int col, f16 *__restrict__ d)
-{
-    int64_t n = (int64_t)out * in;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        int c = (int)(i % in), o = (int)(i / in);
-        d[(int64_t)c * ld + col + o] = (f16)s[i];
-    }
-}
-
 extern "C" int32_t ctx_vae_set_param(ctx_vae_t *v, int32_t i, const float *src, ctx_stream_t stream)
 {
-    CTX_REQUIRE(v && v->W && src && i >= 0 && i < (int)v->params.size(), "vae_set_param: bad args / not bound");
-    const VParam &p = v->params[i];
-    int64_t n = 1;
-    for (int k = 0; k < p.ndim; ++k) n *= p.shape[k];
-    unsigned nb = (unsigned)(cdiv64(n, 256) > 4096 ? 4096 : cdiv64(n, 256));
-    hipStream_t s = (hipStream_t)stream;
-    if (p.kind == 0) hipLaunchKernelGGL(k_vpack_copy, dim3(nb), dim3(256), 0, s, src, n, v->W + p.dst);
-    else hipLaunchKernelGGL(k_vpack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.kind == 2 ? 8 : p.b, v->W + p.dst);
-    if (p.kind2 == 1) hipLaunchKernelGGL(k_vpack_conv3_T, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.pad2, v->W + p.dst2);
-    else if (p.kind2 == 2) hipLaunchKernelGGL(k_vpack_mat_T, dim3(nb), dim3(256), 0, s, src, (int)p.shape[0], (int)p.shape[1], p.ld2, p.col2, v->W + p.dst2);
-    CTX_CHECK_LAUNCH("vae_set_param");
-    return CTX_OK;
+    return engine_set_param(v, i, src, stream, "vae_set_param");
 }
 
 // post_quant_conv: 1x1 conv over <= 8 latent channels, f32 NCHW in/out (16 MACs per pixel)
@@ -300,19 +221,16 @@ __global__ __launch_bounds__(256) void k_softmax_rows(const f16 *__restrict__ s,
     }
 }
 
-#define VRUN(expr) do { if (!v->dry && v->rc == 0) { int r__ = (expr); if (r__ != 0) v->rc = r__; } } while (0)
+#define VRUN(expr) ENGINE_RUN(v, expr)
 
-static void vgemm(ctx_vae *v, const f16 *X, const f16 *Wt, const f16 *bias, const f16 *res, int M, int N, int K, f16 *out)
+// ldc: row stride of out (0 = N)
+static void vgemm(ctx_vae *v, const f16 *X, const f16 *Wt, const f16 *bias, const f16 *res, int M, int N, int K, f16 *out, int ldc = 0)
 {
     GemmArgs a = {};
-    a.X = X; a.Wt = Wt; a.bias = bias; a.residual = res; a.out = out; a.M = M; a.N = N; a.K = K; a.ldc = N; a.ldr = N;
+    a.X = X; a.Wt = Wt; a.bias = bias; a.residual = res; a.out = out; a.M = M; a.N = N; a.K = K; a.ldc = ldc ? ldc : N; a.ldr = N;
     a.rows_per_batch = 1; a.ldrb = N; a.epi = 0;
     v->flops += 2.0 * M * N * K;
-    size_t mark = v->top;
-    ctx_gemm_plan(a, false);
-    if (a.splitk > 1) a.part = (float *)v->alloc((size_t)a.splitk * M * N * 4);
-    VRUN(ctx_gemm_dispatch(a, false, v->s));
-    v->top = mark;
+    engine_gemm(*v, a, false);
 }
 static void vconv(ctx_vae *v, const f16 *x, size_t w, size_t bias, const f16 *res, int B, int H, int W, int Cin, int Cout, int ups, f16 *out,
                   int down = 0)
@@ -323,11 +241,7 @@ static void vconv(ctx_vae *v, const f16 *x, size_t w, size_t bias, const f16 *re
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = Cout;
     a.H = H; a.W = W; a.Cin = Cin; a.stride = down ? 2 : 1; a.ups = ups; a.poff = down ? 1 : 0;
     v->flops += 2.0 * a.M * a.N * a.K;
-    size_t mark = v->top;
-    ctx_gemm_plan(a, true);
-    if (a.splitk > 1) a.part = (float *)v->alloc((size_t)a.splitk * a.M * a.N * 4);
-    VRUN(ctx_gemm_dispatch(a, true, v->s));
-    v->top = mark;
+    engine_gemm(*v, a, true);
 }
 static void vgn(ctx_vae *v, const f16 *x, size_t g, size_t b, int B, int HW, int C, int silu, f16 *y, void *stats)
 {
@@ -758,24 +672,11 @@ static void vconv_ex(ctx_vae *v, const f16 *x, const f16 *Wt, const f16 *res, in
     a.M = B * Ho * Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = Ho * Wo; a.ldrb = Cout;
     a.H = H; a.W = W; a.Cin = Cin; a.stride = 1; a.ups = ups; a.poff = poff; a.zins = zins;
     v->flops += 2.0 * a.M * a.N * a.K;
-    size_t mark = v->top;
-    ctx_gemm_plan(a, true);
-    if (zins) a.use8 = 0;
-    if (a.splitk > 1) a.part = (float *)v->alloc((size_t)a.splitk * a.M * a.N * 4);
-    VRUN(ctx_gemm_dispatch(a, true, v->s));
-    v->top = mark;
+    engine_gemm(*v, a, true);                          // zins: the shared sequence forces use8 = 0 after the plan
 }
 static void vgemm_ld(ctx_vae *v, const f16 *X, const f16 *Wt, const f16 *res, int M, int N, int K, f16 *out, int ldc)
 {
-    GemmArgs a = {};
-    a.X = X; a.Wt = Wt; a.bias = nullptr; a.residual = res; a.out = out; a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.ldr = N;
-    a.rows_per_batch = 1; a.ldrb = N; a.epi = 0;
-    v->flops += 2.0 * M * N * K;
-    size_t mark = v->top;
-    ctx_gemm_plan(a, false);
-    if (a.splitk > 1) a.part = (float *)v->alloc((size_t)a.splitk * M * N * 4);
-    VRUN(ctx_gemm_dispatch(a, false, v->s));
-    v->top = mark;
+    vgemm(v, X, Wt, nullptr, res, M, N, K, out, ldc);
 }
 
 // resnet backward: dout [M,cout] -> dx [M,cin] (dx may alias nothing the forward still needs)

@@ -10,6 +10,7 @@ import ctypes as C
 import math
 import torch
 from . import _lib as L
+from .engine import HipEngine
 
 
 class UNetConfig(C.Structure):
@@ -29,128 +30,43 @@ def _pad4(xs):
     return (C.c_int32 * 4)(*(xs + [0] * (4 - len(xs))))
 
 
-class UNet2DConditionModel:
+class UNet2DConditionModel(HipEngine):
+    _prefix = 'ctx_unet'
+
     def __init__(self, config=None, device="cuda:0", seed=0, init=True):
-        cfg = dict(SD2_DEPTH if config is None else config)
-        self.config = cfg
-        self.in_channels = cfg['in_channels']
-        self.device = torch.device(device)
-        self._lib = L.load()
-        self._h = self._create_handle()
-        self._names, self._shapes = [], []
-        shp = (C.c_int64 * 4)()
-        for i in range(self._lib.ctx_unet_param_count(self._h)):
-            nd = self._lib.ctx_unet_param_shape(self._h, i, shp)
-            self._names.append(self._lib.ctx_unet_param_name(self._h, i).decode())
-            self._shapes.append(tuple(int(shp[k]) for k in range(nd)))
-        self._index = {n: i for i, n in enumerate(self._names)}
-        self._weights = None
-        self._ws = None
-        self._ws_key = None
-        self._t = None
-        self._res32 = False
-        if self.device.type == 'cuda':
-            self._weights = torch.empty(self._lib.ctx_unet_weight_bytes(self._h), dtype=torch.uint8, device=self.device)
-            self._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
-            self._bind()
-            if init:
-                self.init_random(seed)
+        super().__init__(dict(SD2_DEPTH if config is None else config), device=device, seed=seed, init=init)
+
+    def _config_struct(self):
+        cfg = self.config
+        return UNetConfig(cfg['in_channels'], cfg['out_channels'], len(cfg['block_out_channels']),
+                          _pad4(cfg['block_out_channels']), _pad4(cfg['heads']), _pad4(cfg['down_attn']),
+                          _pad4(cfg['up_attn']), cfg['layers_per_block'], cfg['cross_attention_dim'], cfg['groups'],
+                          cfg['norm_eps'])
 
     def _create_handle(self):
-        cfg = self.config
-        c = UNetConfig(cfg['in_channels'], cfg['out_channels'], len(cfg['block_out_channels']),
-                       _pad4(cfg['block_out_channels']), _pad4(cfg['heads']), _pad4(cfg['down_attn']),
-                       _pad4(cfg['up_attn']), cfg['layers_per_block'], cfg['cross_attention_dim'], cfg['groups'],
-                       cfg['norm_eps'])
-        h = self._lib.ctx_unet_create(C.byref(c))
+        h = self._lib.ctx_unet_create(C.byref(self._config_struct()))
         if not h:
             raise L.CtxError("ctx_unet_create: " + self._lib.ctx_last_error().decode())
         return h
 
-    def clone_shared(self):
-        """A second engine over the SAME weight blob with its own workspace, so two evaluations (two views of a mesh) can be
-        in flight on two HIP streams at once: the kernels of the deep UNet levels do not fill the chip, and two concurrent
-        evaluations finish ~1.25x sooner than back to back (tools/bench_concurrent.py)."""
-        o = UNet2DConditionModel.__new__(UNet2DConditionModel)
-        o.config, o.in_channels, o.device, o._lib = self.config, self.in_channels, self.device, self._lib
-        o._names, o._shapes, o._index = self._names, self._shapes, self._index
-        o._h = o._create_handle()
-        o._weights = self._weights                      # shared, read-only during forward
-        o._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
-        o._ws_key, o._t, o._res32 = None, None, False
-        o._bind()
-        if self._res32:                                 # handle-level switches live in the C handle: re-apply them
-            o.set_residual_fp32(True)
-        return o
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                self._lib.ctx_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # -- parameter table ---------------------------------------------------------------------------------
-    def param_shapes(self):
-        return dict(zip(self._names, self._shapes))
-
-    def num_parameters(self):
-        return sum(math.prod(s) for s in self._shapes)
-
-    def _bind(self):
-        L.check(self._lib.ctx_unet_bind(self._h, L.ptr(self._weights), L.ptr(self._ws), self._ws.numel()))
-
-    def _set(self, i, t):
-        t = L.f32c(t, self.device)
-        if tuple(t.shape) != self._shapes[i]:
-            raise L.CtxError(f"{self._names[i]}: shape {tuple(t.shape)} != {self._shapes[i]}")
-        L.check(self._lib.ctx_unet_set_param(self._h, i, L.ptr(t, torch.float32, self._names[i]), L.stream()))
-        return t
+    def _init_state(self, src=None):
+        self.in_channels = self.config['in_channels']
+        self._res32 = False
+        if src is not None and src._res32:              # handle-level switches live in the C handle: re-apply them
+            self.set_residual_fp32(True)
 
     def load_state_dict(self, sd, strict=True):
         missing = [n for n in self._names if n not in sd]
         extra = [k for k in sd if k not in self._index]
         if strict and (missing or extra):
             raise L.CtxError(f"load_state_dict: missing {missing[:5]}... ({len(missing)}), unexpected {extra[:5]}... ({len(extra)})")
-        keep = []
-        for n, i in self._index.items():
-            if n in sd:
-                keep.append(self._set(i, sd[n]))
-        torch.cuda.synchronize(self.device)   # sources must outlive the async repack kernels
+        self._load(sd)
         return missing, extra
 
-    def load_file(self, path, strict=True):
-        """Weights from a local safetensors file with diffusers' parameter names (what `from_pretrained` would have fetched by
-        model name, src/stable_diffusion_depth.py:58-88); fp16 / bf16 / fp32 payloads are accepted and repacked to the engine's
-        fp16 layout.  The file is memory-mapped: tensors go to the device one at a time."""
-        from .safetensors_io import load_file
-        return self.load_state_dict(load_file(path), strict=strict)
-
-    @classmethod
-    def from_file(cls, path, config=None, device="cuda:0", strict=True):
-        net = cls(config, device=device, init=False)
-        net.load_file(path, strict=strict)
-        return net
-
-    def init_random(self, seed=0):
-        """torch default initialisers (kaiming_uniform(a=sqrt 5) => U(-1/sqrt(fan_in), +)), norms = (1, 0)."""
-        g = torch.Generator(device=self.device).manual_seed(seed)
-        fan = {}
-        for n, s in zip(self._names, self._shapes):
-            if n.endswith('.weight') and len(s) >= 2:
-                fan[n[:-7]] = math.prod(s[1:])
-        for i, (n, s) in enumerate(zip(self._names, self._shapes)):
-            base = n.rsplit('.', 1)[0]
-            if len(s) == 1 and base not in fan:                 # norm affine
-                t = torch.ones(s, device=self.device) if n.endswith('.weight') else torch.zeros(s, device=self.device)
-            else:
-                b = 1.0 / math.sqrt(fan[base])
-                t = (torch.rand(s, generator=g, device=self.device) * 2 - 1) * b
-            self._set(i, t)
-            if i % 64 == 63:
-                torch.cuda.synchronize(self.device)
-        torch.cuda.synchronize(self.device)
+    @staticmethod
+    def _init_scale(u, fan):
+        b = 1.0 / math.sqrt(fan)
+        return u * b
 
     # -- forward ---------------------------------------------------------------------------------------------
     def workspace_bytes(self, B, H, W, ctx_len):
@@ -222,18 +138,11 @@ class UNet2DConditionModel:
                 bank = torch.empty(nb, dtype=torch.uint8, device=self.device)
         elif bank is None:
             raise L.CtxError("unet.forward_ref: mode 'r' needs the bank of a 'w' pass")
-        need = self._lib.ctx_unet_workspace_bytes_ref(self._h, B, H, W, Lc, m, ref_row0 if m == 2 else 0)
-        if need < 0:
-            raise L.CtxError(self._lib.ctx_last_error().decode())
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._bind()
+        self._reserve(self._lib.ctx_unet_workspace_bytes_ref(self._h, B, H, W, Lc, m, ref_row0 if m == 2 else 0))
         self._ws_key = None
-        if self._t is None:
-            self._t = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._t.fill_(float(timestep))
+        t = self._timestep(timestep)
         out = torch.empty(B, self.config['out_channels'], H, W, device=self.device)
-        L.check(self._lib.ctx_unet_forward_ref(self._h, L.ptr(x, torch.float32, "sample"), L.ptr(self._t), L.ptr(ctx), B, H, W, Lc, m,
+        L.check(self._lib.ctx_unet_forward_ref(self._h, L.ptr(x, torch.float32, "sample"), L.ptr(t), L.ptr(ctx), B, H, W, Lc, m,
                                                L.ptr(bank), ref_row0, L.ptr(out), L.stream()))
         return {'sample': out}, bank
 
@@ -249,18 +158,9 @@ class UNet2DConditionModel:
         Lc = ctx.shape[1]
         key = (B, H, W, Lc)
         if self._ws_key != key:
-            need = self.workspace_bytes(B, H, W, Lc)
-            if self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                self._bind()
+            self._reserve(self.workspace_bytes(B, H, W, Lc))
             self._ws_key = key
-        if isinstance(timestep, torch.Tensor) and timestep.is_cuda and timestep.dtype == torch.float32 and timestep.numel() == 1:
-            t = timestep.reshape(1)
-        else:
-            if self._t is None:
-                self._t = torch.empty(1, dtype=torch.float32, device=self.device)
-            self._t.fill_(float(timestep))
-            t = self._t
+        t = self._timestep(timestep)
         out = torch.empty(B, self.config['out_channels'], H, W, device=self.device)
         L.check(self._lib.ctx_unet_forward(self._h, L.ptr(x, torch.float32, "sample"), L.ptr(t), L.ptr(ctx), B, H, W, Lc,
                                            L.ptr(out), L.stream()))
@@ -283,19 +183,19 @@ class ControlNetModel(UNet2DConditionModel):
     def __init__(self, config=None, device="cuda:0", seed=0, init=True, conditioning_channels=3):
         self.conditioning_channels = conditioning_channels
         super().__init__(config, device=device, seed=seed, init=init)
-        self._res = None
-        self._cond_cache, self._cond_key = None, None      # embedding of the last conditioning image (same tensor, same version)
 
     def _create_handle(self):
-        cfg = self.config
-        c = UNetConfig(cfg['in_channels'], cfg['out_channels'], len(cfg['block_out_channels']),
-                       _pad4(cfg['block_out_channels']), _pad4(cfg['heads']), _pad4(cfg['down_attn']),
-                       _pad4(cfg['up_attn']), cfg['layers_per_block'], cfg['cross_attention_dim'], cfg['groups'],
-                       cfg['norm_eps'])
-        h = self._lib.ctx_controlnet_create(C.byref(c), self.conditioning_channels)
+        h = self._lib.ctx_controlnet_create(C.byref(self._config_struct()), self.conditioning_channels)
         if not h:
             raise L.CtxError("ctx_controlnet_create: " + self._lib.ctx_last_error().decode())
         return h
+
+    def _init_state(self, src=None):
+        if src is not None:
+            self.conditioning_channels = src.conditioning_channels
+        super()._init_state(src)
+        self._res = None
+        self._cond_cache, self._cond_key = None, None      # embedding of the last conditioning image (same tensor, same version)
 
     def __call__(self, sample, timestep, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=1.0,
                  return_dict=False, **kw):
@@ -307,22 +207,17 @@ class ControlNetModel(UNet2DConditionModel):
             raise L.CtxError(f"controlnet: sample {tuple(x.shape)}, encoder_hidden_states {tuple(ctx.shape)}, controlnet_cond "
                              f"{tuple(cond.shape)} do not fit (the conditioning image is 8x the latent grid)")
         Lc = ctx.shape[1]
-        need = self.workspace_bytes(B, H, W, Lc)
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._bind()
+        self._reserve(self.workspace_bytes(B, H, W, Lc))
         nb = self._lib.ctx_controlnet_residual_bytes(self._h, B, H, W)
         if self._res is None or self._res.numel() < nb:
             self._res = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        if self._t is None:
-            self._t = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._t.fill_(float(timestep))
+        t = self._timestep(timestep)
         cb = self._lib.ctx_controlnet_cond_cache_bytes(self._h, B, H, W)
         if self._cond_cache is None or self._cond_cache.numel() < cb:
             self._cond_cache, self._cond_key = torch.empty(cb, dtype=torch.uint8, device=self.device), None
         key = (controlnet_cond.data_ptr(), controlnet_cond._version, tuple(controlnet_cond.shape))
         valid = int(key == self._cond_key)                  # the depth image does not change between the steps of one denoise
-        L.check(self._lib.ctx_controlnet_forward(self._h, L.ptr(x, torch.float32, "sample"), L.ptr(self._t), L.ptr(ctx),
+        L.check(self._lib.ctx_controlnet_forward(self._h, L.ptr(x, torch.float32, "sample"), L.ptr(t), L.ptr(ctx),
                                                  L.ptr(cond, torch.float32, "controlnet_cond"), L.ptr(self._cond_cache), valid, B, H, W, Lc,
                                                  L.ptr(self._res), L.stream()))
         self._cond_key = key

@@ -7,6 +7,7 @@ import math
 import types
 import torch
 from . import _lib as L
+from .engine import HipEngine
 
 
 class VAEConfig(C.Structure):
@@ -17,53 +18,27 @@ class VAEConfig(C.Structure):
 SD_VAE = dict(latent_channels=4, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2, groups=32)
 
 
-class AutoencoderKL:
+class AutoencoderKL(HipEngine):
+    _prefix = 'ctx_vae'
+
     def __init__(self, config=None, device="cuda:0", seed=0, init=True):
-        cfg = dict(SD_VAE if config is None else config)
-        self.config = cfg
-        self.device = torch.device(device)
-        self._lib = L.load()
+        super().__init__(dict(SD_VAE if config is None else config), device=device, seed=seed, init=init)
+
+    def _create_handle(self):
+        cfg = self.config
         ch = [int(c) for c in cfg['block_out_channels']]
         c = VAEConfig(cfg['latent_channels'], cfg['out_channels'], len(ch), (C.c_int32 * 4)(*(ch + [0] * (4 - len(ch)))),
                       cfg['layers_per_block'], cfg['groups'])
-        self._h = self._lib.ctx_vae_create(C.byref(c))
-        if not self._h:
+        h = self._lib.ctx_vae_create(C.byref(c))
+        if not h:
             raise L.CtxError("ctx_vae_create: " + self._lib.ctx_last_error().decode())
-        self._names, self._shapes = [], []
-        shp = (C.c_int64 * 4)()
-        for i in range(self._lib.ctx_vae_param_count(self._h)):
-            nd = self._lib.ctx_vae_param_shape(self._h, i, shp)
-            self._names.append(self._lib.ctx_vae_param_name(self._h, i).decode())
-            self._shapes.append(tuple(int(shp[k]) for k in range(nd)))
-        self._index = {n: i for i, n in enumerate(self._names)}
+        return h
+
+    def _init_state(self, src=None):
         self._n_dec = self._lib.ctx_vae_decoder_param_count(self._h)
-        self._has_encoder = True
-        self._ws_key = None
+        self._has_encoder = src._has_encoder if src is not None else True
         self._tape_pending = False       # a training forward's tape lives in this engine's workspace until its backward runs
         self._sibling = None
-        if self.device.type == 'cuda':
-            self._weights = torch.empty(self._lib.ctx_vae_weight_bytes(self._h), dtype=torch.uint8, device=self.device)
-            self._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
-            self._bind()
-            if init:
-                self.init_random(seed)
-
-    def clone_shared(self):
-        """A second engine handle over the SAME weight blob with its own workspace (as UNet2DConditionModel.clone_shared)."""
-        o = AutoencoderKL.__new__(AutoencoderKL)
-        o.config, o.device, o._lib = self.config, self.device, self._lib
-        ch = [int(c) for c in self.config['block_out_channels']]
-        c = VAEConfig(self.config['latent_channels'], self.config['out_channels'], len(ch), (C.c_int32 * 4)(*(ch + [0] * (4 - len(ch)))),
-                      self.config['layers_per_block'], self.config['groups'])
-        o._h = self._lib.ctx_vae_create(C.byref(c))
-        if not o._h:
-            raise L.CtxError("ctx_vae_create: " + self._lib.ctx_last_error().decode())
-        o._names, o._shapes, o._index, o._n_dec = self._names, self._shapes, self._index, self._n_dec
-        o._has_encoder, o._ws_key, o._tape_pending, o._sibling = self._has_encoder, None, False, None
-        o._weights = self._weights
-        o._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
-        o._bind()
-        return o
 
     def _free_engine(self):
         """The engine to run a no-grad call on: this one, unless it holds the tape of a training forward whose backward is still
@@ -76,27 +51,6 @@ class AutoencoderKL:
         self._sibling._has_encoder = self._has_encoder
         return self._sibling
 
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                self._lib.ctx_vae_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def param_shapes(self):
-        return dict(zip(self._names, self._shapes))
-
-    def _bind(self):
-        L.check(self._lib.ctx_vae_bind(self._h, L.ptr(self._weights), L.ptr(self._ws), self._ws.numel()))
-
-    def _set(self, i, t):
-        t = L.f32c(t, self.device)
-        if tuple(t.shape) != self._shapes[i]:
-            raise L.CtxError(f"{self._names[i]}: shape {tuple(t.shape)} != {self._shapes[i]}")
-        L.check(self._lib.ctx_vae_set_param(self._h, i, L.ptr(t, torch.float32, self._names[i]), L.stream()))
-        return t
-
     def load_state_dict(self, sd, strict=True):
         """Accepts a full AutoencoderKL state_dict, or a decoder-only one (post_quant_conv + decoder.*): `encode` is then off."""
         missing = [n for n in self._names if n not in sd]
@@ -108,32 +62,12 @@ class AutoencoderKL:
             self._has_encoder = True
         if strict and missing:
             raise L.CtxError(f"load_state_dict: missing {missing[:5]} ({len(missing)})")
-        keep = [self._set(i, sd[n]) for n, i in self._index.items() if n in sd]
-        torch.cuda.synchronize(self.device)
+        self._load(sd)
         return missing
 
-    def load_file(self, path, strict=True):
-        """Weights from a local safetensors file with diffusers' AutoencoderKL names (memory-mapped, any float dtype)."""
-        from .safetensors_io import load_file
-        return self.load_state_dict(load_file(path), strict=strict)
-
-    @classmethod
-    def from_file(cls, path, config=None, device="cuda:0", strict=True):
-        vae = cls(config, device=device, init=False)
-        vae.load_file(path, strict=strict)
-        return vae
-
-    def init_random(self, seed=0):
-        g = torch.Generator(device=self.device).manual_seed(seed)
-        fan = {n[:-7]: math.prod(s[1:]) for n, s in zip(self._names, self._shapes) if n.endswith('.weight') and len(s) >= 2}
-        for i, (n, s) in enumerate(zip(self._names, self._shapes)):
-            base = n.rsplit('.', 1)[0]
-            if len(s) == 1 and base not in fan:
-                t = torch.ones(s, device=self.device) if n.endswith('.weight') else torch.zeros(s, device=self.device)
-            else:
-                t = (torch.rand(s, generator=g, device=self.device) * 2 - 1) / math.sqrt(fan[base])
-            self._set(i, t)
-        torch.cuda.synchronize(self.device)
+    @staticmethod
+    def _init_scale(u, fan):
+        return u / math.sqrt(fan)
 
     def decode(self, z):
         eng = self._free_engine()
@@ -145,12 +79,7 @@ class AutoencoderKL:
             raise L.CtxError(f"vae.decode: expected {self.config['latent_channels']} latent channels, got {Lc}")
         key = (B, H, W)
         if self._ws_key != key:
-            need = self._lib.ctx_vae_workspace_bytes(self._h, B, H, W)
-            if need < 0:
-                raise L.CtxError("vae.decode: latent h*w must be a multiple of 64")
-            if self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                self._bind()
+            self._reserve(self._lib.ctx_vae_workspace_bytes(self._h, B, H, W), "vae.decode: latent h*w must be a multiple of 64")
             self._ws_key = key
         up = 2 ** (len(self.config['block_out_channels']) - 1)
         out = torch.empty(B, self.config['out_channels'], H * up, W * up, device=self.device)
@@ -167,15 +96,10 @@ class AutoencoderKL:
         B, Cc, H, W = x.shape
         if Cc != self.config['out_channels']:
             raise L.CtxError(f"vae.encode: expected {self.config['out_channels']} image channels, got {Cc}")
-        need = self._lib.ctx_vae_encode_workspace_bytes(self._h, B, H, W)
-        if need < 0:
-            f = 2 ** (len(self.config['block_out_channels']) - 1)
-            raise L.CtxError(f"vae.encode: H, W must be multiples of {f} with (H/{f})*(W/{f}) a multiple of 64 (got {H}x{W})")
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._bind()
-        self._ws_key = None
         f = 2 ** (len(self.config['block_out_channels']) - 1)
+        self._reserve(self._lib.ctx_vae_encode_workspace_bytes(self._h, B, H, W),
+                      f"vae.encode: H, W must be multiples of {f} with (H/{f})*(W/{f}) a multiple of 64 (got {H}x{W})")
+        self._ws_key = None
         Lc = self.config['latent_channels']
         mom = torch.empty(B, 2 * Lc, H // f, W // f, device=self.device)
         L.check(self._lib.ctx_vae_encode(self._h, L.ptr(x, torch.float32, "image"), B, H, W, L.ptr(mom), L.stream()))
@@ -238,15 +162,10 @@ class _VaeEncodeFn(torch.autograd.Function):
         # exception, or the call was an eval on a tensor that happened to require grad): the generation counter makes the stale
         # context's backward fail loudly instead of differentiating through the wrong tape.
         vae._tape_gen = getattr(vae, '_tape_gen', 0) + 1
-        need = vae._lib.ctx_vae_encode_train_workspace_bytes(vae._h, B, H, W)
-        if need < 0:
-            f = 2 ** (len(vae.config['block_out_channels']) - 1)
-            raise L.CtxError(f"vae.encode: H, W must be multiples of {f} with (H/{f})*(W/{f}) a multiple of 64 (got {H}x{W})")
-        if vae._ws.numel() < need:
-            vae._ws = torch.empty(need, dtype=torch.uint8, device=vae.device)
-            vae._bind()
-        vae._ws_key = None
         f = 2 ** (len(vae.config['block_out_channels']) - 1)
+        vae._reserve(vae._lib.ctx_vae_encode_train_workspace_bytes(vae._h, B, H, W),
+                     f"vae.encode: H, W must be multiples of {f} with (H/{f})*(W/{f}) a multiple of 64 (got {H}x{W})")
+        vae._ws_key = None
         mom = torch.empty(B, 2 * vae.config['latent_channels'], H // f, W // f, device=vae.device)
         L.check(vae._lib.ctx_vae_encode_train(vae._h, L.ptr(x, torch.float32, "image"), B, H, W, L.ptr(mom), L.stream()))
         ctx.vae, ctx.shape, ctx.gen = vae, (B, Cc, H, W), vae._tape_gen
@@ -266,7 +185,7 @@ class _VaeEncodeFn(torch.autograd.Function):
             return None, torch.full(ctx.shape, float('nan'), device=vae.device)
         if not (gmax > 0.0):
             return None, torch.zeros(ctx.shape, device=vae.device)
-        gscale = 2.0 ** round(__import__('math').log2(16.0 / gmax))          # fp16 gradients: max |g| scaled to ~16, a power of two
+        gscale = 2.0 ** round(math.log2(16.0 / gmax))          # fp16 gradients: max |g| scaled to ~16, a power of two
         dx = torch.empty(ctx.shape, device=vae.device)
         L.check(vae._lib.ctx_vae_encode_bwd(vae._h, L.ptr(g, torch.float32, "grad_moments"), gscale, L.ptr(dx), L.stream()))
         return None, dx

@@ -81,6 +81,21 @@ def test_vae_param_table_matches_diffusers_naming():
     assert 83e6 < sum(t.numel() for t in r.parameters()) < 84e6                     # AutoencoderKL of SD: 83.65 M parameters
 
 
+def test_engine_layout_is_pinned():
+    """What is layout and not tuning: the fp16 weight-blob sizes of the three engines (every table entry rounded up to 128
+    elements) and the SD2 UNet's launches per forward by kernel class.  Workspace sizes follow the tuned plan table: not pinned."""
+    from contexture_nerf_amd.unet import UNet2DConditionModel, ControlNetModel, SD2_DEPTH
+    from contexture_nerf_amd.vae import AutoencoderKL
+    net = UNet2DConditionModel(SD2_DEPTH, device="cpu", init=False)
+    cn = ControlNetModel(SD2_DEPTH, device="cpu", init=False)
+    vae = AutoencoderKL(device="cpu", init=False)
+    assert net._lib.ctx_unet_weight_bytes(net._h) == 1731858176
+    assert cn._lib.ctx_unet_weight_bytes(cn._h) == 728486912
+    assert vae._lib.ctx_vae_weight_bytes(vae._h) == 236137728
+    fl = net.flops(2, 32, 32, 77)
+    assert [fl[k][0] for k in ('gemm_conv', 'attention', 'other')] == [193, 32, 189]
+
+
 def test_size_queries():
     from contexture_nerf_amd import _lib as L
     lib = L.load()
