@@ -8,11 +8,8 @@
 // single cross-half shuffle, and the exponentiated tile, converted to f16 in place, is already the B
 // operand of the second product O^T = V^T . P^T (no LDS round trip for P).  V arrives pre-transposed
 // ([B, heads, 64, Skv_pad], keys contiguous) so its fragment is two 8-byte LDS reads.
-#include "common.h"
-#include "kernels.h"
-#include <hip/hip_ext.h>
+#include "gemm_common.h"
 #include <math.h>
-#include <stdlib.h>
 
 #define AT_KB 64                // keys per tile
 #define AT_KROW 72              // f16 per K row in LDS (144 B: conflict-free ds_read_b128)
@@ -32,9 +29,6 @@ struct AttnArgs {
 // LDS-DMA variant (default): K and V^T tiles arrive by global_load_lds into a ring of AT_NS stages (1 KiB pieces of
 // 8 rows x 128 B, chunk swizzle c ^ ((row>>1)&7) on the source address and on the fragment reads), prefetch distance
 // AT_NS-1 tiles, one raw s_barrier + counted vmcnt per tile — the same pipeline as k_gemm_pipe.
-__device__ __attribute__((aligned(16))) f16 g_attn_zero[64];
-typedef const __attribute__((address_space(1))) void *agptr_t;
-typedef __attribute__((address_space(3))) void *alptr_t;
 
 
 // One 64-key tile of the online-softmax recurrence for this wave's 32 queries (MASK only for the last, ragged tile).
@@ -194,14 +188,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_attention_dma(Attn
         const int k0 = issued * AT_KB;
 #pragma unroll
         for (int i = 0; i < PI; ++i) {
-            const f16 *src = (k0 + krow[i] < a.Skv) ? kp[i] : g_attn_zero;
-            __builtin_amdgcn_global_load_lds((agptr_t)src, (alptr_t)(Ks + (wave + NW * i) * 512), 16, 0, 0);
+            const f16 *src = (k0 + krow[i] < a.Skv) ? kp[i] : ctx_zero_page;
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Ks + (wave + NW * i) * 512), 16, 0, 0);
             kp[i] += (size_t)AT_KB * a.kv_stride;
         }
 #pragma unroll
         for (int i = 0; i < PI; ++i) {
-            const f16 *src = (k0 + krow[i] < a.Skv) ? vp[i] : g_attn_zero;
-            __builtin_amdgcn_global_load_lds((agptr_t)src, (alptr_t)(Vs + (wave + NW * i) * 512), 16, 0, 0);
+            const f16 *src = (k0 + krow[i] < a.Skv) ? vp[i] : ctx_zero_page;
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Vs + (wave + NW * i) * 512), 16, 0, 0);
             vp[i] += (size_t)AT_KB * a.kv_stride;
         }
         ++issued;
@@ -213,8 +207,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_attention_dma(Attn
         const int k0 = issued * AT_KB;
         const int i = idx < PI ? idx : idx - PI;
         const f16 *&gp = idx < PI ? kp[i] : vp[i];
-        const f16 *src = (k0 + krow[i] < a.Skv) ? gp : g_attn_zero;
-        __builtin_amdgcn_global_load_lds((agptr_t)src, (alptr_t)((idx < PI ? Ks : Vs) + (wave + NW * i) * 512), 16, 0, 0);
+        const f16 *src = (k0 + krow[i] < a.Skv) ? gp : ctx_zero_page;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)((idx < PI ? Ks : Vs) + (wave + NW * i) * 512), 16, 0, 0);
         gp += (size_t)AT_KB * a.kv_stride;
     };
 #pragma unroll
@@ -283,6 +277,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_attention_dma(Attn
     }
 }
 
+template <int NS, int NW, bool SPREAD = true>
+static void attn_launch(const AttnArgs &a, int B, bool report, hipStream_t s)
+{
+    constexpr auto kern = k_attention_dma<NS, NW, SPREAD>;
+    if (report) {
+        int nb = 0;
+        hipFuncAttributes fa;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 64 * NW, 0);
+        (void)hipFuncGetAttributes(&fa, (const void *)kern);
+        fprintf(stderr, "[ctx] attention: %d blocks/CU by the occupancy API, %d VGPRs, %zu B static LDS\n", nb, fa.numRegs, fa.sharedSizeBytes);
+    }
+    ctx_launch<kern>(1, dim3(cdiv(a.Sq, 32 * NW), a.heads, B), dim3(64 * NW), 0, s, a);
+}
+
 int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int q_stride,
                        int kv_stride, float scale, f16 *O, int o_stride, hipStream_t s)
 {
@@ -293,34 +301,22 @@ int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, 
     static float lazy = -1.f;           // CTX_ATTN_LAZY: threshold in log2 units (default 8 = a factor 256; 0 = rescale on every change)
     if (lazy < 0.f) { const char *e = getenv("CTX_ATTN_LAZY"); lazy = e ? (float)atof(e) : 8.0f; if (!(lazy >= 0.f && lazy <= 12.f)) lazy = 8.0f; }
     a.lazy = lazy;
-    static int ns = -1, nw8 = -1;
-    if (ns < 0) { const char *e = getenv("CTX_ATTN_NS"); ns = e ? atoi(e) : 3; }
+    static const int ns = ctx_env_int("CTX_ATTN_NS", 3);
     // 8-wave workgroups (two per CU at 128 VGPRs) measured against three 4-wave ones (148 VGPRs): 72 vs 77 us at 2304 tokens
     // x 10 heads, 411 vs 371 us at 9216 x 5 — so only the mid-size self-attention takes them (CTX_ATTN_NW8: 0 never, 1 always)
-    if (nw8 < 0) { const char *e = getenv("CTX_ATTN_NW8"); nw8 = e ? atoi(e) : -1; }
+    static const int nw8 = ctx_env_int("CTX_ATTN_NW8", -1);
     const bool w8 = nw8 == 1 || (nw8 < 0 && Sq >= 1024 && Sq < 4096 && Skv >= 1024);
-    static int spread = -1;             // CTX_ATTN_SPREAD=0: all DMA pieces of a tile right after the barrier (the A/B switch)
-    if (spread < 0) { const char *e = getenv("CTX_ATTN_SPREAD"); spread = e ? atoi(e) : 1; }
-    auto kern = w8 ? (ns == 2 ? k_attention_dma<2, 8> : (ns == 4 ? k_attention_dma<4, 8> : (spread ? k_attention_dma<3, 8> : k_attention_dma<3, 8, false>)))
-                   : (ns == 2 ? k_attention_dma<2, 4> : (ns == 4 ? k_attention_dma<4, 4> : (spread ? k_attention_dma<3, 4> : k_attention_dma<3, 4, false>)));
-    const int nthr = w8 ? 512 : 256, qpw = w8 ? 256 : 128;
-    static int dbg = -1;
-    if (dbg < 0) {
-        const char *e = getenv("CTX_ATTN_DEBUG"); dbg = e ? atoi(e) : 0;
-        if (dbg) {
-            int nb = 0;
-            hipFuncAttributes fa;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, nthr, 0);
-            (void)hipFuncGetAttributes(&fa, (const void *)kern);
-            fprintf(stderr, "[ctx] attention: %d blocks/CU by the occupancy API, %d VGPRs, %zu B static LDS\n", nb, fa.numRegs, fa.sharedSizeBytes);
-        }
+    static const int spread = ctx_env_int("CTX_ATTN_SPREAD", 1);    // 0: all DMA pieces of a tile right after the barrier (the A/B switch)
+    static int dbg = -1;                                            // CTX_ATTN_DEBUG: the first launch reports its kernel's occupancy
+    bool report = false;
+    if (dbg < 0) { dbg = ctx_env_int("CTX_ATTN_DEBUG", 0); report = dbg != 0; }
+    if (w8) {
+        if (ns == 2) attn_launch<2, 8>(a, B, report, s); else if (ns == 4) attn_launch<4, 8>(a, B, report, s);
+        else if (spread) attn_launch<3, 8>(a, B, report, s); else attn_launch<3, 8, false>(a, B, report, s);
+    } else {
+        if (ns == 2) attn_launch<2, 4>(a, B, report, s); else if (ns == 4) attn_launch<4, 4>(a, B, report, s);
+        else if (spread) attn_launch<3, 4>(a, B, report, s); else attn_launch<3, 4, false>(a, B, report, s);
     }
-    if (ctx_prof_on()) {
-        hipEvent_t e0, e1;
-        ctx_prof_events(1, &e0, &e1);
-        hipExtLaunchKernelGGL(kern, dim3(cdiv(Sq, qpw), heads, B), dim3(nthr), 0, s, e0, e1, 0, a);
-    } else
-        hipLaunchKernelGGL(kern, dim3(cdiv(Sq, qpw), heads, B), dim3(nthr), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         ctx_set_error("attention launch failed: %s", hipGetErrorString(e));

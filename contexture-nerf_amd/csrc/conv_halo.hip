@@ -18,23 +18,10 @@
 // wave groups one barrier apart (as gemm8.hip), counted vmcnt; every wave
 // issues the same number of DMA pieces per stage (one slot of the NEXT chunk's halo + its share of the weight stage two
 // ahead; slots past the end go to the scratch from a zero page) so one immediate vmcnt count is right for all waves.
-#include "common.h"
-#include "kernels.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
-
-typedef const __attribute__((address_space(1))) void *ch_gptr_t;
-typedef __attribute__((address_space(3))) void *ch_lptr_t;
-__device__ __attribute__((aligned(128))) f16 ch_zero[64];
+#include "gemm_common.h"
 
 #define CH_HP 328                 // halo rows per buffer: 18 x 18 = 324 pixels, padded to 41 pieces of 8
 #define CH_XPIECES 41
-
-__device__ __forceinline__ int ch_xcd_remap(int bid, int nwg)
-{
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 template <int NI>
 __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
@@ -55,7 +42,7 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
 
     const int pw = a.W >> 4, ph = a.H >> 4;                      // patches per row / column
     const int ntiles = a.ntm * a.ntn;
-    const int lin = ch_xcd_remap(blockIdx.x, ntiles * a.splitk);
+    const int lin = xcd_remap(blockIdx.x, ntiles * a.splitk);
     const int slice = lin / ntiles, bid = lin - slice * ntiles;
     const int tile_n = bid % a.ntn, tile_m = bid / a.ntn;
     const int b = tile_m / (pw * ph), pr = tile_m - b * (pw * ph);
@@ -86,9 +73,9 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
         const int hy = hp / 18, hx = hp - hy * 18;
         const int y = py0 + hy - 1, x = px0 + hx - 1;
         const bool ok = xs < CH_XPIECES && hp < 324 && c < cbeg + nch && y >= 0 && y < a.H && x >= 0 && x < a.W;
-        const f16 *src = ok ? xbase + ((size_t)y * a.W + x) * a.Cin + c * 64 + ((pc ^ ((hp >> 1) & 7)) * 8) : ch_zero;
+        const f16 *src = ok ? xbase + ((size_t)y * a.W + x) * a.Cin + c * 64 + ((pc ^ ((hp >> 1) & 7)) * 8) : ctx_zero_page;
         f16 *dst = (xs < CH_XPIECES && c < cbeg + nch) ? halo + hb * HALO + xs * 512 : scratch + wave * 512;
-        __builtin_amdgcn_global_load_lds((ch_gptr_t)src, (ch_lptr_t)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
     };
     // issue the weight pieces of stage g (chunk cbeg + g / 9, tap g % 9) into ring slot g % 4
     auto issue_w = [&](int g) {
@@ -97,9 +84,9 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
         const size_t off = (size_t)t * a.Cin + (size_t)c * 64;
 #pragma unroll
         for (int i = 0; i < WP; ++i) {
-            const f16 *src = (live && wok[i]) ? wp[i] + off : ch_zero;
+            const f16 *src = (live && wok[i]) ? wp[i] + off : ctx_zero_page;
             f16 *dst = live ? wring + (g & 3) * WST + (wave + 8 * i) * 512 : scratch + wave * 512;
-            __builtin_amdgcn_global_load_lds((ch_gptr_t)src, (ch_lptr_t)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
         }
     };
 
@@ -187,10 +174,7 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
 #pragma unroll
             for (int j = 0; j < NI; ++j)
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int nn = nw + j * 32 + 8 * g4 + 4 * h;
-                    if (nn < a.N) *(f32x4 *)(pb + nn) = (f32x4){acc[mi][j][4 * g4], acc[mi][j][4 * g4 + 1], acc[mi][j][4 * g4 + 2], acc[mi][j][4 * g4 + 3]};
-                }
+                for (int g4 = 0; g4 < 4; ++g4) store_part4(a, pb, nw + j * 32 + 8 * g4 + 4 * h, acc4(acc[mi][j], g4));
             continue;
         }
         const int bidx = a.rowbias ? (int)(m / a.rows_per_batch) : 0;
@@ -200,28 +184,9 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int nn = nw + j * 32 + 8 * g4 + 4 * h;
                 if (nn >= a.N) continue;
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[mi][j][4 * g4 + e];
-                if (a.bias) {
-                    f16x4 bb = *(const f16x4 *)(a.bias + nn);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)bb[e];
-                }
-                if (a.rowbias) {
-                    f16x4 bb = *(const f16x4 *)(a.rowbias + (size_t)bidx * a.ldrb + nn);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)bb[e];
-                }
-                if (a.residual) {
-                    f16x4 bb = *(const f16x4 *)(a.residual + m * a.ldr + nn);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)bb[e];
-                }
-                f16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (f16)v[e];
-                *(f16x4 *)(a.out + m * a.ldc + nn) = o;
+                f32x4 v = acc4(acc[mi][j], g4);
+                if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + nn));
+                store4(a, v, m, bidx, nn);
             }
     }
 }
@@ -238,19 +203,7 @@ int ctx_conv_halo_try(GemmArgs &a, int ni, hipStream_t s)
     if (S > a.Cin / 64) return 0;
     a.splitk = S;
     const size_t lds = (size_t)(2 * CH_HP * 64 + 4 * BN * 64 + 8 * 512) * sizeof(f16);
-    static bool attr[2] = {false, false};
-    auto go = [&](auto kern, int which) {
-        if (!attr[which]) {
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr[which] = true;
-        }
-        if (ctx_prof_on()) {
-            hipEvent_t e0, e1;
-            ctx_prof_events(0, &e0, &e1);
-            hipExtLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * S), dim3(512), lds, s, e0, e1, 0, a);
-        } else
-            hipLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * S), dim3(512), lds, s, a);
-    };
-    if (ni == 2) go(k_conv_halo<2>, 0); else go(k_conv_halo<1>, 1);
+    const dim3 grid(a.ntm * a.ntn * S);
+    if (ni == 2) ctx_launch<k_conv_halo<2>>(0, grid, dim3(512), lds, s, a); else ctx_launch<k_conv_halo<1>>(0, grid, dim3(512), lds, s, a);
     return 1;
 }

@@ -14,27 +14,7 @@
 // byte (big tiles) against waves that issue (small problems want 4-8 waves even on a 64x64 tile).  The conv variant
 // only changes the activation address generator (im2col on the fly, NHWC, zero padding by pointing at a zero page,
 // optional fused nearest x2 upsample and stride 2).  The large layers go to gemm8.hip (256x256, 8 staggered waves).
-#include "common.h"
-#include "kernels.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg)
-{
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-// exact-GELU (erf form) with a branch-free erf: Abramowitz-Stegun 7.1.26, |abs err| <= 1.5e-7 (far below fp16 resolution)
-__device__ __forceinline__ float fast_erf(float x)
-{
-    float ax = __builtin_fabsf(x);
-    float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * ax);
-    float p = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    float e = 1.0f - p * __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
-    return __builtin_copysignf(e, x);
-}
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752f)); }
+#include "gemm_common.h"
 
 // Direct epilogue (GEGLU, or when strides are not 16-byte friendly): lane owns row m, registers walk n.
 template <int MI, int NI>
@@ -58,7 +38,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[M
                     for (int j = 0; j < 4; ++j) {
                         float xv = acc[mi][0][4 * g + j], gv = acc[mi][1][4 * g + j];
                         if (a.bias) { xv += (float)a.bias[nn + j]; gv += (float)a.bias[nn + 32 + j]; }
-                        o[j] = (f16)(xv * gelu_erf(gv));
+                        o[j] = geglu(xv, gv);
                     }
                     *(f16x4 *)(a.out + (size_t)m * a.ldc + fbase + 8 * g + 4 * h) = o;
                 }
@@ -70,38 +50,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[M
                 for (int g = 0; g < 4; ++g) {
                     int nn = nw + ni * 32 + 8 * g + 4 * h;
                     if (nn >= a.N) continue;
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = acc[mi][ni][4 * g + j];
-                    if (a.bias) {
-                        f16x4 b = *(const f16x4 *)(a.bias + nn);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += (float)b[j];
-                    }
-                    if (a.rowbias) {
-                        f16x4 b = *(const f16x4 *)(a.rowbias + (size_t)bidx * a.ldrb + nn);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += (float)b[j];
-                    }
-                    if (a.residual) {
-                        if (a.res32) {
-                            f32x4 b = *(const f32x4 *)((const float *)a.residual + (size_t)m * a.ldr + nn);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] += b[j];
-                        } else {
-                            f16x4 b = *(const f16x4 *)(a.residual + (size_t)m * a.ldr + nn);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] += (float)b[j];
-                        }
-                    }
-                    if (a.out32) {
-                        *(f32x4 *)((float *)a.out + (size_t)m * a.ldc + nn) = (f32x4){v[0], v[1], v[2], v[3]};
-                    } else {
-                        f16x4 o;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) o[j] = (f16)v[j];
-                        *(f16x4 *)(a.out + (size_t)m * a.ldc + nn) = o;
-                    }
+                    f32x4 v = acc4(acc[mi][ni], g);
+                    if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + nn));
+                    store4<true>(a, v, m, bidx, nn);
                 }
         }
     }
@@ -128,10 +79,8 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v = {acc[mi][ni][4 * g], acc[mi][ni][4 * g + 1], acc[mi][ni][4 * g + 2], acc[mi][ni][4 * g + 3]};
-                *(f32x4 *)(stage + r * RS + ni * 32 + 8 * g + 4 * h) = v;
-            }
+            for (int g = 0; g < 4; ++g)
+                *(f32x4 *)(stage + r * RS + ni * 32 + 8 * g + 4 * h) = acc4(acc[mi][ni], g);
 #pragma unroll
         for (int p = 0; p < 32 / RPP; ++p) {
             const int row = RPP * p + prow;
@@ -139,43 +88,12 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (
             f32x4 v0 = *(const f32x4 *)(stage + row * RS + c8), v1 = *(const f32x4 *)(stage + row * RS + c8 + 4);
             if (m < a.M && n < a.N) {
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += (float)bs[j];
-                if (a.rowbias) {
-                    f16x8 b = *(const f16x8 *)(a.rowbias + (size_t)(m / a.rows_per_batch) * a.ldrb + n);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] += (float)b[j];
-                }
-                if (a.residual) {
-                    if (a.res32) {
-                        const float *rp = (const float *)a.residual + (size_t)m * a.ldr + n;
-                        f32x4 b0 = *(const f32x4 *)rp, b1 = *(const f32x4 *)(rp + 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
-                    } else {
-                        f16x8 b = *(const f16x8 *)(a.residual + (size_t)m * a.ldr + n);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] += (float)b[j];
-                    }
-                }
-                if (a.out32) {
-                    float *op = (float *)a.out + (size_t)m * a.ldc + n;
-                    *(f32x4 *)op = (f32x4){v[0], v[1], v[2], v[3]}; *(f32x4 *)(op + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-                } else {
-                    f16x8 o;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = (f16)v[j];
-                    *(f16x8 *)(a.out + (size_t)m * a.ldc + n) = o;
-                }
+                add8(v, bs);
+                store8<true>(a, v, m, n);
             }
         }
     }
 }
-
-__device__ __attribute__((aligned(16))) f16 g_zero_page[64];
-
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
 
 // ------------------------------------------------------------------------------------------------
 // Pipelined LDS-DMA variant: K-stages of 32, ring of NS stages, prefetch distance NS-1, ONE raw s_barrier per
@@ -204,39 +122,28 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     // 1-D grid of tiles x K-slices, slice-major, cut into 8 contiguous runs (one per XCD: blocks b and b+8 share an L2):
     // an XCD then streams ~1/8 of the K range of both operands.  Inside a slice the tile order walks the operand that is
     // re-read most (mfast: consecutive blocks share the weight panel; else the activation panel).
-    const int ntiles = a.ntm * a.ntn;
-    const int lin = xcd_remap(blockIdx.x, ntiles * a.splitk);
-    const int slice = lin / ntiles, bid = lin - slice * ntiles;
-    const int tile_n = a.mfast ? bid / a.ntm : bid % a.ntn, tile_m = a.mfast ? bid % a.ntm : bid / a.ntn;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const GemmTile t = gemm_tile(a, blockIdx.x, PKT, BM, BN);
+    const int slice = t.slice, tile_m = t.tile_m, tile_n = t.tile_n, m0 = t.m0, n0 = t.n0, kbeg = t.kbeg, nk = t.nk;
     const int lr = lane / LPR, pc = lane % LPR;        // row within the piece's 16 rows, physical 16-B chunk
-
-    const int nk_all = a.K / PKT;
-    const int kbeg = (int)((long)nk_all * slice / a.splitk);
-    const int nk = (int)((long)nk_all * (slice + 1) / a.splitk) - kbeg;
 
     // ---- issue-side state: one running source pointer per DMA piece (advanced by a fixed step per stage; rows that
     // are out of range / conv padding point at a zero page with step 0), so a stage costs G loads + G pointer adds
     const f16 *xp[XI], *wp[WI];
     int xst[XI], wst[WI];
-    int xoff[XI], xoy[XI], xox[XI], xlc[XI];
+    int xoff[XI], xoy[XI], xox[XI];
     bool xok[XI];
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
         int row = RP * (wave + NW * i) + lr;
         int m = m0 + row;
-        xlc[i] = (pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8;
+        const int lc = (pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8;
         xok[i] = m < a.M;
         if (CONV) {
-            int hw = a.Ho * a.Wo;
-            int b = m / hw, p = m - b * hw;
-            int oy = p / a.Wo, ox = p - oy * a.Wo;
-            xoy[i] = oy * a.stride; xox[i] = ox * a.stride;
-            xoff[i] = b * a.H * a.W * a.Cin;
-            xp[i] = g_zero_page; xst[i] = 0;
+            conv_pixel(a, m, lc, xoy[i], xox[i], xoff[i]);
+            xp[i] = ctx_zero_page; xst[i] = 0;
         } else {
             xoff[i] = 0; xoy[i] = 0; xox[i] = 0;
-            xp[i] = xok[i] ? a.X + (size_t)m * a.K + kbeg * PKT + xlc[i] : g_zero_page;
+            xp[i] = xok[i] ? a.X + (size_t)m * a.K + kbeg * PKT + lc : ctx_zero_page;
             xst[i] = xok[i] ? PKT : 0;
         }
     }
@@ -244,7 +151,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     for (int i = 0; i < WI; ++i) {
         int row = RP * (wave + NW * i) + lr;
         bool ok = (n0 + row) < a.N;
-        wp[i] = ok ? a.Wt + (size_t)(n0 + row) * a.K + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : g_zero_page;
+        wp[i] = ok ? a.Wt + (size_t)(n0 + row) * a.K + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : ctx_zero_page;
         wst[i] = ok ? PKT : 0;
     }
     // K rotation: workgroups that stream the same weight rows (same tile_n) or the same activation rows (same tile_m)
@@ -260,17 +167,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     for (int i = 0; i < WI; ++i) wp[i] += (wst[i] ? rot * PKT : 0);
 
     auto retap = [&]() {                            // CONV: new 3x3 tap -> recompute the activation pointers
-        int tap = k_issue / a.Cin, c0 = k_issue - tap * a.Cin;
-        int dy = tap / 3 - 1 + a.poff, dx = tap % 3 - 1 + a.poff;
-        int Hv = a.H << a.ups, Wv = a.W << a.ups;
+        const ConvTap tap = conv_tap(a, k_issue);
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
-            int iy = xoy[i] + dy, ix = xox[i] + dx;
-            bool ok = xok[i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv && !(a.zins && ((iy | ix) & 1));
-            xp[i] = ok ? a.X + xoff[i] + (((iy >> a.ups) * a.W + (ix >> a.ups)) * a.Cin) + c0 + xlc[i] : g_zero_page;
+            bool ok = xok[i];
+            xp[i] = conv_tap_src<true>(a, tap, xoy[i], xox[i], xoff[i], ok);
             xst[i] = ok ? PKT : 0;
         }
-        tap_left = (a.Cin - c0) / PKT;
+        tap_left = (a.Cin - tap.c0) / PKT;
     };
     auto issue = [&](int buf) {
         if (k_issue == k_hi) {                       // wrap of the rotated K range
@@ -386,12 +290,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    int nn = n0 + wn * 32 * NI + ni * 32 + 8 * g + 4 * h;
-                    if (nn >= a.N) continue;
-                    f32x4 v = {acc[mi][ni][4 * g], acc[mi][ni][4 * g + 1], acc[mi][ni][4 * g + 2], acc[mi][ni][4 * g + 3]};
-                    *(f32x4 *)(pb + (size_t)m * a.N + nn) = v;
-                }
+                for (int g = 0; g < 4; ++g)
+                    store_part4(a, pb + (size_t)m * a.N, n0 + wn * 32 * NI + ni * 32 + 8 * g + 4 * h, acc4(acc[mi][ni], g));
         }
         return;
     }
@@ -416,19 +316,8 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(GemmArgs a)
             f32x4 p = *(const f32x4 *)(a.part + sidx * MN + (size_t)m * a.N + nn);
             v += p;
         }
-        if (a.bias) { f16x4 b = *(const f16x4 *)(a.bias + nn); for (int j = 0; j < 4; ++j) v[j] += (float)b[j]; }
-        if (a.rowbias) {
-            f16x4 b = *(const f16x4 *)(a.rowbias + (size_t)(m / a.rows_per_batch) * a.ldrb + nn);
-            for (int j = 0; j < 4; ++j) v[j] += (float)b[j];
-        }
-        if (a.residual) {
-            if (a.res32) { f32x4 b = *(const f32x4 *)((const float *)a.residual + (size_t)m * a.ldr + nn); v += b; }
-            else { f16x4 b = *(const f16x4 *)(a.residual + (size_t)m * a.ldr + nn); for (int j = 0; j < 4; ++j) v[j] += (float)b[j]; }
-        }
-        if (a.out32) { *(f32x4 *)((float *)a.out + (size_t)m * a.ldc + nn) = v; continue; }
-        f16x4 o;
-        for (int j = 0; j < 4; ++j) o[j] = (f16)v[j];
-        *(f16x4 *)(a.out + (size_t)m * a.ldc + nn) = o;
+        if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + nn));
+        store4<true>(a, v, m, a.rowbias ? m / a.rows_per_batch : 0, nn);
     }
 }
 
@@ -452,52 +341,30 @@ static void launch_gemm(GemmArgs &a, hipStream_t s)
     a.ntm = cdiv(a.M, BM);
     a.ntn = cdiv(a.N, BN);
     if (a.splitk < 1 || !a.part) a.splitk = 1;
-    static int mfast = -2;
-    if (mfast == -2) { const char *e = getenv("CTX_GEMM_MFAST"); mfast = e ? atoi(e) : -1; }
-    // unique operand bytes: weights N*K vs activations M*K (conv: M*Cin, the 9 taps re-read the same pixels)
-    const double wbytes = (double)a.N * a.K, xbytes = (double)a.M * (CONV ? a.Cin : a.K);
-    a.mfast = mfast >= 0 ? mfast : (wbytes > xbytes ? 1 : 0);
-    static int stg = -1;
-    if (stg < 0) { const char *e = getenv("CTX_GEMM_STAGE_EPI"); stg = e ? atoi(e) : 1; }
+    static const int mfast = ctx_env_int("CTX_GEMM_MFAST", -1);
+    a.mfast = mfast >= 0 ? mfast : ctx_gemm_mfast(a, CONV);
+    static const int stg = ctx_env_int("CTX_GEMM_STAGE_EPI", 1);
     a.stage_epi = stg && (a.ldc % 8 == 0) && (!a.residual || a.ldr % 8 == 0) && (!a.rowbias || a.ldrb % 8 == 0) &&
                   (size_t)WM * WN * 32 * (32 * NI + 4) * sizeof(float) <= 160 * 1024;       // the per-wave fp32 patch must fit the LDS
-    static int steady = -1;
-    if (steady < 0) { const char *e = getenv("CTX_GEMM_STEADY"); steady = e ? atoi(e) : 1; }
+    static const int steady = ctx_env_int("CTX_GEMM_STEADY", 1);
     a.pk = PKT; a.krot = steady ? 0 : 2;                 // krot = 2: no rotation, general K loop only (A/B switch of the steady loop)
     constexpr int NT = 64 * WM * WN;
     constexpr size_t ring = (size_t)NS * (BM + BN) * PKT * sizeof(f16);
     constexpr size_t patch = (size_t)WM * WN * 32 * (32 * NI + 4) * sizeof(float);
     constexpr size_t lds = (ring > patch || patch > 160 * 1024) ? ring : patch;
-    auto kern = k_gemm_pipe<WM, WN, MI, NI, CONV, NS, PKT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done = true;
-    }
-    if (ctx_prof_on()) {
-        hipEvent_t e0, e1;
-        ctx_prof_events(0, &e0, &e1);
-        hipExtLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * a.splitk), dim3(NT), lds, s, e0, e1, 0, a);
-    } else
-        hipLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * a.splitk), dim3(NT), lds, s, a);
+    ctx_launch<k_gemm_pipe<WM, WN, MI, NI, CONV, NS, PKT>>(0, dim3(a.ntm * a.ntn * a.splitk), dim3(NT), lds, s, a);
 }
 
 static void launch_reduce(GemmArgs &a, hipStream_t s)
 {
     size_t total = (size_t)a.M * (a.N / 4);
     unsigned nb = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (ctx_prof_on()) {
-        hipEvent_t e0, e1;
-        ctx_prof_events(0, &e0, &e1);
-        hipExtLaunchKernelGGL(k_splitk_reduce, dim3(nb), dim3(256), 0, s, e0, e1, 0, a);
-    } else
-        hipLaunchKernelGGL(k_splitk_reduce, dim3(nb), dim3(256), 0, s, a);
+    ctx_launch<k_splitk_reduce>(0, dim3(nb), dim3(256), 0, s, a);
 }
 
 int ctx_gemm_pick_split(int M, int N, int K, int epi)
 {
-    static int en = -1;
-    if (en < 0) { const char *e = getenv("CTX_SPLITK"); en = e ? atoi(e) : 1; }
+    static const int en = ctx_env_int("CTX_SPLITK", 1);
     if (!en || epi != 0 || N % 4) return 1;
     bool wide = (N % 128 == 0);
     int tiles = wide ? cdiv(M, 128) * cdiv(N, 128) : cdiv(M, 256) * cdiv(N, 64);
@@ -514,8 +381,7 @@ int ctx_gemm_pick_split(int M, int N, int K, int epi)
 void ctx_gemm_plan(GemmArgs &a, bool conv)
 {
     a.tile = -1; a.use8 = -1;
-    static int use_table = -1;
-    if (use_table < 0) { const char *e = getenv("CTX_GEMM_TUNED"); use_table = e ? atoi(e) : 1; }
+    static const int use_table = ctx_env_int("CTX_GEMM_TUNED", 1);
     if (use_table) {
         const int flags = conv ? ((a.stride == 2 ? 1 : 0) | (a.ups ? 2 : 0)) : 0;
         for (const TunedGemm &t : g_tuned)
@@ -530,7 +396,7 @@ void ctx_gemm_plan(GemmArgs &a, bool conv)
         // Large plain-epilogue problems (other lockstep batch sizes than the tuned 2 and 12, other latent sizes): the 144 x 160 kernel
         // family of gemm144.hip where it has enough tiles to fill the chip and <= 10 % masked waste along N — the 288-row form from ~512
         // tiles on, the software-pipelined 144-row form from ~220 (what the plan search chose for such shapes at batch 2 / 12).
-        static const int heur144 = [] { const char *e = getenv("CTX_GEMM_HEUR144"); return e ? atoi(e) : 1; }();    // 0: the r2 rules only (A/B)
+        static const int heur144 = ctx_env_int("CTX_GEMM_HEUR144", 1);    // 0: the r2 rules only (A/B)
         if (heur144 && a.epi == 0 && a.N % 8 == 0 && !a.zins && !a.res32 && !a.out32) {
             const int nt = cdiv(a.N, 160);
             const double fill = (double)a.N / (160.0 * nt);
@@ -568,29 +434,24 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
     if (only_pipe) a.use8 = 0;
     const int want8 = only_pipe ? 0 : (g_force_gemm8 >= 0 ? g_force_gemm8 : a.use8);          // -1: gemm8's own heuristic
     const int want_tile = g_force_tile >= 0 ? g_force_tile : (g_force_gemm8 >= 0 ? -1 : a.tile);
-    if (want_tile < 0 && want8 >= 4 && want8 <= 8 && ctx_gemm144_try(a, conv, want8 - 4, s)) {
-        if (a.splitk > 1) launch_reduce(a, s);
-    } else if (want_tile < 0 && conv && (want8 == 2 || want8 == 3) && ctx_conv_halo_try(a, want8 == 2 ? 2 : 1, s)) {
-        if (a.splitk > 1) launch_reduce(a, s);
-    } else if (want_tile < 0 && want8 != 0 && want8 < 2 && ctx_gemm8_try(a, conv, want8 == 1, s)) {
-        if (a.splitk > 1) launch_reduce(a, s);
-    } else {
-        static int big = -1;
-        if (big < 0) { const char *e = getenv("CTX_GEMM_BIG"); big = e ? atoi(e) : 1; }
+    // the kernels of the other files first (each *_try launches and returns 1 when the problem suits it), else this file's tiles
+    const bool launched = want_tile < 0 && ((want8 >= 4 && want8 <= 8 && ctx_gemm144_try(a, conv, want8 - 4, s)) ||
+                                            (conv && (want8 == 2 || want8 == 3) && ctx_conv_halo_try(a, want8 == 2 ? 2 : 1, s)) ||
+                                            (want8 != 0 && want8 < 2 && ctx_gemm8_try(a, conv, want8 == 1, s)));
+    if (!launched) {
+        static const int big = ctx_env_int("CTX_GEMM_BIG", 1);
         const int S = a.splitk > 1 && a.part ? a.splitk : 1;
         auto wgs = [&](int bm, int bn) { return cdiv(a.M, bm) * cdiv(a.N, bn) * S; };
         const bool n128 = (a.N % 128 == 0);
         int pick;
-        static int bigk = -1;
-        if (bigk < 0) { const char *e = getenv("CTX_GEMM_BIGK"); bigk = e ? atoi(e) : 1024; }
+        static const int bigk = ctx_env_int("CTX_GEMM_BIGK", 1024);
         if (big && a.M >= 8192 && a.N >= 256 && a.K >= bigk) pick = 0;                 // 256x128, 8 waves
         else if (n128 && wgs(128, 128) >= 384) pick = 1;                               // 128x128
         else if (!n128 && wgs(256, 64) >= 384) pick = 2;                               // 256x64
         else if (wgs(128, 64) >= 320) pick = 3;                                        // 128x64, 2 waves
         else if (S > 1) pick = n128 ? 1 : 2;                                           // split-K already spreads it
         else pick = 4;                                                                 // 64x64, 1 wave
-        static int force = -2;
-        if (force == -2) { const char *e = getenv("CTX_GEMM_TILE"); force = e ? atoi(e) : -1; }
+        static const int force = ctx_env_int("CTX_GEMM_TILE", -1);
         if (force >= 0) pick = force;
         if (want_tile >= 0) pick = want_tile;
         if (a.epi == 1 && (pick == 5 || pick == 6 || pick == 9 || pick == 11 || pick == 13 || pick == 15 || pick == 17 || pick == 19 || pick == 21 || pick == 23 || pick == 26 || pick == 27)) pick = 1;   // GEGLU needs 64-wide wave tiles
@@ -635,8 +496,8 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
 #undef CTX_LAUNCH64
         }
 #undef CTX_LAUNCH
-        if (a.splitk > 1) launch_reduce(a, s);
     }
+    if (a.splitk > 1) launch_reduce(a, s);                                   // every kernel above leaves fp32 partials then
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         ctx_set_error("gemm launch failed: %s", hipGetErrorString(e));

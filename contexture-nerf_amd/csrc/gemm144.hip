@@ -16,25 +16,12 @@
 // round-robin to the waves: a wave has SL or SL - 1 of them and waits with its own immediate vmcnt count), ring of 3 stages,
 // one raw s_barrier per stage.
 // LDS image and fragment reads as gemm8.hip (16-byte chunk index XORed with (row>>1)&7 on the DMA source and on the read).
-#include "common.h"
-#include "kernels.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
+#include "gemm_common.h"
 #include <type_traits>
-
-typedef const __attribute__((address_space(1))) void *g144_gptr_t;
-typedef __attribute__((address_space(3))) void *g144_lptr_t;
-__device__ __attribute__((aligned(128))) f16 g144_zero[64];
 
 #define G144_BM 144
 #define G144_BN 160
 #define G144_STAGE ((G144_BM + G144_BN) * 64)      // f16 per stage
-
-__device__ __forceinline__ int g144_xcd_remap(int bid, int nwg)
-{
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 // UPS: the convolution has the fused nearest x2 upsample (generic per-tap address arithmetic); without it a tap is one scalar
 // offset from the lane's centre-tap pointer and a bit of a 9-bit in-bounds mask
@@ -55,14 +42,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     const int wm = wave / WN, wn = wave % WN;
     const int r16 = lane & 15, kg = lane >> 4;
 
-    const int ntiles = a.ntm * a.ntn;
-    const int lin = g144_xcd_remap(blockIdx.x, ntiles * a.splitk);
-    const int slice = lin / ntiles, bid = lin - slice * ntiles;
-    const int tile_n = a.mfast ? bid / a.ntm : bid % a.ntn, tile_m = a.mfast ? bid % a.ntm : bid / a.ntn;
-    const int m0 = tile_m * BM, n0 = tile_n * G144_BN;
-    const int nk_all = a.K / 64;
-    const int kbeg = (int)((long)nk_all * slice / a.splitk);
-    const int nk = (int)((long)nk_all * (slice + 1) / a.splitk) - kbeg;
+    const GemmTile tl = gemm_tile(a, blockIdx.x, 64, BM, G144_BN);
+    const int slice = tl.slice, m0 = tl.m0, n0 = tl.n0, kbeg = tl.kbeg, nk = tl.nk;
 
     // ---- DMA state: piece p = wave + NW i of the stage image; p < 18 activation rows 8p.., else weight rows 8(p-18).. -----
     const int prow = lane >> 3, pc = lane & 7;
@@ -70,7 +51,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     const f16 *pp[SL], *xcen[SL];
     int pst[SL], xoff[SL], xoy[SL], xox[SL], xlc[SL], xval[SL];
     bool xok[SL];
-    const f16 *const zp = g144_zero;
+    const f16 *const zp = ctx_zero_page;
     const bool full = wave + NW * (SL - 1) < NP;                    // this wave uses its last slot
 #pragma unroll
     for (int i = 0; i < SL; ++i) {
@@ -83,12 +64,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
             const int m = m0 + s;
             xok[i] = m < a.M;
             if (CONV) {
-                const int hw = a.Ho * a.Wo;
-                const int mm = xok[i] ? m : 0;
-                const int b = mm / hw, q = mm - b * hw;
-                const int oy = q / a.Wo, ox = q - oy * a.Wo;
-                xoy[i] = oy * a.stride; xox[i] = ox * a.stride;
-                xoff[i] = b * a.H * a.W * a.Cin + xlc[i];
+                conv_pixel(a, xok[i] ? m : 0, xlc[i], xoy[i], xox[i], xoff[i]);
                 pp[i] = zp; pst[i] = 0;
                 if (FAST) {
                     xcen[i] = a.X + (size_t)xoff[i] + (size_t)(xoy[i] * a.W + xox[i]) * a.Cin;
@@ -101,13 +77,13 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
                     xval[i] = v;
                 }
             } else {
-                pp[i] = xok[i] ? a.X + (size_t)m * a.K + (size_t)kbeg * 64 + xlc[i] : g144_zero;
+                pp[i] = xok[i] ? a.X + (size_t)m * a.K + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
                 pst[i] = xok[i] ? 64 : 0;
             }
         } else {
             const bool ok = live && (n0 + s) < a.N;
             xok[i] = ok;
-            pp[i] = ok ? a.Wt + (size_t)(n0 + s) * a.K + (size_t)kbeg * 64 + xlc[i] : g144_zero;
+            pp[i] = ok ? a.Wt + (size_t)(n0 + s) * a.K + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
             pst[i] = ok ? 64 : 0;
         }
     }
@@ -128,18 +104,15 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
             tap_left = (a.Cin - cur_c0) >> 6;
             return;
         }
-        const int tap = k_issue / a.Cin, c0 = k_issue - tap * a.Cin;
-        const int dy = tap / 3 - 1 + a.poff, dx = tap % 3 - 1 + a.poff;
-        const int Hv = a.H << a.ups, Wv = a.W << a.ups;
+        const ConvTap tap = conv_tap(a, k_issue);
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             if (wave + NW * i >= NPX) continue;
-            const int iy = xoy[i] + dy, ix = xox[i] + dx;
-            const bool ok = xok[i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
-            pp[i] = ok ? a.X + xoff[i] + (((iy >> a.ups) * a.W + (ix >> a.ups)) * a.Cin) + c0 : zp;
+            bool ok = xok[i];
+            pp[i] = conv_tap_src(a, tap, xoy[i], xox[i], xoff[i], ok);
             pst[i] = ok ? 64 : 0;
         }
-        tap_left = (a.Cin - c0) / 64;
+        tap_left = (a.Cin - tap.c0) / 64;
     };
     auto issue_begin = [&]() {
         if (CONV) {
@@ -150,7 +123,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     auto issue_slot = [&](int buf, int i) {
         const int p = wave + NW * i;
         if (p < NP) {
-            __builtin_amdgcn_global_load_lds((g144_gptr_t)pp[i], (g144_lptr_t)(smem + buf * STAGE + p * 512), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)pp[i], (lptr_t)(smem + buf * STAGE + p * 512), 16, 0, 0);
             pp[i] += pst[i];
         }
     };
@@ -403,10 +376,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
             const int m = mb + 16 * i + r16;
             if (m >= a.M) continue;
 #pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int nn = nb + 16 * j + 4 * kg;
-                if (nn < a.N) *(f32x4 *)(pb + (size_t)m * a.N + nn) = acc[i][j];
-            }
+            for (int j = 0; j < NI; ++j) store_part4(a, pb + (size_t)m * a.N, nb + 16 * j + 4 * kg, acc[i][j]);
         }
         return;
     }
@@ -438,25 +408,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
                 if (m >= a.M || n >= a.N) continue;
                 const f32x4 v0 = *(const f32x4 *)(tile + row * RS + c8), v1 = *(const f32x4 *)(tile + row * RS + c8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if (a.bias) {
-                    const f16x8 bb = *(const f16x8 *)(a.bias + n);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
-                }
-                if (a.rowbias) {
-                    const f16x8 bb = *(const f16x8 *)(a.rowbias + (size_t)(m / a.rows_per_batch) * a.ldrb + n);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
-                }
-                if (a.residual) {
-                    const f16x8 bb = *(const f16x8 *)(a.residual + (size_t)m * a.ldr + n);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += (float)bb[e];
-                }
-                f16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (f16)v[e];
-                *(f16x8 *)(a.out + (size_t)m * a.ldc + n) = o;
+                if (a.bias) add8(v, *(const f16x8 *)(a.bias + n));
+                store8(a, v, m, n);
             }
         }
         return;
@@ -476,29 +429,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         for (int j = 0; j < NI; ++j) {
             const int nn = nb + 16 * j + 4 * kg;
             if (nn >= a.N) continue;
-            f32x4 v = acc[i][j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += (float)bs[j][e];
-            if (a.rowbias) {
-                f16x4 b = *(const f16x4 *)(a.rowbias + (size_t)bidx * a.ldrb + nn);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
-            }
-            if (a.residual) {
-                f16x4 b = *(const f16x4 *)(a.residual + (size_t)m * a.ldr + nn);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
-            }
-            f16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (f16)v[e];
-            *(f16x4 *)(a.out + (size_t)m * a.ldc + nn) = o;
+            store4(a, add4(acc[i][j], bs[j]), m, bidx, nn);
         }
     }
 }
 
 // Launch when the problem fits (returns 1): K a multiple of 64 (conv: Cin too), plain epilogue, fp16 in and out.
-// form 0: 6 waves (3 x 2, wave tile 48 x 80); 1: 15 waves (3 x 5, wave tile 48 x 32), lockstep; 2: 15 waves, ring of 4, software-pipelined (MFMAs first, DMA and reads between them); 3: 15 waves, one barrier per two stages.
+// form 0: 6 waves (3 x 2, wave tile 48 x 80); 1: 15 waves (3 x 5, wave tile 48 x 32), lockstep; 2: 15 waves, ring of 4, software-pipelined
+// (MFMAs first, DMA and reads between them); 3: 15 waves, one barrier per two stages; 4: 288 x 160 tile, 15 waves, lockstep, ring of 2.
 int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
 {
     if (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || a.N % 4 != 0 || a.epi != 0 || a.res32 || a.out32 || a.zins) return 0;
@@ -509,47 +447,35 @@ int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
     int S = (a.splitk > 1 && a.part) ? a.splitk : 1;
     if (S > a.K / 64) S = a.K / 64;
     a.splitk = S;
-    const double wbytes = (double)a.N * a.K, xbytes = (double)a.M * (conv ? a.Cin : a.K);
-    a.mfast = wbytes > xbytes ? 1 : 0;
-    static int stg = -1;
-    if (stg < 0) { const char *e = getenv("CTX_G144_STAGE"); stg = e ? atoi(e) : 1; }
+    a.mfast = ctx_gemm_mfast(a, conv);
+    static const int stg = ctx_env_int("CTX_G144_STAGE", 1);
     a.stage_epi = stg && form != 0 && a.N % 8 == 0 && a.ldc % 8 == 0 && (!a.residual || a.ldr % 8 == 0) && (!a.rowbias || a.ldrb % 8 == 0);
-    static bool attr[20] = {};
-    auto go = [&](auto kern, int which, int threads, int ns) {
-        const size_t lds = (size_t)ns * (bm + G144_BN) * 64 * sizeof(f16);
-        if (!attr[which]) {
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr[which] = true;
-        }
-        if (ctx_prof_on()) {
-            hipEvent_t e0, e1;
-            ctx_prof_events(0, &e0, &e1);
-            hipExtLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * S), dim3(threads), lds, s, e0, e1, 0, a);
-        } else
-            hipLaunchKernelGGL(kern, dim3(a.ntm * a.ntn * S), dim3(threads), lds, s, a);
-    };
+    const dim3 grid(a.ntm * a.ntn * S);
+    // threads, ring depth, then the kernel's template arguments
+#define G144_GO(NT_, NS_, ...) ctx_launch<k_gemm144<__VA_ARGS__>>(0, grid, dim3(NT_), (size_t)NS_ * (bm + G144_BN) * 64 * sizeof(f16), s, a)
     const bool ups = conv && a.ups;
     switch (form) {
     case 4:                                                          // 288 x 160, 15 waves, lockstep, ring of 2
-        if (!conv) go(k_gemm144<3, 5, false, 2, 0, false, 18>, 12, 960, 2);
-        else if (ups) go(k_gemm144<3, 5, true, 2, 0, true, 18>, 13, 960, 2); else go(k_gemm144<3, 5, true, 2, 0, false, 18>, 14, 960, 2);
+        if (!conv) G144_GO(960, 2, 3, 5, false, 2, 0, false, 18);
+        else if (ups) G144_GO(960, 2, 3, 5, true, 2, 0, true, 18); else G144_GO(960, 2, 3, 5, true, 2, 0, false, 18);
         break;
     case 1:
-        if (!conv) go(k_gemm144<3, 5, false, 3, 0>, 2, 960, 3);
-        else if (ups) go(k_gemm144<3, 5, true, 3, 0, true>, 8, 960, 3); else go(k_gemm144<3, 5, true, 3, 0>, 3, 960, 3);
+        if (!conv) G144_GO(960, 3, 3, 5, false, 3, 0);
+        else if (ups) G144_GO(960, 3, 3, 5, true, 3, 0, true); else G144_GO(960, 3, 3, 5, true, 3, 0);
         break;
     case 2:
-        if (!conv) go(k_gemm144<3, 5, false, 4, 1>, 4, 960, 4);
-        else if (ups) go(k_gemm144<3, 5, true, 4, 1, true>, 9, 960, 4); else go(k_gemm144<3, 5, true, 4, 1>, 5, 960, 4);
+        if (!conv) G144_GO(960, 4, 3, 5, false, 4, 1);
+        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 1, true); else G144_GO(960, 4, 3, 5, true, 4, 1);
         break;
     case 3:
-        if (!conv) go(k_gemm144<3, 5, false, 4, 2>, 6, 960, 4);
-        else if (ups) go(k_gemm144<3, 5, true, 4, 2, true>, 10, 960, 4); else go(k_gemm144<3, 5, true, 4, 2>, 7, 960, 4);
+        if (!conv) G144_GO(960, 4, 3, 5, false, 4, 2);
+        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 2, true); else G144_GO(960, 4, 3, 5, true, 4, 2);
         break;
     default:
-        if (!conv) go(k_gemm144<3, 2, false, 3, 0>, 0, 384, 3);
-        else if (ups) go(k_gemm144<3, 2, true, 3, 0, true>, 11, 384, 3); else go(k_gemm144<3, 2, true, 3, 0>, 1, 384, 3);
+        if (!conv) G144_GO(384, 3, 3, 2, false, 3, 0);
+        else if (ups) G144_GO(384, 3, 3, 2, true, 3, 0, true); else G144_GO(384, 3, 3, 2, true, 3, 0);
         break;
     }
+#undef G144_GO
     return 1;
 }

@@ -26,31 +26,8 @@
 //    is in R.  Refill order X0 W0 W1 X1, each slot refilled two phases after its last read (WAR) and waited for in the
 //    R section of the phase BEFORE the one that reads it (RAW: own pieces by vmcnt, the other waves' by the barrier);
 //    four half-tiles (64 KiB) are always in flight: vmcnt(8), never 0 until the tail.
-#include "common.h"
-#include "kernels.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
+#include "gemm_common.h"
 #include <type_traits>
-
-typedef const __attribute__((address_space(1))) void *g8_gptr_t;
-typedef __attribute__((address_space(3))) void *g8_lptr_t;
-__device__ __attribute__((aligned(128))) f16 g8_zero[64];
-
-__device__ __forceinline__ int g8_xcd_remap(int bid, int nwg)
-{
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ float g8_erf(float x)
-{
-    float ax = __builtin_fabsf(x);
-    float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * ax);
-    float p = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    float e = 1.0f - p * __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
-    return __builtin_copysignf(e, x);
-}
-__device__ __forceinline__ float g8_gelu(float x) { return 0.5f * x * (1.0f + g8_erf(x * 0.70710678118654752f)); }
 
 #define G8_WAIT(n)                                                              \
     do {                                                                        \
@@ -69,14 +46,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
     const int wr = wave >> 2, wc = wave & 3;
     const int r16 = lane & 15, kg = lane >> 4;
 
-    const int ntiles = a.ntm * a.ntn;
-    const int lin = g8_xcd_remap(blockIdx.x, ntiles * a.splitk);
-    const int slice = lin / ntiles, bid = lin - slice * ntiles;
-    const int tile_n = a.mfast ? bid / a.ntm : bid % a.ntn, tile_m = a.mfast ? bid % a.ntm : bid / a.ntn;
-    const int m0 = tile_m * 256, n0 = tile_n * 256;
-    const int nkt_all = a.K / 64;
-    const int kbeg = (int)((long)nkt_all * slice / a.splitk);
-    const int nkt = (int)((long)nkt_all * (slice + 1) / a.splitk) - kbeg;
+    const GemmTile tl = gemm_tile(a, blockIdx.x, 64, 256, 256);
+    const int slice = tl.slice, m0 = tl.m0, n0 = tl.n0, kbeg = tl.kbeg, nkt = tl.nk;
     const int nht = 4 * nkt;                                       // half-tiles to stage
 
     // ---- staging state: per half-tile kind (issue order X0 W0 W1 X1) two pieces per wave ------------------------------
@@ -97,23 +68,18 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
                 const int m = m0 + (s >> 6) * 128 + h * 64 + (s & 63);
                 const bool ok = m < a.M;
                 if (CONV) {
-                    const int hw = a.Ho * a.Wo;
-                    const int mm = ok ? m : 0;
-                    const int b = mm / hw, p = mm - b * hw;
-                    const int oy = p / a.Wo, ox = p - oy * a.Wo;
-                    xb[h][i] = b * a.H * a.W * a.Cin + lc;
-                    xoy[h][i] = oy * a.stride; xox[h][i] = ox * a.stride;
+                    conv_pixel(a, ok ? m : 0, lc, xoy[h][i], xox[h][i], xb[h][i]);
                     xok[h][i] = ok;
-                    gp[kind][i] = g8_zero; gst[kind][i] = 0;
+                    gp[kind][i] = ctx_zero_page; gst[kind][i] = 0;
                 } else {
-                    gp[kind][i] = ok ? a.X + (size_t)m * a.K + (size_t)kbeg * 64 + lc : g8_zero + lc;
+                    gp[kind][i] = ok ? a.X + (size_t)m * a.K + (size_t)kbeg * 64 + lc : ctx_zero_page + lc;
                     gst[kind][i] = ok ? 64 : 0;
                 }
             } else {
                 const int h = kind == 1 ? 0 : 1;
                 const int n = n0 + (s >> 5) * 64 + h * 32 + (s & 31);
                 const bool ok = n < a.N;
-                gp[kind][i] = ok ? a.Wt + (size_t)n * a.K + (size_t)kbeg * 64 + lc : g8_zero + lc;
+                gp[kind][i] = ok ? a.Wt + (size_t)n * a.K + (size_t)kbeg * 64 + lc : ctx_zero_page + lc;
                 gst[kind][i] = ok ? 64 : 0;
             }
         }
@@ -127,21 +93,17 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
         f16 *dst = smem + (t & 1) * 32768 + slot * 8192;
         if (CONV && (kind == 0 || kind == 3)) {
             const int h = kind == 0 ? 0 : 1;
-            const int k0 = (kbeg + t) * 64;
-            const int tap = k0 / a.Cin, c0 = k0 - tap * a.Cin;
-            const int dy = tap / 3 - 1 + a.poff, dx = tap - (tap / 3) * 3 - 1 + a.poff;
-            const int Hv = a.H << a.ups, Wv = a.W << a.ups;
+            const ConvTap tap = conv_tap(a, (kbeg + t) * 64);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int iy = xoy[h][i] + dy, ix = xox[h][i] + dx;
-                const bool ok = xok[h][i] && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
-                const f16 *src = ok ? a.X + xb[h][i] + (((iy >> a.ups) * a.W + (ix >> a.ups)) * a.Cin) + c0 : g8_zero;
-                __builtin_amdgcn_global_load_lds((g8_gptr_t)src, (g8_lptr_t)(dst + (wave + 8 * i) * 512), 16, 0, 0);
+                bool ok = xok[h][i];
+                const f16 *src = conv_tap_src(a, tap, xoy[h][i], xox[h][i], xb[h][i], ok);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + (wave + 8 * i) * 512), 16, 0, 0);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                __builtin_amdgcn_global_load_lds((g8_gptr_t)gp[kind][i], (g8_lptr_t)(dst + (wave + 8 * i) * 512), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)gp[kind][i], (lptr_t)(dst + (wave + 8 * i) * 512), 16, 0, 0);
                 gp[kind][i] += gst[kind][i];
             }
         }
@@ -266,10 +228,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
             const int m = mb + 16 * i + r16;
             if (m >= a.M) continue;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int nn = nb + 16 * j + 4 * kg;
-                if (nn < a.N) *(f32x4 *)(pb + (size_t)m * a.N + nn) = acc[i][j];
-            }
+            for (int j = 0; j < 4; ++j) store_part4(a, pb + (size_t)m * a.N, nb + 16 * j + 4 * kg, acc[i][j]);
         }
         return;
     }
@@ -293,10 +252,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
                 if (nn >= a.N) continue;
                 f16x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float xv = acc[i][j][e] + (float)bv[j][e], gv = acc[i][2 + j][e] + (float)bg[j][e];
-                    o[e] = (f16)(xv * g8_gelu(gv));
-                }
+                for (int e = 0; e < 4; ++e) o[e] = geglu(acc[i][j][e] + (float)bv[j][e], acc[i][2 + j][e] + (float)bg[j][e]);
                 *(f16x4 *)(a.out + (size_t)m * a.ldc + fbase + 16 * j + 4 * kg) = o;
             }
         }
@@ -317,23 +273,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
         for (int j = 0; j < 4; ++j) {
             const int nn = nb + 16 * j + 4 * kg;
             if (nn >= a.N) continue;
-            f32x4 v = acc[i][j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += (float)bs[j][e];
-            if (a.rowbias) {
-                f16x4 b = *(const f16x4 *)(a.rowbias + (size_t)bidx * a.ldrb + nn);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
-            }
-            if (a.residual) {
-                f16x4 b = *(const f16x4 *)(a.residual + (size_t)m * a.ldr + nn);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)b[e];
-            }
-            f16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (f16)v[e];
-            *(f16x4 *)(a.out + (size_t)m * a.ldc + nn) = o;
+            store4(a, add4(acc[i][j], bs[j]), m, bidx, nn);
         }
     }
 }
@@ -342,11 +282,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm8(GemmArgs a)
 int ctx_gemm8_try(GemmArgs &a, bool conv, bool force, hipStream_t s)
 {
     // CTX_GEMM8: 0 off, 1 auto (default), 2 force whenever the kernel is applicable (tests); read per call on purpose
-    const char *e = getenv("CTX_GEMM8");
-    int en = e ? atoi(e) : 1;
-    if (force) en = 2;
-    const char *tt = getenv("CTX_GEMM8_MIN_TILES");
-    const int min_tiles = tt ? atoi(tt) : 180;
+    const int en = force ? 2 : ctx_env_int("CTX_GEMM8", 1);
+    const int min_tiles = ctx_env_int("CTX_GEMM8_MIN_TILES", 180);
     if (!en) return 0;
     if (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || a.N % 8 != 0) return 0;
     if (a.epi == 1 && a.N % 64 != 0) return 0;
@@ -358,22 +295,8 @@ int ctx_gemm8_try(GemmArgs &a, bool conv, bool force, hipStream_t s)
         if (ntm * ntn * S < min_tiles || useful < 0.8 || a.K / 64 / S < 4) return 0;
     }
     a.ntm = ntm; a.ntn = ntn; a.splitk = S;
-    const double wbytes = (double)a.N * a.K, xbytes = (double)a.M * (conv ? a.Cin : a.K);
-    a.mfast = wbytes > xbytes ? 1 : 0;
-    const size_t lds = 131072;
-    static bool attr[2] = {false, false};
-    auto go = [&](auto kern, int which) {
-        if (!attr[which]) {
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr[which] = true;
-        }
-        if (ctx_prof_on()) {
-            hipEvent_t e0, e1;
-            ctx_prof_events(0, &e0, &e1);
-            hipExtLaunchKernelGGL(kern, dim3(ntm * ntn * S), dim3(512), lds, s, e0, e1, 0, a);
-        } else
-            hipLaunchKernelGGL(kern, dim3(ntm * ntn * S), dim3(512), lds, s, a);
-    };
-    if (conv) go(k_gemm8<true>, 1); else go(k_gemm8<false>, 0);
+    a.mfast = ctx_gemm_mfast(a, conv);
+    const dim3 grid(ntm * ntn * S);
+    if (conv) ctx_launch<k_gemm8<true>>(0, grid, dim3(512), 131072, s, a); else ctx_launch<k_gemm8<false>>(0, grid, dim3(512), 131072, s, a);
     return 1;
 }

@@ -32,7 +32,7 @@ def _close(got, want, rtol=2e-3, atol=2e-3, what=""):
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 320, 320), (257, 64, 128), (18, 1280, 1024), (1000, 2560, 320),
                                    (4096, 640, 1920)])
-def test_gemm(dev, M, N, K):
+def test_gemm(dev, M, N, K, with_bias=True, with_res=True):
     L, lib = _lib()
     g = torch.Generator().manual_seed(M + N + K)
     A = (torch.randn(M, K, generator=g)).half()
@@ -41,9 +41,14 @@ def test_gemm(dev, M, N, K):
     res = torch.randn(M, N, generator=g).half()
     Ad, Wd, bd, rd = A.to(dev), W.to(dev), bias.to(dev), res.to(dev)
     out = torch.empty(M, N, dtype=torch.float16, device=dev)
-    L.check(lib.ctx_gemm_f16(L.ptr(Ad), L.ptr(Wd), L.ptr(bd), L.ptr(rd), M, N, K, L.ptr(out), L.stream()))
-    want = A.float() @ W.float().T + bias.float() + res.float()
-    _close(out, want, what=f"gemm {M}x{N}x{K}")
+    L.check(lib.ctx_gemm_f16(L.ptr(Ad), L.ptr(Wd), L.ptr(bd) if with_bias else None, L.ptr(rd) if with_res else None, M, N, K,
+                             L.ptr(out), L.stream()))
+    want = A.float() @ W.float().T
+    if with_bias:
+        want = want + bias.float()
+    if with_res:
+        want = want + res.float()
+    _close(out, want, what=f"gemm {M}x{N}x{K} bias={with_bias} res={with_res}")
     out2 = torch.empty(M, N, dtype=torch.float16, device=dev)
     L.check(lib.ctx_gemm_f16(L.ptr(Ad), L.ptr(Wd), None, None, M, N, K, L.ptr(out2), L.stream()))
     _close(out2, A.float() @ W.float().T, what="gemm no-epilogue")
@@ -52,7 +57,7 @@ def test_gemm(dev, M, N, K):
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride,ups", [(2, 16, 16, 64, 64, 1, 0), (1, 9, 13, 128, 320, 1, 0),
                                                         (2, 16, 12, 64, 128, 2, 0), (2, 8, 8, 128, 64, 1, 1),
                                                         (2, 32, 32, 320, 320, 1, 0), (1, 24, 24, 1920, 640, 1, 0)])
-def test_conv3x3(dev, B, H, W, Cin, Cout, stride, ups):
+def test_conv3x3(dev, B, H, W, Cin, Cout, stride, ups, with_bias=True, with_rowb=True, with_res=True):
     L, lib = _lib()
     g = torch.Generator().manual_seed(B * H + Cin + Cout)
     x = torch.randn(B, Cin, H, W, generator=g).half()
@@ -60,17 +65,21 @@ def test_conv3x3(dev, B, H, W, Cin, Cout, stride, ups):
     bias = torch.randn(Cout, generator=g).half()
     rowb = torch.randn(B, Cout, generator=g).half()
     xin = F.interpolate(x.float(), scale_factor=2.0, mode='nearest') if ups else x.float()
-    want = F.conv2d(xin, w.float(), bias.float(), stride=stride, padding=1) + rowb.float()[:, :, None, None]
+    want = F.conv2d(xin, w.float(), bias.float() if with_bias else None, stride=stride, padding=1)
+    if with_rowb:
+        want = want + rowb.float()[:, :, None, None]
     res = torch.randn(want.shape, generator=g).half()
-    want = want + res.float()
+    if with_res:
+        want = want + res.float()
     xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
     wd = w.permute(0, 2, 3, 1).contiguous().to(dev)
     bd, rbd = bias.to(dev), rowb.to(dev)
     rd = res.permute(0, 2, 3, 1).contiguous().to(dev)
     Ho, Wo = want.shape[2], want.shape[3]
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float16, device=dev)
-    L.check(lib.ctx_conv3x3_f16(L.ptr(xd), L.ptr(wd), L.ptr(bd), L.ptr(rbd), L.ptr(rd), B, H, W, Cin, Cout, stride, ups, L.ptr(y), L.stream()))
-    _close(y.permute(0, 3, 1, 2), want, rtol=3e-3, atol=4e-3, what="conv3x3")
+    L.check(lib.ctx_conv3x3_f16(L.ptr(xd), L.ptr(wd), L.ptr(bd) if with_bias else None, L.ptr(rbd) if with_rowb else None,
+                                L.ptr(rd) if with_res else None, B, H, W, Cin, Cout, stride, ups, L.ptr(y), L.stream()))
+    _close(y.permute(0, 3, 1, 2), want, rtol=3e-3, atol=4e-3, what=f"conv3x3 bias={with_bias} rowbias={with_rowb} res={with_res}")
 
 
 @pytest.fixture
@@ -147,6 +156,24 @@ def test_gemm144_forced(dev, form):
             ms = lib.ctx_bench_gemm(L.ptr(Ad), L.ptr(Wd), L.ptr(bd), L.ptr(rd), M, N, K, L.ptr(out), 0, 0, 0, 0, 0, 0, L.ptr(part), splitk, 1, L.stream())
             assert ms > 0, lib.ctx_last_error()
             _close(out, A.float() @ W.float().T + bias.float() + res.float(), what=f"gemm144 split-K {splitk}")
+    finally:
+        lib.ctx_gemm_tune(-1, -1)
+
+
+@pytest.mark.parametrize("tile,use8", [(1, 0), (27, 0), (-1, 1), (-1, 3), (-1, 4), (-1, 6), (-1, 8)])
+def test_epilogue_each_operand_alone(dev, tile, use8):
+    """The epilogue operands one at a time and none at all (the other tests pass bias and residual together, and a row bias only
+    with a bias): one form of each kernel family, forced through the tuning override: gemm.hip's LDS-staged epilogue (tile 1) and
+    its direct one (tile 27, whose patch exceeds the LDS), gemm8.hip, conv_halo.hip and three forms of gemm144.hip.  GEMM ragged in
+    M for every tile height; convolution with 16 x 16 images (what the halo kernel needs) and 72 features, ragged against every
+    tile width."""
+    L, lib = _lib()
+    lib.ctx_gemm_tune(tile, use8)
+    try:
+        for with_bias, with_res in [(True, False), (False, True), (False, False)]:
+            test_gemm(dev, 300, 320, 320, with_bias=with_bias, with_res=with_res)
+        for with_bias, with_rowb, with_res in [(True, False, False), (False, True, False), (False, False, True), (False, False, False)]:
+            test_conv3x3(dev, 2, 16, 16, 64, 72, 1, 0, with_bias=with_bias, with_rowb=with_rowb, with_res=with_res)
     finally:
         lib.ctx_gemm_tune(-1, -1)
 
