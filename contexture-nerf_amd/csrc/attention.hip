@@ -291,6 +291,33 @@ static void attn_launch(const AttnArgs &a, int B, bool report, hipStream_t s)
     ctx_launch<kern>(1, dim3(cdiv(a.Sq, 32 * NW), a.heads, B), dim3(64 * NW), 0, s, a);
 }
 
+// Kernel selection (A/B switches): the environment seeds it once per process, ctx_attention_tune overrides it while set.
+//   ns      CTX_ATTN_NS      ring depth 2 | 3 | 4 (default 3; anything else runs 3)
+//   nw8     CTX_ATTN_NW8     0 never, 1 always the 8-wave workgroups, -1 by size
+//   spread  CTX_ATTN_SPREAD  0: all DMA pieces of a tile right after the barrier
+//   lazy    CTX_ATTN_LAZY    rescale threshold in log2 units (default 8 = a factor 256; 0 = rescale on every change; 0 .. 12)
+struct AttnTune { int ns, nw8, spread; float lazy; };
+static AttnTune g_attn_force = {-1, -1, -1, -1.f};          // -1 / negative lazy: what the environment or the default says
+static const AttnTune &attn_tune_env()
+{
+    static const AttnTune env = [] {
+        AttnTune t;
+        t.ns = ctx_env_int("CTX_ATTN_NS", 3);
+        t.nw8 = ctx_env_int("CTX_ATTN_NW8", -1);
+        t.spread = ctx_env_int("CTX_ATTN_SPREAD", 1);
+        const char *e = getenv("CTX_ATTN_LAZY");
+        t.lazy = e ? (float)atof(e) : 8.0f;
+        if (!(t.lazy >= 0.f && t.lazy <= 12.f)) t.lazy = 8.0f;
+        return t;
+    }();
+    return env;
+}
+
+extern "C" void ctx_attention_tune(int32_t ns, int32_t nw8, int32_t spread, float lazy)
+{
+    g_attn_force.ns = ns; g_attn_force.nw8 = nw8; g_attn_force.spread = spread; g_attn_force.lazy = lazy;
+}
+
 int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int q_stride,
                        int kv_stride, float scale, f16 *O, int o_stride, hipStream_t s)
 {
@@ -298,15 +325,15 @@ int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, 
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.Sq = Sq; a.Skv = Skv; a.heads = heads;
     a.q_stride = q_stride; a.kv_stride = kv_stride; a.o_stride = o_stride;
     a.scale_log2e = scale * 1.4426950408889634f;
-    static float lazy = -1.f;           // CTX_ATTN_LAZY: threshold in log2 units (default 8 = a factor 256; 0 = rescale on every change)
-    if (lazy < 0.f) { const char *e = getenv("CTX_ATTN_LAZY"); lazy = e ? (float)atof(e) : 8.0f; if (!(lazy >= 0.f && lazy <= 12.f)) lazy = 8.0f; }
-    a.lazy = lazy;
-    static const int ns = ctx_env_int("CTX_ATTN_NS", 3);
+    const AttnTune &tu = attn_tune_env();
+    const float lazy = g_attn_force.lazy >= 0.f ? g_attn_force.lazy : tu.lazy;
+    a.lazy = lazy >= 0.f && lazy <= 12.f ? lazy : 8.0f;
+    const int ns = g_attn_force.ns >= 0 ? g_attn_force.ns : tu.ns;
     // 8-wave workgroups (two per CU at 128 VGPRs) measured against three 4-wave ones (148 VGPRs): 72 vs 77 us at 2304 tokens
     // x 10 heads, 411 vs 371 us at 9216 x 5 — so only the mid-size self-attention takes them (CTX_ATTN_NW8: 0 never, 1 always)
-    static const int nw8 = ctx_env_int("CTX_ATTN_NW8", -1);
+    const int nw8 = g_attn_force.nw8 >= 0 ? g_attn_force.nw8 : tu.nw8;
     const bool w8 = nw8 == 1 || (nw8 < 0 && Sq >= 1024 && Sq < 4096 && Skv >= 1024);
-    static const int spread = ctx_env_int("CTX_ATTN_SPREAD", 1);    // 0: all DMA pieces of a tile right after the barrier (the A/B switch)
+    const int spread = g_attn_force.spread >= 0 ? g_attn_force.spread : tu.spread;
     static int dbg = -1;                                            // CTX_ATTN_DEBUG: the first launch reports its kernel's occupancy
     bool report = false;
     if (dbg < 0) { dbg = ctx_env_int("CTX_ATTN_DEBUG", 0); report = dbg != 0; }

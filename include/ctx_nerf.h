@@ -384,6 +384,11 @@ float ctx_bench_gemm(const void *A, const void *Wt, const void *bias, const void
    gemm8.hip (-1 planner, 0 never, 1 whenever applicable) for every following GEMM / conv launch of this process. */
 void ctx_gemm_tune(int32_t tile, int32_t gemm8);
 
+/* Tuning / test support (tests/test_attention_gpu.py, tools/bench_attn.py): select the attention kernel for every following
+   launch of this process instead of CTX_ATTN_NS (2 | 3 | 4), CTX_ATTN_NW8 (0 | 1), CTX_ATTN_SPREAD (0 | 1) and CTX_ATTN_LAZY
+   (0 .. 12).  -1 (a negative lazy) = what the environment or the default says. */
+void ctx_attention_tune(int32_t ns, int32_t nw8, int32_t spread, float lazy);
+
 /* Unit-test support: one 32x32 tile through the MFMA fragment maps the kernels assume.
    which 0: f16 32x32x16 (A[32][16], Bt[32][16]); 1: f32 32x32x2 (A[32][2], Bt[32][2]); C[32][32] f32.
    which 2: the transposing LDS read ds_read_b64_tr_b16 on an f16 tile A[8][32]; C[64 lanes][4] f32 (Bt unused but non-null). */

@@ -30,6 +30,18 @@ def _close(got, want, rtol=2e-3, atol=2e-3, what=""):
     assert bad == 0, f"{what}: {bad}/{got.numel()} off; max err {err.max():.4e}, rel L2 {(got - want).norm() / want.norm():.3e}"
 
 
+def _attention_gates(o, q, k, v, what, lazy=8.0):
+    """Attention against float64 (oracle/attention_ref.py): every element within the contract's worst-case bound
+    2^-11 * (2 |want| + softmax(s) @ |V|) + 1e-7, and the whole tensor's relative L2 within 1.5x of what a plain fp32 emulation of
+    the kernel's recurrence (fp16 P, stale maximum, fp16 output) reaches on the same inputs."""
+    from oracle import attention_ref as A
+    f = A.compare(o, q, k, v, 0.125, lazy)
+    print(f"{what}: element/bound {f['elem']:.3f}, rel L2 {f['rel']:.3e} vs emulation {f['rel_emu']:.3e}")
+    assert f["finite"], f"{what}: non-finite output"
+    assert f["elem"] <= 1.0, f"{what}: an element is at {f['elem']:.3f} of the bound"
+    assert f["rel"] <= 1.5 * f["rel_emu"], f"{what}: rel L2 {f['rel']:.3e} > 1.5 x the emulation's {f['rel_emu']:.3e}"
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 320, 320), (257, 64, 128), (18, 1280, 1024), (1000, 2560, 320),
                                    (4096, 640, 1920)])
 def test_gemm(dev, M, N, K, with_bias=True, with_res=True):
@@ -365,12 +377,7 @@ def test_attention(dev, B, Sq, Skv, heads):
     o = torch.empty(B, Sq, Cc, dtype=torch.float16, device=dev)
     ws = torch.empty(lib.ctx_attention_ws_bytes(B, Skv, heads), dtype=torch.uint8, device=dev)
     L.check(lib.ctx_attention_f16(L.ptr(qd), L.ptr(kd), L.ptr(vd), B, Sq, Skv, heads, Cc, Cc, 0.125, L.ptr(o), Cc, L.ptr(ws), L.stream()))
-    qh = q.float().view(B, Sq, heads, 64).transpose(1, 2)
-    kh = k.float().view(B, Skv, heads, 64).transpose(1, 2)
-    vh = v.float().view(B, Skv, heads, 64).transpose(1, 2)
-    want = (torch.softmax(qh @ kh.transpose(-1, -2) * 0.125, -1) @ vh).transpose(1, 2).reshape(B, Sq, Cc)
-    # P is rounded to fp16 before the second product: 2^-11 relative per term, averaged over Skv terms
-    _close(o, want, rtol=3e-3, atol=3e-3, what="attention")
+    _attention_gates(o, q, k, v, "attention")
 
 
 def test_attention_rescale_branch(dev):
@@ -387,8 +394,7 @@ def test_attention_rescale_branch(dev):
     o = torch.empty(B, S, 64, dtype=torch.float16, device=dev)
     ws = torch.empty(lib.ctx_attention_ws_bytes(B, S, heads), dtype=torch.uint8, device=dev)
     L.check(lib.ctx_attention_f16(L.ptr(qd), L.ptr(kd), L.ptr(vd), B, S, S, heads, 64, 64, 0.125, L.ptr(o), 64, L.ptr(ws), L.stream()))
-    want = torch.softmax(q.double() @ k.double().transpose(-1, -2) * 0.125, -1) @ v.double()
-    _close(o, want, rtol=3e-3, atol=3e-3, what="attention rescale")
+    _attention_gates(o, q, k, v, "attention rescale")
 
 
 def test_attention_creeping_maximum_lazy_rescale(dev):
@@ -409,10 +415,8 @@ def test_attention_creeping_maximum_lazy_rescale(dev):
     qd, kd, vd = q.to(dev), k.to(dev), v.to(dev)
     o = torch.empty(B, S, heads * 64, dtype=torch.float16, device=dev)
     L.check(lib.ctx_attention_f16(L.ptr(qd), L.ptr(kd), L.ptr(vd), B, S, Skv, heads, heads * 64, heads * 64, 0.125, L.ptr(o), heads * 64, None, L.stream()))
-    qh = q.double().view(B, S, heads, 64).transpose(1, 2); kh = k.double().view(B, Skv, heads, 64).transpose(1, 2); vh = v.double().view(B, Skv, heads, 64).transpose(1, 2)
-    want = (torch.softmax(qh @ kh.transpose(-1, -2) * 0.125, -1) @ vh).transpose(1, 2).reshape(B, S, heads * 64)
     assert torch.isfinite(o.float()).all()
-    _close(o, want, rtol=3e-3, atol=3e-3, what="attention, creeping maximum")
+    _attention_gates(o, q, k, v, "attention, creeping maximum")
     # the textbook recurrence in a fresh process (the threshold is read once per process)
     with tempfile.TemporaryDirectory() as td:
         torch.save({"q": q, "k": k, "v": v}, td + "/in.pt")

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Attention micro-benchmark at the UNet's shapes. Usage: python tools/bench_attn.py [iters]"""
+"""Attention micro-benchmark at the UNet's shapes. Usage: python tools/bench_attn.py [iters] [shape indices] [ns,nw8,spread,lazy]
+(the last: ctx_attention_tune's kernel override, -1 = what CTX_ATTN_* / the default says)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,6 +10,8 @@ iters = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 shapes = [(2, 9216, 9216, 5), (2, 2304, 2304, 10), (2, 576, 576, 20), (2, 9216, 77, 5), (2, 8192, 8192, 12), (12, 9216, 9216, 5), (4, 9216, 9216, 5), (6, 9216, 9216, 5), (1, 9216, 9216, 5), (2, 9216, 9216, 10), (2, 4608, 9216, 5)]   # the last: 6144 waves = whole rounds at 2 and at 3 waves per SIMD
 if len(sys.argv) > 2:
     shapes = [shapes[int(i)] for i in sys.argv[2].split(',')]
+if len(sys.argv) > 3:
+    ns, nw8, spread, lazy = sys.argv[3].split(','); lib.ctx_attention_tune(int(ns), int(nw8), int(spread), float(lazy))
 for (B, S, Skv, heads) in shapes:
     C = heads * 64
     g = torch.Generator(device=dev).manual_seed(0)
