@@ -2,22 +2,40 @@
 // Replaces get_embedder + NeRF2D.forward (src/run_nerf_helpers.py:15-135) as called from
 // TexturedMeshModel.get_texture_map (src/models/textured_mesh.py:266-301).
 //
-// The reference computes this in fp32, so the contraction runs on the exact-f32 matrix pipe
-// (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, 157 TFLOP/s peak on MI355X).
+// The reference computes this in fp32.  Two matrix pipes carry the contraction at that accuracy:
+//   * the reference's own 2-D texture field (W = 256, 48-wide embedding) runs by default on the 16-bit pipe with SPLIT
+//     operands (k_uvmlp_fwd16 / k_uvmlp_dgrad16: every operand is two fp16 numbers, 22 bits of mantissa);
+//   * every other shape, the weight gradients, and everything under CTX_UVMLP_EXACT_F32=1 run on the exact-f32 pipe
+//     (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, 157 TFLOP/s peak on MI355X).
 //
-// One workgroup = 64 texels x W hidden units; wave w owns hidden columns [64w, 64w+64) as 2x2
-// accumulator tiles of 32x32.  Activations never leave the CU: they live in LDS as
-// act[64][STRIDE] floats with the (zero-padded to 48) embedding in columns [0,48) and the hidden
-// vector in [48,48+W); the skip layer simply reads columns [0,48+W).  Weights are pre-packed so a
-// lane's four k-steps of an 8-wide k-block are one 16-byte global load (L2-resident: 1.9 MB).
+// In all four chain kernels one workgroup = 64 texels x W hidden units; wave w owns hidden columns [64w, 64w+64) as 2x2
+// accumulator tiles of 32x32.  Activations never leave the CU: the f32 kernels keep them in LDS as act[64][STRIDE] floats
+// with the (zero-padded to 48) embedding in columns [0,48) and the hidden vector in [48,48+W); the skip layer simply reads
+// columns [0,48+W).  The split kernels keep the same columns as two fp16 planes.  Weights are pre-packed so a lane's
+// k-steps of one k-block are one 16-byte global load (L2-resident: 1.9 MB).
+//
+// Shared device pieces, each written once below and used by the kernels named:
+//   uvm_split / uvm_join          hi / lo operands            pack16 kernels, fwd16, dgrad16
+//   uvm_acc_row / uvm_relu_bit    accumulator element -> (row, ReLU bit)   all chain kernels, wgrad's slab store
+//   uvm_stage_planes              a wave's packed outputs -> hi / lo planes   fwd16, dgrad16
+//   uvm_kloop_f32                 f32-pipe K-loop             fwd (all three uses), dgrad
+//   uvm_kloop_split               split-fp16 K-loop           fwd16, dgrad16
+//   uvm_point / uvm_embed_col     Fourier embedding           fwd, fwd16
+//   uvm_store_out                 raw / tex store             fwd, fwd16
+//   UvmOutGrad + uvm_draw_tile / uvm_bwd_out_layer / uvm_fold_out_grad   draw tile, backward output layer, gwo / gbo fold   dgrad, dgrad16
+//   uvm_frag / uvm_src_k          fragment decode of the packed weights   the four pack kernels
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #define UVM_MAX_LAYERS 16
 #define UVM_EPAD 48       // padded embedding width of the 2-D field (42 -> 48)
 #define UVM_EPAD3 64      // ... of the 3-D field (63 -> 64); the plan carries the one in use
 #define UVM_TM 64         // texels per workgroup
+#define UVM16_TM 64       // ... of the split-fp16 kernels
+// The saved ReLU masks are [layer][64-texel tile][thread] u64 and are indexed by blockIdx / tile in every chain kernel, f32 or split.
+static_assert(UVM16_TM == UVM_TM, "forward and backward, f32 and split, index the saved ReLU masks by the same 64-texel tile");
 
 // Weight fragments of the NEXT k-block are fetched while the current one feeds the matrix pipe.  hipcc re-materialises a plain
 // C++ prefetch (it proves the carried value equals a load of this iteration's address and re-loads it at the loop top), so the
@@ -27,6 +45,149 @@ __device__ __forceinline__ int uvm_opaque(int k)
 {
     asm volatile("" : "+s"(k));
     return k;
+}
+
+// ---- split operands: x = hi + lo * 2^-11 with hi = rn16(x), lo = rn16((x - hi) * 2^11): 22 bits of mantissa in two fp16 numbers ----
+#define UVM_LO_SCALE 2048.0f            // 2^11
+#define UVM_LO_INV (1.0f / 2048.0f)
+__device__ __forceinline__ void uvm_split(float v, f16 &hi, f16 &lo)
+{
+    const f16 a = (f16)v;
+    hi = a;
+    lo = (f16)((v - (float)a) * UVM_LO_SCALE);
+}
+__device__ __forceinline__ float uvm_join(f16 hi, f16 lo) { return (float)hi + (float)lo * UVM_LO_INV; }
+__device__ __forceinline__ void uvm_split4(const float (&v)[4], f16x4 &hi, f16x4 &lo)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { f16 a, b; uvm_split(v[j], a, b); hi[j] = a; lo[j] = b; }
+}
+__device__ __forceinline__ float4 uvm_join4(const f16 *hi, const f16 *lo)   // four consecutive (8-byte aligned) elements of both planes
+{
+    const f16x4 vh = *(const f16x4 *)hi, vl = *(const f16x4 *)lo;
+    return make_float4(uvm_join(vh[0], vl[0]), uvm_join(vh[1], vl[1]), uvm_join(vh[2], vl[2]), uvm_join(vh[3], vl[3]));
+}
+__device__ __forceinline__ uint32_t uvm_split_packed(float v)               // hi | lo << 16: one register until the planes may be written
+{
+    f16 hi, lo;
+    uvm_split(v, hi, lo);
+    return (uint32_t)__builtin_bit_cast(unsigned short, hi) | ((uint32_t)__builtin_bit_cast(unsigned short, lo) << 16);
+}
+
+// ---- accumulator layout of the 32x32 MFMAs: element q of lane (r, h) of the tile whose first row is row0 (32 mb within a wave's 2 x 2
+// tiles (mb, nb)) sits at column nb*32 + r and this row ----
+__device__ __forceinline__ int uvm_acc_row(int row0, int q, int h) { return row0 + (q & 3) + 8 * (q >> 2) + 4 * h; }
+// ... and its ReLU pattern is this bit of the lane's u64 (what the forward saves is what the backward chain's tiles read)
+__device__ __forceinline__ int uvm_relu_bit(int nb, int mb, int q) { return (nb * 2 + mb) * 16 + q; }
+
+// a wave's outputs outv[nb][mb][q] (hi | lo << 16) to columns COL0 + [64 wave, 64 wave + 64) of the two planes; STRIDE in halves
+template <int STRIDE, int COL0>
+__device__ __forceinline__ void uvm_stage_planes(f16 *phi, f16 *plo, const uint32_t (&outv)[2][2][16], int wave, int r, int h)
+{
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+        const int col = wave * 64 + nb * 32 + r;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int o = uvm_acc_row(mb * 32, q, h) * STRIDE + COL0 + col;
+                ((unsigned short *)phi)[o] = (unsigned short)(outv[nb][mb][q] & 0xffffu);
+                ((unsigned short *)plo)[o] = (unsigned short)(outv[nb][mb][q] >> 16);
+            }
+    }
+}
+
+__device__ __forceinline__ void uvm_zero(f32x16 &a)
+{
+#pragma unroll
+    for (int q = 0; q < 16; ++q) a[q] = 0.f;
+}
+
+// ---- K-loop of the f32 pipe: acc[mb][nb] += A[rows 32 mb ..][k] . B[k][cols 32 nb ..] over k-blocks [kb0, kb1) (an even count) ----
+// wp: the lane's float4 of the layer's k-block 0, column block 2 wave (KBS float4 per k-block, the second column block 64 further);
+// arow0 / arow1: the lane's LDS rows r and r + 32 at the column of k-block 0 (+ 4h), so k-block kb is read at + 8 kb.
+template <int W>
+__device__ __forceinline__ void uvm_kloop_f32(f32x16 (&acc)[2][2], const float4 *wp, const float *arow0, const float *arow1, int kb0, int kb1)
+{
+    constexpr size_t KBS = (size_t)(W / 32) * 64;   // float4 per k-block
+    auto kstep = [&](int kb, const float4 &b0, const float4 &b1) {
+        float4 a0 = *(const float4 *)(arow0 + kb * 8);
+        float4 a1 = *(const float4 *)(arow1 + kb * 8);
+        const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
+        const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv0[j], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv1[j], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv0[j], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv1[j], acc[1][1], 0, 0, 0);
+        }
+    };
+    const float4 *p0 = wp + (size_t)kb0 * KBS;
+    float4 wa0 = p0[0], wa1 = p0[64], wb0, wb1;
+    for (int kb = kb0; kb < kb1; kb += 2) {          // every k-block range here has an even length
+        const float4 *pb = wp + (size_t)uvm_opaque(kb + 1) * KBS;
+        wb0 = pb[0]; wb1 = pb[64];
+        __builtin_amdgcn_sched_barrier(0);           // keep the prefetch above the MFMAs it hides under
+        kstep(kb, wa0, wa1);
+        const float4 *pa = wp + (size_t)uvm_opaque(kb + 2 < kb1 ? kb + 2 : kb) * KBS;
+        wa0 = pa[0]; wa1 = pa[64];
+        __builtin_amdgcn_sched_barrier(0);
+        kstep(kb + 1, wb0, wb1);
+    }
+}
+
+// ---- K-loop of the split pipe: one 32-column block of the wave against its two 32-row blocks, nkb 16-deep k-steps ----
+// A product a.w = ah.wh + 2^-11 (ah.wl + al.wh) + 2^-22 al.wl: the first three terms are three v_mfma_f32_32x32x16_f16 passes into TWO
+// fp32 accumulator sets (acc: main, acx: cross, to be joined as acc + acx * 2^-11), the last (relative 2^-22) is dropped.
+// wbase: the lane's 8 halves of weight block (k-step 0, this column block): block (kb, nbg) at ((kb * 8 + nbg) * 1024) halves, hi[64][8]
+// then lo[64][8].  ah_base / al_base: the lane's row r at the column of k-step 0 (+ 8h) in the hi / lo plane; STRIDE in halves.
+template <int STRIDE>
+__device__ __forceinline__ void uvm_kloop_split(f32x16 (&acc_io)[2], f32x16 (&acx_io)[2], const f16 *wbase, const f16 *ah_base, const f16 *al_base, int nkb)
+{
+    // The loop runs on local copies declared before the operand sets and hands them back at the end.  Inlined, that is no code at all,
+    // but it is the order the register allocator then sees them in: with the caller's arrays used directly, k_uvmlp_fwd16 comes out with
+    // 20 bytes/lane of scratch and 64 accumulator copies behind its odd tail; this way it has neither.
+    f32x16 acc[2] = {acc_io[0], acc_io[1]}, acx[2] = {acx_io[0], acx_io[1]};
+    f16x8 b0h, b0l, b1h, b1l, b2h, b2l;    // k-steps kb, kb+1, kb+2: two steps of prefetch (one wave per SIMD hides nothing)
+    auto load_b = [&](int kb, f16x8 &xh, f16x8 &xl) {
+        const f16 *p = wbase + (size_t)uvm_opaque(kb < nkb ? kb : nkb - 1) * 8 * 1024;
+        xh = *(const f16x8 *)(p); xl = *(const f16x8 *)(p + 512);
+    };
+    load_b(0, b0h, b0l); load_b(1, b1h, b1l);
+    f16x8 ah[2], al[2], nah[2], nal[2];
+    auto load_a = [&](int kb, f16x8 (&xh)[2], f16x8 (&xl)[2]) {
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            xh[mb] = *(const f16x8 *)(ah_base + mb * 32 * STRIDE + kb * 16);
+            xl[mb] = *(const f16x8 *)(al_base + mb * 32 * STRIDE + kb * 16);
+        }
+    };
+    load_a(0, ah, al);
+    // One k-step: the next step's activation fragments (LDS) and the weights two steps ahead (L2) are requested before this
+    // step's MFMAs issue — with one wave per SIMD nothing else covers their latency.  The loop walks two steps per trip over
+    // the two activation register sets (no copies); only the three small weight sets rotate.
+    auto step = [&](int kb, f16x8 (&ch)[2], f16x8 (&cl)[2], f16x8 (&nh)[2], f16x8 (&nl)[2]) {
+        load_b(kb + 2, b2h, b2l);
+        load_a(kb + 1 < nkb ? kb + 1 : kb, nh, nl);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0h, acc[mb], 0, 0, 0);
+            acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0l, acx[mb], 0, 0, 0);
+            acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[mb], b0h, acx[mb], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        b0h = b1h; b0l = b1l; b1h = b2h; b1l = b2l;
+    };
+    int kb = 0;
+    for (; kb + 2 <= nkb; kb += 2) {
+        step(kb, ah, al, nah, nal);
+        step(kb + 1, nah, nal, ah, al);
+    }
+    if (kb < nkb) step(kb, ah, al, nah, nal);       // K = 48 and 304 are an odd number of 16-deep steps; a constant even nkb has no tail
+    acc_io[0] = acc[0]; acc_io[1] = acc[1]; acx_io[0] = acx[0]; acx_io[1] = acx[1];
 }
 
 struct UvmLayer {
@@ -49,10 +210,17 @@ struct UvmPlan {
     int64_t wt16_off[UVM_MAX_LAYERS]; // layer i >= 1: wt_off's operand as two fp16 planes (backward chain of k_uvmlp_dgrad16), or -1
 };
 
+// the shapes every entry point accepts
+static inline bool uvm_envelope(int D, int W, int input_ch = 1 /* where the answer does not depend on it */)
+{
+    return D >= 1 && D <= UVM_MAX_LAYERS && W >= 64 && W % 64 == 0 && W <= 256 && input_ch >= 1 && input_ch <= UVM_EPAD3;
+}
+static inline int uvm_epad(int input_ch) { return input_ch <= UVM_EPAD ? UVM_EPAD : UVM_EPAD3; }
+
 static int uvm_build_plan(int D, int W, int input_ch, int output_ch, int skip, UvmPlan &p, int64_t &total)
 {
-    if (D < 1 || D > UVM_MAX_LAYERS || W % 64 != 0 || W > 256 || input_ch < 1 || input_ch > UVM_EPAD3 || output_ch < 1 || output_ch > 4) return -1;
-    const int EP = input_ch <= UVM_EPAD ? UVM_EPAD : UVM_EPAD3;
+    if (!uvm_envelope(D, W, input_ch) || output_ch < 1 || output_ch > 4) return -1;
+    const int EP = uvm_epad(input_ch);
     p.n_hidden = D; p.W = W; p.in_ch = input_ch; p.out_ch = output_ch; p.epad = EP; p.dims = 2;
     int64_t off = 0;
     for (int i = 0; i < D; ++i) {
@@ -80,6 +248,24 @@ static int uvm_build_plan(int D, int W, int input_ch, int output_ch, int skip, U
     return 0;
 }
 
+// The split-fp16 kernels serve the reference's texture field (2-D, W = 256, 48-wide embedding) unless the exact-f32 pipe is asked for.
+// The environment is read on every call: the switch may be flipped inside one process.
+static bool uvm_use_split16(const UvmPlan &p, int dims, bool backward)
+{
+    const char *ex = getenv("CTX_UVMLP_EXACT_F32");
+    bool fast = dims == 2 && p.W == 256 && p.epad == UVM_EPAD && !(ex && ex[0] == '1');
+    for (int i = backward ? 1 : 0; i < p.n_hidden && fast; ++i) fast = (backward ? p.wt16_off[i] : p.w16_off[i]) >= 0;
+    return fast;
+}
+
+// (W, EP) of a plan as compile-time constants: f(integral_constant<W>, integral_constant<EP>)
+template <int V> using uvm_c = std::integral_constant<int, V>;
+template <class F> static void uvm_dispatch(int W, int EP, F f)
+{
+    auto with_w = [&](auto w) { if (EP == UVM_EPAD) f(w, uvm_c<UVM_EPAD>{}); else f(w, uvm_c<UVM_EPAD3>{}); };
+    if (W == 256) with_w(uvm_c<256>{}); else if (W == 128) with_w(uvm_c<128>{}); else with_w(uvm_c<64>{});
+}
+
 extern "C" int64_t ctx_uvmlp_packed_bytes(int32_t D, int32_t W, int32_t input_ch, int32_t output_ch, int32_t skip)
 {
     UvmPlan p; int64_t total = 0;
@@ -87,27 +273,48 @@ extern "C" int64_t ctx_uvmlp_packed_bytes(int32_t D, int32_t W, int32_t input_ch
     return total * 4;
 }
 
+// ---- packed weights: B fragments of the 32x32 MFMAs, J values per lane and k-block (4: x2_f32 in four steps, 8: x16_f16) ----
+// Element idx of a packed layer = (block (kb, nb), lane (r, h), j): position k = kb*2J + J*h + j along the contraction, n = nb*32 + r across.
+struct UvmFrag { int64_t blk; int lane, j, k, n; };
+template <int J>
+__device__ __forceinline__ UvmFrag uvm_frag(int64_t idx, int W)
+{
+    UvmFrag f;
+    f.j = idx & (J - 1);
+    f.lane = ((uint64_t)idx / J) & 63;
+    f.blk = (uint64_t)idx / (64 * J);
+    const int nb = f.blk % (W / 32), kb = f.blk / (W / 32);
+    f.k = kb * 2 * J + J * (f.lane >> 5) + f.j;
+    f.n = nb * 32 + (f.lane & 31);
+    return f;
+}
+// padded LDS column k -> column of the nn.Linear weight (or -1: zero).  mode 0: first layer (embedding, padded to epad);
+// 1: skip layer (padded embedding, then the hidden vector); 2: plain hidden layer
+__device__ __forceinline__ int uvm_src_k(int mode, int k, int in_ch, int epad)
+{
+    if (mode == 2) return k;
+    if (mode == 0) return k < in_ch ? k : -1;
+    return k < in_ch ? k : (k < epad ? -1 : k - epad + in_ch);
+}
+__device__ __forceinline__ float uvm_src_w(const float *w, int kin, int n, int src_k) { return (src_k >= 0 && src_k < kin) ? w[(int64_t)n * kin + src_k] : 0.0f; }
+// a split element to block f.blk = hi[64 lanes][8] then lo[64 lanes][8]: one 16-byte load per lane and plane
+__device__ __forceinline__ void uvm_put16(f16 *dw, const UvmFrag &f, float v)
+{
+    f16 hi, lo;
+    uvm_split(v, hi, lo);
+    dw[f.blk * 1024 + f.lane * 8 + f.j] = hi;
+    dw[f.blk * 1024 + 512 + f.lane * 8 + f.j] = lo;
+}
+
 // src: nn.Linear weight [W][kin]; dst packed [(kb*(W/32)+nb)*64+lane][4] with
 // lane=(r,h): value j = weight[nb*32+r][map(kb*8+4h+j)].
 __global__ void k_uvm_pack(const float *__restrict__ w, const float *__restrict__ b, int W, int kin, int kp,
-                           int in_ch, int epad, int mode /*0 first,1 skip,2 plain*/, float *__restrict__ dw, float *__restrict__ db)
+                           int in_ch, int epad, int mode, float *__restrict__ dw, float *__restrict__ db)
 {
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    int64_t total = (int64_t)kp * W;
-    if (idx < total) {
-        int j = idx & 3;
-        int lane = (idx >> 2) & 63;
-        int64_t blk = idx >> 8;
-        int nb = blk % (W / 32);
-        int kb = blk / (W / 32);
-        int r = lane & 31, h = lane >> 5;
-        int k = kb * 8 + 4 * h + j;
-        int n = nb * 32 + r;
-        int src_k;
-        if (mode == 2) src_k = k;
-        else if (mode == 0) src_k = k < in_ch ? k : -1;
-        else src_k = k < in_ch ? k : (k < epad ? -1 : k - epad + in_ch);
-        dw[idx] = (src_k >= 0 && src_k < kin) ? w[(int64_t)n * kin + src_k] : 0.0f;
+    if (idx < (int64_t)kp * W) {
+        const UvmFrag f = uvm_frag<4>(idx, W);
+        dw[idx] = uvm_src_w(w, kin, f.n, uvm_src_k(mode, f.k, in_ch, epad));
     }
     if (idx < W) db[idx] = b[idx];
 }
@@ -118,54 +325,28 @@ __global__ void k_uvm_pack_t(const float *__restrict__ w, int W, int kin, int of
 {
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)W * W) return;
-    int j = idx & 3;
-    int lane = (idx >> 2) & 63;
-    int64_t blk = idx >> 8;
-    int nb = blk % (W / 32);
-    int kb = blk / (W / 32);
-    int r = lane & 31, h = lane >> 5;
-    int n = kb * 8 + 4 * h + j;
-    int k = nb * 32 + r;
-    dw[idx] = w[(int64_t)n * kin + off + k];
+    const UvmFrag f = uvm_frag<4>(idx, W);
+    dw[idx] = w[(int64_t)f.k * kin + off + f.n];
 }
 
-// fp16 split of the layer weights for k_uvmlp_fwd16: w = hi + lo * 2^-11 with hi = rn16(w), lo = rn16((w - hi) * 2^11): 22 bits of
-// mantissa in two fp16 planes.  Block (kb, nb) = hi[64 lanes][8] then lo[64 lanes][8]; lane (r, h) element j = w[nb*32 + r][map(kb*16 + 8h + j)]
-// — the B fragment of v_mfma_f32_32x32x16_f16, one 16-byte load per lane and plane.
+// fp16 split of the layer weights for k_uvmlp_fwd16: lane (r, h) element j = w[nb*32 + r][map(kb*16 + 8h + j)]
+// — the B fragment of v_mfma_f32_32x32x16_f16.
 __global__ void k_uvm_pack16(const float *__restrict__ w, int W, int kin, int kp, int in_ch, int epad, int mode, f16 *__restrict__ dw)
 {
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)kp * W) return;
-    const int j = idx & 7, lane = (idx >> 3) & 63;
-    const int64_t blk = idx >> 9;
-    const int nb = blk % (W / 32), kb = blk / (W / 32);
-    const int r = lane & 31, h = lane >> 5;
-    const int k = kb * 16 + 8 * h + j, n = nb * 32 + r;
-    int src_k;
-    if (mode == 2) src_k = k;
-    else if (mode == 0) src_k = k < in_ch ? k : -1;
-    else src_k = k < in_ch ? k : (k < epad ? -1 : k - epad + in_ch);
-    const float v = (src_k >= 0 && src_k < kin) ? w[(int64_t)n * kin + src_k] : 0.0f;
-    const f16 hi = (f16)v;
-    const f16 lo = (f16)((v - (float)hi) * 2048.0f);
-    dw[blk * 1024 + lane * 8 + j] = hi;
-    dw[blk * 1024 + 512 + lane * 8 + j] = lo;
+    const UvmFrag f = uvm_frag<8>(idx, W);
+    uvm_put16(dw, f, uvm_src_w(w, kin, f.n, uvm_src_k(mode, f.k, in_ch, epad)));
 }
 
-// backward-chain operand of k_uvmlp_dgrad16: block (kb over the contraction index n, nb over the output column k) = hi[64][8] | lo[64][8],
+// backward-chain operand of k_uvmlp_dgrad16: block (kb over the contraction index n, nb over the output column k),
 // lane (r, h) element j = w[kb*16 + 8h + j][off + nb*32 + r]
 __global__ void k_uvm_pack16_t(const float *__restrict__ w, int W, int kin, int off, f16 *__restrict__ dw)
 {
     int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)W * W) return;
-    const int j = idx & 7, lane = (idx >> 3) & 63;
-    const int64_t blk = idx >> 9;
-    const int nb = blk % (W / 32), kb = blk / (W / 32);
-    const int r = lane & 31, h = lane >> 5;
-    const float v = w[(int64_t)(kb * 16 + 8 * h + j) * kin + off + nb * 32 + r];
-    const f16 hi = (f16)v;
-    dw[blk * 1024 + lane * 8 + j] = hi;
-    dw[blk * 1024 + 512 + lane * 8 + j] = (f16)((v - (float)hi) * 2048.0f);
+    const UvmFrag f = uvm_frag<8>(idx, W);
+    uvm_put16(dw, f, w[(int64_t)f.k * kin + off + f.n]);
 }
 
 __global__ void k_uvm_pack_out(const float *__restrict__ w, const float *__restrict__ b, int W, int out_ch,
@@ -207,6 +388,50 @@ extern "C" int32_t ctx_uvmlp_pack(const float *const *ws, const float *const *bs
     return CTX_OK;
 }
 
+// ---- Fourier embedding: uvm_point yields a texel's coordinates, uvm_embed_col column e of its embedding ----
+struct UvmPoint { float x0, x1, x2; };
+// row n of uv (d = 2) / xyz (d = 3), or node n of the res x res atlas grid; zero past N and on the `emb` seam
+__device__ __forceinline__ UvmPoint uvm_point(const float *__restrict__ uv, const float *__restrict__ emb, int64_t n, int64_t N, int res, int d)
+{
+    UvmPoint p = {0.f, 0.f, 0.f};
+    if (n < N && !emb) {
+        if (uv) { p.x0 = uv[n * d + 0]; p.x1 = uv[n * d + 1]; if (d > 2) p.x2 = uv[n * d + 2]; }
+        else {
+            // torch.linspace(0,1,res): start + i*step for the first half, end - (res-1-i)*step after
+            int i = (int)(n / res), j = (int)(n % res);
+            float step = 1.0f / (float)(res - 1);
+            p.x0 = (j < res / 2) ? (float)j * step : 1.0f - (float)(res - 1 - j) * step;
+            p.x1 = (i < res / 2) ? (float)i * step : 1.0f - (float)(res - 1 - i) * step;
+        }
+    }
+    return p;
+}
+// column e of [x, sin(2^l x) (d), cos(2^l x) (d) per frequency l < L], zero from in_ch on; `emb` given: that row of it instead
+__device__ __forceinline__ float uvm_embed_col(const UvmPoint &p, const float *__restrict__ emb, int64_t n, int64_t N, int e, int d, int L, int in_ch)
+{
+    float val = 0.f;
+    if (emb) val = (e < in_ch && n < N) ? emb[n * in_ch + e] : 0.f;
+    else if (e < d) val = e == 0 ? p.x0 : (e == 1 ? p.x1 : p.x2);
+    else if (e < d * (1 + 2 * L)) {
+        int l = (e - d) / (2 * d), q = (e - d) % (2 * d);
+        int c = q % d;
+        float a = (c == 0 ? p.x0 : (c == 1 ? p.x1 : p.x2)) * (float)(1 << l);
+        val = (q >= d) ? cosf(a) : sinf(a);
+    }
+    return val;
+}
+
+// the forward output layer's result s[c] (before the bias) of texel n < N: raw [N][out_ch] and, for the atlas, (tanh + 1) / 2 as [out_ch][N]
+__device__ __forceinline__ void uvm_store_out(const float (&s)[4], const float *__restrict__ packed, const UvmPlan &plan, float *__restrict__ raw,
+                                              float *__restrict__ tex, int64_t n, int64_t N)
+{
+    for (int c = 0; c < plan.out_ch; ++c) {
+        float v = s[c] + packed[plan.out_b_off + c];
+        raw[n * plan.out_ch + c] = v;
+        if (tex) tex[(int64_t)c * N + n] = (tanhf(v) + 1.0f) / 2.0f;
+    }
+}
+
 template <int W, int EP>
 __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, const float *__restrict__ emb, int64_t N, int res, int L,
                                                  const float *__restrict__ packed, UvmPlan plan,
@@ -226,34 +451,12 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
     const int r = lane & 31, h = lane >> 5;
     const int64_t n0 = (int64_t)blockIdx.x * UVM_TM;
 
-    // ---- Fourier embedding into columns [0,EP) -------------------------------------------------
+    // ---- Fourier embedding into columns [0,EP): one texel per lane, the waves share the columns ----
     auto put_embedding = [&]() {
         int row = tid & 63;
         int64_t n = n0 + row;
-        const int d = plan.dims;
-        float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-        if (n < N && !emb) {
-            if (uv) { x0 = uv[n * d + 0]; x1 = uv[n * d + 1]; if (d > 2) x2 = uv[n * d + 2]; }
-            else {
-                // torch.linspace(0,1,res): start + i*step for the first half, end - (res-1-i)*step after
-                int i = (int)(n / res), j = (int)(n % res);
-                float step = 1.0f / (float)(res - 1);
-                x0 = (j < res / 2) ? (float)j * step : 1.0f - (float)(res - 1 - j) * step;
-                x1 = (i < res / 2) ? (float)i * step : 1.0f - (float)(res - 1 - i) * step;
-            }
-        }
-        for (int e = wave; e < EP; e += W / 64) {
-            float val = 0.f;
-            if (emb) val = (e < plan.in_ch && n < N) ? emb[n * plan.in_ch + e] : 0.f;
-            else if (e < d) val = e == 0 ? x0 : (e == 1 ? x1 : x2);
-            else if (e < d * (1 + 2 * L)) {
-                int l = (e - d) / (2 * d), q = (e - d) % (2 * d);      // [sin(2^l x) (d), cos(2^l x) (d)] per frequency
-                int c = q % d;
-                float a = (c == 0 ? x0 : (c == 1 ? x1 : x2)) * (float)(1 << l);
-                val = (q >= d) ? cosf(a) : sinf(a);
-            }
-            act[row * STRIDE + e] = val;
-        }
+        const UvmPoint pt = uvm_point(uv, emb, n, N, res, plan.dims);
+        for (int e = wave; e < EP; e += W / 64) act[row * STRIDE + e] = uvm_embed_col(pt, emb, n, N, e, plan.dims, L, plan.in_ch);
     };
     put_embedding();
     __syncthreads();
@@ -268,43 +471,12 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
     for (int li = 0; li < plan.n_hidden; ++li) {
         const UvmLayer ly = plan.layer[li];
         f32x16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
+        uvm_zero(acc[0][0]); uvm_zero(acc[0][1]); uvm_zero(acc[1][0]); uvm_zero(acc[1][1]);
         const float4 *wp = (const float4 *)(packed + ly.w_off) + ((size_t)(wave * 2) * 64 + lane);
-        constexpr size_t KBS = (size_t)(W / 32) * 64;   // float4 per k-block
         // k-blocks [kb0, kb1) of the layer's packed weights against LDS columns lc0 + 8 (kb - kb0) ...
         auto run_k = [&](int kb0, int kb1, int lc0) {
             const float *arow0 = act + r * STRIDE + lc0 + 4 * h - kb0 * 8;
-            const float *arow1 = arow0 + 32 * STRIDE;
-            auto kstep = [&](int kb, const float4 &b0, const float4 &b1) {
-                float4 a0 = *(const float4 *)(arow0 + kb * 8);
-                float4 a1 = *(const float4 *)(arow1 + kb * 8);
-                const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
-                const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv0[j], acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv1[j], acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv0[j], acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv1[j], acc[1][1], 0, 0, 0);
-                }
-            };
-            const float4 *p0 = wp + (size_t)kb0 * KBS;
-            float4 wa0 = p0[0], wa1 = p0[64], wb0, wb1;
-            for (int kb = kb0; kb < kb1; kb += 2) {          // every k-block range here has an even length
-                const float4 *pb = wp + (size_t)uvm_opaque(kb + 1) * KBS;
-                wb0 = pb[0]; wb1 = pb[64];
-                __builtin_amdgcn_sched_barrier(0);           // keep the prefetch above the MFMAs it hides under
-                kstep(kb, wa0, wa1);
-                const float4 *pa = wp + (size_t)uvm_opaque(kb + 2 < kb1 ? kb + 2 : kb) * KBS;
-                wa0 = pa[0]; wa1 = pa[64];
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(kb + 1, wb0, wb1);
-            }
+            uvm_kloop_f32<W>(acc, wp, arow0, arow0 + 32 * STRIDE, kb0, kb1);
         };
         if (!RC) run_k(0, ly.kp / 8, ly.col0);
         else if (ly.kp == EP + W) {                          // skip layer of the overlaid layout: hidden part, then embedding
@@ -316,7 +488,7 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
         } else run_k(0, ly.kp / 8, 0);
         __syncthreads();   // everyone has finished reading this layer's input
         const float *bias = packed + ly.b_off;
-        unsigned long long relu_bits = 0;   // bit (nb*2+mb)*16+q of this lane: its accumulator element is > 0
+        unsigned long long relu_bits = 0;   // bit uvm_relu_bit(nb, mb, q) of this lane: its accumulator element is > 0
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             int col = wave * 64 + nb * 32 + r;
@@ -325,10 +497,9 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    int row = mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
                     float v = acc[mb][nb][q] + bv;
-                    relu_bits |= (unsigned long long)(v > 0.f) << ((nb * 2 + mb) * 16 + q);
-                    act[row * STRIDE + HOFF + col] = v > 0.f ? v : 0.f;
+                    relu_bits |= (unsigned long long)(v > 0.f) << uvm_relu_bit(nb, mb, q);
+                    act[uvm_acc_row(mb * 32, q, h) * STRIDE + HOFF + col] = v > 0.f ? v : 0.f;
                 }
         }
         if (saved) {   // the ReLU pattern in the accumulator layout the backward chain's tiles have: [layer][tile][thread] u64
@@ -361,29 +532,20 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             for (int o = 1; o < PARTS; o <<= 1) s[c] += __shfl_xor(s[c], o, 64);
-        int64_t n = n0 + row;
-        if (part == 0 && n < N) {
-            for (int c = 0; c < plan.out_ch; ++c) {
-                float v = s[c] + packed[plan.out_b_off + c];
-                raw[n * plan.out_ch + c] = v;
-                if (tex) tex[(int64_t)c * N + n] = (tanhf(v) + 1.0f) / 2.0f;
-            }
-        }
+        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, n0 + row, N);
     }
 }
 
 
 // =====================================================================================================================
 // Fast forward of the 2-D texture field (W = 256): the same network on the 16-bit matrix pipe with SPLIT operands.
-// Every activation and weight is carried as two fp16 numbers, x = hi + lo * 2^-11 (hi = rn16(x), lo = rn16((x - hi) * 2^11)): 22 bits
-// of mantissa, i.e. fp32-grade operands.  A product a.w = ah.wh + 2^-11 (ah.wl + al.wh) + 2^-22 al.wl: the first three terms are three
-// v_mfma_f32_32x32x16_f16 passes into TWO fp32 accumulator sets (main, cross), the last (relative 2^-22) is dropped.  Per 16-deep k-step
-// that is 3 x 32 cycles against 8 x 64 for v_mfma_f32_32x32x2_f32: 5.3x the matrix rate at the f32 path's accuracy (measured against
-// the reference's vectors at the same tolerances; CTX_UVMLP_EXACT_F32=1 selects the exact-f32 kernel).
-// One workgroup = 128 texels, 4 waves; wave w owns hidden columns [64w, 64w+64) as 4 x 2 accumulator tiles of 32 x 32 (x 2 sets), one
-// wave per SIMD, so a weight fragment fetched from L2 serves 128 texels.  Activations live in LDS as two fp16 planes [128][312].
+// Every activation and weight is carried as two fp16 numbers (uvm_split): 22 bits of mantissa, i.e. fp32-grade operands; the product
+// is three v_mfma_f32_32x32x16_f16 passes into two fp32 accumulator sets (uvm_kloop_split).  Per 16-deep k-step that is 3 x 32 cycles
+// against 8 x 64 for v_mfma_f32_32x32x2_f32: 5.3x the matrix rate at the f32 path's accuracy (measured against the reference's vectors
+// at the same tolerances; CTX_UVMLP_EXACT_F32=1 selects the exact-f32 kernel).
+// One workgroup = 64 texels, 4 waves, two workgroups per CU; wave w owns hidden columns [64w, 64w+64) as 2 x 2 accumulator tiles of
+// 32 x 32 (x 2 sets), one 32-column block at a time.  Activations live in LDS as two fp16 planes, [64][hi 312 | lo 312 | pad 8].
 // `saved` gets what k_uvmlp_fwd leaves (embedding, post-ReLU activations as hi + lo * 2^-11, ReLU bit masks per 64-texel tile).
-#define UVM16_TM 64
 #define UVM16_LO 312              // halves: a row's lo plane sits this far behind its hi plane (48 + 256 + 8)
 #define UVM16_STRIDE 632          // halves per row PAIR (hi | lo): 1264 bytes = 16 x odd -> conflict-free ds_read_b128 over 16 rows, and
                                   // the lo plane within the 16-bit immediate offset of every DS access to the hi plane
@@ -392,50 +554,25 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
                                                      float *__restrict__ raw, float *__restrict__ tex, float *__restrict__ saved)
 {
     constexpr int W = 256, EP = UVM_EPAD, STRIDE = UVM16_STRIDE;
-    extern __shared__ __attribute__((aligned(16))) f16 pl[];      // [128 rows][hi 312 | lo 312 | pad 8] halves
+    extern __shared__ __attribute__((aligned(16))) f16 pl[];      // [64 rows][hi 312 | lo 312 | pad 8] halves
     f16 *phi = pl, *plo = pl + UVM16_LO;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int64_t n0 = (int64_t)blockIdx.x * UVM16_TM;
-    auto put = [&](int row, int col, float v) {
-        const f16 hi = (f16)v;
-        phi[row * STRIDE + col] = hi;
-        plo[row * STRIDE + col] = (f16)((v - (float)hi) * 2048.0f);
-    };
-    auto get = [&](int row, int col) { return (float)phi[row * STRIDE + col] + (float)plo[row * STRIDE + col] * (1.0f / 2048.0f); };
 
     // ---- Fourier embedding into columns [0,48): four threads per texel, 12 columns each ------------------------------
     {
-        const int row = tid >> 2, half = tid & 3;
+        const int row = tid >> 2, quarter = tid & 3;
         const int64_t n = n0 + row;
-        const int d = plan.dims;
-        float x0 = 0.f, x1 = 0.f;
-        if (n < N && !emb) {
-            if (uv) { x0 = uv[n * d + 0]; x1 = uv[n * d + 1]; }
-            else {
-                int i = (int)(n / res), j = (int)(n % res);
-                float step = 1.0f / (float)(res - 1);
-                x0 = (j < res / 2) ? (float)j * step : 1.0f - (float)(res - 1 - j) * step;
-                x1 = (i < res / 2) ? (float)i * step : 1.0f - (float)(res - 1 - i) * step;
-            }
-        }
-        for (int e = half * (EP / 4); e < (half + 1) * (EP / 4); ++e) {
-            float val = 0.f;
-            if (emb) val = (e < plan.in_ch && n < N) ? emb[n * plan.in_ch + e] : 0.f;
-            else if (e < d) val = e == 0 ? x0 : x1;
-            else if (e < d * (1 + 2 * L)) {
-                int l = (e - d) / (2 * d), q = (e - d) % (2 * d);
-                float a = ((q % d) == 0 ? x0 : x1) * (float)(1 << l);
-                val = (q >= d) ? cosf(a) : sinf(a);
-            }
-            put(row, e, val);
-        }
+        const UvmPoint pt = uvm_point(uv, emb, n, N, res, plan.dims);
+        for (int e = quarter * (EP / 4); e < (quarter + 1) * (EP / 4); ++e)
+            uvm_split(uvm_embed_col(pt, emb, n, N, e, plan.dims, L, plan.in_ch), phi[row * STRIDE + e], plo[row * STRIDE + e]);
     }
     __syncthreads();
     if (saved) {
         for (int i = tid; i < UVM16_TM * EP; i += 256) {
             int row = i / EP, c = i % EP;
-            if (n0 + row < N) saved[(n0 + row) * EP + c] = get(row, c);
+            if (n0 + row < N) saved[(n0 + row) * EP + c] = uvm_join(phi[row * STRIDE + c], plo[row * STRIDE + c]);
         }
     }
 
@@ -450,75 +587,21 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {           // the wave's two 32-column blocks one after the other: 64 accumulator registers
             f32x16 acc[2], acx[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) { acc[a][q] = 0.f; acx[a][q] = 0.f; }
-            // weight fragments: block (kb, nbg) at ((kb * 8 + nbg) * 1024) halves, hi[64][8] then lo[64][8]
+            uvm_zero(acc[0]); uvm_zero(acx[0]); uvm_zero(acc[1]); uvm_zero(acx[1]);
             const f16 *wbase = (const f16 *)(packed + plan.w16_off[li]) + (size_t)(wave * 2 + nb) * 1024 + lane * 8;
-            f16x8 b0h, b0l, b1h, b1l, b2h, b2l;    // k-steps kb, kb+1, kb+2: two steps of prefetch (one wave per SIMD hides nothing)
-            auto load_b = [&](int kb, f16x8 &xh, f16x8 &xl) {
-                const f16 *p = wbase + (size_t)uvm_opaque(kb < nkb ? kb : nkb - 1) * 8 * 1024;
-                xh = *(const f16x8 *)(p); xl = *(const f16x8 *)(p + 512);
-            };
-            load_b(0, b0h, b0l); load_b(1, b1h, b1l);
-            f16x8 ah[2], al[2], nah[2], nal[2];
-            auto load_a = [&](int kb, f16x8 (&xh)[2], f16x8 (&xl)[2]) {
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    xh[mb] = *(const f16x8 *)(ah_base + mb * 32 * STRIDE + kb * 16);
-                    xl[mb] = *(const f16x8 *)(al_base + mb * 32 * STRIDE + kb * 16);
-                }
-            };
-            load_a(0, ah, al);
-            // One k-step: the next step's activation fragments (LDS) and the weights two steps ahead (L2) are requested before this
-            // step's MFMAs issue — with one wave per SIMD nothing else covers their latency.  The loop walks two steps per trip over
-            // the two activation register sets (no copies); only the three small weight sets rotate.
-            auto step = [&](int kb, f16x8 (&ch)[2], f16x8 (&cl)[2], f16x8 (&nh)[2], f16x8 (&nl)[2]) {
-                load_b(kb + 2, b2h, b2l);
-                load_a(kb + 1 < nkb ? kb + 1 : kb, nh, nl);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0h, acc[mb], 0, 0, 0);
-                    acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0l, acx[mb], 0, 0, 0);
-                    acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[mb], b0h, acx[mb], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                b0h = b1h; b0l = b1l; b1h = b2h; b1l = b2l;
-            };
-            int kb = 0;
-            for (; kb + 2 <= nkb; kb += 2) {
-                step(kb, ah, al, nah, nal);
-                step(kb + 1, nah, nal, ah, al);
-            }
-            if (kb < nkb) step(kb, ah, al, nah, nal);       // K = 48 and 304 are an odd number of 16-deep steps
+            uvm_kloop_split<STRIDE>(acc, acx, wbase, ah_base, al_base, nkb);
             const float bv = bias[wave * 64 + nb * 32 + r];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const float v = acc[mb][q] + acx[mb][q] * (1.0f / 2048.0f) + bv;
-                    bits0 |= (unsigned long long)(v > 0.f) << ((nb * 2 + mb) * 16 + q);
-                    const float y = v > 0.f ? v : 0.f;
-                    const f16 yh = (f16)y;
-                    const f16 yl = (f16)((y - (float)yh) * 2048.0f);
-                    outv[nb][mb][q] = (uint32_t)__builtin_bit_cast(unsigned short, yh) | ((uint32_t)__builtin_bit_cast(unsigned short, yl) << 16);
+                    const float v = acc[mb][q] + acx[mb][q] * UVM_LO_INV + bv;
+                    bits0 |= (unsigned long long)(v > 0.f) << uvm_relu_bit(nb, mb, q);
+                    outv[nb][mb][q] = uvm_split_packed(v > 0.f ? v : 0.f);
                 }
         }
         __syncthreads();                       // everyone has finished reading this layer's input
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int col = wave * 64 + nb * 32 + r;
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int o = (mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * STRIDE + EP + col;
-                    ((unsigned short *)phi)[o] = (unsigned short)(outv[nb][mb][q] & 0xffffu);
-                    ((unsigned short *)plo)[o] = (unsigned short)(outv[nb][mb][q] >> 16);
-                }
-        }
+        uvm_stage_planes<STRIDE, EP>(phi, plo, outv, wave, r, h);
         if (saved) {
             unsigned long long *mk = (unsigned long long *)(saved + N * (int64_t)(EP + plan.n_hidden * W));
             mk[((int64_t)li * gridDim.x + blockIdx.x) * W + tid] = bits0;
@@ -528,13 +611,7 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
             float *dst = saved + N * EP + (int64_t)li * N * W;
             for (int i = tid; i < UVM16_TM * (W / 4); i += 256) {
                 const int row = i / (W / 4), c4 = i % (W / 4);
-                if (n0 + row < N) {
-                    const f16x4 vh = *(const f16x4 *)(phi + row * STRIDE + EP + c4 * 4), vl = *(const f16x4 *)(plo + row * STRIDE + EP + c4 * 4);
-                    float4 o;
-                    o.x = (float)vh[0] + (float)vl[0] * (1.0f / 2048.0f); o.y = (float)vh[1] + (float)vl[1] * (1.0f / 2048.0f);
-                    o.z = (float)vh[2] + (float)vl[2] * (1.0f / 2048.0f); o.w = (float)vh[3] + (float)vl[3] * (1.0f / 2048.0f);
-                    *(float4 *)(dst + (n0 + row) * W + c4 * 4) = o;
-                }
+                if (n0 + row < N) *(float4 *)(dst + (n0 + row) * W + c4 * 4) = uvm_join4(phi + row * STRIDE + EP + c4 * 4, plo + row * STRIDE + EP + c4 * 4);
             }
         }
     }
@@ -548,7 +625,7 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
             const f16x8 vh = *(const f16x8 *)(phi + row * STRIDE + EP + part * 64 + k), vl = *(const f16x8 *)(plo + row * STRIDE + EP + part * 64 + k);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float x = (float)vh[j] + (float)vl[j] * (1.0f / 2048.0f);
+                const float x = uvm_join(vh[j], vl[j]);
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     if (c < plan.out_ch) s[c] += x * ow[c * W + k + j];
@@ -556,22 +633,13 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) { s[c] += __shfl_xor(s[c], 1, 64); s[c] += __shfl_xor(s[c], 2, 64); }
-        const int64_t n = n0 + row;
-        if (part == 0 && n < N) {
-            for (int c = 0; c < plan.out_ch; ++c) {
-                float v = s[c] + packed[plan.out_b_off + c];
-                raw[n * plan.out_ch + c] = v;
-                if (tex) tex[(int64_t)c * N + n] = (tanhf(v) + 1.0f) / 2.0f;
-            }
-        }
+        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, n0 + row, N);
     }
 }
 
-static inline int uvm_epad(int input_ch) { return input_ch <= UVM_EPAD ? UVM_EPAD : UVM_EPAD3; }
-
 extern "C" int64_t ctx_uvmlp_saved_bytes(int64_t N, int32_t D, int32_t W, int32_t input_ch)
 {
-    if (N <= 0 || D < 1 || D > UVM_MAX_LAYERS || W % 64 != 0 || W > 256 || input_ch < 1 || input_ch > UVM_EPAD3) return -1;
+    if (N <= 0 || !uvm_envelope(D, W, input_ch)) return -1;
     return N * (int64_t)(uvm_epad(input_ch) + D * W) * 4 + (int64_t)D * cdiv64(N, UVM_TM) * W * 8;   // + ReLU bit masks
 }
 
@@ -590,33 +658,20 @@ extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t
                 "uvmlp_fwd: unsupported D=%d W=%d dims=%d L=%d output_ch=%d", D, W, dims, L, output_ch);
     p.dims = dims;
     hipStream_t s = (hipStream_t)stream;
-    unsigned grid = (unsigned)cdiv64(N, UVM_TM);
-    size_t lds = (size_t)UVM_TM * ((p.epad == UVM_EPAD ? UVM_EPAD : 0) + W + 4) * 4;   // the 3-D layout overlays the embedding
     const float *pk = (const float *)packed;
-    {
-        // the split-fp16 kernel for the reference's texture field (2-D, W = 256) unless the exact-f32 pipe is asked for
-        const char *ex = getenv("CTX_UVMLP_EXACT_F32");
-        bool fast = dims == 2 && W == 256 && p.epad == UVM_EPAD && !(ex && ex[0] == '1');
-        for (int i = 0; i < D && fast; ++i) fast = p.w16_off[i] >= 0;
-        if (fast) {
-            const size_t lds16 = (size_t)UVM16_TM * UVM16_STRIDE * sizeof(f16);
-            (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-            hipLaunchKernelGGL(k_uvmlp_fwd16, dim3((unsigned)cdiv64(N, UVM16_TM)), dim3(256), lds16, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved);
-            CTX_CHECK_LAUNCH("uvmlp_fwd16");
-            return CTX_OK;
-        }
+    if (uvm_use_split16(p, dims, false)) {
+        const size_t lds16 = (size_t)UVM16_TM * UVM16_STRIDE * sizeof(f16);
+        (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
+        hipLaunchKernelGGL(k_uvmlp_fwd16, dim3((unsigned)cdiv64(N, UVM16_TM)), dim3(256), lds16, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved);
+        CTX_CHECK_LAUNCH("uvmlp_fwd16");
+        return CTX_OK;
     }
-#define UVM_FWD(WW, EE)                                                                                                     \
-    do {                                                                                                                    \
-        (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd<WW, EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_uvmlp_fwd<WW, EE>), dim3(grid), dim3(WW), lds, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved); \
-    } while (0)
-    if (p.epad == UVM_EPAD) {
-        if (W == 256) UVM_FWD(256, UVM_EPAD); else if (W == 128) UVM_FWD(128, UVM_EPAD); else UVM_FWD(64, UVM_EPAD);
-    } else {
-        if (W == 256) UVM_FWD(256, UVM_EPAD3); else if (W == 128) UVM_FWD(128, UVM_EPAD3); else UVM_FWD(64, UVM_EPAD3);
-    }
-#undef UVM_FWD
+    uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
+        constexpr int WW = decltype(w)::value, EE = decltype(ep)::value;
+        const size_t lds = (size_t)UVM_TM * ((EE == UVM_EPAD ? UVM_EPAD : 0) + WW + 4) * 4;   // the 3-D layout overlays the embedding
+        (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd<WW, EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((k_uvmlp_fwd<WW, EE>), dim3((unsigned)cdiv64(N, UVM_TM)), dim3(WW), lds, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved);
+    });
     CTX_CHECK_LAUNCH("uvmlp_fwd");
     return CTX_OK;
 }
@@ -646,6 +701,100 @@ extern "C" int32_t ctx_uvmlp_fwd(const float *uv, const float *emb, int64_t N, i
 #define UVM_WG_GROUPS_EMB 768   // the 48-column embedding gradients run 3 workgroups per CU
 #define UVM_DGRAD_GRID 512      // persistent dgrad workgroups (2 per CU)
 
+// ---- what the two dZ-chain kernels share around their K-loops.  W threads; thread (rg, c4) = (row group of 4, float4 column) of a W-wide row ----
+struct UvmOutGrad {      // a thread's share of the output layer
+    float wo[4][4];      // Wout[c][4 c4 + j] (zero from out_ch on)
+    float gwo[4][4];     // the gradient of those weights, summed over the thread's rows
+    float gbo;           // the gradient of the bias of channel tid & 3, summed over the thread's draw elements
+};
+template <int W>
+__device__ __forceinline__ void uvm_out_grad_init(UvmOutGrad &og, const float *__restrict__ packed, const UvmPlan &plan, int c4)
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            og.wo[c][j] = c < plan.out_ch ? packed[plan.out_w_off + c * W + c4 * 4 + j] : 0.f;
+            og.gwo[c][j] = 0.f;
+        }
+    og.gbo = 0.f;
+}
+// d loss / d raw of the tile's 64 texels -> dr[64][4]: grad_raw + grad_tex . d((tanh + 1) / 2)
+template <int W>
+__device__ __forceinline__ void uvm_draw_tile(float *dr, UvmOutGrad &og, const float *__restrict__ grad_raw, const float *__restrict__ grad_tex,
+                                              const float *__restrict__ raw, int64_t N, int64_t n0, int out_ch, int tid)
+{
+    for (int i = tid; i < UVM_TM * 4; i += W) {
+        int t = i >> 2, c = i & 3;
+        int64_t n = n0 + t;
+        float v = 0.f;
+        if (n < N && c < out_ch) {
+            if (grad_raw) v = grad_raw[n * out_ch + c];
+            if (grad_tex) {
+                float y = tanhf(raw[n * out_ch + c]);
+                v += grad_tex[(int64_t)c * N + n] * 0.5f * (1.0f - y * y);
+            }
+        }
+        dr[i] = v;
+        og.gbo += v;
+    }
+}
+// output layer on the VALU (f32): dA = draw . Wout, dWout += draw^T . A, dZ = dA * (A > 0) -> HBM; put(t, o) leaves the thread's four
+// columns o[0..3] of row t in LDS in the form the chain's K-loop reads
+template <int W, class Put>
+__device__ __forceinline__ void uvm_bwd_out_layer(UvmOutGrad &og, const float *dr, const float *__restrict__ a_top, float *__restrict__ dz_top,
+                                                  int64_t N, int64_t n0, int rg, int c4, Put put)
+{
+#pragma unroll 4
+    for (int p = 0; p < UVM_TM / 4; ++p) {
+        int t = p * 4 + rg;
+        int64_t n = n0 + t;
+        int64_t nc = n < N ? n : N - 1;
+        float4 a = *(const float4 *)(a_top + nc * W + c4 * 4);
+        float4 d = *(const float4 *)(dr + t * 4);
+        const float av[4] = {a.x, a.y, a.z, a.w}, dv[4] = {d.x, d.y, d.z, d.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float da = dv[0] * og.wo[0][j];
+            da = fmaf(dv[1], og.wo[1][j], da);
+            da = fmaf(dv[2], og.wo[2][j], da);
+            da = fmaf(dv[3], og.wo[3][j], da);
+            o[j] = av[j] > 0.f ? da : 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) og.gwo[c][j] = fmaf(dv[c], av[j], og.gwo[c][j]);
+        }
+        put(t, o);
+        if (n < N) *(float4 *)(dz_top + n * W + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+// output-layer gradients of this workgroup: fold the 4 row groups through gf[16][W], one partial row per channel; dr is scratch for the bias
+template <int W>
+__device__ __forceinline__ void uvm_fold_out_grad(const UvmOutGrad &og, float *gf, float *dr, float *__restrict__ part_w /*[grid][4][W]*/,
+                                                  float *__restrict__ part_b /*[grid][4]*/, int tid, int rg, int c4)
+{
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gf[(rg * 4 + c) * W + c4 * 4 + j] = og.gwo[c][j];
+    __syncthreads();
+    for (int c = 0; c < 4; ++c) {
+        float s = gf[(0 * 4 + c) * W + tid];
+        s += gf[(1 * 4 + c) * W + tid];
+        s += gf[(2 * 4 + c) * W + tid];
+        s += gf[(3 * 4 + c) * W + tid];
+        part_w[((int64_t)blockIdx.x * 4 + c) * W + tid] = s;
+    }
+    dr[tid] = og.gbo;
+    __syncthreads();
+    if (tid < 4) {
+        float s = 0.f;
+        for (int i = tid; i < W; i += 4) s += dr[i];
+        part_b[(int64_t)blockIdx.x * 4 + tid] = s;
+    }
+}
+
 template <int W>
 __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ grad_raw, const float *__restrict__ grad_tex,
                                                    const float *__restrict__ raw, int64_t N, const float *__restrict__ packed,
@@ -663,104 +812,26 @@ __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ 
     const int D = plan.n_hidden;
     const float *acts = saved + N * plan.epad;
     const unsigned long long *masks = (const unsigned long long *)(saved + N * (int64_t)(plan.epad + D * W));
-
-    float wo[4][4], gwo[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wo[c][j] = c < plan.out_ch ? packed[plan.out_w_off + c * W + c4 * 4 + j] : 0.f;
-            gwo[c][j] = 0.f;
-        }
-    float gbo = 0.f;                            // this thread's channel is tid & 3
+    UvmOutGrad og;
+    uvm_out_grad_init<W>(og, packed, plan, c4);
 
     const int64_t ntiles = (N + UVM_TM - 1) / UVM_TM;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t n0 = tile * UVM_TM;
-        // ---- d loss / d raw for the tile's 64 texels --------------------------------------------
-        for (int i = tid; i < UVM_TM * 4; i += W) {
-            int t = i >> 2, c = i & 3;
-            int64_t n = n0 + t;
-            float v = 0.f;
-            if (n < N && c < plan.out_ch) {
-                if (grad_raw) v = grad_raw[n * plan.out_ch + c];
-                if (grad_tex) {
-                    float y = tanhf(raw[n * plan.out_ch + c]);
-                    v += grad_tex[(int64_t)c * N + n] * 0.5f * (1.0f - y * y);
-                }
-            }
-            dr[i] = v;
-            gbo += v;
-        }
+        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, N, n0, plan.out_ch, tid);
         __syncthreads();
-        // ---- output layer: dA = draw . Wout, dWout += draw^T . A, dZ = dA * (A > 0) -----------
-        {
-            const float *a_top = acts + (int64_t)(D - 1) * N * W;
-            float *dz_top = dz + (int64_t)(D - 1) * N * W;
-#pragma unroll 4
-            for (int p = 0; p < UVM_TM / 4; ++p) {
-                int t = p * 4 + rg;
-                int64_t n = n0 + t;
-                int64_t nc = n < N ? n : N - 1;
-                float4 a = *(const float4 *)(a_top + nc * W + c4 * 4);
-                float4 d = *(const float4 *)(dr + t * 4);
-                const float av[4] = {a.x, a.y, a.z, a.w}, dv[4] = {d.x, d.y, d.z, d.w};
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float da = dv[0] * wo[0][j];
-                    da = fmaf(dv[1], wo[1][j], da);
-                    da = fmaf(dv[2], wo[2][j], da);
-                    da = fmaf(dv[3], wo[3][j], da);
-                    o[j] = av[j] > 0.f ? da : 0.f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) gwo[c][j] = fmaf(dv[c], av[j], gwo[c][j]);
-                }
-                float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-                *(float4 *)(g + t * STRIDE + c4 * 4) = ov;
-                if (n < N) *(float4 *)(dz_top + n * W + c4 * 4) = ov;
-            }
-        }
+        uvm_bwd_out_layer<W>(og, dr, acts + (int64_t)(D - 1) * N * W, dz + (int64_t)(D - 1) * N * W, N, n0, rg, c4,
+                             [&](int t, const float (&o)[4]) { *(float4 *)(g + t * STRIDE + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]); });
         __syncthreads();
         // ---- hidden layers, last to second ------------------------------------------------------
         for (int li = D - 1; li >= 1; --li) {
             float *dz_prev = dz + (int64_t)(li - 1) * N * W;
             const unsigned long long relu_bits = masks[((int64_t)(li - 1) * ntiles + tile) * W + tid];
             f32x16 acc[2][2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
+            uvm_zero(acc[0][0]); uvm_zero(acc[0][1]); uvm_zero(acc[1][0]); uvm_zero(acc[1][1]);
             const float4 *wp = (const float4 *)(packed + plan.wt_off[li]) + ((size_t)(wave * 2) * 64 + lane);
             const float *arow0 = g + r * STRIDE + 4 * h;
-            const float *arow1 = arow0 + 32 * STRIDE;
-            auto kstep = [&](int kb, const float4 &b0, const float4 &b1) {
-                float4 a0 = *(const float4 *)(arow0 + kb * 8);
-                float4 a1 = *(const float4 *)(arow1 + kb * 8);
-                const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
-                const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv0[j], acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], bv1[j], acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv0[j], acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], bv1[j], acc[1][1], 0, 0, 0);
-                }
-            };
-            constexpr size_t KBS = (size_t)(W / 32) * 64;
-            float4 wa0 = wp[0], wa1 = wp[64], wb0, wb1;
-            for (int kb = 0; kb < W / 8; kb += 2) {
-                const float4 *pb = wp + (size_t)uvm_opaque(kb + 1) * KBS;
-                wb0 = pb[0]; wb1 = pb[64];
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(kb, wa0, wa1);
-                const float4 *pa = wp + (size_t)uvm_opaque(kb + 2 < W / 8 ? kb + 2 : kb) * KBS;
-                wa0 = pa[0]; wa1 = pa[64];
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(kb + 1, wb0, wb1);
-            }
+            uvm_kloop_f32<W>(acc, wp, arow0, arow0 + 32 * STRIDE, 0, W / 8);
             __syncthreads();                     // all fragment reads of dZ_li (and the row copies of it below) are done
             // dZ_{li-1} = dA_{li-1} * relu'(layer li-1): the forward left the pattern in this very accumulator layout
 #pragma unroll
@@ -770,9 +841,8 @@ __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ 
                 for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        int row = mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                        bool on = (relu_bits >> ((nb * 2 + mb) * 16 + q)) & 1ull;
-                        g[row * STRIDE + col] = on ? acc[mb][nb][q] : 0.f;
+                        bool on = (relu_bits >> uvm_relu_bit(nb, mb, q)) & 1ull;
+                        g[uvm_acc_row(mb * 32, q, h) * STRIDE + col] = on ? acc[mb][nb][q] : 0.f;
                     }
             }
             __syncthreads();
@@ -786,27 +856,7 @@ __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ 
         }
         __syncthreads();                         // the last row copies read g before the next tile overwrites it
     }
-    // ---- output-layer gradients of this workgroup: fold the 4 row groups, one partial row per channel ----
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g[(rg * 4 + c) * W + c4 * 4 + j] = gwo[c][j];
-    __syncthreads();
-    for (int c = 0; c < 4; ++c) {
-        float s = g[(0 * 4 + c) * W + tid];
-        s += g[(1 * 4 + c) * W + tid];
-        s += g[(2 * 4 + c) * W + tid];
-        s += g[(3 * 4 + c) * W + tid];
-        part_w[((int64_t)blockIdx.x * 4 + c) * W + tid] = s;
-    }
-    dr[tid] = gbo;
-    __syncthreads();
-    if (tid < 4) {
-        float s = 0.f;
-        for (int i = tid; i < W; i += 4) s += dr[i];
-        part_b[(int64_t)blockIdx.x * 4 + tid] = s;
-    }
+    uvm_fold_out_grad<W>(og, g, dr, part_w, part_b, tid, rg, c4);
 }
 
 // ---- the dZ chain on the 16-bit matrix pipe with split operands (the backward twin of k_uvmlp_fwd16) ---------------------------------
@@ -860,67 +910,23 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_dgrad16(const float *__restric
     const float *acts = saved + N * plan.epad;
     const unsigned long long *masks = (const unsigned long long *)(saved + N * (int64_t)(plan.epad + D * W));
     const int e = ctl->e;
-
-    float wo[4][4], gwo[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wo[c][j] = c < plan.out_ch ? packed[plan.out_w_off + c * W + c4 * 4 + j] : 0.f;
-            gwo[c][j] = 0.f;
-        }
-    float gbo = 0.f;
+    UvmOutGrad og;
+    uvm_out_grad_init<W>(og, packed, plan, c4);
 
     const int64_t ntiles = (N + UVM_TM - 1) / UVM_TM;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t n0 = tile * UVM_TM;
-        for (int i = tid; i < UVM_TM * 4; i += 256) {
-            int t = i >> 2, c = i & 3;
-            int64_t n = n0 + t;
-            float v = 0.f;
-            if (n < N && c < plan.out_ch) {
-                if (grad_raw) v = grad_raw[n * plan.out_ch + c];
-                if (grad_tex) {
-                    float y = tanhf(raw[n * plan.out_ch + c]);
-                    v += grad_tex[(int64_t)c * N + n] * 0.5f * (1.0f - y * y);
-                }
-            }
-            dr[i] = v;
-            gbo += v;
-        }
+        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, N, n0, plan.out_ch, tid);
         __syncthreads();
-        // ---- output layer on the VALU (f32): dA = draw . Wout, dWout += draw^T . A, dZ = dA * (A > 0) -> HBM as is, LDS scaled and split
-        {
-            const float *a_top = acts + (int64_t)(D - 1) * N * W;
-            float *dz_top = dz + (int64_t)(D - 1) * N * W;
-#pragma unroll 4
-            for (int p = 0; p < UVM_TM / 4; ++p) {
-                int t = p * 4 + rg;
-                int64_t n = n0 + t;
-                int64_t nc = n < N ? n : N - 1;
-                float4 a = *(const float4 *)(a_top + nc * W + c4 * 4);
-                float4 d = *(const float4 *)(dr + t * 4);
-                const float av[4] = {a.x, a.y, a.z, a.w}, dv[4] = {d.x, d.y, d.z, d.w};
-                float o[4];
-                f16x4 oh, ol;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float da = dv[0] * wo[0][j];
-                    da = fmaf(dv[1], wo[1][j], da);
-                    da = fmaf(dv[2], wo[2][j], da);
-                    da = fmaf(dv[3], wo[3][j], da);
-                    o[j] = av[j] > 0.f ? da : 0.f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) gwo[c][j] = fmaf(dv[c], av[j], gwo[c][j]);
-                    const float sv = ldexpf(o[j], e);
-                    oh[j] = (f16)sv;
-                    ol[j] = (f16)((sv - (float)oh[j]) * 2048.0f);
-                }
-                *(f16x4 *)(ghi + t * STRIDE + c4 * 4) = oh;
-                *(f16x4 *)(glo + t * STRIDE + c4 * 4) = ol;
-                if (n < N) *(float4 *)(dz_top + n * W + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-        }
+        // dZ of the output layer goes to HBM as it is, to LDS scaled and split
+        uvm_bwd_out_layer<W>(og, dr, acts + (int64_t)(D - 1) * N * W, dz + (int64_t)(D - 1) * N * W, N, n0, rg, c4,
+                             [&](int t, const float (&o)[4]) {
+                                 const float sv[4] = {ldexpf(o[0], e), ldexpf(o[1], e), ldexpf(o[2], e), ldexpf(o[3], e)};
+                                 f16x4 oh, ol;
+                                 uvm_split4(sv, oh, ol);
+                                 *(f16x4 *)(ghi + t * STRIDE + c4 * 4) = oh;
+                                 *(f16x4 *)(glo + t * STRIDE + c4 * 4) = ol;
+                             });
         __syncthreads();
         // ---- hidden layers, last to second ------------------------------------------------------------------------------
         for (int li = D - 1; li >= 1; --li) {
@@ -931,68 +937,19 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_dgrad16(const float *__restric
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 f32x16 acc[2], acx[2];
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) { acc[a][q] = 0.f; acx[a][q] = 0.f; }
+                uvm_zero(acc[0]); uvm_zero(acx[0]); uvm_zero(acc[1]); uvm_zero(acx[1]);
                 const f16 *wbase = (const f16 *)(packed + plan.wt16_off[li]) + (size_t)(wave * 2 + nb) * 1024 + lane * 8;
-                constexpr int nkb = W / 16;
-                f16x8 b0h, b0l, b1h, b1l, b2h, b2l;
-                auto load_b = [&](int kb, f16x8 &xh, f16x8 &xl) {
-                    const f16 *p = wbase + (size_t)uvm_opaque(kb < nkb ? kb : nkb - 1) * 8 * 1024;
-                    xh = *(const f16x8 *)(p); xl = *(const f16x8 *)(p + 512);
-                };
-                load_b(0, b0h, b0l); load_b(1, b1h, b1l);
-                f16x8 ah[2], al[2], nah[2], nal[2];
-                auto load_a = [&](int kb, f16x8 (&xh)[2], f16x8 (&xl)[2]) {
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb) {
-                        xh[mb] = *(const f16x8 *)(ah_base + mb * 32 * STRIDE + kb * 16);
-                        xl[mb] = *(const f16x8 *)(al_base + mb * 32 * STRIDE + kb * 16);
-                    }
-                };
-                load_a(0, ah, al);
-                auto step = [&](int kb, f16x8 (&ch)[2], f16x8 (&cl)[2], f16x8 (&nh)[2], f16x8 (&nl)[2]) {
-                    load_b(kb + 2, b2h, b2l);
-                    load_a(kb + 1 < nkb ? kb + 1 : kb, nh, nl);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb) {
-                        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0h, acc[mb], 0, 0, 0);
-                        acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[mb], b0l, acx[mb], 0, 0, 0);
-                        acx[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[mb], b0h, acx[mb], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    b0h = b1h; b0l = b1l; b1h = b2h; b1l = b2l;
-                };
-                for (int kb = 0; kb < nkb; kb += 2) {
-                    step(kb, ah, al, nah, nal);
-                    step(kb + 1, nah, nal, ah, al);
-                }
+                uvm_kloop_split<STRIDE>(acc, acx, wbase, ah_base, al_base, W / 16);   // a constant, even count: no tail
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const bool on = (relu_bits >> ((nb * 2 + mb) * 16 + q)) & 1ull;
-                        const float y = on ? acc[mb][q] + acx[mb][q] * (1.0f / 2048.0f) : 0.f;
-                        const f16 yh = (f16)y;
-                        const f16 yl = (f16)((y - (float)yh) * 2048.0f);
-                        outv[nb][mb][q] = (uint32_t)__builtin_bit_cast(unsigned short, yh) | ((uint32_t)__builtin_bit_cast(unsigned short, yl) << 16);
+                        const bool on = (relu_bits >> uvm_relu_bit(nb, mb, q)) & 1ull;
+                        outv[nb][mb][q] = uvm_split_packed(on ? acc[mb][q] + acx[mb][q] * UVM_LO_INV : 0.f);
                     }
             }
             __syncthreads();                     // all fragment reads of dZ_li (and the row copies of it below) are done
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const int col = wave * 64 + nb * 32 + r;
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int o = (mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h) * STRIDE + col;
-                        ((unsigned short *)ghi)[o] = (unsigned short)(outv[nb][mb][q] & 0xffffu);
-                        ((unsigned short *)glo)[o] = (unsigned short)(outv[nb][mb][q] >> 16);
-                    }
-            }
+            uvm_stage_planes<STRIDE, 0>(ghi, glo, outv, wave, r, h);
             __syncthreads();
             // whole rows of dZ_{li-1} to HBM, unscaled; the next layer's fragment reads run alongside (both only read)
 #pragma unroll 4
@@ -1000,38 +957,14 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_dgrad16(const float *__restric
                 int t = p * 4 + rg;
                 int64_t n = n0 + t;
                 if (n < N) {
-                    const f16x4 vh = *(const f16x4 *)(ghi + t * STRIDE + c4 * 4), vl = *(const f16x4 *)(glo + t * STRIDE + c4 * 4);
-                    float4 o;
-                    o.x = ldexpf((float)vh[0] + (float)vl[0] * (1.0f / 2048.0f), -e); o.y = ldexpf((float)vh[1] + (float)vl[1] * (1.0f / 2048.0f), -e);
-                    o.z = ldexpf((float)vh[2] + (float)vl[2] * (1.0f / 2048.0f), -e); o.w = ldexpf((float)vh[3] + (float)vl[3] * (1.0f / 2048.0f), -e);
-                    *(float4 *)(dz_prev + n * W + c4 * 4) = o;
+                    const float4 v = uvm_join4(ghi + t * STRIDE + c4 * 4, glo + t * STRIDE + c4 * 4);
+                    *(float4 *)(dz_prev + n * W + c4 * 4) = make_float4(ldexpf(v.x, -e), ldexpf(v.y, -e), ldexpf(v.z, -e), ldexpf(v.w, -e));
                 }
             }
         }
         __syncthreads();                         // the last row copies read the planes before the next tile overwrites them
     }
-    // ---- output-layer gradients of this workgroup: fold the 4 row groups, one partial row per channel ----
-    float *gf = (float *)gp;                     // 16 x 256 floats
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gf[(rg * 4 + c) * W + c4 * 4 + j] = gwo[c][j];
-    __syncthreads();
-    for (int c = 0; c < 4; ++c) {
-        float s = gf[(0 * 4 + c) * W + tid];
-        s += gf[(1 * 4 + c) * W + tid];
-        s += gf[(2 * 4 + c) * W + tid];
-        s += gf[(3 * 4 + c) * W + tid];
-        part_w[((int64_t)blockIdx.x * 4 + c) * W + tid] = s;
-    }
-    dr[tid] = gbo;
-    __syncthreads();
-    if (tid < 4) {
-        float s = 0.f;
-        for (int i = tid; i < W; i += 4) s += dr[i];
-        part_b[(int64_t)blockIdx.x * 4 + tid] = s;
-    }
+    uvm_fold_out_grad<W>(og, (float *)gp /* 16 x 256 floats */, dr, part_w, part_b, tid, rg, c4);
 }
 
 // dW[rows x cols] = dZ^T . In over the texel range of this workgroup.  Waves WR x WC, wave tile (32 NI) x (32 NJ).
@@ -1164,7 +1097,7 @@ void k_uvmlp_wgrad(const float *__restrict__ dz, const float *__restrict__ in, i
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                int n = row0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+                int n = uvm_acc_row(row0 + i * 32, q, h);
                 sl[n * COLS + col0 + j * 32 + r] = acc[i][j][q];
             }
     if (wc == 0 && bslab) {
@@ -1213,16 +1146,30 @@ __global__ __launch_bounds__(256) void k_uvm_reduce(const float *__restrict__ sl
 
 static inline int64_t uvm_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
+// The backward's workspace: byte offsets of its parts and the total.  ctx_uvmlp_bwd_ws_bytes and ctx_uvmlp_bwd both take it from here.
+struct UvmWs { int64_t dz, slab, bslab, part_w, part_b, ctl, bytes; };
+static UvmWs uvm_ws_layout(int64_t N, int D, int W)
+{
+    UvmWs l;
+    int64_t off = 0;
+    auto carve = [&](int64_t bytes) { const int64_t at = off; off += uvm_align(bytes); return at; };
+    // every workgroup of a weight-gradient launch owns one slab: up to UVM_WG_GROUPS of W x max(W, 64) floats (hidden part),
+    // up to UVM_WG_GROUPS_EMB of W x 64 (embedding part, whichever its padded width)
+    const int64_t slab_hid = (int64_t)UVM_WG_GROUPS * W * (W > 64 ? W : 64), slab_emb = (int64_t)UVM_WG_GROUPS_EMB * W * 64;
+    l.dz = carve((int64_t)D * N * W * 4);                              // dZ [layer][texel][W]
+    l.slab = carve((slab_hid > slab_emb ? slab_hid : slab_emb) * 4);   // weight-gradient slabs
+    l.bslab = carve((int64_t)UVM_WG_GROUPS_EMB * W * 4);               // bias slabs
+    l.part_w = carve((int64_t)UVM_DGRAD_GRID * 4 * W * 4);             // output-layer weight partials
+    l.part_b = carve((int64_t)UVM_DGRAD_GRID * 4 * 4);                 // output-layer bias partials
+    l.ctl = carve(256);                                                // control words of the split-fp16 chain (gradient scale)
+    l.bytes = off;
+    return l;
+}
+
 extern "C" int64_t ctx_uvmlp_bwd_ws_bytes(int64_t N, int32_t D, int32_t W)
 {
-    if (N <= 0 || D < 1 || D > UVM_MAX_LAYERS || W % 64 != 0 || W > 256) return -1;
-    int64_t b = uvm_align((int64_t)D * N * W * 4);                       // dZ
-    b += uvm_align((int64_t)UVM_WG_GROUPS * W * (W > 64 ? W : 64) * 4);  // weight-gradient slabs
-    b += uvm_align((int64_t)UVM_WG_GROUPS_EMB * W * 4);                  // bias slabs
-    b += uvm_align((int64_t)UVM_DGRAD_GRID * 4 * W * 4);                 // output-layer weight partials
-    b += uvm_align((int64_t)UVM_DGRAD_GRID * 4 * 4);                     // output-layer bias partials
-    b += 256;                                                            // control words of the split-fp16 chain (gradient scale)
-    return b;
+    if (N <= 0 || !uvm_envelope(D, W)) return -1;
+    return uvm_ws_layout(N, D, W).bytes;
 }
 
 template <int WR, int WC, int NI, int NJ, int LDZ, int LDIN, int INCOLS>
@@ -1250,25 +1197,16 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
     hipStream_t s = (hipStream_t)stream;
     const float *pk = (const float *)packed;
     const float *saved = (const float *)saved_v;
-    char *wp = (char *)ws;
-    float *dz = (float *)wp;          wp += uvm_align((int64_t)D * N * W * 4);
-    float *slab = (float *)wp;        wp += uvm_align((int64_t)UVM_WG_GROUPS * W * (W > 64 ? W : 64) * 4);
-    float *bslab = (float *)wp;       wp += uvm_align((int64_t)UVM_WG_GROUPS_EMB * W * 4);
-    float *part_w = (float *)wp;      wp += uvm_align((int64_t)UVM_DGRAD_GRID * 4 * W * 4);
-    float *part_b = (float *)wp;      wp += uvm_align((int64_t)UVM_DGRAD_GRID * 4 * 4);
-    UvmCtl *ctl = (UvmCtl *)wp;
+    const UvmWs l = uvm_ws_layout(N, D, W);
+    char *const base = (char *)ws;
+    float *dz = (float *)(base + l.dz), *slab = (float *)(base + l.slab), *bslab = (float *)(base + l.bslab);
+    float *part_w = (float *)(base + l.part_w), *part_b = (float *)(base + l.part_b);
+    UvmCtl *ctl = (UvmCtl *)(base + l.ctl);
 
     // ---- phase 1: the dZ chain ----
     int64_t ntiles = cdiv64(N, UVM_TM);
     int dg = (int)(ntiles < UVM_DGRAD_GRID ? ntiles : UVM_DGRAD_GRID);
-    size_t lds = (size_t)(UVM_TM * (W + 4) + UVM_TM * 4) * 4;
-    bool fast = dims == 2 && W == 256 && p.epad == UVM_EPAD;
-    {
-        const char *ex = getenv("CTX_UVMLP_EXACT_F32");
-        if (ex && ex[0] == '1') fast = false;
-        for (int i = 1; i < D && fast; ++i) fast = p.wt16_off[i] >= 0;
-    }
-    if (fast) {
+    if (uvm_use_split16(p, dims, true)) {
         // split-fp16 chain: scale from max|grad| on the device, then the same phases as the f32 kernel
         (void)hipMemsetAsync(ctl, 0, sizeof(UvmCtl), s);
         hipLaunchKernelGGL(k_uvm_absmax, dim3(512), dim3(256), 0, s, grad_raw, grad_raw ? N * output_ch : 0, grad_tex, grad_tex ? N * output_ch : 0, ctl);
@@ -1276,13 +1214,13 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
         const size_t lds16 = (size_t)UVM_TM * UVM16B_STRIDE * sizeof(f16) + UVM_TM * 4 * 4;
         (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
         hipLaunchKernelGGL(k_uvmlp_dgrad16, dim3(dg), dim3(256), lds16, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b, ctl);
-    } else if (W == 256) {
-        (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_uvmlp_dgrad<256>, dim3(dg), dim3(256), lds, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b);
-    } else if (W == 128) {
-        hipLaunchKernelGGL(k_uvmlp_dgrad<128>, dim3(dg), dim3(128), lds, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b);
     } else {
-        hipLaunchKernelGGL(k_uvmlp_dgrad<64>, dim3(dg), dim3(64), lds, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b);
+        uvm_dispatch(W, p.epad, [&](auto w, auto) {
+            constexpr int WW = decltype(w)::value;
+            const size_t lds = (size_t)(UVM_TM * (WW + 4) + UVM_TM * 4) * 4;
+            (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad<WW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(k_uvmlp_dgrad<WW>, dim3(dg), dim3(WW), lds, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b);
+        });
     }
     CTX_CHECK_LAUNCH("uvmlp_dgrad");
     hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(output_ch * W / 4, 64)), dim3(256), 0, s, part_w, dg, (int64_t)4 * W, output_ch, W, W,
@@ -1307,11 +1245,11 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
         const bool has_hid = li != 0;
         if (has_hid) {
             const float *in = acts + (int64_t)(li - 1) * N * W;
-            if (W == 256) {
-                if (wg8) uvm_launch_wgrad<2, 4, 4, 2, 256, 256, 256>(G, dzl, in, N, chunk, slab, bslab, s);
-                else uvm_launch_wgrad<2, 2, 4, 4, 256, 256, 256>(G, dzl, in, N, chunk, slab, bslab, s);
-            } else if (W == 128) uvm_launch_wgrad<2, 2, 2, 2, 128, 128, 128>(G, dzl, in, N, chunk, slab, bslab, s);
-            else uvm_launch_wgrad<2, 2, 1, 1, 64, 64, 64>(G, dzl, in, N, chunk, slab, bslab, s);
+            uvm_dispatch(W, p.epad, [&](auto w, auto) {
+                constexpr int WW = decltype(w)::value;
+                if (WW == 256 && wg8) uvm_launch_wgrad<2, 4, 4, 2, 256, 256, 256>(G, dzl, in, N, chunk, slab, bslab, s);
+                else uvm_launch_wgrad<2, 2, WW / 64, WW / 64, WW, WW, WW>(G, dzl, in, N, chunk, slab, bslab, s);
+            });
             CTX_CHECK_LAUNCH("uvmlp_wgrad");
             hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(W * W / 4, 64)), dim3(256), 0, s, slab, G, (int64_t)W * W, W, W, W, gws[li], kin,
                                has_emb ? input_ch : 0);
@@ -1319,15 +1257,10 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
         }
         if (has_emb) {
             float *bsl = has_hid ? nullptr : bslab;
-            if (p.epad == UVM_EPAD) {
-                if (W == 256) uvm_launch_wgrad<4, 1, 2, 2, 256, UVM_EPAD, UVM_EPAD>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-                else if (W == 128) uvm_launch_wgrad<2, 1, 2, 2, 128, UVM_EPAD, UVM_EPAD>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-                else uvm_launch_wgrad<1, 1, 2, 2, 64, UVM_EPAD, UVM_EPAD>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-            } else {
-                if (W == 256) uvm_launch_wgrad<4, 1, 2, 2, 256, UVM_EPAD3, UVM_EPAD3>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-                else if (W == 128) uvm_launch_wgrad<2, 1, 2, 2, 128, UVM_EPAD3, UVM_EPAD3>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-                else uvm_launch_wgrad<1, 1, 2, 2, 64, UVM_EPAD3, UVM_EPAD3>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
-            }
+            uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
+                constexpr int WW = decltype(w)::value, EE = decltype(ep)::value;
+                uvm_launch_wgrad<WW / 64, 1, 2, 2, WW, EE, EE>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
+            });
             CTX_CHECK_LAUNCH("uvmlp_wgrad_emb");
             hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(W * 64 / 4, 64)), dim3(256), 0, s, slab, Ge, (int64_t)W * 64, W, 64, input_ch, gws[li], kin, 0);
             if (!has_hid)

@@ -369,7 +369,8 @@ def _field_bwd_abi(net, uv, c_raw, res=0, c_tex=None):
     saved = torch.zeros(lib.ctx_uvmlp_saved_bytes(N, D, W, net.input_ch) // 4, device=dev)
     L.check(lib.ctx_uvmlp_fwd_save(L.ptr(uv), None, N, res, L.ptr(blob), D, W, net.dims, net.multires, net.output_ch, 4, L.ptr(raw), None,
                                    L.ptr(saved), L.stream()))
-    ws = torch.empty(lib.ctx_uvmlp_bwd_ws_bytes(N, D, W), dtype=torch.uint8, device=dev)
+    ws_bytes, guard = lib.ctx_uvmlp_bwd_ws_bytes(N, D, W), 4 << 20
+    ws = torch.full((ws_bytes + guard,), 0xA5, dtype=torch.uint8, device=dev)       # the workspace, then a guard nobody may write
     layers = list(net.pts_linears) + [net.output_linear]
     gws = [torch.empty_like(l.weight) for l in layers]
     gbs = [torch.empty_like(l.bias) for l in layers]
@@ -377,6 +378,7 @@ def _field_bwd_abi(net, uv, c_raw, res=0, c_tex=None):
     gbp = (C.c_void_p * (D + 1))(*[L.ptr(t).value for t in gbs])
     L.check(lib.ctx_uvmlp_bwd(L.ptr(c_raw), L.ptr(c_tex), L.ptr(raw), N, L.ptr(blob), D, W, net.dims, net.multires, net.output_ch, 4,
                               L.ptr(saved), L.ptr(ws), gwp, gbp, L.stream()))
+    assert bool((ws[ws_bytes:] == 0xA5).all()), "the backward wrote past ctx_uvmlp_bwd_ws_bytes"
     ep = 48 if net.input_ch <= 48 else 64
     return gws, gbs, saved[N * ep:N * ep + D * N * W].reshape(D, N, W)     # (the ReLU bit masks follow)
 
@@ -384,7 +386,7 @@ def _field_bwd_abi(net, uv, c_raw, res=0, c_tex=None):
 def test_texture_field_split_fp16_vs_exact_f32(dev, golden):
     """The default forward of the 2-D texture field (k_uvmlp_fwd16: fp16 hi + lo split operands, three MFMA passes, fp32 accumulate)
     against the exact-f32 kernel behind CTX_UVMLP_EXACT_F32=1 and against the REFERENCE's stored outputs at the f32 path's own
-    tolerance; ragged N (not a multiple of the 128-texel tile), the training forward's saved tensors, and the backward through
+    tolerance; ragged N (not a multiple of the 64-texel tile), the training forward's saved tensors, and the backward through
     either forward."""
     import os
     from contexture_nerf_amd import run_nerf_helpers as rnh
@@ -430,9 +432,10 @@ def test_texture_field_split_fp16_vs_exact_f32(dev, golden):
         assert float((ga - gb).abs().max()) <= 1e-3 * max(float(gb.abs().max()), 1e-6)
 
 
-@pytest.mark.parametrize("W,N", [(64, 1), (128, 517), (256, 4133), (256, 64 * 300), (256, 64 * 700 + 5)])
+@pytest.mark.parametrize("W,N", [(64, 1), (128, 517), (256, 4133), (256, 64 * 300), (256, 64 * 700 + 5), (64, 20000), (128, 30000)])
 def test_texture_field_backward_vs_oracle(dev, W, N):
-    """ragged texel counts (tile tails, fewer texel ranges than workgroups, more tiles than persistent workgroups), the
+    """ragged texel counts (tile tails, fewer texel ranges than workgroups, more tiles than persistent workgroups; at the narrow
+    widths more embedding-gradient workgroups (417, 625) than a slab sized for the hidden part alone holds), the
     fused-uv seam, against the float64 oracle.  The ReLU derivative pattern is taken from the device's saved activations
     (checked against the oracle's pre-activations: they may only differ where |pre-activation| < 1e-5), because a unit
     that rounds to the other side of 0 moves a gradient by a whole term (~1/sqrt(N) relative)."""
@@ -545,12 +548,13 @@ def test_volume_render_3d_field(dev, golden):
     assert rgb.shape == (H * W_, 3) and torch.isfinite(rgb).all()
 
 
-def test_field_3d_backward(dev):
-    """the 3-D field (padded embedding 64, 4 outputs) through the same backward, ragged N."""
+@pytest.mark.parametrize("W,N", [(64, 64 * 3 + 11), (128, 64 * 3 + 11), (256, 64 * 37 + 11)])
+def test_field_3d_backward(dev, W, N):
+    """the 3-D field (padded embedding 64, 4 outputs) through the same backward, ragged N, at every width (the overlaid
+    forward k_uvmlp_fwd<W, 64> and the 64-column embedding weight gradients exist per width)."""
     from contexture_nerf_amd import run_nerf_helpers as rnh
     torch.manual_seed(33)
-    net = rnh.NeRF2D(D=8, W=256, input_ch=63, output_ch=4, skips=[4]).to(dev)
-    N = 64 * 37 + 11
+    net = rnh.NeRF2D(D=8, W=W, input_ch=63, output_ch=4, skips=[4]).to(dev)
     g = torch.Generator().manual_seed(4)
     pts = torch.rand(N, 3, generator=g) * 2 - 1
     c_raw = torch.randn(N, 4, generator=g)
