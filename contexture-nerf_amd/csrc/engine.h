@@ -1,7 +1,12 @@
 // Engine core shared by the UNet / ControlNet engine (unet.hip) and the VAE engine (vae.hip): the parameter table over one
 // fp16 weight blob, the workspace arena (bump allocator with mark/release; sized by a dry run of the same code path), the
-// GEMM / conv launch sequence and the fp32 -> fp16 parameter repack.  `struct ctx_unet : Engine`, `struct ctx_vae : Engine`;
-// nothing here asks which of the two it serves.
+// fp32 -> fp16 parameter repack, and the op layer the two graphs are written in: guarded launches and copies, the linear /
+// 3x3-conv builders over the GEMM launch sequence, FLOP / launch accounting, the dry run behind every size query and the
+// error tail.  `struct ctx_unet : Engine`, `struct ctx_vae : Engine`; nothing here asks which of the two it serves.
+//
+// A run keeps its first error (a workspace overflow in alloc(), a kernel entry's refusal) in `rc`, and from then on launches and
+// copies nothing: a graph launches and copies only through ENGINE_RUN / ENGINE_LAUNCH / copy() / copy2d(), which do nothing on a
+// dry run or once rc != 0.  (After an overflow alloc() hands out the workspace base: a pointer that must never reach a kernel.)
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -35,6 +40,9 @@ struct Engine {
     bool dry = false;
     hipStream_t s = nullptr;
     int rc = 0;
+    // accounting of the current run by kernel class: 0 GEMM / conv, 1 attention, 2 everything else (a dry run counts the same)
+    int64_t launches[3] = {0, 0, 0};
+    double flops[3] = {0, 0, 0};
 
     size_t walloc(size_t n) { size_t o = wtop; wtop += (n + 127) / 128 * 128; return o; }
     size_t add(const std::string &name, std::vector<int64_t> shp, int kind, size_t dst, int a = 0, int b = 0)
@@ -56,13 +64,39 @@ struct Engine {
         return dry ? nullptr : (void *)(ws + o);
     }
     f16 *allocH(size_t n) { return (f16 *)alloc(n * 2); }
+
+    void begin() { top = 0; peak = 0; rc = 0; for (int k = 0; k < 3; ++k) { launches[k] = 0; flops[k] = 0; } }   // a run from an empty arena
+    void note(int klass, double fl, int n = 1) { launches[klass] += n; flops[klass] += fl; }
+    bool live() const { return !dry && rc == 0; }
+    // device-to-device copies on the run's stream
+    void copy(void *dst, const void *src, size_t bytes) { if (live()) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); }
+    void copy2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows)
+    { if (live()) (void)hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, s); }
 };
 
-// skip launches on a dry run or after an error, keep the first error code
-#define ENGINE_RUN(e, expr) do { if (!(e)->dry && (e)->rc == 0) { int r__ = (expr); if (r__ != 0) (e)->rc = r__; } } while (0)
+// a kernel entry that returns a code / a bare kernel on the run's stream: skipped on a dry run or after an error; the first error code is kept
+#define ENGINE_RUN(e, expr) do { if ((e)->live()) { int r__ = (expr); if (r__ != 0) (e)->rc = r__; } } while (0)
+#define ENGINE_LAUNCH(e, kernel, grid, block, lds, ...) do { if ((e)->live()) hipLaunchKernelGGL(kernel, grid, block, lds, (e)->s, __VA_ARGS__); } while (0)
 
-// one GEMM / implicit-GEMM conv of a fully described problem: plan, split-K scratch above the arena mark, dispatch, release
-void engine_gemm(Engine &e, GemmArgs &a, bool conv);
+// out[M, ldc] = X[M,K] Wt[N,K]^T (+ bias[N]) (+ res[M,N]); ldc 0 = dense; epi 1 = GEGLU (out has N/2 columns); res32 / out32: res / out are fp32
+void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, const void *res, int M, int N, int K, void *out, int ldc = 0,
+                   int epi = 0, bool res32 = false, bool out32 = false);
+// a 3x3 convolution's geometry beyond "stride 1, padding 1" (GemmArgs has each meaning); Ho = ((H << ups) - 1) / stride + 1, Wo alike
+struct ConvGeom { int stride = 1, ups = 0, poff = 0, zins = 0; };
+// out[B,Ho,Wo,Cout] = conv3x3(x[B,H,W,Cin]; Wt[Cout][3][3][Cin]) (+ bias[Cout]) (+ rowbias[b * ldrb ..]) (+ res); NHWC
+void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
+                  ConvGeom g = ConvGeom(), const f16 *rowbias = nullptr, int ldrb = 0, bool res32 = false, bool out32 = false);
+
+// `run` as a dry run: nothing is launched, the arena only measures (e.peak), the counters count; -> the run's return code
+template <class F> int engine_dry_run(Engine *e, F run)
+{
+    const bool was = e->dry;
+    e->dry = true; const int rc = run(); e->dry = was;
+    return rc;
+}
+inline int64_t engine_workspace_need(const Engine *e) { return (int64_t)e->peak + 4096; }
+// tail of a run: a launch error of the runtime, else the run's first error (`who` is the entry point's name in the message)
+int engine_finish(Engine *e, const char *who);
 
 // bodies of the ctx_<engine>_param_count / _param_name / _param_shape / _weight_bytes / _bind / _set_param entry points
 // (`who` is the entry point's name in error messages)

@@ -1,4 +1,5 @@
-// Engine core (engine.h): table accessors, bind, the parameter repack kernels and the GEMM launch sequence.
+// Engine core (engine.h): table accessors, bind, the parameter repack kernels, the linear / conv builders over the GEMM launch
+// sequence and the tail of a run.
 #include "engine.h"
 
 int32_t engine_param_count(const Engine *e) { return e ? (int32_t)e->params.size() : 0; }
@@ -22,14 +23,44 @@ int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace
     return CTX_OK;
 }
 
-void engine_gemm(Engine &e, GemmArgs &a, bool conv)
+// one GEMM / implicit-GEMM conv of a fully described problem: plan, split-K scratch above the arena mark, dispatch, release
+static void engine_gemm(Engine &e, GemmArgs &a, bool conv)
 {
+    e.note(0, 2.0 * a.M * a.N * a.K);
     size_t mark = e.top;
     ctx_gemm_plan(a, conv);
     if (a.zins) a.use8 = 0;        // the zero-inserted grid is an addressing mode of gemm.hip only
     if (a.splitk > 1) a.part = (float *)e.alloc((size_t)a.splitk * a.M * a.N * 4);
     ENGINE_RUN(&e, ctx_gemm_dispatch(a, conv, e.s));
     e.top = mark;
+}
+
+void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, const void *res, int M, int N, int K, void *out, int ldc, int epi,
+                   bool res32, bool out32)
+{
+    GemmArgs a = {};
+    a.X = X; a.Wt = Wt; a.bias = bias; a.residual = (const f16 *)res; a.out = (f16 *)out;
+    a.M = M; a.N = N; a.K = K; a.ldc = ldc ? ldc : epi == 1 ? N / 2 : N; a.ldr = N; a.rows_per_batch = 1; a.ldrb = N; a.epi = epi;
+    a.res32 = res32; a.out32 = out32;
+    engine_gemm(e, a, false);
+}
+
+void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
+                  ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32)
+{
+    GemmArgs a = {};
+    a.Ho = ((H << g.ups) - 1) / g.stride + 1; a.Wo = ((W << g.ups) - 1) / g.stride + 1;
+    a.X = x; a.Wt = Wt; a.bias = bias; a.rowbias = rowbias; a.residual = (const f16 *)res; a.out = (f16 *)out;
+    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = ldrb;
+    a.H = H; a.W = W; a.Cin = Cin; a.stride = g.stride; a.ups = g.ups; a.poff = g.poff; a.zins = g.zins;
+    a.res32 = res32; a.out32 = out32;
+    engine_gemm(e, a, true);
+}
+
+int engine_finish(Engine *e, const char *who)
+{
+    if (e->live()) CTX_CHECK_LAUNCH(who);
+    return e->rc;
 }
 
 // ---- parameter repack kernels ----------------------------------------------------------------------

@@ -56,6 +56,10 @@ extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 // norms over the fp32 residual stream (x32 != 0) or fp16 activations; output fp16
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
                       void *y, void *stats_ws, hipStream_t stream);
+// GroupNorm(+SiLU) backward, input gradient only, fp16 NHWC: dx = d(loss)/dx (+ add); ws of ctx_groupnorm_bwd_ws_bytes(B, groups)
+int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups);
+int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,
+                          float eps, int silu, f16 *dx, void *ws, hipStream_t s);
 int ctx_layernorm_any(const void *x, int x32, const void *gamma, const void *beta, int64_t rows, int C, float eps, void *y, hipStream_t stream);
 int ctx_concat_f32(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s);
 int ctx_f16_to_f32(const f16 *x, int64_t n, float *y, hipStream_t s);

@@ -341,6 +341,133 @@ int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *bet
     return CTX_OK;
 }
 
+// GroupNorm(+SiLU) backward, input gradient only (the VAE encoder's backward: the VAE is frozen): two reductions (statistics of
+// x, then sum(du) and sum(du x^)) and one apply pass, all deterministic (fixed-order partial sums).
+#define GNB_MAX_SPLITS 128
+
+// MODE 0: per-group partial (sum x, sum x^2); MODE 1: partial (sum du, sum du x^) with du = dy silu'(u) gamma, u = gamma x^ + beta
+template <int MODE>
+__global__ __launch_bounds__(256) void k_gnb_reduce(const f16 *__restrict__ x, const f16 *__restrict__ dy, const f16 *__restrict__ gamma,
+                                                    const f16 *__restrict__ beta, const float *__restrict__ mr, int HW, int C, int G, int NS,
+                                                    int silu, float *__restrict__ part)
+{
+    extern __shared__ float sm[];                    // [PL][C][2] then [C][2]
+    const int c8n = C / 8, PL = 256 / c8n;
+    const int b = blockIdx.y, sp = blockIdx.x;
+    const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
+    const int per = (HW + NS - 1) / NS, p0 = sp * per, p1 = min(HW, p0 + per), cg = C / G;
+    float s[8], q[8], a[8], b0[8], ga[8], mu[8], rs[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        s[j] = 0.f; q[j] = 0.f;
+        if (MODE == 1) {
+            const int c = c8 * 8 + j, g = c / cg;
+            mu[j] = mr[((size_t)b * G + g) * 2]; rs[j] = mr[((size_t)b * G + g) * 2 + 1];
+            ga[j] = (float)gamma[c]; a[j] = rs[j] * ga[j]; b0[j] = (float)beta[c] - mu[j] * a[j];
+        }
+    }
+    if (pl < PL)
+        for (int p = p0 + pl; p < p1; p += PL) {
+            const size_t off = ((size_t)b * HW + p) * C + c8 * 8;
+            const f16x8 xv = *(const f16x8 *)(x + off);
+            if (MODE == 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { float f = (float)xv[j]; s[j] += f; q[j] += f * f; }
+            } else {
+                const f16x8 dv = *(const f16x8 *)(dy + off);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float xf = (float)xv[j], u = xf * a[j] + b0[j];
+                    float d = (float)dv[j];
+                    if (silu) { const float sg = 1.0f / (1.0f + __expf(-u)); d *= sg * (1.0f + u * (1.0f - sg)); }
+                    const float du = d * ga[j];
+                    s[j] += du; q[j] += du * ((xf - mu[j]) * rs[j]);
+                }
+            }
+        }
+    if (pl < PL) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { sm[((size_t)pl * C + c8 * 8 + j) * 2] = s[j]; sm[((size_t)pl * C + c8 * 8 + j) * 2 + 1] = q[j]; }
+    }
+    __syncthreads();
+    float *ch = sm + (size_t)PL * C * 2;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float ss = 0.f, qq = 0.f;
+        for (int l = 0; l < PL; ++l) { ss += sm[((size_t)l * C + c) * 2]; qq += sm[((size_t)l * C + c) * 2 + 1]; }
+        ch[c * 2] = ss; ch[c * 2 + 1] = qq;
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < G; g += 256) {
+        float ss = 0.f, qq = 0.f;
+        for (int c = g * cg; c < (g + 1) * cg; ++c) { ss += ch[c * 2]; qq += ch[c * 2 + 1]; }
+        part[(((size_t)b * NS + sp) * G + g) * 2] = ss; part[(((size_t)b * NS + sp) * G + g) * 2 + 1] = qq;
+    }
+}
+// MODE 0 -> (mean, rstd); MODE 1 -> (sum du / n, sum du x^ / n)
+template <int MODE>
+__global__ void k_gnb_finalize(const float *__restrict__ part, int G, int NS, float n, float eps, float *__restrict__ out)
+{
+    const int b = blockIdx.x;
+    for (int g = threadIdx.x; g < G; g += blockDim.x) {
+        float ss = 0.f, qq = 0.f;
+        for (int k = 0; k < NS; ++k) { ss += part[(((size_t)b * NS + k) * G + g) * 2]; qq += part[(((size_t)b * NS + k) * G + g) * 2 + 1]; }
+        if (MODE == 0) {
+            const float mean = ss / n;
+            out[((size_t)b * G + g) * 2] = mean; out[((size_t)b * G + g) * 2 + 1] = rsqrtf(fmaxf(qq / n - mean * mean, 0.f) + eps);
+        } else { out[((size_t)b * G + g) * 2] = ss / n; out[((size_t)b * G + g) * 2 + 1] = qq / n; }
+    }
+}
+// dx = rstd (du - c1 - x^ c2) (+ add)
+__global__ __launch_bounds__(256) void k_gnb_apply(const f16 *__restrict__ x, const f16 *__restrict__ dy, const f16 *__restrict__ gamma,
+                                                   const f16 *__restrict__ beta, const float *__restrict__ mr, const float *__restrict__ cc,
+                                                   const f16 *__restrict__ add, int HW, int C, int G, int silu, f16 *__restrict__ dx)
+{
+    const int b = blockIdx.y, c8n = C / 8, cg = C / G;
+    const size_t total = (size_t)HW * c8n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c0 = (int)(i % c8n) * 8;
+        const size_t off = (size_t)b * HW * C + i * 8;
+        const f16x8 xv = *(const f16x8 *)(x + off), dv = *(const f16x8 *)(dy + off);
+        f16x8 av = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (add) av = *(const f16x8 *)(add + off);
+        f16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = c0 + j, g = c / cg;
+            const float mu = mr[((size_t)b * G + g) * 2], rs = mr[((size_t)b * G + g) * 2 + 1];
+            const float c1 = cc[((size_t)b * G + g) * 2], c2 = cc[((size_t)b * G + g) * 2 + 1];
+            const float ga = (float)gamma[c], xh = ((float)xv[j] - mu) * rs, u = xh * ga + (float)beta[c];
+            float d = (float)dv[j];
+            if (silu) { const float sg = 1.0f / (1.0f + __expf(-u)); d *= sg * (1.0f + u * (1.0f - sg)); }
+            o[j] = (f16)(rs * (d * ga - c1 - xh * c2) + (float)av[j]);
+        }
+        *(f16x8 *)(dx + off) = o;
+    }
+}
+
+int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups) { return ((int64_t)B * GNB_MAX_SPLITS * groups * 2 + (int64_t)B * groups * 4) * 4; }
+
+// dx = d(loss)/dx (+ add) of y = GroupNorm(x) (SiLU after it when `silu`), fp16 NHWC; ws: ctx_groupnorm_bwd_ws_bytes(B, groups)
+int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,
+                          float eps, int silu, f16 *dx, void *ws, hipStream_t s)
+{
+    const int G = groups, c8n = C / 8;
+    CTX_REQUIRE(C % 8 == 0 && 256 % c8n == 0 && C % G == 0, "groupnorm backward: C=%d groups=%d is outside the kernel's envelope", C, G);
+    const int PL = 256 / c8n;
+    int NS = HW / (PL * 4); if (NS < 1) NS = 1; if (NS > GNB_MAX_SPLITS) NS = GNB_MAX_SPLITS;
+    float *part = (float *)ws, *mr = part + (size_t)B * GNB_MAX_SPLITS * G * 2, *cc = mr + (size_t)B * G * 2;
+    const size_t lds = ((size_t)PL * C * 2 + (size_t)C * 2) * sizeof(float);
+    const float n = (float)HW * (float)(C / G);
+    hipLaunchKernelGGL(k_gnb_reduce<0>, dim3(NS, B), dim3(256), lds, s, x, (const f16 *)nullptr, gamma, beta, (const float *)nullptr, HW, C, G, NS, silu, part);
+    hipLaunchKernelGGL(k_gnb_finalize<0>, dim3(B), dim3(64), 0, s, part, G, NS, n, eps, mr);
+    hipLaunchKernelGGL(k_gnb_reduce<1>, dim3(NS, B), dim3(256), lds, s, x, dy, gamma, beta, mr, HW, C, G, NS, silu, part);
+    hipLaunchKernelGGL(k_gnb_finalize<1>, dim3(B), dim3(64), 0, s, part, G, NS, n, 0.f, cc);
+    const size_t total = (size_t)HW * c8n;
+    unsigned nb = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_gnb_apply, dim3(nb, B), dim3(256), 0, s, x, dy, gamma, beta, mr, cc, add, HW, C, G, silu, dx);
+    return CTX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // LayerNorm over the last dim: one wave per LN_R rows at a time, up to 4 x 16-byte chunks per lane per row
 // (C <= 2048); all LN_R rows' loads are issued before the first reduction.

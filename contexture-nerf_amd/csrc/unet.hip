@@ -39,9 +39,6 @@ struct ctx_unet : Engine {
     int kv_rows_total = 0, kv_rows = 0;
     std::vector<LevelP> down, up;
     LevelP mid;
-    // stats
-    int64_t launches[3] = {0, 0, 0};
-    double flops[3] = {0, 0, 0};
     // reference-only self-attention (Zero123++'s RefOnlyNoisedUNet, spec in src/zero123plus.py:127-237): a 'w' pass parks the
     // attn1 inputs (LayerNorm-1 outputs) of the noised condition latent in a bank, an 'r' pass appends them to the K/V source of
     // the same attn1 layer for the batch rows >= ref_row0 (is_cfg_guidance: the unconditional row 0 attends without them)
@@ -82,7 +79,7 @@ struct ctx_unet : Engine {
         const size_t n = (size_t)rows * C;
         Tap t = {tap_cursor, rows, C};
         taps.push_back(t);
-        if (!dry && rc == 0 && tap_cursor + n <= tap_cap) (void)hipMemcpyAsync(tap_buf + tap_cursor, x, n * 2, hipMemcpyDeviceToDevice, s);
+        if (tap_cursor + n <= tap_cap) copy(tap_buf + tap_cursor, x, n * 2);
         tap_cursor += n;
     }
 };
@@ -363,43 +360,30 @@ __global__ __launch_bounds__(256) void k_add_scaled_f16(f16 *__restrict__ dst, c
     }
 }
 
-// ---- op wrappers (skip launches on a dry run, keep accounting identical) ---------------------------------
-static void note(ctx_unet *u, int klass, double fl, int n = 1) { u->launches[klass] += n; u->flops[klass] += fl; }
+// ---- op wrappers: the shared op layer (engine.h) on this engine's weight offsets and residual-stream flags ------
 #define RUN(expr) ENGINE_RUN(u, expr)
 
 // res / out are residual-stream tensors (fp32 when u->res32) iff res_s / out_s
 static void op_gemm(ctx_unet *u, const f16 *X, size_t w, size_t bias, bool has_bias, const void *res, int M, int N, int K, void *out,
                     int epi = 0, bool res_s = false, bool out_s = false)
 {
-    GemmArgs a = {};
-    a.X = X; a.Wt = u->W + w; a.bias = has_bias ? u->W + bias : nullptr; a.residual = (const f16 *)res; a.out = (f16 *)out;
-    a.M = M; a.N = N; a.K = K; a.ldc = epi == 1 ? N / 2 : N; a.ldr = N; a.rows_per_batch = 1; a.ldrb = N; a.epi = epi;
-    a.res32 = (u->res32 && res_s && res) ? 1 : 0; a.out32 = (u->res32 && out_s) ? 1 : 0;
-    note(u, 0, 2.0 * M * N * K);
-    engine_gemm(*u, a, false);
+    engine_linear(*u, X, u->W + w, has_bias ? u->W + bias : nullptr, res, M, N, K, out, 0, epi, u->res32 && res_s && res, u->res32 && out_s);
 }
 static void op_conv(ctx_unet *u, const f16 *x, size_t w, size_t bias, const f16 *rowbias, int ldrb, const void *res, int B, int H,
                     int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false)
 {
-    GemmArgs a = {};
-    int Hv = H << ups, Wv = W << ups;
-    a.Ho = (Hv - 1) / stride + 1; a.Wo = (Wv - 1) / stride + 1;
-    a.X = x; a.Wt = u->W + w; a.bias = u->W + bias; a.rowbias = rowbias; a.residual = (const f16 *)res; a.out = (f16 *)out;
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = ldrb;
-    a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.ups = ups;
-    a.res32 = (u->res32 && res_s && res) ? 1 : 0; a.out32 = (u->res32 && out_s) ? 1 : 0;
-    note(u, 0, 2.0 * a.M * a.N * a.K);
-    engine_gemm(*u, a, true);
+    engine_conv3(*u, x, u->W + w, u->W + bias, res, B, H, W, Cin, Cout, out, ConvGeom{stride, ups}, rowbias, ldrb, u->res32 && res_s && res,
+                 u->res32 && out_s);
 }
 // x_s: x is a residual-stream tensor
 static void op_gn(ctx_unet *u, const void *x, size_t g, size_t b, int B, int HW, int C, float eps, int silu, f16 *y, void *stats, bool x_s = true)
 {
-    note(u, 2, 0, 2);
+    u->note(2, 0, 2);
     RUN(ctx_groupnorm_any(x, (u->res32 && x_s) ? 1 : 0, u->W + g, u->W + b, B, HW, C, u->cfg.groups, eps, silu, y, stats, u->s));
 }
 static void op_ln(ctx_unet *u, const void *x, size_t g, size_t b, int64_t rows, int C, f16 *y)
 {
-    note(u, 2, 0);
+    u->note(2, 0);
     RUN(ctx_layernorm_any(x, u->res32 ? 1 : 0, u->W + g, u->W + b, rows, C, 1e-5f, y, u->s));
 }
 // fp16 GEMM / conv operand of a residual-stream tensor: the tensor itself, or (res32) a rounded copy above the arena mark
@@ -407,13 +391,13 @@ static const f16 *op_as16(ctx_unet *u, const void *x, size_t n)
 {
     if (!u->res32) return (const f16 *)x;
     f16 *c = u->allocH(n);
-    note(u, 2, 0);
+    u->note(2, 0);
     RUN(ctx_f32_to_f16((const float *)x, (int64_t)n, c, u->s));
     return c;
 }
 static void op_attn(ctx_unet *u, const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int qs, int kvs, f16 *O)
 {
-    note(u, 1, 4.0 * B * heads * (double)Sq * Skv * 64);
+    u->note(1, 4.0 * B * heads * (double)Sq * Skv * 64);
     RUN(ctx_attention_core(Q, K, V, B, Sq, Skv, heads, qs, kvs, 0.125f, O, heads * 64, u->s));
 }
 
@@ -486,8 +470,7 @@ static void *run_transformer(ctx_unet *u, const FwdCtx &f, const TrP &t, const v
             ctx_unet::RefSlot sl; sl.off = u->ref_cursor; sl.tokens = S; sl.C = C; sl.rows = B;
             u->ref_slots.push_back(sl);
             u->ref_cursor += (size_t)M * C;
-            if (!u->dry && u->rc == 0 && u->ref_bank)
-                (void)hipMemcpyAsync(u->ref_bank + sl.off, l, (size_t)M * C * 2, hipMemcpyDeviceToDevice, u->s);
+            if (u->ref_bank) u->copy(u->ref_bank + sl.off, l, (size_t)M * C * 2);
         }
         f16 *qkv = u->allocH((size_t)M * 3 * C);
         op_gemm(u, l, t.qkv, 0, false, nullptr, M, 3 * C, C, qkv);
@@ -521,25 +504,24 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     const ctx_unet_config_t &c = u->cfg;
     const int n = c.n_levels, lpb = c.layers_per_block;
     const int *ch = c.block_out_channels;
-    u->top = 0; u->peak = 0; u->rc = 0;
+    u->begin();
     u->ref_k = 0; u->ref_cursor = 0;
     u->taps.clear(); u->tap_cursor = 0;
     if (u->ref_mode == 1) u->ref_slots.clear();
-    for (int k = 0; k < 3; ++k) { u->launches[k] = 0; u->flops[k] = 0; }
     FwdCtx f; f.B = B; f.L = L;
     f.gn_stats = u->alloc((size_t)ctx_groupnorm_ws_bytes(B, c.groups));
     // time embedding
     f16 *te0 = u->allocH((size_t)B * ch[0]);
-    note(u, 2, 0); RUN(ctx_time_embed_f16(timestep, B, ch[0], te0, u->s));
+    u->note(2, 0); RUN(ctx_time_embed_f16(timestep, B, ch[0], te0, u->s));
     f16 *te1 = u->allocH((size_t)B * u->temb_dim);
-    note(u, 2, 2.0 * B * ch[0] * u->temb_dim); RUN(ctx_gemv_f16(te0, u->W + u->t1w, u->W + u->t1b, B, u->temb_dim, ch[0], 0, 1, te1, u->s));
+    u->note(2, 2.0 * B * ch[0] * u->temb_dim); RUN(ctx_gemv_f16(te0, u->W + u->t1w, u->W + u->t1b, B, u->temb_dim, ch[0], 0, 1, te1, u->s));
     f16 *te2 = u->allocH((size_t)B * u->temb_dim);
-    note(u, 2, 2.0 * B * u->temb_dim * u->temb_dim); RUN(ctx_gemv_f16(te1, u->W + u->t2w, u->W + u->t2b, B, u->temb_dim, u->temb_dim, 0, 1, te2, u->s));   // + the resnets' SiLU(temb), once
+    u->note(2, 2.0 * B * u->temb_dim * u->temb_dim); RUN(ctx_gemv_f16(te1, u->W + u->t2w, u->W + u->t2b, B, u->temb_dim, u->temb_dim, 0, 1, te2, u->s));   // + the resnets' SiLU(temb), once
     f16 *tproj = u->allocH((size_t)B * u->temb_rows);
-    note(u, 2, 2.0 * B * u->temb_rows * u->temb_dim); RUN(ctx_gemv_f16(te2, u->W + u->tpw, u->W + u->tpb, B, u->temb_rows, u->temb_dim, 0, 0, tproj, u->s));
+    u->note(2, 2.0 * B * u->temb_rows * u->temb_dim); RUN(ctx_gemv_f16(te2, u->W + u->tpw, u->W + u->tpb, B, u->temb_rows, u->temb_dim, 0, 0, tproj, u->s));
     f.tproj = tproj;
     f16 *ctx16 = u->allocH((size_t)B * L * c.cross_attention_dim);
-    note(u, 2, 0); RUN(ctx_f32_to_f16(ctx, (int64_t)B * L * c.cross_attention_dim, ctx16, u->s));
+    u->note(2, 0); RUN(ctx_f32_to_f16(ctx, (int64_t)B * L * c.cross_attention_dim, ctx16, u->s));
     f.ctx16 = ctx16;
     // cross-attention K/V of every transformer block in one GEMM: they depend only on the context
     f16 *kv_all = u->allocH((size_t)B * L * u->kv_rows_total);
@@ -555,15 +537,14 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     {
         size_t m0 = u->top;
         f16 *x16 = u->res32 ? u->allocH((size_t)B * h * w * ch[0]) : (f16 *)x;
-        note(u, 2, 2.0 * B * h * w * ch[0] * c.in_channels * 9); RUN(ctx_conv_in_f16(sample, u->W + u->ciw, u->W + u->cib, B, c.in_channels, h, w, ch[0], x16, u->s));
-        if (u->res32) { note(u, 2, 0); RUN(ctx_f16_to_f32(x16, (int64_t)B * h * w * ch[0], (float *)x, u->s)); u->top = m0; }
+        u->note(2, 2.0 * B * h * w * ch[0] * c.in_channels * 9); RUN(ctx_conv_in_f16(sample, u->W + u->ciw, u->W + u->cib, B, c.in_channels, h, w, ch[0], x16, u->s));
+        if (u->res32) { u->note(2, 0); RUN(ctx_f16_to_f32(x16, (int64_t)B * h * w * ch[0], (float *)x, u->s)); u->top = m0; }
     }
 
     auto add_scaled = [&](f16 *dst, const f16 *src, float scale, size_t n) {
-        note(u, 2, 0);
-        if (!u->dry && u->rc == 0)
-            hipLaunchKernelGGL(k_add_scaled_f16, dim3((unsigned)std::min<int64_t>(cdiv64((int64_t)n / 8, 256), 4096)), dim3(256), 0, u->s, dst, src,
-                               scale, (int64_t)n / 8);
+        u->note(2, 0);
+        ENGINE_LAUNCH(u, k_add_scaled_f16, dim3((unsigned)std::min<int64_t>(cdiv64((int64_t)n / 8, 256), 4096)), dim3(256), 0, dst, src, scale,
+                      (int64_t)n / 8);
     };
     if (u->is_controlnet) {
         // sample = conv_in(sample) + controlnet_cond_embedding(cond): the conditioning image is 8x the latent grid
@@ -577,12 +558,10 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             const bool last = k + 2 == nconv;                   // its output is what the cache holds
             f16 *o = (last && u->cn_cache) ? u->cn_cache : u->allocH((size_t)B * oh * ow * cc.cout);
             if (!u->cn_cache_valid) {
-                note(u, 2, 2.0 * B * oh * ow * cc.cout * cc.cin * 9);
-                if (!u->dry && u->rc == 0) {
-                    int64_t items = (int64_t)B * oh * ow * (cc.cout / 8);
-                    hipLaunchKernelGGL(k_conv_small, dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 65535)), dim3(256), 0, u->s,
-                                       k == 0 ? u->cn_cond : nullptr, cur16, u->W + cc.w, u->W + cc.b, B, eh, ew, cc.cin, cc.cout, cc.stride, 1, o);
-                }
+                u->note(2, 2.0 * B * oh * ow * cc.cout * cc.cin * 9);
+                const int64_t items = (int64_t)B * oh * ow * (cc.cout / 8);
+                ENGINE_LAUNCH(u, k_conv_small, dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 65535)), dim3(256), 0,
+                              k == 0 ? u->cn_cond : nullptr, cur16, u->W + cc.w, u->W + cc.b, B, eh, ew, cc.cin, cc.cout, cc.stride, 1, o);
             }
             cur16 = o; eh = oh; ew = ow;
         }
@@ -590,7 +569,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
         const ctx_unet::CondConv &co = u->cond_convs.back();
         f16 *emb = u->allocH((size_t)B * h * w * ch[0]);
         op_conv(u, cur16, co.w, co.b, nullptr, 0, x, B, h, w, co.cin, ch[0], 1, 0, emb);       // + conv_in(sample) as the residual operand
-        if (!u->dry && u->rc == 0) (void)hipMemcpyAsync(x, emb, (size_t)B * h * w * ch[0] * 2, hipMemcpyDeviceToDevice, u->s);
+        u->copy(x, emb, (size_t)B * h * w * ch[0] * 2);
         u->top = mark;
     }
     struct Skip { void *p; int C, h, w; };
@@ -643,7 +622,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             const size_t nel = (size_t)B * sk.h * sk.w * sk.C;
             if (sk.p == x) {                   // the last skip tensor is also the mid block's input, which stays as it is
                 f16 *cp = u->allocH(nel);
-                if (!u->dry && u->rc == 0) (void)hipMemcpyAsync(cp, sk.p, nel * 2, hipMemcpyDeviceToDevice, u->s);
+                u->copy(cp, sk.p, nel * 2);
                 sk.p = cp;
             }
             add_scaled((f16 *)sk.p, u->add_res + res_off, u->add_scale, nel);
@@ -666,11 +645,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
         op_gemm(u, (const f16 *)x, u->zm_w, u->zm_b, true, nullptr, B * h * w, cur, cur, u->cn_out ? u->cn_out + res_off : nullptr);
         res_off += (size_t)B * h * w * cur;
         u->ref_cursor = res_off;               // element count of the residual buffer (read by the size query)
-        if (!u->dry && u->rc == 0) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { ctx_set_error("controlnet_forward: launch failed: %s", hipGetErrorString(e)); return CTX_E_LAUNCH; }
-        }
-        return u->rc;
+        return engine_finish(u, "controlnet_forward");
     }
     if (u->add_res) add_scaled((f16 *)x, u->add_res + res_off, u->add_scale, (size_t)B * h * w * cur);
     for (int i = 0; i < n; ++i) {
@@ -682,7 +657,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             void *o = u->allocS((size_t)B * h * w * cout);
             size_t mark = u->top;
             void *cat = u->allocS((size_t)B * h * w * cin);
-            note(u, 2, 0);
+            u->note(2, 0);
             if (u->res32) RUN(ctx_concat_f32((const float *)x, (const float *)sk.p, (int64_t)B * h * w, cur, sk.C, (float *)cat, u->s));
             else RUN(ctx_concat_f16((const f16 *)x, (const f16 *)sk.p, (int64_t)B * h * w, cur, sk.C, (f16 *)cat, u->s));
             if (Lv.has_attn) {
@@ -706,13 +681,14 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     }
     f16 *y = u->allocH((size_t)B * h * w * cur);
     op_gn(u, x, u->cng, u->cnb, B, h * w, cur, c.norm_eps, 1, y, f.gn_stats);
-    note(u, 2, 2.0 * B * h * w * cur * c.out_channels * 9);
+    u->note(2, 2.0 * B * h * w * cur * c.out_channels * 9);
     RUN(ctx_conv_out_f16(y, u->W + u->cow, u->W + u->cob, B, h, w, cur, c.out_channels, out, u->s));
-    if (!u->dry && u->rc == 0) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { ctx_set_error("unet_forward: launch failed: %s", hipGetErrorString(e)); return CTX_E_LAUNCH; }
-    }
-    return u->rc;
+    return engine_finish(u, "unet_forward");
+}
+
+static int unet_dry(ctx_unet *u, int B, int H, int W, int L)
+{
+    return engine_dry_run(u, [&] { return unet_run(u, nullptr, nullptr, nullptr, B, H, W, L, nullptr); });
 }
 
 static int check_dims(const ctx_unet *u, int B, int H, int W, int L)
@@ -729,11 +705,8 @@ extern "C" int64_t ctx_unet_workspace_bytes(const ctx_unet_t *cu, int32_t B, int
 {
     ctx_unet *u = const_cast<ctx_unet *>(cu);
     if (!u || check_dims(u, B, H, W, ctx_len)) return -1;
-    bool was = u->dry;
-    u->dry = true;
-    unet_run(u, nullptr, nullptr, nullptr, B, H, W, ctx_len, nullptr);
-    u->dry = was;
-    return (int64_t)u->peak + 4096;
+    unet_dry(u, B, H, W, ctx_len);
+    return engine_workspace_need(u);
 }
 
 extern "C" int32_t ctx_unet_forward(ctx_unet_t *u, const float *sample, const float *timestep, const float *ctx, int32_t B,
@@ -752,11 +725,7 @@ extern "C" int64_t ctx_controlnet_residual_bytes(const ctx_unet_t *cu, int32_t B
 {
     ctx_unet *u = const_cast<ctx_unet *>(cu);
     if (!u || !u->is_controlnet || check_dims(u, B, H, W, 1)) return -1;
-    bool was = u->dry;
-    u->dry = true;
-    int rc = unet_run(u, nullptr, nullptr, nullptr, B, H, W, 1, nullptr);
-    u->dry = was;
-    return rc ? -1 : (int64_t)u->ref_cursor * 2 + 256;
+    return unet_dry(u, B, H, W, 1) ? -1 : (int64_t)u->ref_cursor * 2 + 256;
 }
 
 extern "C" int64_t ctx_controlnet_cond_cache_bytes(const ctx_unet_t *u, int32_t B, int32_t H, int32_t W)
@@ -794,12 +763,11 @@ extern "C" int64_t ctx_unet_ref_bank_bytes(const ctx_unet_t *cu, int32_t B, int3
     ctx_unet *u = const_cast<ctx_unet *>(cu);
     if (!u || check_dims(u, B, H, W, 1)) return -1;
     std::vector<ctx_unet::RefSlot> keep = u->ref_slots;
-    bool was = u->dry; int mode = u->ref_mode;
-    u->dry = true; u->ref_mode = 1;
-    unet_run(u, nullptr, nullptr, nullptr, B, H, W, 1, nullptr);
-    int64_t n = (int64_t)u->ref_cursor * 2 + 256;
-    u->dry = was; u->ref_mode = mode; u->ref_slots = keep;
-    return n;
+    int mode = u->ref_mode;
+    u->ref_mode = 1;
+    unet_dry(u, B, H, W, 1);
+    u->ref_mode = mode; u->ref_slots = keep;
+    return (int64_t)u->ref_cursor * 2 + 256;
 }
 
 extern "C" int64_t ctx_unet_workspace_bytes_ref(const ctx_unet_t *cu, int32_t B, int32_t H, int32_t W, int32_t ctx_len, int32_t mode,
@@ -808,13 +776,12 @@ extern "C" int64_t ctx_unet_workspace_bytes_ref(const ctx_unet_t *cu, int32_t B,
     ctx_unet *u = const_cast<ctx_unet *>(cu);
     if (!u || check_dims(u, B, H, W, ctx_len) || mode < 1 || mode > 2 || ref_row0 < 0 || ref_row0 >= B) return -1;
     std::vector<ctx_unet::RefSlot> keep = u->ref_slots;
-    bool was = u->dry; int m0 = u->ref_mode, r0 = u->ref_row0;
-    u->dry = true; u->ref_mode = mode; u->ref_row0 = ref_row0;
-    int rc = unet_run(u, nullptr, nullptr, nullptr, B, H, W, ctx_len, nullptr);
-    int64_t n = rc ? -1 : (int64_t)u->peak + 4096;
-    u->dry = was; u->ref_mode = m0; u->ref_row0 = r0;
+    int m0 = u->ref_mode, r0 = u->ref_row0;
+    u->ref_mode = mode; u->ref_row0 = ref_row0;
+    int rc = unet_dry(u, B, H, W, ctx_len);
+    u->ref_mode = m0; u->ref_row0 = r0;
     if (mode == 1) u->ref_slots = keep;
-    return n;
+    return rc ? -1 : engine_workspace_need(u);
 }
 
 extern "C" int32_t ctx_unet_forward_ref(ctx_unet_t *u, const float *sample, const float *timestep, const float *ctx, int32_t B,

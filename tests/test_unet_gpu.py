@@ -886,3 +886,56 @@ def test_clone_shared_keeps_residual_fp32(dev):
     y32 = net(x, 333.0, ctx)['sample'].clone()
     assert not torch.equal(y16, y32)                                                   # the switch changes this net's output
     assert torch.equal(net.clone_shared()(x, 333.0, ctx)['sample'], y32)
+
+
+@pytest.mark.parametrize("what", ["vae_decode", "vae_encode", "vae_encode_train", "unet_forward"])
+def test_short_workspace_is_refused_and_nothing_runs_on(dev, what):
+    """The C ABI's error contract: a handle bound with the workspace of a smaller shape refuses a larger call with CTX_E_STATE,
+    names the workspace, and launches nothing after the point of failure (the output keeps its sentinel); after a correct bind
+    the same handle gives the bits it gave before.  The buffer is physically large enough throughout: only the declared size
+    is short."""
+    from contexture_nerf_amd.unet import UNet2DConditionModel
+    from contexture_nerf_amd.vae import AutoencoderKL
+    from oracle import unet_ref
+    L, lib = _lib()
+    g = torch.Generator().manual_seed(5)
+    if what == "unet_forward":
+        cfg = unet_ref.tiny_config()
+        eng = UNet2DConditionModel(cfg, device=dev, seed=1)
+        x = torch.randn(2, 5, 16, 16, generator=g).to(dev)
+        ctx = torch.randn(2, 7, cfg['cross_attention_dim'], generator=g).to(dev)
+        t = eng._timestep(481.0)
+        out_shape = (2, cfg['out_channels'], 16, 16)
+        need = lambda h, w: lib.ctx_unet_workspace_bytes(eng._h, 2, h, w, 7)
+        small, large = need(8, 8), need(16, 16)
+        run = lambda out: lib.ctx_unet_forward(eng._h, L.ptr(x), L.ptr(t), L.ptr(ctx), 2, 16, 16, 7, L.ptr(out), L.stream())
+    else:
+        eng = AutoencoderKL(dict(latent_channels=4, out_channels=3, block_out_channels=(64, 128), layers_per_block=1, groups=32), device=dev, seed=3)
+        if what == "vae_decode":
+            x = torch.randn(1, 4, 16, 8, generator=g).to(dev)
+            out_shape = (1, 3, 32, 16)
+            need = lambda h, w: lib.ctx_vae_workspace_bytes(eng._h, 1, h, w)
+            small, large = need(8, 8), need(16, 8)
+            run = lambda out: lib.ctx_vae_decode(eng._h, L.ptr(x), 1, 16, 8, L.ptr(out), L.stream())
+        else:
+            x = (torch.rand(1, 3, 128, 128, generator=g) * 2 - 1).to(dev)
+            out_shape = (1, 8, 64, 64)
+            query, call = ((lib.ctx_vae_encode_workspace_bytes, lib.ctx_vae_encode) if what == "vae_encode" else
+                           (lib.ctx_vae_encode_train_workspace_bytes, lib.ctx_vae_encode_train))
+            small, large = query(eng._h, 1, 64, 32), query(eng._h, 1, 128, 128)
+            run = lambda out: call(eng._h, L.ptr(x), 1, 128, 128, L.ptr(out), L.stream())
+    assert 0 < small < large
+    ws = torch.empty(large, dtype=torch.uint8, device=dev)
+    bind = lambda declared: L.check(eng._c('bind')(eng._h, L.ptr(eng._weights), L.ptr(ws), declared))
+    bind(large)
+    before = torch.empty(out_shape, device=dev)
+    assert run(before) == 0
+    bind(small)
+    out = torch.full(out_shape, -123.0, device=dev)
+    assert run(out) == -3                                     # CTX_E_STATE
+    assert "workspace" in lib.ctx_last_error().decode()
+    torch.cuda.synchronize()
+    assert (out == -123.0).all(), "a kernel ran on after the workspace overflow"
+    bind(large)
+    assert run(out) == 0
+    assert torch.isfinite(out).all() and torch.equal(out, before)
