@@ -828,11 +828,53 @@ extern "C" int32_t ctx_get_rays(int32_t H, int32_t W, float fx, float fy, float 
     return CTX_OK;
 }
 
+// Per-sample terms of nerf-pytorch raw2outputs, shared by the forward and the backward so both see the same bits.
+// zx: lane 63's next depth (the first depth of the following chunk); noise is added to the density before the ReLU.
+template <bool NOISE>
+__device__ __forceinline__ void composite_sample(float qw, float nz, float zv, float zx, int s, int S, bool ok, float nrm,
+                                                 float &dist, float &e, float &alpha, float &t)
+{
+    // next sample's depth: wave_shl:1 on the DPP path (lane 63 keeps `old` = the first depth of the following chunk)
+    float zn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, zx), __builtin_bit_cast(int, zv), 0x130, 0xf, 0xf, false));
+    dist = (s + 1 < S) ? (zn - zv) : 1e10f;
+    dist = dist * nrm;
+    float pre = NOISE ? qw + nz : qw;
+    float sigma = pre > 0.f ? pre : 0.f;
+    e = __builtin_amdgcn_exp2f(-1.4426950408889634f * sigma * dist);
+    alpha = ok ? 1.0f - e : 0.f;
+    t = ok ? (1.0f - alpha) + 1e-10f : 1.0f;
+}
+
+// inclusive prefix product over the 64 lanes on the DPP path (no LDS crossbar): Hillis-Steele inside the 16-lane
+// rows (row_shr 1, 2, 4, 8; lanes without a source multiply by `old` = 1), then row_bcast 15 / 31 across rows;
+// exc = inclusive shifted right by one lane (wave_shr:1; lane 0 keeps `old` = 1)
+__device__ __forceinline__ void composite_prefix(float t, float &inc, float &exc)
+{
+    inc = t;
+    const int one = 0x3f800000;
+#define CTX_SCAN_STEP(ctrl, rmask) inc = inc * __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
+    CTX_SCAN_STEP(0x111, 0xf);
+    CTX_SCAN_STEP(0x112, 0xf);
+    CTX_SCAN_STEP(0x114, 0xf);
+    CTX_SCAN_STEP(0x118, 0xf);
+    CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
+    CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
+#undef CTX_SCAN_STEP
+    exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float composite_sigmoid(float x)
+{
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+
 // One wavefront per ray: lane s holds sample s of the current 64-sample chunk.  Transmittance is an
 // exclusive prefix product across lanes (6 DPP steps), colour/depth/acc are wave sums on the DPP path.  The next chunk's (or next
 // ray's first) loads are issued before the current chunk is reduced, so HBM latency overlaps the shuffle chain.
+template <bool NOISE>
 __global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ raw, const float *__restrict__ z,
-                                                   const float *__restrict__ rays_d, int64_t R, int S, int white,
+                                                   const float *__restrict__ rays_d, const float *__restrict__ noise,
+                                                   int64_t R, int S, int white,
                                                    float *__restrict__ rgb, float *__restrict__ disp,
                                                    float *__restrict__ acc, float *__restrict__ weights,
                                                    float *__restrict__ depth)
@@ -845,19 +887,20 @@ __global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ ra
     int64_t r = wave;
     int ch = 0;
     float4 q_n = make_float4(0.f, 0.f, 0.f, 0.f);
-    float z_n = 0.f, zx_n = 0.f;
+    float z_n = 0.f, zx_n = 0.f, nz_n = 0.f;
     auto fetch = [&](int64_t rr, int cc) {
         int s = cc * 64 + lane;
         bool ok = rr < R && s < S;
         q_n = ok ? raw[rr * S + s] : make_float4(0.f, 0.f, 0.f, 0.f);
         z_n = ok ? z[rr * S + s] : 0.f;
         zx_n = (rr < R && lane == 63 && s + 1 < S) ? z[rr * S + s + 1] : 0.f;      // first depth of the following chunk
+        if (NOISE) nz_n = ok ? noise[rr * S + s] : 0.f;
     };
     if (r < R) fetch(r, 0);
     float Tc = 1.0f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dep = 0.f, a = 0.f, nrm = 0.f;
     while (r < R) {
         float4 q = q_n;
-        float zv = z_n, zx = zx_n;
+        float zv = z_n, zx = zx_n, nz = nz_n;
         const int s = ch * 64 + lane;
         const bool ok = s < S;
         if (ch == 0) {
@@ -869,32 +912,14 @@ __global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ ra
         int64_t rn = r; int cn = ch + 1;
         if (cn == nch) { cn = 0; rn = r + nwaves; }
         fetch(rn, cn);
-        // next sample's depth: wave_shl:1 on the DPP path (lane 63 keeps `old` = the first depth of the following chunk)
-        float zn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, zx), __builtin_bit_cast(int, zv), 0x130, 0xf, 0xf, false));
-        float dist = (s + 1 < S) ? (zn - zv) : 1e10f;
-        dist = dist * nrm;
-        float sigma = q.w > 0.f ? q.w : 0.f;
-        float alpha = ok ? 1.0f - __builtin_amdgcn_exp2f(-1.4426950408889634f * sigma * dist) : 0.f;
-        float t = ok ? (1.0f - alpha) + 1e-10f : 1.0f;
-        // inclusive prefix product over the 64 lanes on the DPP path (no LDS crossbar): Hillis-Steele inside the 16-lane
-        // rows (row_shr 1, 2, 4, 8; lanes without a source multiply by `old` = 1), then row_bcast 15 / 31 across rows
-        float inc = t;
-        const int one = 0x3f800000;
-#define CTX_SCAN_STEP(ctrl, rmask) inc = inc * __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
-        CTX_SCAN_STEP(0x111, 0xf);
-        CTX_SCAN_STEP(0x112, 0xf);
-        CTX_SCAN_STEP(0x114, 0xf);
-        CTX_SCAN_STEP(0x118, 0xf);
-        CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
-        CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
-#undef CTX_SCAN_STEP
-        // exclusive = inclusive shifted right by one lane (wave_shr:1; lane 0 keeps `old` = 1)
-        float exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
+        float dist, e, alpha, t, inc, exc;
+        composite_sample<NOISE>(q.w, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
+        composite_prefix(t, inc, exc);
         float w = alpha * (Tc * exc);
         if (weights && ok) weights[r * S + s] = w;
-        c0 += w * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * q.x));
-        c1 += w * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * q.y));
-        c2 += w * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * q.z));
+        c0 += w * composite_sigmoid(q.x);
+        c1 += w * composite_sigmoid(q.y);
+        c2 += w * composite_sigmoid(q.z);
         dep += w * zv;
         a += w;
         Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
@@ -913,17 +938,142 @@ __global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ ra
     }
 }
 
+static int composite_blocks(int64_t R)
+{
+    int64_t nb = cdiv64(R, 4);
+    static int cap = -1;
+    if (cap < 0) { const char *e = getenv("CTX_COMPOSITE_BLOCKS"); cap = e ? atoi(e) : 262144; }   // one ray per wave up to 1 M rays: 136.8 us vs 142.6 at 32768 blocks (512^2 x 128)
+    return (int)(nb > cap ? cap : nb);
+}
+
+extern "C" int32_t ctx_raymarch_composite_fwd_noise(const float *raw, const float *z_vals, const float *rays_d, const float *noise,
+                                                    int64_t R, int32_t S, int32_t white_bkgd, float *rgb, float *disp, float *acc,
+                                                    float *weights, float *depth, ctx_stream_t stream)
+{
+    CTX_REQUIRE(raw && z_vals && rays_d && rgb && disp && acc && depth && R > 0 && S > 0, "raymarch: bad args");
+    if (noise)
+        hipLaunchKernelGGL(k_composite<true>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
+                           z_vals, rays_d, noise, R, S, white_bkgd, rgb, disp, acc, weights, depth);
+    else
+        hipLaunchKernelGGL(k_composite<false>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
+                           z_vals, rays_d, noise, R, S, white_bkgd, rgb, disp, acc, weights, depth);
+    CTX_CHECK_LAUNCH("raymarch_composite");
+    return CTX_OK;
+}
+
 extern "C" int32_t ctx_raymarch_composite_fwd(const float *raw, const float *z_vals, const float *rays_d, int64_t R,
                                               int32_t S, int32_t white_bkgd, float *rgb, float *disp, float *acc,
                                               float *weights, float *depth, ctx_stream_t stream)
 {
-    CTX_REQUIRE(raw && z_vals && rays_d && rgb && disp && acc && depth && R > 0 && S > 0, "raymarch: bad args");
-    int64_t nb = cdiv64(R, 4);
-    static int cap = -1;
-    if (cap < 0) { const char *e = getenv("CTX_COMPOSITE_BLOCKS"); cap = e ? atoi(e) : 262144; }   // one ray per wave up to 1 M rays: 136.8 us vs 142.6 at 32768 blocks (512^2 x 128)
-    if (nb > cap) nb = cap;
-    hipLaunchKernelGGL(k_composite, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw, z_vals,
-                       rays_d, R, S, white_bkgd, rgb, disp, acc, weights, depth);
-    CTX_CHECK_LAUNCH("raymarch_composite");
+    return ctx_raymarch_composite_fwd_noise(raw, z_vals, rays_d, nullptr, R, S, white_bkgd, rgb, disp, acc, weights, depth, stream);
+}
+
+// Backward of k_composite with respect to raw (closed form: DESIGN section 4d).  One wavefront per ray, two sweeps over the
+// ray's 64-sample chunks.  Sweep 1 (front to back) re-runs the forward's alpha / transmittance sequence for acc and depth and
+// leaves chunk c's entry transmittance in lane c of one register, which bounds S at 64 chunks.  Sweep 2 (back to front)
+// recomputes the chunk, carries the suffix sum of G_k w_k over the chunks behind it and adds a true in-wave suffix scan (row_shl
+// inside the 16-lane rows, the three row totals behind a row by readlane), so a sample deep behind an opaque one keeps its
+// relative accuracy.  No atomics, one fixed summation order; every element of grad_raw is written.
+#define COMPOSITE_BWD_MAX_S 4096
+template <bool NOISE>
+__global__ __launch_bounds__(256) void k_composite_bwd(const float4 *__restrict__ raw, const float *__restrict__ z,
+                                                       const float *__restrict__ rays_d, const float *__restrict__ noise,
+                                                       int64_t R, int S, int white,
+                                                       const float *__restrict__ g_rgb, const float *__restrict__ g_disp,
+                                                       const float *__restrict__ g_acc, const float *__restrict__ g_weights,
+                                                       const float *__restrict__ g_depth, float4 *__restrict__ grad_raw)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
+    const int nch = (S + 63) >> 6;
+    for (int64_t r = wave; r < R; r += nwaves) {
+        const float d0 = rays_d[r * 3 + 0], d1 = rays_d[r * 3 + 1], d2 = rays_d[r * 3 + 2];
+        const float nrm = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+        const float4 *rawr = raw + r * S;
+        const float *zr = z + r * S, *nr = NOISE ? noise + r * S : nullptr;
+        float Tc = 1.0f, tcv = 1.0f, dep = 0.f, a = 0.f;
+        for (int ch = 0; ch < nch; ++ch) {
+            const int s = ch * 64 + lane;
+            const bool ok = s < S;
+            float qw = ok ? rawr[s].w : 0.f;
+            float zv = ok ? zr[s] : 0.f;
+            float zx = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
+            float nz = (NOISE && ok) ? nr[s] : 0.f;
+            float dist, e, alpha, t, inc, exc;
+            composite_sample<NOISE>(qw, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
+            composite_prefix(t, inc, exc);
+            if (lane == ch) tcv = Tc;
+            float w = alpha * (Tc * exc);
+            dep += w * zv;
+            a += w;
+            Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
+        }
+        const float sd = wave_sum_dpp(dep), sa = wave_sum_dpp(a);
+        const float g0 = g_rgb ? g_rgb[r * 3 + 0] : 0.f, g1 = g_rgb ? g_rgb[r * 3 + 1] : 0.f, g2 = g_rgb ? g_rgb[r * 3 + 2] : 0.f;
+        const float qd = sd / sa;
+        const bool hasq = qd > 1e-10f;                                  // false on the acc == 0 ray (0 / 0): both gq terms drop
+        const float gq = (hasq && g_disp) ? -g_disp[r] / (qd * qd) : 0.f;
+        const float gd = (g_depth ? g_depth[r] : 0.f) + (hasq ? gq / sa : 0.f);
+        const float ga = ((g_acc ? g_acc[r] : 0.f) - (hasq ? gq * sd / (sa * sa) : 0.f)) - (white ? (g0 + g1) + g2 : 0.f);
+        float carry = 0.f;                                              // sum of G_k w_k over the chunks behind this one
+        for (int ch = nch - 1; ch >= 0; --ch) {
+            const int s = ch * 64 + lane;
+            const bool ok = s < S;
+            float4 q = ok ? rawr[s] : make_float4(0.f, 0.f, 0.f, 0.f);
+            float zv = ok ? zr[s] : 0.f;
+            float zx = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
+            float nz = (NOISE && ok) ? nr[s] : 0.f;
+            float gw = (g_weights && ok) ? g_weights[r * S + s] : 0.f;
+            float dist, e, alpha, t, inc, exc;
+            composite_sample<NOISE>(q.w, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
+            composite_prefix(t, inc, exc);
+            const float T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tcv), ch)) * exc;
+            const float w = alpha * T;
+            const float c0 = composite_sigmoid(q.x), c1 = composite_sigmoid(q.y), c2 = composite_sigmoid(q.z);
+            const float G = ((((g0 * c0 + g1 * c1) + g2 * c2) + gd * zv) + ga) + gw;          // dL/dw_s
+            // inclusive suffix sum of G_k w_k over the lanes at and behind this one
+            float suf = ok ? G * w : 0.f;
+#define CTX_SUFFIX_STEP(ctrl) suf = suf + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), ctrl, 0xf, 0xf, false))
+            CTX_SUFFIX_STEP(0x101);                   // row_shl 1, 2, 4, 8: lanes without a source add `old` = 0
+            CTX_SUFFIX_STEP(0x102);
+            CTX_SUFFIX_STEP(0x104);
+            CTX_SUFFIX_STEP(0x108);
+#undef CTX_SUFFIX_STEP
+            const int si = __builtin_bit_cast(int, suf);
+            const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16)), r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 32));
+            const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 48));
+            const int row = lane >> 4;
+            suf = suf + (row == 0 ? (r1 + (r2 + r3)) : row == 1 ? (r2 + r3) : row == 2 ? r3 : 0.f);
+            // exclusive: the inclusive sum of the next lane (wave_shl:1; lane 63 keeps `old` = 0)
+            const float X = carry + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), 0x130, 0xf, 0xf, false));
+            carry = carry + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, suf), 0));
+            // dL/dalpha_s * dist_s * e_s with e_s folded in before the division: e / t <= 1 and dist * e stays finite at dist = 1e10
+            const float da = (G * T) * (dist * e) - (X * (e * __builtin_amdgcn_rcpf(t))) * dist;
+            const float pre = NOISE ? q.w + nz : q.w;
+            float4 o;
+            o.x = (w * g0) * (c0 * (1.0f - c0));
+            o.y = (w * g1) * (c1 * (1.0f - c1));
+            o.z = (w * g2) * (c2 * (1.0f - c2));
+            o.w = pre > 0.f ? da : 0.f;                // the ReLU mask is a select: dist is 1e10 on the last sample
+            if (ok) grad_raw[r * S + s] = o;
+        }
+    }
+}
+
+extern "C" int32_t ctx_raymarch_composite_bwd(const float *raw, const float *z_vals, const float *rays_d, const float *noise,
+                                              int64_t R, int32_t S, int32_t white_bkgd, const float *g_rgb, const float *g_disp,
+                                              const float *g_acc, const float *g_weights, const float *g_depth, float *grad_raw,
+                                              ctx_stream_t stream)
+{
+    CTX_REQUIRE(raw && z_vals && rays_d && grad_raw && R > 0 && S > 0, "raymarch_bwd: bad args");
+    CTX_REQUIRE(S <= COMPOSITE_BWD_MAX_S, "raymarch_bwd: S exceeds the 4096 samples per ray the backward supports");
+    if (noise)
+        hipLaunchKernelGGL(k_composite_bwd<true>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
+                           z_vals, rays_d, noise, R, S, white_bkgd, g_rgb, g_disp, g_acc, g_weights, g_depth, (float4 *)grad_raw);
+    else
+        hipLaunchKernelGGL(k_composite_bwd<false>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
+                           z_vals, rays_d, noise, R, S, white_bkgd, g_rgb, g_disp, g_acc, g_weights, g_depth, (float4 *)grad_raw);
+    CTX_CHECK_LAUNCH("raymarch_composite_bwd");
     return CTX_OK;
 }

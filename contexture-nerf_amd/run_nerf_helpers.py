@@ -222,7 +222,7 @@ def ndc_rays(H, W, focal, near, rays_o, rays_d):
     return torch.stack([o0, o1, o2], -1), torch.stack([d0, d1, d2], -1)
 
 
-def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
+def sample_pdf(bins, weights, N_samples, det=False, pytest=False, generator=None):
     dev = bins.device
     weights = weights + 1e-5
     pdf = weights / torch.sum(weights, -1, keepdim=True)
@@ -231,7 +231,7 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     if det:
         u = torch.linspace(0., 1., steps=N_samples, device=dev).expand(list(cdf.shape[:-1]) + [N_samples])
     else:
-        u = torch.rand(list(cdf.shape[:-1]) + [N_samples], device=dev)
+        u = torch.rand(list(cdf.shape[:-1]) + [N_samples], device=dev, generator=generator)
     if pytest:
         np.random.seed(0)
         new_shape = list(cdf.shape[:-1]) + [N_samples]
@@ -251,32 +251,112 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return bins_g[..., 0] + t * (bins_g[..., 1] - bins_g[..., 0])
 
 
-def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False):
-    """nerf-pytorch raw2outputs (the compositing step src/run_nerf_helpers.py:130-133 points to), as one
-    wave-per-ray HIP kernel -> (rgb_map, disp_map, acc_map, weights, depth_map)."""
-    if raw_noise_std != 0:
-        raise L.CtxError("raw2outputs: raw_noise_std != 0 is not implemented on the HIP path")
+def raw_noise(R, S, std, device, pytest=False, generator=None):
+    """nerf-pytorch's density noise [R,S]: randn * std, or with pytest=True numpy's seeded uniform draw * std."""
+    if pytest:
+        np.random.seed(0)
+        return torch.tensor(np.random.rand(R, S) * std, dtype=torch.float32, device=device)
+    return torch.randn(R, S, device=device, generator=generator) * std
+
+
+def perturb_z_vals(z_vals, pytest=False, generator=None):
+    """nerf-pytorch's stratified jitter: one uniform draw inside each sample's interval [lower, upper] between the midpoints."""
+    mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
+    upper = torch.cat([mids, z_vals[..., -1:]], -1)
+    lower = torch.cat([z_vals[..., :1], mids], -1)
+    if pytest:
+        np.random.seed(0)
+        t_rand = torch.tensor(np.random.rand(*list(z_vals.shape)), dtype=torch.float32, device=z_vals.device)
+    else:
+        t_rand = torch.rand(z_vals.shape, device=z_vals.device, generator=generator)
+    return lower + (upper - lower) * t_rand
+
+
+def _composite_fwd(r, z, d, noise, white_bkgd):
     lib = L.load()
-    r, z, d = L.f32c(raw), L.f32c(z_vals), L.f32c(rays_d)
     R, S, _ = r.shape
     dev = r.device
     rgb = torch.empty(R, 3, device=dev); disp = torch.empty(R, device=dev); acc = torch.empty(R, device=dev)
     w = torch.empty(R, S, device=dev); depth = torch.empty(R, device=dev)
-    L.check(lib.ctx_raymarch_composite_fwd(L.ptr(r, torch.float32, "raw"), L.ptr(z), L.ptr(d), R, S, int(white_bkgd), L.ptr(rgb),
-                                           L.ptr(disp), L.ptr(acc), L.ptr(w), L.ptr(depth), L.stream()))
+    if noise is None:
+        L.check(lib.ctx_raymarch_composite_fwd(L.ptr(r, torch.float32, "raw"), L.ptr(z), L.ptr(d), R, S, int(white_bkgd), L.ptr(rgb),
+                                               L.ptr(disp), L.ptr(acc), L.ptr(w), L.ptr(depth), L.stream()))
+    else:
+        L.check(lib.ctx_raymarch_composite_fwd_noise(L.ptr(r, torch.float32, "raw"), L.ptr(z), L.ptr(d), L.ptr(noise, torch.float32, "noise"),
+                                                     R, S, int(white_bkgd), L.ptr(rgb), L.ptr(disp), L.ptr(acc), L.ptr(w), L.ptr(depth),
+                                                     L.stream()))
     return rgb, disp, acc, w, depth
 
 
-def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None):
-    """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays without perturbation /
-    hierarchical pass — z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from
-    sample_pdf), pts = o + d*z, raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused
-    embed+MLP kernel, then raw2outputs.  rays_o, rays_d: [R,3] -> (rgb [R,3], disp [R], acc [R], weights [R,S], depth [R])."""
+class _CompositeFn(torch.autograd.Function):
+    """raw2outputs with the gradient to raw (`ctx_raymarch_composite_bwd`); the backward recomputes alpha / transmittance /
+    acc / depth from the saved inputs, so nothing of size [R,S] is kept beside them."""
+
+    @staticmethod
+    def forward(ctx, raw, z, d, noise, white_bkgd):
+        out = _composite_fwd(raw, z, d, noise, white_bkgd)
+        ctx.save_for_backward(raw, z, d, noise)
+        ctx.white = int(white_bkgd)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
+        lib = L.load()
+        raw, z, d, noise = ctx.saved_tensors
+        R, S, _ = raw.shape
+        gs = [None if g is None else L.f32c(g) for g in (g_rgb, g_disp, g_acc, g_w, g_depth)]
+        grad = torch.empty_like(raw)
+        L.check(lib.ctx_raymarch_composite_bwd(L.ptr(raw), L.ptr(z), L.ptr(d), L.ptr(noise), R, S, ctx.white, L.ptr(gs[0]),
+                                               L.ptr(gs[1]), L.ptr(gs[2]), L.ptr(gs[3]), L.ptr(gs[4]), L.ptr(grad), L.stream()))
+        return grad, None, None, None, None
+
+
+def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False, generator=None):
+    """nerf-pytorch raw2outputs (the compositing step src/run_nerf_helpers.py:130-133 points to), as one
+    wave-per-ray HIP kernel -> (rgb_map, disp_map, acc_map, weights, depth_map).
+    raw_noise_std > 0 adds nerf-pytorch's noise to the density before the ReLU (`raw_noise`).  Under grad mode a `raw` that
+    requires grad gets its gradient from `ctx_raymarch_composite_bwd`; gradients go to raw only, so a z_vals or rays_d that
+    requires grad is refused instead of silently receiving None."""
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (z_vals, rays_d)):
+        raise L.CtxError("raw2outputs: the HIP path has no gradient with respect to z_vals / rays_d; detach them")
+    r, z, d = L.f32c(raw), L.f32c(z_vals), L.f32c(rays_d)
+    noise = raw_noise(r.shape[0], r.shape[1], raw_noise_std, r.device, pytest, generator) if raw_noise_std > 0 else None
+    if grad_mode and r.requires_grad:
+        return _CompositeFn.apply(r, z, d, noise, white_bkgd)
+    return _composite_fwd(r, z, d, noise, white_bkgd)
+
+
+def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None, perturb=0., raw_noise_std=0.,
+                N_importance=0, pytest=False, generator=None, return_extras=False):
+    """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays —
+    z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from sample_pdf), pts = o + d*z,
+    raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused embed+MLP kernel, then
+    raw2outputs.  rays_o, rays_d: [R,3] -> (rgb [R,3], disp [R], acc [R], weights [R,S], depth [R]).
+    perturb > 0 jitters the samples inside their intervals (`perturb_z_vals`), raw_noise_std > 0 adds the density noise, and
+    N_importance > 0 adds the hierarchical pass: sample_pdf (deterministic when perturb == 0) on the detached coarse weights,
+    merged and sorted with the coarse samples and evaluated by the same field; the returned tuple is then the fine one.
+    return_extras=True returns (outputs, extras) with extras = dict(z_vals) and, after a hierarchical pass, the coarse
+    rgb0 / disp0 / acc0 / weights0 / depth0 (part of the autograd graph) and z_fine."""
     ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
     if z_vals is None:
         t = torch.linspace(0., 1., steps=N_samples, device=ro.device)
         z_vals = (near * (1. - t) + far * t).expand(ro.shape[0], N_samples)
+    if perturb > 0.:
+        z_vals = perturb_z_vals(z_vals, pytest, generator)
     z_vals = L.f32c(z_vals)
     pts = ro[:, None, :] + rd[:, None, :] * z_vals[:, :, None]          # [R,S,3]
     raw = field.forward_pts(pts)                                         # [R,S,4]
-    return raw2outputs(raw, z_vals, rd, white_bkgd=white_bkgd)
+    out = raw2outputs(raw, z_vals, rd, raw_noise_std, white_bkgd, pytest, generator)
+    extras = {'z_vals': z_vals}
+    if N_importance > 0:
+        z_mid = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
+        z_fine = sample_pdf(z_mid, out[3][..., 1:-1].detach(), N_importance, det=(perturb == 0.), pytest=pytest, generator=generator)
+        z_all, _ = torch.sort(torch.cat([z_vals, z_fine], -1), -1)
+        z_all = z_all.contiguous()
+        extras = {'z_vals': z_all, 'z_fine': z_fine, 'rgb0': out[0], 'disp0': out[1], 'acc0': out[2], 'weights0': out[3],
+                  'depth0': out[4]}
+        pts = ro[:, None, :] + rd[:, None, :] * z_all[:, :, None]
+        out = raw2outputs(field.forward_pts(pts), z_all, rd, raw_noise_std, white_bkgd, pytest, generator)
+    return (out, extras) if return_extras else out

@@ -8,6 +8,10 @@ ray-march is absent), so this module is the thin host glue over the p
   ->  depth normalised like Renderer.normalize_multiple_depth's output convention (closer = larger, background 0)
   ->  StableDiffusion.img2img_step (src/stable_diffusion_depth.py:284-578) on the rendered image + depth.
 
+Training: `train_step` is nerf-pytorch's optimisation step on a batch of rays (stratified jitter, density noise, hierarchical
+pass, photometric MSE) with the gradient through the compositing kernel's backward into the field; `fit_views` distils posed
+images (e.g. renders of a painted mesh) into the 3-D field with it.
+
 Multi-GPU: rays shard by contiguous row tiles with NO exchange until the image gather (`all_gather` of the
 tiles); the refine step is one UNet denoise per image, i.e. replicas only.
 """
@@ -33,20 +37,12 @@ def shard_rows(H, rank, world):
 @torch.no_grad()
 def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0):
     """-> dict(rgb [h,W,3], depth [h,W], acc [h,W], disp [h,W]) for the row range `rows` (default: all).
-    N_importance > 0 adds nerf-pytorch's hierarchical pass: sample_pdf(det=True) on the coarse weights, merged and sorted
-    with the coarse samples, evaluated by the same field."""
+    N_importance > 0 adds nerf-pytorch's hierarchical pass (render_rays: sample_pdf(det=True) on the coarse weights, merged
+    and sorted with the coarse samples, evaluated by the same field)."""
     ro, rd = rnh.get_rays(H, W, K, c2w)
     r0, r1 = (0, H) if rows is None else rows
     ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
-    rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd)
-    if N_importance > 0:
-        t = torch.linspace(0., 1., N_samples, device=ro.device)
-        z = (near * (1. - t) + far * t).expand(ro.shape[0], N_samples)
-        z_mid = .5 * (z[..., 1:] + z[..., :-1])
-        z_fine = rnh.sample_pdf(z_mid, wts[..., 1:-1], N_importance, det=True)
-        z_all, _ = torch.sort(torch.cat([z, z_fine], -1), -1)
-        rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, z_all.shape[-1], white_bkgd=white_bkgd,
-                                                     z_vals=z_all.contiguous())
+    rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance)
     h = r1 - r0
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
@@ -96,3 +92,47 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
                                  num_inference_steps=num_inference_steps, update_mask=mask, fixed_seed=fixed_seed,
                                  image_size=image_size)
     return refined, {'rgb': rgb, 'depth': depth, 'acc': acc}
+
+
+def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
+               white_bkgd=False, generator=None):
+    """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
+    loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
+    rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync."""
+    optimizer.zero_grad(set_to_none=True)
+    out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
+                                  raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
+                                  return_extras=True)
+    target = target_rgb.reshape(-1, 3)
+    img_loss = rnh.img2mse(out[0], target)
+    loss = img_loss
+    if 'rgb0' in extras:
+        loss = loss + rnh.img2mse(extras['rgb0'], target)
+    loss.backward()
+    optimizer.step()
+    return {'loss': loss.detach(), 'psnr': rnh.mse2psnr(img_loss.detach()).reshape(())}
+
+
+def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
+              perturb=1., raw_noise_std=0., white_bkgd=False):
+    """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
+    Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
+    and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
+    The views can be renders of a painted mesh: TexturedMeshModel.render on a white background (pass white_bkgd=True then)
+    with the camera-to-world matrices of the same poses."""
+    dev = next(field.parameters()).device
+    images = images.to(device=dev, dtype=torch.float32)
+    V, H, W, _ = images.shape
+    rays = [rnh.get_rays(H, W, K, c2ws[v].to(dev)) for v in range(V)]
+    ro = torch.stack([r[0] for r in rays]).reshape(-1, 3)
+    rd = torch.stack([r[1] for r in rays]).reshape(-1, 3)
+    target = images.reshape(-1, 3)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    opt = torch.optim.Adam(field.parameters(), lr=lr)
+    hist = []
+    for _ in range(iters):
+        idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
+        step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
+                          perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen)
+        hist.append(step['loss'])
+    return torch.stack(hist).tolist()

@@ -215,6 +215,22 @@ int32_t ctx_get_rays(int32_t H, int32_t W, float fx, float fy, float cx, float c
 int32_t ctx_raymarch_composite_fwd(const float *raw, const float *z_vals, const float *rays_d,
                                    int64_t R, int32_t S, int32_t white_bkgd, float *rgb, float *disp,
                                    float *acc, float *weights, float *depth, ctx_stream_t stream);
+/* The same with nerf-pytorch's density noise: sigma = relu(raw.w + noise), noise[R,S] (nullable: then this is
+   ctx_raymarch_composite_fwd bit for bit; with noise it equals that call on raw with the noise added to .w). */
+int32_t ctx_raymarch_composite_fwd_noise(const float *raw, const float *z_vals, const float *rays_d,
+                                         const float *noise /*nullable*/, int64_t R, int32_t S, int32_t white_bkgd,
+                                         float *rgb, float *disp, float *acc, float *weights /*nullable*/, float *depth,
+                                         ctx_stream_t stream);
+/* Backward of the compositing with respect to raw: grad_raw[R,S,4] = d loss / d raw, every element written.  The
+   upstream gradients g_rgb[R,3] g_disp[R] g_acc[R] g_weights[R,S] g_depth[R] are each nullable (= zero).  alpha,
+   transmittance, acc and depth are recomputed from the inputs with the forward's instruction sequence: nothing is
+   carried over from the forward.  On a ray with acc == 0 the disparity terms are dropped (finite result); grad_raw.w
+   is exactly 0 where raw.w + noise <= 0.  S <= 4096, larger S is refused with a message.  No gradient with respect
+   to z_vals or rays_d.  Deterministic (no atomics, fixed summation order). */
+int32_t ctx_raymarch_composite_bwd(const float *raw, const float *z_vals, const float *rays_d,
+                                   const float *noise /*nullable*/, int64_t R, int32_t S, int32_t white_bkgd,
+                                   const float *g_rgb, const float *g_disp, const float *g_acc, const float *g_weights,
+                                   const float *g_depth, float *grad_raw, ctx_stream_t stream);
 
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
