@@ -152,11 +152,6 @@ __device__ __forceinline__ void store_part4(const GemmArgs &a, float *row, int n
 __device__ __forceinline__ f16 geglu(float xv, float gv) { return (f16)(xv * gelu_erf(gv)); }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static inline int ctx_env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 // 1: the weights are the larger operand (unique bytes: weights N*K, activations M*K; conv: M*Cin, the 9 taps re-read the same pixels)
 static inline int ctx_gemm_mfast(const GemmArgs &a, bool conv)
 {

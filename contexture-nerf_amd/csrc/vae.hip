@@ -297,7 +297,7 @@ static void vattn(ctx_vae *v, const VAttn &at, const f16 *o, f16 *x, int B, int 
         const f16 *base = qkv ? qkv + (size_t)b * S * 3 * top : nullptr;
         vrows(v, base, S, top, qb);
         vrows(v, base ? base + top : nullptr, S, top, kb);
-        VRUN(ctx_transpose_v_f16(base + 2 * top, 1, S, 3 * top, top / 64, S, 0, vt, v->s));     // V^T through the head-transpose kernel
+        VRUN(ctx_transpose_v_f16(base + 2 * top, 1, S, 3 * top, top / 64, S, vt, v->s));     // V^T through the head-transpose kernel
         vprobs(v, qb, kb, S, top, 1.4426950408889634f / sqrtf((float)top), sc, pr);
         engine_linear(*v, pr, vt, nullptr, nullptr, S, top, S, att ? att + (size_t)b * S * top : nullptr);
     }
@@ -568,16 +568,16 @@ static void vattn_bwd(ctx_vae *v, const VAttn &at, const f16 *o, const f16 *qkv,
         vprobs(v, qb, kb, S, top, 1.4426950408889634f * scale, sc, pr);                             // P (recomputed)
         engine_linear(*v, da, vb, nullptr, nullptr, S, S, top, dp);                                 // dP = dAtt V^T
         // dV = P^T dAtt : X = P^T [S,S], Wt = dAtt^T [top,S]
-        VRUN(ctx_transpose_v_f16(pr, 1, S, S, S / 64, S, 0, tr, v->s));
-        VRUN(ctx_transpose_v_f16(da, 1, S, top, top / 64, S, 0, tb, v->s));
+        VRUN(ctx_transpose_v_f16(pr, 1, S, S, S / 64, S, tr, v->s));
+        VRUN(ctx_transpose_v_f16(da, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, tr, tb, nullptr, nullptr, S, top, S, dq ? dq + 2 * top : nullptr, 3 * top);
         ENGINE_LAUNCH(v, k_softmax_bwd_rows, dim3(S), dim3(256), 0, pr, dp, S, scale, sc);          // dS -> sc
         // dQ = dS K : Wt = K^T [top,S]
-        VRUN(ctx_transpose_v_f16(kb, 1, S, top, top / 64, S, 0, tb, v->s));
+        VRUN(ctx_transpose_v_f16(kb, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, sc, tb, nullptr, nullptr, S, top, S, dq, 3 * top);
         // dK = dS^T Q : X = dS^T, Wt = Q^T
-        VRUN(ctx_transpose_v_f16(sc, 1, S, S, S / 64, S, 0, tr, v->s));
-        VRUN(ctx_transpose_v_f16(qb, 1, S, top, top / 64, S, 0, tb, v->s));
+        VRUN(ctx_transpose_v_f16(sc, 1, S, S, S / 64, S, tr, v->s));
+        VRUN(ctx_transpose_v_f16(qb, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, tr, tb, nullptr, nullptr, S, top, S, dq ? dq + top : nullptr, 3 * top);
     }
     f16 *dg = datt;                                    // datt is dead
