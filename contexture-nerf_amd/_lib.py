@@ -34,6 +34,8 @@ SIGNATURES = {
     "ctx_texmap_plan_stale": (_i32, [_vp, _vp]),
     "ctx_uv_scatter_fixed": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "ctx_fixed_to_float": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "ctx_uv_gather_ws_bytes": (_i64, [_i32, _i32]),
+    "ctx_uv_gather_fixed": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "ctx_atlas_fill_ws_bytes": (_i64, [_i32]),
     "ctx_nearest_seed": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "ctx_atlas_fill": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),

@@ -51,6 +51,7 @@ class MeshBatchPainter:
         contrib = [torch.zeros(4, T, T, dtype=torch.int64, device=self.device) for _ in self.trainers]   # 2^-32 fixed point
         optim = self.trainers[0].cfg.optim
         vpe, infl = int(optim.views_per_eval), int(optim.views_in_flight)
+        project = {m: tr.projector() for m, tr in enumerate(self.trainers)}       # guide.projection: scatter | gather
         for wave in plan_waves(len(mine), vpe, infl):
             items = [mine[k] for grp in wave for k in grp]
             preps = [self.trainers[m]._paint_prepare(self.trainers[m].train_views[self.view_ids[v]], image_size, num_inference_steps)
@@ -60,7 +61,7 @@ class MeshBatchPainter:
                 tr = self.trainers[m]
                 rgb_output, obj_mask = tr._paint_finish(ctx, rgb)
                 k = slot[(m, self.view_ids[v])]
-                tr.project_back_scatter(ctx['render_cache'], rgb_output, tr.view_weights[k:k + 1] & (obj_mask > 0), acc=contrib[m])
+                project[m](ctx['render_cache'], rgb_output, tr.view_weights[k:k + 1] & (obj_mask > 0), acc=contrib[m])
         # phase C: one all-reduce(SUM) per mesh
         res = []
         for m, tr in enumerate(self.trainers):

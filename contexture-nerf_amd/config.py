@@ -60,6 +60,10 @@ class GuideConfig:
                                      # 'nearest': after the atlas merge every uncovered chart texel copies its nearest covered texel and the
                                      # charts are padded outward (ConTEXTure.complete_atlas, csrc/atlasfill.hip)
     atlas_pad: int = 8               # texels of chart-edge padding of atlas_fill = 'nearest' (0: hole fill only)
+    projection: str = 'scatter'      # how painted views reach the atlas.  'scatter': every visible pixel splats into the four texels round its
+                                     # UV (ConTEXTure.project_back_scatter, csrc/uvscatter.hip; the outputs of earlier builds, bit for bit);
+                                     # 'gather': every chart texel looks its surface point up in the views (project_back_gather,
+                                     # csrc/uvgather.hip): no pinholes where the surface is magnified, nothing outside the charts
 
 
 @dataclass
@@ -138,6 +142,7 @@ def _apply(obj, key, value):
 
 
 ATLAS_FILL_MODES = ('none', 'nearest')
+PROJECTION_MODES = ('scatter', 'gather')
 
 
 def validate(cfg):
@@ -148,6 +153,8 @@ def validate(cfg):
             raise ValueError(f"guide.atlas_fill={guide.atlas_fill!r}: expected one of {ATLAS_FILL_MODES}")
         if guide.atlas_pad < 0:
             raise ValueError(f"guide.atlas_pad={guide.atlas_pad}: expected >= 0")
+        if guide.projection not in PROJECTION_MODES:
+            raise ValueError(f"guide.projection={guide.projection!r}: expected one of {PROJECTION_MODES}")
     optim = getattr(cfg, 'optim', None)
     if optim is not None and not optim.consistency_weight >= 0:
         raise ValueError(f"optim.consistency_weight={optim.consistency_weight}: expected >= 0")

@@ -191,6 +191,37 @@ def scatter_fixed(values, uv, mask_idx, acc, frac_bits=SCATTER_FRAC_BITS, reuse=
     return acc
 
 
+def gather_fixed(values, weight, face_idx, face_vertices_image, faces, texel_face, texel_bary, acc, frac_bits=SCATTER_FRAC_BITS):
+    """acc [C+1,T,T] int64 += the texel-side gather of painted views (uvgather.hip): every chart texel of (texel_face [T,T] i64,
+    texel_bary [T,T,3] f32: TexturedMeshModel.texel_map) projects its surface point into every view of face_idx [B,H,W] i64 /
+    face_vertices_image [B,F,3,2] f32, takes the bilinear colour of values [B,H,W,C] f32 there if its face (or one sharing a
+    vertex in faces [F,3] i64) owns the pixel, and adds round(colour * w * 2^frac_bits) to acc[:C] and round(w * 2^frac_bits)
+    to acc[C]; w = weight [B,H,W] f32 at the nearest pixel, or 1 for weight = None.  Integer sums, as scatter_fixed."""
+    lib = L.load()
+    p = (L.ptr(values, torch.float32, "values"), L.ptr(weight, torch.float32, "weight"), L.ptr(face_idx, torch.int64, "face_idx"),
+         L.ptr(face_vertices_image, torch.float32, "face_vertices_image"), L.ptr(faces, torch.int64, "faces"),
+         L.ptr(texel_face, torch.int64, "texel_face"), L.ptr(texel_bary, torch.float32, "texel_bary"))
+    p_acc = L.ptr(acc, torch.int64, "acc")
+    if values.dim() != 4 or face_idx.dim() != 3 or faces.dim() != 2 or faces.shape[1] != 3 or texel_face.dim() != 2 or acc.dim() != 3:
+        raise L.CtxError(f"gather_fixed: want values [B,H,W,C], face_idx [B,H,W], faces [F,3], texel_face [T,T], acc [C+1,T,T]; got "
+                         f"{tuple(values.shape)}, {tuple(face_idx.shape)}, {tuple(faces.shape)}, {tuple(texel_face.shape)}, {tuple(acc.shape)}")
+    B, H, W, C = values.shape
+    F, T = faces.shape[0], texel_face.shape[0]
+    want = dict(face_idx=(B, H, W), face_vertices_image=(B, F, 3, 2), texel_face=(T, T), texel_bary=(T, T, 3), acc=(C + 1, T, T))
+    got = dict(face_idx=face_idx, face_vertices_image=face_vertices_image, texel_face=texel_face, texel_bary=texel_bary, acc=acc)
+    if weight is not None:
+        want['weight'], got['weight'] = (B, H, W), weight
+    for k, shp in want.items():
+        if tuple(got[k].shape) != shp:
+            raise L.CtxError(f"gather_fixed: {k} is {tuple(got[k].shape)}, expected {shp} (values {tuple(values.shape)}, faces {tuple(faces.shape)})")
+    n = lib.ctx_uv_gather_ws_bytes(B, F)
+    if n < 0:
+        raise L.CtxError(f"gather_fixed: B={B} or F={F} < 1")
+    ws = torch.empty(n, dtype=torch.uint8, device=values.device)
+    L.check(lib.ctx_uv_gather_fixed(*p, B, H, W, C, F, T, int(frac_bits), p_acc, L.ptr(ws), n, L.stream()))
+    return acc
+
+
 def fixed_to_float(acc, frac_bits=SCATTER_FRAC_BITS, out=None):
     """int64 sums in units of 2^-frac_bits -> float32 (one rounding per texel)."""
     lib = L.load()

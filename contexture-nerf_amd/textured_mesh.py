@@ -63,6 +63,18 @@ def uv_chart_mask(face_uv, T):
         return (idx[0] >= 0).to(torch.uint8).contiguous()
 
 
+def uv_texel_map(face_uv, T):
+    """face_uv [1,F,3,2] (vt[ft]) -> (texel_face [T,T] int64, -1 = no chart; texel_bary [T,T,3] f32): the same drawing of the UV
+    triangles as uv_chart_mask, with the 3 x 3 identity as every face's features, so the interpolated features are the
+    barycentrics of the texel centre in its face.  texel_face >= 0 is uv_chart_mask."""
+    with torch.no_grad():
+        xy = (face_uv.detach().to(torch.float32) * 2 - 1).contiguous()
+        z = torch.full(xy.shape[:3], -1.0, device=xy.device)
+        eye = torch.eye(3, device=xy.device).expand(1, xy.shape[1], 3, 3).contiguous()
+        bary, idx = kal.render.mesh.rasterize(T, T, z, xy, eye)
+        return idx[0].contiguous(), bary[0].contiguous()
+
+
 class TexturedMeshModel(torch.nn.Module):
     def __init__(self, opt, render_grid_size=1024, texture_resolution=1024, initial_texture_path=None, cache_path=None,
                  device=torch.device('cuda'), augmentations=False, augment_prob=0.5, fovyangle=np.pi / 3,
@@ -145,6 +157,15 @@ class TexturedMeshModel(torch.nn.Module):
         cached = getattr(self, '_chart_mask', None)
         if cached is None or cached.shape[0] != T:
             cached = self._chart_mask = uv_chart_mask(self.face_attributes, T)
+        return cached
+
+    def texel_map(self):
+        """uv_texel_map of this mesh's UV triangles at the texture resolution: (texel_face [T,T] int64, texel_bary [T,T,3] f32), what
+        the texel-side gather (ConTEXTure.project_back_gather) looks up.  Built once, like chart_mask."""
+        T = int(self.texture_resolution)
+        cached = getattr(self, '_texel_map', None)
+        if cached is None or cached[0].shape[0] != T:
+            cached = self._texel_map = uv_texel_map(self.face_attributes, T)
         return cached
 
     def export_mesh(self, path, texture=None):

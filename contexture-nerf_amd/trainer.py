@@ -174,6 +174,31 @@ class ConTEXTure:
         kal.scatter_fixed(go, uvc, face_idx.contiguous(), acc)
         return acc
 
+    def project_back_gather(self, render_cache, rgb_output, weight_mask, acc=None):
+        """The same back-projection from the texel side (guide.projection = 'gather', uvgather.hip): every chart texel of
+        mesh_model.texel_map() projects its surface point into the view and, where its face (or a face sharing a vertex with it)
+        owns that pixel, adds w*rgb to acc[0:3] and w to acc[3]; rgb is the bilinear colour of the painted view over the taps
+        such a face owns, w the weight mask at the nearest pixel.  No pinholes where the surface is magnified and nothing
+        outside the charts.  acc as in project_back_scatter (int64, 2^-32): merge_atlas, complete_atlas and export apply as
+        they are."""
+        from . import kal
+        face_idx = render_cache['face_idx']
+        T = self.cfg.guide.texture_resolution
+        texel_face, texel_bary = self.mesh_model.texel_map()
+        values = rgb_output.permute(0, 2, 3, 1).to(torch.float32).contiguous()
+        w = weight_mask.to(torch.float32).reshape(face_idx.shape).contiguous()
+        if acc is None:
+            acc = torch.zeros(4, T, T, dtype=torch.int64, device=face_idx.device)
+        fvi = render_cache['face_vertices_image']
+        fvi = fvi if (fvi.dtype == torch.float32 and fvi.is_contiguous()) else L.f32c(fvi)
+        kal.gather_fixed(values, w, face_idx.contiguous(), fvi, self.mesh_model.mesh.faces.to(torch.int64).contiguous(), texel_face, texel_bary, acc)
+        return acc
+
+    def projector(self):
+        """project_back_scatter or project_back_gather, as guide.projection says."""
+        from .config import validate
+        return self.project_back_gather if validate(self.cfg).guide.projection == 'gather' else self.project_back_scatter
+
     @torch.no_grad()
     def project_back(self, render_cache, background, rgb_output, object_mask, update_mask, z_normals=None, z_normals_cache=None):
         """The call the reference makes at trainer.py:1076-1090 (its body is missing there; upstream TEXTure fits the
@@ -189,7 +214,7 @@ class ConTEXTure:
             w = w * z_normals.clamp(0, 1)
         if getattr(self, 'atlas_acc', None) is None:
             self.atlas_acc = torch.zeros(4, T, T, dtype=torch.int64, device=self.device)
-        self.project_back_scatter(render_cache, rgb_output, w, acc=self.atlas_acc)
+        self.projector()(render_cache, rgb_output, w, acc=self.atlas_acc)
         self.atlas_contrib = kal.fixed_to_float(self.atlas_acc)
         wsum = self.atlas_contrib[3:]
         atlas = (self.atlas_contrib[:3] / wsum.clamp_min(1e-8))[None]

@@ -103,7 +103,27 @@ int32_t ctx_uv_scatter_fixed(const float *values, const float *uv, const int64_t
                              const void *plan, int32_t frac_bits, int64_t *acc, ctx_stream_t stream);
 int32_t ctx_fixed_to_float(const int64_t *acc, int64_t n, int32_t frac_bits, int32_t accumulate, float *out, ctx_stream_t stream);
 
-/* Atlas completion (atlasfill.hip): the step after the scatter above.  The scatter is a forward one, so texels no screen pixel
+/* The same back-projection as a texel-side GATHER (uvgather.hip): every chart texel looks its own surface point up in every view,
+   so a magnified surface leaves no pinholes and nothing is written outside a chart.  No atomics, no plan.
+   texel_face [T,T] i64 (-1 = no chart) and texel_bary [T,T,3] f32: the UV triangles drawn at T x T with the identity as face
+   features.  faces [F,3] i64, face_vertices_image [B,F,3,2] f32, face_idx [B,H,W] i64 (-1 = background), values [B,H,W,C] f32
+   (NHWC, colour only), weight [B,H,W] f32 or NULL (= 1), acc [C+1,T,T] int64 in units of 2^-frac_bits, 1 <= C <= 4.
+   For texel p with f = texel_face[p] >= 0, barycentrics (b0,b1,b2) and view v, in binary32 in the order written:
+     f must own a pixel of face_idx[v];  X = (b0*x0 + b1*x1) + b2*x2, Y likewise, from face_vertices_image[v,f];
+     px = ((X + 1)*W - 1)/2, py = ((1 - Y)*H - 1)/2;  xn = floor(px + 0.5), yn = floor(py + 0.5), inside the image;
+     g = face_idx[v,yn,xn] must be related to f (equal, or sharing a vertex id in faces);
+     colour_c = (sum w_k * values[v,tap_k,c]) / (sum w_k) over the bilinear taps at (floor(px), floor(py)) + {0,1}^2 (weights
+     and order of ctx_texture_mapping_fwd: nw, ne, sw, se) that are inside the image and whose owner is related to f;
+     omega = weight[v,yn,xn]; omega == 0 or a non-finite omega or colour: no contribution;
+     acc[c,p] += rint(colour_c * omega * 2^frac_bits), acc[C,p] += rint(omega * 2^frac_bits)   (the conversion of the scatter).
+   One thread owns a texel: integer sums, one plain read-modify-write, independent of grid, order and stream; texels outside
+   every chart are never written.  ws: ctx_uv_gather_ws_bytes(B, F) bytes (the [B,F] map of faces that own a pixel). */
+int64_t ctx_uv_gather_ws_bytes(int32_t B, int32_t F);
+int32_t ctx_uv_gather_fixed(const float *values, const float *weight, const int64_t *face_idx, const float *face_vertices_image,
+                            const int64_t *faces, const int64_t *texel_face, const float *texel_bary, int32_t B, int32_t H, int32_t W,
+                            int32_t C, int32_t F, int32_t T, int32_t frac_bits, int64_t *acc, void *ws, int64_t ws_bytes, ctx_stream_t stream);
+
+/* Atlas completion (atlasfill.hip): the step after the scatter above. The scatter is a forward one, so texels no screen pixel
    reaches stay empty; the call site it completes is src/training/trainer.py:1076-1090 (project_back, which has no body upstream).
    Colours are copied, never computed, so the result is defined by an integer source map:
      nearest seed of texel (y, x) = the seed (sy, sx) minimising (d2, sy, sx) lexicographically, d2 = (y-sy)^2 + (x-sx)^2 (exact).
