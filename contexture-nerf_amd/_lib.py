@@ -56,6 +56,11 @@ SIGNATURES = {
     "ctx_uvmlp_fwd_save": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ctx_uvmlp_bwd_ws_bytes": (_i64, [_i64, _i32, _i32]),
     "ctx_uvmlp_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_texel_active_mark": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_texel_compact_ws_bytes": (_i64, [_i64]),
+    "ctx_texel_compact": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "ctx_uvmlp_fwd_save_idx": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ctx_uvmlp_bwd_idx": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ctx_get_rays": (_i32, [_i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "ctx_raymarch_composite_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctx_raymarch_composite_fwd_noise": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -84,6 +84,9 @@ class OptimConfig:
     consistency_weight: float = 0.0  # > 0: the SDS loop back-propagates loss - weight * view consistency of the six rendered views
                                      # (src/training/trainer.py:856-863, where upstream fixed the weight at 500 and then switched the term
                                      # off); 0.0: the kernel is not called and the loop computes what it computed before
+    field_texels: str = 'all'        # the texels the SDS loop evaluates and trains the texture field on.  'all': the whole atlas (the outputs
+                                     # of earlier builds, bit for bit); 'active': only the texels the loop's cached raster can read
+                                     # (kal.active_texels; the rendered images keep their bits, src/models/textured_mesh.py:303-347)
 
 
 @dataclass
@@ -143,6 +146,7 @@ def _apply(obj, key, value):
 
 ATLAS_FILL_MODES = ('none', 'nearest')
 PROJECTION_MODES = ('scatter', 'gather')
+FIELD_TEXELS_MODES = ('all', 'active')
 
 
 def validate(cfg):
@@ -158,6 +162,8 @@ def validate(cfg):
     optim = getattr(cfg, 'optim', None)
     if optim is not None and not optim.consistency_weight >= 0:
         raise ValueError(f"optim.consistency_weight={optim.consistency_weight}: expected >= 0")
+    if optim is not None and optim.field_texels not in FIELD_TEXELS_MODES:
+        raise ValueError(f"optim.field_texels={optim.field_texels!r}: expected one of {FIELD_TEXELS_MODES}")
     return cfg
 
 

@@ -619,6 +619,39 @@ extern "C" int32_t ctx_texture_mapping_bwd(const float *grad_out, const float *u
     return CTX_OK;
 }
 
+// The texels a raster can read (the set get_texture_map_only_valid_areas, src/models/textured_mesh.py:303-347, restricts the field to,
+// taken from the pixels instead of the charts): the four bilinear taps of every foreground pixel, with k_texmap_fwd's index
+// arithmetic, whatever their weights.  Plain byte stores of 1 (as k_vc_seen): idempotent, so several rasters accumulate a union.
+// A background pixel's uv may hold anything and is not read.
+__global__ __launch_bounds__(256) void k_texel_mark(const float *__restrict__ uv, const int64_t *__restrict__ face_idx, int64_t HW, int T,
+                                                    uint8_t *__restrict__ mask)
+{
+    int b = blockIdx.y;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
+        size_t pix = (size_t)b * HW + i;
+        if (face_idx[pix] < 0) continue;
+        float2 q = *(const float2 *)(uv + pix * 2);
+        float ix = src_index(q.x * 2.0f - 1.0f, T), iy = src_index((1.0f - q.y) * 2.0f - 1.0f, T);
+        int x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;
+        bool bx0 = x0 >= 0 && x0 < T, bx1 = x1 >= 0 && x1 < T, by0 = y0 >= 0 && y0 < T, by1 = y1 >= 0 && y1 < T;
+        if (bx0 && by0) mask[(size_t)y0 * T + x0] = 1;
+        if (bx1 && by0) mask[(size_t)y0 * T + x1] = 1;
+        if (bx0 && by1) mask[(size_t)y1 * T + x0] = 1;
+        if (bx1 && by1) mask[(size_t)y1 * T + x1] = 1;
+    }
+}
+
+extern "C" int32_t ctx_texel_active_mark(const float *uv, const int64_t *face_idx, int32_t B, int32_t H, int32_t W, int32_t T, uint8_t *mask,
+                                         ctx_stream_t stream)
+{
+    CTX_REQUIRE(uv && face_idx && mask, "texel_active_mark: null pointer");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && T >= 2, "texel_active_mark: bad sizes B=%d H=%d W=%d T=%d", B, H, W, T);
+    const int64_t HW = (int64_t)H * W;
+    hipLaunchKernelGGL(k_texel_mark, dim3(capped_blocks(HW, 256, 4096), B), dim3(256), 0, (hipStream_t)stream, uv, face_idx, HW, T, mask);
+    CTX_CHECK_LAUNCH("texel_active_mark");
+    return CTX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // View weights.  max over pixels of fnz[b, face_idx[b,p]] per face == max over the views in which
 // the face is visible, so phase 0 only marks (view, face) visibility (idempotent byte stores, no
@@ -690,10 +723,9 @@ extern "C" int32_t ctx_view_weights_mask(const int64_t *face_idx, const float *f
 
 // create_face_view_map: ordered stream compaction (count -> scan -> write).
 #define FVM_BLK 1024
-__global__ __launch_bounds__(FVM_BLK) void k_fvm_count(const int64_t *__restrict__ fi, int64_t N, int *__restrict__ counts)
+// the two block-level steps, shared by the compactions below: counts[block] = the block's kept items; rank of a kept item in the output
+__device__ __forceinline__ void fvm_block_count(bool v, int *__restrict__ counts)
 {
-    int64_t i = (int64_t)blockIdx.x * FVM_BLK + threadIdx.x;
-    bool v = i < N && fi[i] >= 0;
     unsigned long long m = __ballot(v);
     __shared__ int s[FVM_BLK / 64];
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = __popcll(m);
@@ -703,6 +735,23 @@ __global__ __launch_bounds__(FVM_BLK) void k_fvm_count(const int64_t *__restrict
         for (int k = 0; k < FVM_BLK / 64; ++k) t += s[k];
         counts[blockIdx.x] = t;
     }
+}
+__device__ __forceinline__ int64_t fvm_block_rank(bool v, const int64_t *__restrict__ base)
+{
+    unsigned long long m = __ballot(v);
+    __shared__ int s[FVM_BLK / 64];
+    int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) s[w] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    for (int k = 0; k < w; ++k) off += s[k];
+    return base[blockIdx.x] + off + __popcll(m & ((1ull << lane) - 1));
+}
+
+__global__ __launch_bounds__(FVM_BLK) void k_fvm_count(const int64_t *__restrict__ fi, int64_t N, int *__restrict__ counts)
+{
+    int64_t i = (int64_t)blockIdx.x * FVM_BLK + threadIdx.x;
+    fvm_block_count(i < N && fi[i] >= 0, counts);
 }
 
 __global__ __launch_bounds__(1024) void k_fvm_scan(int *__restrict__ counts, int64_t nblk, int64_t *__restrict__ base,
@@ -734,15 +783,8 @@ __global__ __launch_bounds__(FVM_BLK) void k_fvm_write(const int64_t *__restrict
     int64_t i = (int64_t)blockIdx.x * FVM_BLK + threadIdx.x;
     int64_t f = i < N ? fi[i] : -1;
     bool v = f >= 0;
-    unsigned long long m = __ballot(v);
-    __shared__ int s[FVM_BLK / 64];
-    int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) s[w] = __popcll(m);
-    __syncthreads();
-    int off = 0;
-    for (int k = 0; k < w; ++k) off += s[k];
+    int64_t r = fvm_block_rank(v, base);
     if (v) {
-        int64_t r = base[blockIdx.x] + off + __popcll(m & ((1ull << lane) - 1));
         int64_t view = i / HW, pix = i % HW;
         int64_t *o = rows + r * 4;
         o[0] = f; o[1] = view; o[2] = pix / W; o[3] = pix % W;
@@ -767,6 +809,44 @@ extern "C" int32_t ctx_face_view_map(const int64_t *face_idx, int32_t B, int32_t
     hipLaunchKernelGGL(k_fvm_scan, dim3(1), dim3(1024), 0, s, counts, nblk, base, n_rows);
     hipLaunchKernelGGL(k_fvm_write, dim3((unsigned)nblk), dim3(FVM_BLK), 0, s, face_idx, N, (int64_t)H * W, W, base, rows);
     CTX_CHECK_LAUNCH("face_view_map");
+    return CTX_OK;
+}
+
+// The same compaction of a byte mask (ctx_texel_active_mark's): idx_out[0:count] = the flat indices of its non-zero bytes, ascending.
+__global__ __launch_bounds__(FVM_BLK) void k_texel_count(const uint8_t *__restrict__ mask, int64_t n, int *__restrict__ counts)
+{
+    int64_t i = (int64_t)blockIdx.x * FVM_BLK + threadIdx.x;
+    fvm_block_count(i < n && mask[i] != 0, counts);
+}
+
+__global__ __launch_bounds__(FVM_BLK) void k_texel_write(const uint8_t *__restrict__ mask, int64_t n, const int64_t *__restrict__ base,
+                                                         int32_t *__restrict__ idx_out)
+{
+    int64_t i = (int64_t)blockIdx.x * FVM_BLK + threadIdx.x;
+    bool v = i < n && mask[i] != 0;
+    int64_t r = fvm_block_rank(v, base);
+    if (v) idx_out[r] = (int32_t)i;
+}
+
+extern "C" int64_t ctx_texel_compact_ws_bytes(int64_t n)
+{
+    if (n < 1 || n > INT32_MAX) return -1;       // the indices are int32; one block per FVM_BLK bytes stays far inside one grid
+    int64_t nblk = cdiv64(n, FVM_BLK);
+    return nblk * 4 + nblk * 8 + 64;
+}
+
+extern "C" int32_t ctx_texel_compact(const uint8_t *mask, int64_t n, int32_t *idx_out, int64_t *count_out, void *ws, ctx_stream_t stream)
+{
+    CTX_REQUIRE(mask && idx_out && count_out && ws, "texel_compact: null pointer");
+    CTX_REQUIRE(n >= 1 && n <= INT32_MAX, "texel_compact: n=%lld outside [1, 2^31)", (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    int64_t nblk = cdiv64(n, FVM_BLK);
+    int64_t *base = (int64_t *)ws;
+    int *counts = (int *)(base + nblk);
+    hipLaunchKernelGGL(k_texel_count, dim3((unsigned)nblk), dim3(FVM_BLK), 0, s, mask, n, counts);
+    hipLaunchKernelGGL(k_fvm_scan, dim3(1), dim3(1024), 0, s, counts, nblk, base, count_out);
+    hipLaunchKernelGGL(k_texel_write, dim3((unsigned)nblk), dim3(FVM_BLK), 0, s, mask, n, base, idx_out);
+    CTX_CHECK_LAUNCH("texel_compact");
     return CTX_OK;
 }
 

@@ -21,6 +21,7 @@
 //   uvm_kloop_f32                 f32-pipe K-loop             fwd (all three uses), dgrad
 //   uvm_kloop_split               split-fp16 K-loop           fwd16, dgrad16
 //   uvm_point / uvm_embed_col     Fourier embedding           fwd, fwd16
+//   UvmList / uvm_node            texel list: compact row -> atlas node   uvm_point, uvm_store_out, uvm_draw_tile, k_uvm_absmax
 //   uvm_store_out                 raw / tex store             fwd, fwd16
 //   UvmOutGrad + uvm_draw_tile / uvm_bwd_out_layer / uvm_fold_out_grad   draw tile, backward output layer, gwo / gbo fold   dgrad, dgrad16
 //   uvm_frag / uvm_src_k          fragment decode of the packed weights   the four pack kernels
@@ -390,14 +391,27 @@ extern "C" int32_t ctx_uvmlp_pack(const float *const *ws, const float *const *bs
 
 // ---- Fourier embedding: uvm_point yields a texel's coordinates, uvm_embed_col column e of its embedding ----
 struct UvmPoint { float x0, x1, x2; };
-// row n of uv (d = 2) / xyz (d = 3), or node n of the res x res atlas grid; zero past N and on the `emb` seam
-__device__ __forceinline__ UvmPoint uvm_point(const float *__restrict__ uv, const float *__restrict__ emb, int64_t n, int64_t N, int res, int d)
+// Texel list (get_texture_map_only_valid_areas, src/models/textured_mesh.py:303-347): row n of the launch is node idx[n] of the
+// res x res grid.  raw, the saved activations and dZ stay compact ([N] rows); only the atlas planes ([out_ch][plane], plane = res^2)
+// are addressed through the list.  idx == nullptr: row n is its own node and plane == N (every other point source).
+struct UvmList { const int *idx; int64_t plane; };
+// the atlas node of row n < N, or -1 for a list entry outside the grid (never stored to, never read from)
+__device__ __forceinline__ int64_t uvm_node(const UvmList &list, int64_t n)
+{
+    if (!list.idx) return n;
+    const int64_t t = list.idx[n];
+    return (t >= 0 && t < list.plane) ? t : -1;
+}
+// row n of uv (d = 2) / xyz (d = 3), or node n (listed: node idx[n]) of the res x res atlas grid; zero past N and on the `emb` seam
+__device__ __forceinline__ UvmPoint uvm_point(const float *__restrict__ uv, const float *__restrict__ emb, const UvmList &list, int64_t n, int64_t N,
+                                              int res, int d)
 {
     UvmPoint p = {0.f, 0.f, 0.f};
     if (n < N && !emb) {
         if (uv) { p.x0 = uv[n * d + 0]; p.x1 = uv[n * d + 1]; if (d > 2) p.x2 = uv[n * d + 2]; }
         else {
             // torch.linspace(0,1,res): start + i*step for the first half, end - (res-1-i)*step after
+            if (list.idx) { n = uvm_node(list, n); if (n < 0) return p; }
             int i = (int)(n / res), j = (int)(n % res);
             float step = 1.0f / (float)(res - 1);
             p.x0 = (j < res / 2) ? (float)j * step : 1.0f - (float)(res - 1 - j) * step;
@@ -421,19 +435,21 @@ __device__ __forceinline__ float uvm_embed_col(const UvmPoint &p, const float *_
     return val;
 }
 
-// the forward output layer's result s[c] (before the bias) of texel n < N: raw [N][out_ch] and, for the atlas, (tanh + 1) / 2 as [out_ch][N]
+// the forward output layer's result s[c] (before the bias) of texel n < N: raw [N][out_ch] and, for the atlas, (tanh + 1) / 2 at the
+// row's node of [out_ch][plane]
 __device__ __forceinline__ void uvm_store_out(const float (&s)[4], const float *__restrict__ packed, const UvmPlan &plan, float *__restrict__ raw,
-                                              float *__restrict__ tex, int64_t n, int64_t N)
+                                              float *__restrict__ tex, const UvmList &list, int64_t n)
 {
+    const int64_t node = uvm_node(list, n);
     for (int c = 0; c < plan.out_ch; ++c) {
         float v = s[c] + packed[plan.out_b_off + c];
         raw[n * plan.out_ch + c] = v;
-        if (tex) tex[(int64_t)c * N + n] = (tanhf(v) + 1.0f) / 2.0f;
+        if (tex && node >= 0) tex[(int64_t)c * list.plane + node] = (tanhf(v) + 1.0f) / 2.0f;
     }
 }
 
 template <int W, int EP>
-__global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, const float *__restrict__ emb, int64_t N, int res, int L,
+__global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, const float *__restrict__ emb, UvmList list, int64_t N, int res, int L,
                                                  const float *__restrict__ packed, UvmPlan plan,
                                                  float *__restrict__ raw, float *__restrict__ tex, float *__restrict__ saved)
 {
@@ -455,7 +471,7 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
     auto put_embedding = [&]() {
         int row = tid & 63;
         int64_t n = n0 + row;
-        const UvmPoint pt = uvm_point(uv, emb, n, N, res, plan.dims);
+        const UvmPoint pt = uvm_point(uv, emb, list, n, N, res, plan.dims);
         for (int e = wave; e < EP; e += W / 64) act[row * STRIDE + e] = uvm_embed_col(pt, emb, n, N, e, plan.dims, L, plan.in_ch);
     };
     put_embedding();
@@ -532,7 +548,7 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             for (int o = 1; o < PARTS; o <<= 1) s[c] += __shfl_xor(s[c], o, 64);
-        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, n0 + row, N);
+        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, list, n0 + row);
     }
 }
 
@@ -549,7 +565,7 @@ __global__ __launch_bounds__(W) void k_uvmlp_fwd(const float *__restrict__ uv, c
 #define UVM16_LO 312              // halves: a row's lo plane sits this far behind its hi plane (48 + 256 + 8)
 #define UVM16_STRIDE 632          // halves per row PAIR (hi | lo): 1264 bytes = 16 x odd -> conflict-free ds_read_b128 over 16 rows, and
                                   // the lo plane within the 16-bit immediate offset of every DS access to the hi plane
-__global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict__ uv, const float *__restrict__ emb, int64_t N, int res, int L,
+__global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict__ uv, const float *__restrict__ emb, UvmList list, int64_t N, int res, int L,
                                                      const float *__restrict__ packed, UvmPlan plan,
                                                      float *__restrict__ raw, float *__restrict__ tex, float *__restrict__ saved)
 {
@@ -564,7 +580,7 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
     {
         const int row = tid >> 2, quarter = tid & 3;
         const int64_t n = n0 + row;
-        const UvmPoint pt = uvm_point(uv, emb, n, N, res, plan.dims);
+        const UvmPoint pt = uvm_point(uv, emb, list, n, N, res, plan.dims);
         for (int e = quarter * (EP / 4); e < (quarter + 1) * (EP / 4); ++e)
             uvm_split(uvm_embed_col(pt, emb, n, N, e, plan.dims, L, plan.in_ch), phi[row * STRIDE + e], plo[row * STRIDE + e]);
     }
@@ -633,7 +649,7 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_fwd16(const float *__restrict_
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) { s[c] += __shfl_xor(s[c], 1, 64); s[c] += __shfl_xor(s[c], 2, 64); }
-        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, n0 + row, N);
+        if (part == 0 && n0 + row < N) uvm_store_out(s, packed, plan, raw, tex, list, n0 + row);
     }
 }
 
@@ -643,15 +659,24 @@ extern "C" int64_t ctx_uvmlp_saved_bytes(int64_t N, int32_t D, int32_t W, int32_
     return N * (int64_t)(uvm_epad(input_ch) + D * W) * 4 + (int64_t)D * cdiv64(N, UVM_TM) * W * 8;   // + ReLU bit masks
 }
 
-extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
-                                      int32_t dims, int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved_v,
-                                      ctx_stream_t stream)
+// what the list entry points (2-D field only: they take no dims) refuse; the list's values are the caller's to keep inside [0, res^2) (an entry outside is skipped)
+static int32_t uvm_check_list(const char *who, const int32_t *idx, int64_t N, int32_t res)
+{
+    CTX_REQUIRE(idx, "%s: null texel list", who);
+    CTX_REQUIRE(res >= 2 && N >= 1 && N <= (int64_t)res * res, "%s: need res >= 2 and 1 <= N <= res*res (N=%lld res=%d)", who, (long long)N, res);
+    return CTX_OK;
+}
+
+// idx == nullptr: the points are uv / emb / the whole grid and the atlas plane is N long
+static int32_t uvm_fwd(const float *uv, const float *emb, const int32_t *idx, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
+                       int32_t dims, int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved_v, ctx_stream_t stream)
 {
     float *saved = (float *)saved_v;
     UvmPlan p; int64_t total = 0;
+    const UvmList list = {idx, idx ? (int64_t)res * res : N};
     CTX_REQUIRE(packed && raw && N > 0, "uvmlp_fwd: bad args");
     CTX_REQUIRE(dims == 2 || dims == 3, "uvmlp_fwd: dims=%d (2: uv, 3: xyz)", dims);
-    CTX_REQUIRE(uv || emb || (dims == 2 && res > 1 && (int64_t)res * res == N),
+    CTX_REQUIRE(uv || emb || idx || (dims == 2 && res > 1 && (int64_t)res * res == N),
                 "uvmlp_fwd: no inputs needs dims == 2 and N == res*res (N=%lld res=%d)", (long long)N, res);
     int input_ch = dims * (1 + 2 * L);
     CTX_REQUIRE(uvm_build_plan(D, W, input_ch, output_ch, skip, p, total) == 0,
@@ -662,7 +687,7 @@ extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t
     if (uvm_use_split16(p, dims, false)) {
         const size_t lds16 = (size_t)UVM16_TM * UVM16_STRIDE * sizeof(f16);
         (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-        hipLaunchKernelGGL(k_uvmlp_fwd16, dim3((unsigned)cdiv64(N, UVM16_TM)), dim3(256), lds16, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved);
+        hipLaunchKernelGGL(k_uvmlp_fwd16, dim3((unsigned)cdiv64(N, UVM16_TM)), dim3(256), lds16, s, uv, emb, list, N, res, L, pk, p, raw, tex_chw, saved);
         CTX_CHECK_LAUNCH("uvmlp_fwd16");
         return CTX_OK;
     }
@@ -670,17 +695,31 @@ extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t
         constexpr int WW = decltype(w)::value, EE = decltype(ep)::value;
         const size_t lds = (size_t)UVM_TM * ((EE == UVM_EPAD ? UVM_EPAD : 0) + WW + 4) * 4;   // the 3-D layout overlays the embedding
         (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd<WW, EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_uvmlp_fwd<WW, EE>), dim3((unsigned)cdiv64(N, UVM_TM)), dim3(WW), lds, s, uv, emb, N, res, L, pk, p, raw, tex_chw, saved);
+        hipLaunchKernelGGL((k_uvmlp_fwd<WW, EE>), dim3((unsigned)cdiv64(N, UVM_TM)), dim3(WW), lds, s, uv, emb, list, N, res, L, pk, p, raw, tex_chw, saved);
     });
     CTX_CHECK_LAUNCH("uvmlp_fwd");
     return CTX_OK;
+}
+
+extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
+                                      int32_t dims, int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved,
+                                      ctx_stream_t stream)
+{
+    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, dims, L, output_ch, skip, raw, tex_chw, saved, stream);
+}
+
+extern "C" int32_t ctx_uvmlp_fwd_save_idx(const int32_t *idx, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W, int32_t L,
+                                          int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved, ctx_stream_t stream)
+{
+    if (int32_t rc = uvm_check_list("uvmlp_fwd_save_idx", idx, N, res)) return rc;
+    return uvm_fwd(nullptr, nullptr, idx, N, res, packed, D, W, 2, L, output_ch, skip, raw, tex_chw, saved, stream);
 }
 
 extern "C" int32_t ctx_uvmlp_fwd(const float *uv, const float *emb, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
                                  int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw,
                                  ctx_stream_t stream)
 {
-    return ctx_uvmlp_fwd_save(uv, emb, N, res, packed, D, W, 2, L, output_ch, skip, raw, tex_chw, nullptr, stream);
+    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, 2, L, output_ch, skip, raw, tex_chw, nullptr, stream);
 }
 
 // =====================================================================================================================
@@ -719,10 +758,10 @@ __device__ __forceinline__ void uvm_out_grad_init(UvmOutGrad &og, const float *_
         }
     og.gbo = 0.f;
 }
-// d loss / d raw of the tile's 64 texels -> dr[64][4]: grad_raw + grad_tex . d((tanh + 1) / 2)
+// d loss / d raw of the tile's 64 texels -> dr[64][4]: grad_raw (compact rows) + grad_tex (at the rows' nodes) . d((tanh + 1) / 2)
 template <int W>
 __device__ __forceinline__ void uvm_draw_tile(float *dr, UvmOutGrad &og, const float *__restrict__ grad_raw, const float *__restrict__ grad_tex,
-                                              const float *__restrict__ raw, int64_t N, int64_t n0, int out_ch, int tid)
+                                              const float *__restrict__ raw, const UvmList &list, int64_t N, int64_t n0, int out_ch, int tid)
 {
     for (int i = tid; i < UVM_TM * 4; i += W) {
         int t = i >> 2, c = i & 3;
@@ -730,9 +769,10 @@ __device__ __forceinline__ void uvm_draw_tile(float *dr, UvmOutGrad &og, const f
         float v = 0.f;
         if (n < N && c < out_ch) {
             if (grad_raw) v = grad_raw[n * out_ch + c];
-            if (grad_tex) {
+            const int64_t node = grad_tex ? uvm_node(list, n) : -1;
+            if (node >= 0) {
                 float y = tanhf(raw[n * out_ch + c]);
-                v += grad_tex[(int64_t)c * N + n] * 0.5f * (1.0f - y * y);
+                v += grad_tex[(int64_t)c * list.plane + node] * 0.5f * (1.0f - y * y);
             }
         }
         dr[i] = v;
@@ -797,7 +837,7 @@ __device__ __forceinline__ void uvm_fold_out_grad(const UvmOutGrad &og, float *g
 
 template <int W>
 __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ grad_raw, const float *__restrict__ grad_tex,
-                                                   const float *__restrict__ raw, int64_t N, const float *__restrict__ packed,
+                                                   const float *__restrict__ raw, UvmList list, int64_t N, const float *__restrict__ packed,
                                                    UvmPlan plan, const float *__restrict__ saved, float *__restrict__ dz,
                                                    float *__restrict__ part_w /*[grid][4][W]*/, float *__restrict__ part_b /*[grid][4]*/)
 {
@@ -818,7 +858,7 @@ __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ 
     const int64_t ntiles = (N + UVM_TM - 1) / UVM_TM;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t n0 = tile * UVM_TM;
-        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, N, n0, plan.out_ch, tid);
+        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, list, N, n0, plan.out_ch, tid);
         __syncthreads();
         uvm_bwd_out_layer<W>(og, dr, acts + (int64_t)(D - 1) * N * W, dz + (int64_t)(D - 1) * N * W, N, n0, rg, c4,
                              [&](int t, const float (&o)[4]) { *(float4 *)(g + t * STRIDE + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]); });
@@ -866,12 +906,19 @@ __global__ __launch_bounds__(W, 2) void k_uvmlp_dgrad(const float *__restrict__ 
 // draw lands near 16: room for a 4 000-fold growth through the layers before fp16 overflows, 2^-35 of the maximum still resolved), and
 // dZ goes to HBM multiplied by 2^-e (exact).
 struct UvmCtl { uint32_t absmax_raw, absmax_tex; int32_t e; int32_t pad; };
-__global__ __launch_bounds__(256) void k_uvm_absmax(const float *__restrict__ a, int64_t na, const float *__restrict__ b, int64_t nb_, UvmCtl *__restrict__ ctl)
+// a: grad_raw, na elements; b: grad_tex [out_ch][plane], nb_ = out_ch * N elements of it: all of it, or the listed nodes of every plane
+__global__ __launch_bounds__(256) void k_uvm_absmax(const float *__restrict__ a, int64_t na, const float *__restrict__ b, int64_t nb_, UvmList list, int64_t N,
+                                                    UvmCtl *__restrict__ ctl)
 {
     uint32_t ma = 0, mb = 0;
     const int64_t stride = (int64_t)gridDim.x * 256, i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (a) for (int64_t i = i0; i < na; i += stride) ma = max(ma, __float_as_uint(a[i]) & 0x7fffffffu);
-    if (b) for (int64_t i = i0; i < nb_; i += stride) mb = max(mb, __float_as_uint(b[i]) & 0x7fffffffu);
+    if (b && !list.idx) for (int64_t i = i0; i < nb_; i += stride) mb = max(mb, __float_as_uint(b[i]) & 0x7fffffffu);
+    if (b && list.idx)
+        for (int64_t i = i0; i < nb_; i += stride) {
+            const int64_t node = uvm_node(list, i % N);
+            if (node >= 0) mb = max(mb, __float_as_uint(b[(i / N) * list.plane + node]) & 0x7fffffffu);
+        }
     for (int o = 32; o; o >>= 1) { ma = max(ma, (uint32_t)__shfl_xor((int)ma, o)); mb = max(mb, (uint32_t)__shfl_xor((int)mb, o)); }
     __shared__ uint32_t s_m[2][4];                 // one atomic pair per workgroup (atomics on one address serialise)
     if ((threadIdx.x & 63) == 0) { s_m[0][threadIdx.x >> 6] = ma; s_m[1][threadIdx.x >> 6] = mb; }
@@ -895,7 +942,7 @@ __global__ void k_uvm_scale(UvmCtl *ctl)
 #define UVM16B_LO 264             // halves: dZ's lo plane behind its hi plane (256 + 8)
 #define UVM16B_STRIDE 536         // halves per row pair: 1072 bytes = 16 x odd
 __global__ __launch_bounds__(256, 2) void k_uvmlp_dgrad16(const float *__restrict__ grad_raw, const float *__restrict__ grad_tex,
-                                                          const float *__restrict__ raw, int64_t N, const float *__restrict__ packed,
+                                                          const float *__restrict__ raw, UvmList list, int64_t N, const float *__restrict__ packed,
                                                           UvmPlan plan, const float *__restrict__ saved, float *__restrict__ dz,
                                                           float *__restrict__ part_w, float *__restrict__ part_b, const UvmCtl *__restrict__ ctl)
 {
@@ -916,7 +963,7 @@ __global__ __launch_bounds__(256, 2) void k_uvmlp_dgrad16(const float *__restric
     const int64_t ntiles = (N + UVM_TM - 1) / UVM_TM;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t n0 = tile * UVM_TM;
-        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, N, n0, plan.out_ch, tid);
+        uvm_draw_tile<W>(dr, og, grad_raw, grad_tex, raw, list, N, n0, plan.out_ch, tid);
         __syncthreads();
         // dZ of the output layer goes to HBM as it is, to LDS scaled and split
         uvm_bwd_out_layer<W>(og, dr, acts + (int64_t)(D - 1) * N * W, dz + (int64_t)(D - 1) * N * W, N, n0, rg, c4,
@@ -1179,11 +1226,13 @@ static void uvm_launch_wgrad(int G, const float *dz, const float *in, int64_t N,
                        bslab);
 }
 
-extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, const float *raw, int64_t N, const void *packed,
-                                 int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip, const void *saved_v, void *ws,
-                                 float *const *gws, float *const *gbs, ctx_stream_t stream)
+// idx == nullptr: grad_tex is [output_ch][N]; else [output_ch][res^2], read at the listed nodes
+static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32_t *idx, int32_t res, const float *raw, int64_t N, const void *packed,
+                       int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip, const void *saved_v, void *ws,
+                       float *const *gws, float *const *gbs, ctx_stream_t stream)
 {
     UvmPlan p; int64_t total = 0;
+    const UvmList list = {idx, idx ? (int64_t)res * res : N};
     CTX_REQUIRE(packed && saved_v && ws && gws && gbs && N > 0, "uvmlp_bwd: bad args");
     CTX_REQUIRE(grad_raw || grad_tex, "uvmlp_bwd: need grad_raw and / or grad_tex");
     CTX_REQUIRE(!grad_tex || raw, "uvmlp_bwd: grad_tex needs raw (the tanh argument)");
@@ -1209,17 +1258,17 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
     if (uvm_use_split16(p, dims, true)) {
         // split-fp16 chain: scale from max|grad| on the device, then the same phases as the f32 kernel
         (void)hipMemsetAsync(ctl, 0, sizeof(UvmCtl), s);
-        hipLaunchKernelGGL(k_uvm_absmax, dim3(512), dim3(256), 0, s, grad_raw, grad_raw ? N * output_ch : 0, grad_tex, grad_tex ? N * output_ch : 0, ctl);
+        hipLaunchKernelGGL(k_uvm_absmax, dim3(512), dim3(256), 0, s, grad_raw, grad_raw ? N * output_ch : 0, grad_tex, grad_tex ? N * output_ch : 0, list, N, ctl);
         hipLaunchKernelGGL(k_uvm_scale, dim3(1), dim3(1), 0, s, ctl);
         const size_t lds16 = (size_t)UVM_TM * UVM16B_STRIDE * sizeof(f16) + UVM_TM * 4 * 4;
         (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-        hipLaunchKernelGGL(k_uvmlp_dgrad16, dim3(dg), dim3(256), lds16, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b, ctl);
+        hipLaunchKernelGGL(k_uvmlp_dgrad16, dim3(dg), dim3(256), lds16, s, grad_raw, grad_tex, raw, list, N, pk, p, saved, dz, part_w, part_b, ctl);
     } else {
         uvm_dispatch(W, p.epad, [&](auto w, auto) {
             constexpr int WW = decltype(w)::value;
             const size_t lds = (size_t)(UVM_TM * (WW + 4) + UVM_TM * 4) * 4;
             (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad<WW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(k_uvmlp_dgrad<WW>, dim3(dg), dim3(WW), lds, s, grad_raw, grad_tex, raw, N, pk, p, saved, dz, part_w, part_b);
+            hipLaunchKernelGGL(k_uvmlp_dgrad<WW>, dim3(dg), dim3(WW), lds, s, grad_raw, grad_tex, raw, list, N, pk, p, saved, dz, part_w, part_b);
         });
     }
     CTX_CHECK_LAUNCH("uvmlp_dgrad");
@@ -1269,4 +1318,19 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
         CTX_CHECK_LAUNCH("uvmlp_wgrad_reduce");
     }
     return CTX_OK;
+}
+
+extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, const float *raw, int64_t N, const void *packed,
+                                 int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip, const void *saved, void *ws,
+                                 float *const *gws, float *const *gbs, ctx_stream_t stream)
+{
+    return uvm_bwd(grad_raw, grad_tex, nullptr, 0, raw, N, packed, D, W, dims, L, output_ch, skip, saved, ws, gws, gbs, stream);
+}
+
+extern "C" int32_t ctx_uvmlp_bwd_idx(const float *grad_raw, const float *grad_tex, const int32_t *idx, int32_t res, const float *raw, int64_t N,
+                                     const void *packed, int32_t D, int32_t W, int32_t L, int32_t output_ch, int32_t skip, const void *saved,
+                                     void *ws, float *const *gws, float *const *gbs, ctx_stream_t stream)
+{
+    if (int32_t rc = uvm_check_list("uvmlp_bwd_idx", idx, N, res)) return rc;
+    return uvm_bwd(grad_raw, grad_tex, idx, res, raw, N, packed, D, W, 2, L, output_ch, skip, saved, ws, gws, gbs, stream);
 }

@@ -414,6 +414,33 @@ def texture_mapping(texture_coordinates, texture_maps, mode='bilinear', mask_idx
     return _TextureMapping.apply(texture_coordinates, texture_maps, mode, mask_idx)
 
 
+def active_texels(uv, face_idx, T, mask=None):
+    """The texels of a T x T atlas that texture_mapping can read for this raster: the four bilinear taps of every pixel of
+    uv [B,H,W,2] f32 with face_idx [B,H,W] i64 >= 0, whatever their weights (the rule is written out at ctx_texel_active_mark).
+    -> (idx int32 [n]: their flat indices y*T + x, ascending; mask uint8 [T,T]: 1 where active).  mask: a mask an earlier call
+    returned, to add this raster to (the union); it is updated in place.  A set-up call: it reads n back, which SYNCS the host."""
+    lib = L.load()
+    p_uv, p_idx = L.ptr(uv, torch.float32, "uv"), L.ptr(face_idx, torch.int64, "face_idx")
+    T = int(T)
+    if uv.dim() != 4 or uv.shape[-1] != 2 or tuple(face_idx.shape) != tuple(uv.shape[:3]):
+        raise L.CtxError(f"active_texels: want uv [B,H,W,2] and face_idx [B,H,W]; got {tuple(uv.shape)}, {tuple(face_idx.shape)}")
+    if mask is None:
+        mask = torch.zeros(T, T, dtype=torch.uint8, device=uv.device)
+    elif tuple(mask.shape) != (T, T):
+        raise L.CtxError(f"active_texels: mask is {tuple(mask.shape)}, expected {(T, T)}")
+    p_mask = L.ptr(mask, torch.uint8, "mask")
+    B, H, W, _ = uv.shape
+    L.check(lib.ctx_texel_active_mark(p_uv, p_idx, B, H, W, T, p_mask, L.stream()))
+    n_ws = lib.ctx_texel_compact_ws_bytes(T * T)
+    if n_ws < 0:
+        raise L.CtxError(f"active_texels: T={T} gives more texels than an int32 index holds")
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=uv.device)
+    idx = torch.empty(T * T, dtype=torch.int32, device=uv.device)
+    count = torch.empty(1, dtype=torch.int64, device=uv.device)
+    L.check(lib.ctx_texel_compact(p_mask, T * T, L.ptr(idx), L.ptr(count), L.ptr(ws), L.stream()))
+    return idx[:int(count.item())].clone(), mask
+
+
 # ---- OBJ import (host, Python like kaolin's) ------------------------------------------------------
 def import_mesh(path, with_normals=False, with_materials=False, heterogeneous_mesh_handler=None):
     vs, vts, fs, fts = [], [], [], []

@@ -42,10 +42,11 @@ def get_embedder(multires, i=0):
 
 
 class _UvMlpFn(torch.autograd.Function):
-    """(raw [N,C], tex [C,N] or None) = field(uv | emb | grid(res)); gradients flow to the nn.Linear parameters."""
+    """(raw [N,C], tex [C,N] or None) = field(uv | emb | grid(res)); gradients flow to the nn.Linear parameters.
+    texels (int32 [N], nodes of the res x res grid): the field on those nodes only; tex is then [C,res*res], zero off the list."""
 
     @staticmethod
-    def forward(ctx, net, uv, emb, N, res, want_tex, *params):
+    def forward(ctx, net, uv, emb, N, res, want_tex, texels, *params):
         lib = L.load()
         blob = net.packed()
         dev = blob.device
@@ -58,11 +59,8 @@ class _UvMlpFn(torch.autograd.Function):
         net._saved_pool = None
         if saved is None:
             saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        raw = torch.empty(N, net.output_ch, device=dev)
-        tex = torch.empty(net.output_ch, N, device=dev) if want_tex else None
-        L.check(lib.ctx_uvmlp_fwd_save(L.ptr(uv), L.ptr(emb), N, res, L.ptr(blob), net.D, net.W, net.dims, net.multires,
-                                       net.output_ch, net.skips[0], L.ptr(raw), L.ptr(tex), L.ptr(saved), L.stream()))
-        ctx.net, ctx.N, ctx.saved_acts, ctx.blob = net, N, saved, blob
+        raw, tex = net._launch_fwd(uv, emb, N, res, want_tex, texels, blob, saved)
+        ctx.net, ctx.N, ctx.saved_acts, ctx.blob, ctx.texels, ctx.res = net, N, saved, blob, texels, res
         ctx.save_for_backward(raw)          # an output: kept through save_for_backward so the graph holds no reference cycle
         ctx.set_materialize_grads(False)
         return (raw, tex) if want_tex else raw
@@ -85,13 +83,17 @@ class _UvMlpFn(torch.autograd.Function):
         gbp = (C.c_void_p * len(gbs))(*[L.ptr(g).value for g in gbs])
         g_raw = None if g_raw is None else L.f32c(g_raw)
         g_tex = None if g_tex is None else L.f32c(g_tex)
-        L.check(lib.ctx_uvmlp_bwd(L.ptr(g_raw), L.ptr(g_tex), L.ptr(raw), N, L.ptr(ctx.blob), net.D, net.W, net.dims,
-                                  net.multires, net.output_ch, net.skips[0], L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.stream()))
+        if ctx.texels is None:
+            L.check(lib.ctx_uvmlp_bwd(L.ptr(g_raw), L.ptr(g_tex), L.ptr(raw), N, L.ptr(ctx.blob), net.D, net.W, net.dims,
+                                      net.multires, net.output_ch, net.skips[0], L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.stream()))
+        else:
+            L.check(lib.ctx_uvmlp_bwd_idx(L.ptr(g_raw), L.ptr(g_tex), L.ptr(ctx.texels), ctx.res, L.ptr(raw), N, L.ptr(ctx.blob), net.D, net.W,
+                                          net.multires, net.output_ch, net.skips[0], L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.stream()))
         net._saved_pool, ctx.saved_acts = ctx.saved_acts, None          # back to the module for the next forward
         grads = []
         for w, b in zip(gws, gbs):
             grads += [w, b]
-        return (None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, *grads)
 
 
 class NeRF2D(nn.Module):
@@ -151,18 +153,47 @@ class NeRF2D(nn.Module):
             out += [l.weight, l.bias]
         return out
 
-    def _run(self, uv, emb, N, res, want_tex):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            r = _UvMlpFn.apply(self, uv, emb, N, res, want_tex, *self._params())
-            return r if want_tex else (r, None)
+    def _launch_fwd(self, uv, emb, N, res, want_tex, texels, blob, saved):
+        """One forward launch -> (raw [N,C], tex or None).  texels given: the list entry point, tex [C,res*res] zero off the list."""
         lib = L.load()
-        blob = self.packed()
         dev = blob.device
         raw = torch.empty(N, self.output_ch, device=dev)
-        tex = torch.empty(self.output_ch, N, device=dev) if want_tex else None
-        L.check(lib.ctx_uvmlp_fwd_save(L.ptr(uv), L.ptr(emb), N, res, L.ptr(blob), self.D, self.W, self.dims, self.multires,
-                                       self.output_ch, self.skips[0], L.ptr(raw), L.ptr(tex), None, L.stream()))
+        if texels is None:
+            tex = torch.empty(self.output_ch, N, device=dev) if want_tex else None
+            L.check(lib.ctx_uvmlp_fwd_save(L.ptr(uv), L.ptr(emb), N, res, L.ptr(blob), self.D, self.W, self.dims, self.multires,
+                                           self.output_ch, self.skips[0], L.ptr(raw), L.ptr(tex), L.ptr(saved), L.stream()))
+        else:
+            if self.dims != 2:
+                raise L.CtxError(f"a texel list addresses the 2-D atlas grid; this field has dims={self.dims}")
+            tex = torch.zeros(self.output_ch, res * res, device=dev) if want_tex else None
+            L.check(lib.ctx_uvmlp_fwd_save_idx(L.ptr(texels), N, res, L.ptr(blob), self.D, self.W, self.multires, self.output_ch,
+                                               self.skips[0], L.ptr(raw), L.ptr(tex), L.ptr(saved), L.stream()))
         return raw, tex
+
+    def _run(self, uv, emb, N, res, want_tex, texels=None):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            r = _UvMlpFn.apply(self, uv, emb, N, res, want_tex, texels, *self._params())
+            return r if want_tex else (r, None)
+        return self._launch_fwd(uv, emb, N, res, want_tex, texels, self.packed(), None)
+
+    def _checked_texels(self, texels, res):
+        """A texel list is looked at once per tensor (dtype, device, range: the range costs a host sync), not per call."""
+        seen = getattr(self, '_texels_ok', None)
+        if seen is not None and seen[0] is texels and seen[1:] == (texels._version, res):
+            return texels
+        L.ptr(texels, torch.int32, "texels")
+        if texels.dim() != 1:
+            raise L.CtxError(f"texels: expected a 1-D int32 list of grid nodes, got shape {tuple(texels.shape)}")
+        n = texels.numel()
+        if n == 0:
+            raise L.CtxError("texels: the list is empty (no texel is sampled); evaluate the whole atlas with texels=None instead")
+        if n > res * res:
+            raise L.CtxError(f"texels: {n} entries for a {res} x {res} atlas")
+        lo, hi = int(texels.min()), int(texels.max())
+        if lo < 0 or hi >= res * res:
+            raise L.CtxError(f"texels: entries span [{lo}, {hi}], outside the {res} x {res} atlas [0, {res * res})")
+        self._texels_ok = (texels, texels._version, res)
+        return texels
 
     def forward(self, x):
         """x: embedded inputs [N, input_ch] (reference seam) -> raw outputs [N, output_ch]."""
@@ -182,10 +213,17 @@ class NeRF2D(nn.Module):
         raw, _ = self._run(u, None, u.shape[0], 0, False)
         return raw
 
-    def texture_map(self, res):
+    def texture_map(self, res, texels=None):
         """textured_mesh.py:266-301 fused: -> (texture [1,C,res,res] in [0,1], mlp_output [res*res, C]).
         The reference re-evaluates the field on every render() (2x per painted view, 3x per eval view); without gradients the
-        atlas only changes when a parameter does, so the no-grad result is kept until the parameters' version moves."""
+        atlas only changes when a parameter does, so the no-grad result is kept until the parameters' version moves.
+        texels (int32 [n] device list of distinct nodes y*res + x, e.g. kal.active_texels): the field is evaluated, and trained, on
+        those texels only (textured_mesh.py:303-347) -> (texture [1,C,res,res], zero off the list; mlp_output [n, C] in list
+        order).  Listed texels carry the bits of the whole-atlas call.  Never cached."""
+        if texels is not None:
+            texels = self._checked_texels(texels, res)
+            raw, tex = self._run(None, None, texels.numel(), res, True, texels)
+            return tex.reshape(1, self.output_ch, res, res), raw
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             key = (self._version(), res)
             hit = getattr(self, '_tex_cache', None)

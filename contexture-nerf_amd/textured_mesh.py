@@ -147,9 +147,13 @@ class TexturedMeshModel(torch.nn.Module):
         except Exception:
             return False
 
-    def get_texture_map(self):
-        """-> (texture [1,3,res,res] in [0,1], mlp_output [res*res,3]); uv grid, embedding, MLP and (tanh+1)/2 fused."""
-        return self.texture_mlp.texture_map(self.texture_resolution)
+    def get_texture_map(self, texels=None):
+        """-> (texture [1,3,res,res] in [0,1], mlp_output [res*res,3]); uv grid, embedding, MLP and (tanh+1)/2 fused.
+        texels (kal.active_texels of a raster): only those texels, as get_texture_map_only_valid_areas (textured_mesh.py:303-347)
+        -> (texture, zero elsewhere; mlp_output [n,3])."""
+        if texels is None:
+            return self.texture_mlp.texture_map(self.texture_resolution)
+        return self.texture_mlp.texture_map(self.texture_resolution, texels=texels)
 
     def chart_mask(self):
         """uv_chart_mask of this mesh's UV triangles at the texture resolution.  Depends on vt, ft and T only, so it is built once."""
@@ -206,7 +210,9 @@ class TexturedMeshModel(torch.nn.Module):
             batch_size = theta.shape[0]
         else:
             batch_size = render_cache["uv_features"].shape[0]
-        texture_img, mlp_output = self.get_texture_map()
+        # a cached raster may carry the list of texels it can read (render_cache['active_texels']); a fresh render never has one
+        texels = None if render_cache is None else render_cache.get('active_texels')
+        texture_img, mlp_output = self.get_texture_map() if texels is None else self.get_texture_map(texels=texels)
         background_type, use_render_back = 'none', False
         if background is not None and type(background) == str:
             background_type, use_render_back = background, True
@@ -214,6 +220,8 @@ class TexturedMeshModel(torch.nn.Module):
             self.mesh.vertices[None].repeat(batch_size, 1, 1), self.mesh.faces, self.face_attributes,
             texture_img.expand(batch_size, -1, -1, -1), elev=theta, azim=phi, radius=radius, look_at_height=self.dy,
             render_cache=render_cache, dims=dims, background_type=background_type)
+        if texels is not None:
+            render_cache['active_texels'] = texels          # the list stays with the raster it was built from
         mask = mask.detach()
         if use_render_back:
             pred_map, pred_back = pred_features, pred_features

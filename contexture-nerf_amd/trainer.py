@@ -430,7 +430,18 @@ class ConTEXTure:
                 # encode_prompt("") + vision_encoder(feature_extractor_clip(cond)).image_embeds * ramping_coefficients
                 pe, neg = pipe.condition_encoder.prompt_embeds(cond)
                 self.zero123plus_prompt_embeds, pipe.negative_prompt_embeds = pe.to(self.device), neg.to(self.device)
-        self._sds_setup = dict(cond_image=cond_image, depth_grid=depth_grid, boxes=boxes, render_cache=render_cache)
+        self._sds_setup = dict(cond_image=cond_image, depth_grid=depth_grid, boxes=boxes, render_cache=render_cache, field_texels='all')
+        if self.cfg.optim.field_texels == 'active':
+            # the loop renders from this one raster, so the field is evaluated and trained on the texels it can read; the list rides
+            # in the cache (valid for this raster only).  Nothing foreground: nothing to restrict, the loop stays on the whole atlas
+            from . import kal
+            T = int(self.mesh_model.texture_resolution)
+            texels, _ = kal.active_texels(render_cache['uv_features'].contiguous(), render_cache['face_idx'].contiguous(), T)
+            n_active = int(texels.numel())
+            self._sds_setup.update(n_active=n_active, active_fraction=n_active / float(T * T))
+            if n_active > 0:
+                render_cache['active_texels'] = texels
+                self._sds_setup['field_texels'] = 'active'
         params = [p for p in self.texture_mlp.parameters()]
         optimizer = torch.optim.Adam(params, lr=1e-5, betas=(0.9, 0.99), eps=1e-15)
         train_sched = DDPMScheduler(prediction_type="v_prediction")

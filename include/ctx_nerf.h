@@ -226,6 +226,34 @@ int32_t ctx_uvmlp_bwd(const float *grad_raw /*nullable*/, const float *grad_tex 
                       int64_t N, const void *packed, int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip,
                       const void *saved, void *ws, float *const *gws, float *const *gbs, ctx_stream_t stream);
 
+/* ---- texture field on the texels the views sample (TexturedMeshModel.get_texture_map_only_valid_areas,
+   src/models/textured_mesh.py:303-347, queries the MLP on chosen texels only; here the choice is what a cached raster can read) ---- */
+/* The active set of a raster, in binary32 in the order ctx_texture_mapping_fwd / _bwd use: for every pixel of uv [B,H,W,2] with
+   face_idx[b,y,x] >= 0:  ix = src_index(u*2 - 1, T), iy = src_index((1 - v)*2 - 1, T) with src_index(g, T) =
+   min(T - 1, max(((g + 1)*T - 1)/2, 0));  x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;  each of the four
+   (y, x) with 0 <= x < T and 0 <= y < T is active, whatever its bilinear weight.  Background pixels mark nothing and their uv is
+   not read.  mask_u8 [T,T]: plain byte stores of 1, never cleared — the caller zeroes it, several calls accumulate a union.  T >= 2. */
+int32_t ctx_texel_active_mark(const float *uv, const int64_t *face_idx, int32_t B, int32_t H, int32_t W, int32_t T, uint8_t *mask_u8,
+                              ctx_stream_t stream);
+/* Ordered compaction of such a mask (count, scan, write, as ctx_face_view_map): idx_out[0:count_out[0]] = the flat indices y*T + x
+   of the n bytes that are non-zero, ascending; the rest of idx_out [n] is not written.  count_out: device int64[1].
+   1 <= n < 2^31.  ws: ctx_texel_compact_ws_bytes(n) bytes (-1: n refused). */
+int64_t ctx_texel_compact_ws_bytes(int64_t n);
+int32_t ctx_texel_compact(const uint8_t *mask, int64_t n, int32_t *idx_out, int64_t *count_out, void *ws, ctx_stream_t stream);
+/* ctx_uvmlp_fwd_save / ctx_uvmlp_bwd of the 2-D field on a list idx int32 [N] of nodes of the res x res grid (distinct, each in
+   [0, res^2); 1 <= N <= res^2, res >= 2).  Row n of the launch is node idx[n]: its coordinates come from the grid mode's linspace
+   expression, so they carry that mode's bits, and so do raw and the atlas value of a listed texel.  raw [N,output_ch], saved
+   (ctx_uvmlp_saved_bytes(N, ...)) and the backward's scratch (ctx_uvmlp_bwd_ws_bytes(N, ...)) are compact; tex_chw and grad_tex
+   are whole atlases [output_ch, res^2]: tex_chw is written at the listed texels only (the caller fills the rest), grad_tex is
+   read at the listed texels only.  A list entry outside the grid is skipped (nothing stored, nothing read). */
+int32_t ctx_uvmlp_fwd_save_idx(const int32_t *idx, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W, int32_t L,
+                               int32_t output_ch, int32_t skip, float *raw, float *tex_chw /*nullable*/, void *saved /*nullable*/,
+                               ctx_stream_t stream);
+int32_t ctx_uvmlp_bwd_idx(const float *grad_raw /*nullable*/, const float *grad_tex /*nullable*/, const int32_t *idx, int32_t res,
+                          const float *raw /*nullable w/o grad_tex*/, int64_t N, const void *packed, int32_t D, int32_t W, int32_t L,
+                          int32_t output_ch, int32_t skip, const void *saved, void *ws, float *const *gws, float *const *gbs,
+                          ctx_stream_t stream);
+
 /* ---- ray path (north_star; dead/absent in the reference) ------------------------ */
 /* get_rays (run_nerf_helpers.py:139-148): K row-major [3,3] host floats passed by value fields. */
 int32_t ctx_get_rays(int32_t H, int32_t W, float fx, float fy, float cx, float cy,
