@@ -107,7 +107,11 @@ SIGNATURES = {
     "ctx_vae_encode_bwd": (_i32, [_vp, _vp, _f32, _vp, _vp]),
     "ctx_gemm_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ctx_conv3x3_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_conv3x3_seg_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32,
+                                   _vp, _i32, _vp, _vp]),
+    "ctx_gemm_last_kernel": (None, [_vp, _vp]),
     "ctx_groupnorm_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "ctx_groupnorm2_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_layernorm_f16": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
     "ctx_attention_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "ctx_attention_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp]),

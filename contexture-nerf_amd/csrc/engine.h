@@ -83,9 +83,14 @@ void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, cons
                    int epi = 0, bool res32 = false, bool out32 = false);
 // a 3x3 convolution's geometry beyond "stride 1, padding 1" (GemmArgs has each meaning); Ho = ((H << ups) - 1) / stride + 1, Wo alike
 struct ConvGeom { int stride = 1, ups = 0, poff = 0, zins = 0; };
-// out[B,Ho,Wo,Cout] = conv3x3(x[B,H,W,Cin]; Wt[Cout][3][3][Cin]) (+ bias[Cout]) (+ rowbias[b * ldrb ..]) (+ res); NHWC
+// K segments of a convolution (GemmArgs::nseg): n 1x1 products over tensors x[s] [B,H,W,C[s]] of the output's pixel grid, weights
+// w[s] [Cout] rows of C[s] at row stride ldw[s], and their bias; folded into the convolution's K loop (default geometry only)
+struct ConvSegs { int n = 0; const f16 *x[2] = {nullptr, nullptr}; const f16 *w[2] = {nullptr, nullptr}; int C[2] = {0, 0}, ldw[2] = {0, 0}; const f16 *bias2 = nullptr; };
+// out[B,Ho,Wo,Cout] = conv3x3(x[B,H,W,Cin]; Wt[Cout][3][3][Cin]) (+ bias[Cout]) (+ rowbias[b * ldrb ..]) (+ res) (+ segments); NHWC.
+// The segments' product is counted as a class-0 op of its own (the 1x1 convolution it stands for).
 void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
-                  ConvGeom g = ConvGeom(), const f16 *rowbias = nullptr, int ldrb = 0, bool res32 = false, bool out32 = false);
+                  ConvGeom g = ConvGeom(), const f16 *rowbias = nullptr, int ldrb = 0, bool res32 = false, bool out32 = false,
+                  const ConvSegs *segs = nullptr);
 
 // `run` as a dry run: nothing is launched, the arena only measures (e.peak), the counters count; -> the run's return code
 template <class F> int engine_dry_run(Engine *e, F run)

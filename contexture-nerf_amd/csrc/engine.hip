@@ -24,11 +24,21 @@ int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace
 }
 
 // one GEMM / implicit-GEMM conv of a fully described problem: plan, split-K scratch above the arena mark, dispatch, release
-static void engine_gemm(Engine &e, GemmArgs &a, bool conv)
+static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs = nullptr)
 {
     e.note(0, 2.0 * a.M * a.N * a.K);
     size_t mark = e.top;
-    ctx_gemm_plan(a, conv);
+    ctx_gemm_plan(a, conv);                               // a segmented convolution runs the plan of its 3x3 part's shape
+    if (segs && segs->n) {
+        int kseg = 0;
+        a.nseg = segs->n; a.bias2 = segs->bias2;
+        for (int i = 0; i < segs->n; ++i) {
+            a.segX[i] = segs->x[i]; a.segW[i] = segs->w[i]; a.segC[i] = segs->C[i]; a.segLdw[i] = segs->ldw[i];
+            kseg += segs->C[i];
+        }
+        a.K += kseg;
+        e.note(0, 2.0 * a.M * a.N * kseg);
+    }
     if (a.zins) a.use8 = 0;        // the zero-inserted grid is an addressing mode of gemm.hip only
     if (a.splitk > 1) a.part = (float *)e.alloc((size_t)a.splitk * a.M * a.N * 4);
     ENGINE_RUN(&e, ctx_gemm_dispatch(a, conv, e.s));
@@ -46,7 +56,7 @@ void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, cons
 }
 
 void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
-                  ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32)
+                  ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32, const ConvSegs *segs)
 {
     GemmArgs a = {};
     a.Ho = ((H << g.ups) - 1) / g.stride + 1; a.Wo = ((W << g.ups) - 1) / g.stride + 1;
@@ -54,7 +64,7 @@ void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = ldrb;
     a.H = H; a.W = W; a.Cin = Cin; a.stride = g.stride; a.ups = g.ups; a.poff = g.poff; a.zins = g.zins;
     a.res32 = res32; a.out32 = out32;
-    engine_gemm(e, a, true);
+    engine_gemm(e, a, true, segs);
 }
 
 int engine_finish(Engine *e, const char *who)

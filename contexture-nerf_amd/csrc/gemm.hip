@@ -51,8 +51,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[M
                     int nn = nw + ni * 32 + 8 * g + 4 * h;
                     if (nn >= a.N) continue;
                     f32x4 v = acc4(acc[mi][ni], g);
-                    if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + nn));
-                    store4<true>(a, v, m, bidx, nn);
+                    store4<true>(a, bias4(a, v, nn), m, bidx, nn);
                 }
         }
     }
@@ -89,6 +88,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (
             if (m < a.M && n < a.N) {
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 add8(v, bs);
+                if (a.bias2) add8(v, *(const f16x8 *)(a.bias2 + n));
                 store8<true>(a, v, m, n);
             }
         }
@@ -151,13 +151,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     for (int i = 0; i < WI; ++i) {
         int row = RP * (wave + NW * i) + lr;
         bool ok = (n0 + row) < a.N;
-        wp[i] = ok ? a.Wt + (size_t)(n0 + row) * a.K + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : ctx_zero_page;
+        wp[i] = ok ? a.Wt + (size_t)(n0 + row) * (CONV ? 9 * a.Cin : a.K) + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : ctx_zero_page;
         wst[i] = ok ? PKT : 0;
     }
     // K rotation: workgroups that stream the same weight rows (same tile_n) or the same activation rows (same tile_m)
     // start at different K offsets and wrap, so at any instant they hit different cache lines / L2 channels.
     const int k_lo = kbeg * PKT, k_hi = (kbeg + nk) * PKT;
-    const int rot = a.krot == 1 ? (int)(((unsigned)tile_m * 13u + (unsigned)tile_n * 5u) % (unsigned)nk) : 0;
+    // (never with K segments: the wrap below steps back inside ONE weight matrix)
+    const int rot = a.krot == 1 && !a.nseg ? (int)(((unsigned)tile_m * 13u + (unsigned)tile_n * 5u) % (unsigned)nk) : 0;
     int k_issue = k_lo + rot * PKT, issued = 0, tap_left = 0;
     if (!CONV) {
 #pragma unroll
@@ -167,14 +168,32 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     for (int i = 0; i < WI; ++i) wp[i] += (wst[i] ? rot * PKT : 0);
 
     auto retap = [&]() {                            // CONV: new 3x3 tap -> recompute the activation pointers
-        const ConvTap tap = conv_tap(a, k_issue);
+        // ... or a K segment: its tensor has the output's pixel grid, so the lane's pixel is row m of it, read as a centre tap
+        const bool seg = a.nseg && k_issue >= 9 * a.Cin;
+        const ConvSrc cs = conv_stage_src(a, k_issue);
+        const int sg = cs.src - 9;
+        const ConvTap tap = conv_tap(a, seg ? 4 * a.Cin : k_issue);
+        unsigned lox = 0;
+        if (seg) {
+            // a piece's rows start at a multiple of RP and the wave count is even wherever a stage is 64 deep, so the lane's
+            // swizzled chunk is that of its row in piece 0 for every piece: one per-lane offset for all of them
+            static_assert(PKT == 32 || NW % 2 == 0, "the chunk swizzle must not depend on the piece");
+            const int ln = conv_seg_lane(lane), lr = ln / LPR, row0 = RP * wave + lr;
+            lox = (unsigned)(lr * cs.C + ((ln % LPR) ^ (PKT == 32 ? ((row0 >> 2) & 3) : ((row0 >> 1) & 7))) * 8);
+            const ConvWJump wj = conv_seg_wjump(a, sg, cs.c0, k_issue, sg == 0 || issued == 0);
+#pragma unroll
+            for (int i = 0; i < WI; ++i) {
+                const long step = wj.jump + ((long)(n0 + RP * (wave + NW * i)) * wj.dld + lr * wj.dld) * (long)sizeof(f16);
+                wp[i] = (const f16 *)((const char *)wp[i] + (wst[i] ? step : 0));
+            }
+        }
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
             bool ok = xok[i];
-            xp[i] = conv_tap_src<true>(a, tap, xoy[i], xox[i], xoff[i], ok);
+            xp[i] = conv_tap_src<true>(a, tap, xoy[i], xox[i], xoff[i], ok, seg ? conv_seg_x(a, sg, m0 + RP * (wave + NW * i), cs.c0) + lox : nullptr);
             xst[i] = ok ? PKT : 0;
         }
-        tap_left = (a.Cin - tap.c0) / PKT;
+        tap_left = (cs.C - cs.c0) / PKT;
     };
     auto issue = [&](int buf) {
         if (k_issue == k_hi) {                       // wrap of the rotated K range
@@ -316,7 +335,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(GemmArgs a)
             f32x4 p = *(const f32x4 *)(a.part + sidx * MN + (size_t)m * a.N + nn);
             v += p;
         }
-        if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + nn));
+        v = bias4(a, v, nn);
         store4<true>(a, v, m, a.rowbias ? m / a.rows_per_batch : 0, nn);
     }
 }
@@ -328,6 +347,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(GemmArgs a)
 //          64x64 4w | 64x128 4w | 128x64 4w | 128x128 4w;  19-22: ring of 2: 64x64 4w | 128x128 8w | 128x128 16w | 128x128 4w
 //   23-26: deep rings: 64x64 4w x6 | 64x128 4w x5 | 128x128 8w x4 | 128x64 4w x5;  27: 256x320 8w (64x160), ring of 2
 static int g_force_tile = -1, g_force_gemm8 = -1;
+static int g_last_tile = -1, g_last_use8 = -1;      // what the last dispatch launched (ctx_gemm_last_kernel)
 extern "C" void ctx_gemm_tune(int32_t tile, int32_t gemm8)
 {
     g_force_tile = tile;            // -1: heuristic
@@ -430,6 +450,21 @@ void ctx_gemm_plan(GemmArgs &a, bool conv)
 // split-K is counted; small problems fall through to tiles with more waves per staged byte.
 int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
 {
+    bool seg64 = true;                                                       // every K segment is whole 64-deep stages
+    if (a.nseg) {
+        int kseg = 0;
+        bool ok = conv && a.nseg <= CTX_GEMM_MAX_SEG && a.stride == 1 && !a.ups && !a.poff && !a.zins && a.epi == 0;
+        for (int i = 0; ok && i < a.nseg; ++i) {
+            ok = a.segX[i] && a.segW[i] && a.segC[i] > 0 && a.segC[i] % 32 == 0 && a.segLdw[i] % 8 == 0;
+            ok = ok && (int64_t)a.M * a.segC[i] < (1ll << 31) && (int64_t)a.N * a.segLdw[i] < (1ll << 31);
+            seg64 = seg64 && a.segC[i] % 64 == 0;
+            kseg += a.segC[i];
+        }
+        if (!ok || a.K != 9 * a.Cin + kseg) {
+            ctx_set_error("gemm: K segments need a stride-1 3x3 convolution without upsample and channel counts in multiples of 32");
+            return CTX_E_ARG;
+        }
+    }
     const bool only_pipe = a.zins || a.res32 || a.out32;                     // features of this file's kernel only
     if (only_pipe) a.use8 = 0;
     const int want8 = only_pipe ? 0 : (g_force_gemm8 >= 0 ? g_force_gemm8 : a.use8);          // -1: gemm8's own heuristic
@@ -438,6 +473,7 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
     const bool launched = want_tile < 0 && ((want8 >= 4 && want8 <= 8 && ctx_gemm144_try(a, conv, want8 - 4, s)) ||
                                             (conv && (want8 == 2 || want8 == 3) && ctx_conv_halo_try(a, want8 == 2 ? 2 : 1, s)) ||
                                             (want8 != 0 && want8 < 2 && ctx_gemm8_try(a, conv, want8 == 1, s)));
+    g_last_use8 = launched ? (want8 < 0 ? 1 : want8) : 0; g_last_tile = -1;     // want8 -1: only gemm8's own heuristic launches
     if (!launched) {
         static const int big = ctx_env_int("CTX_GEMM_BIG", 1);
         const int S = a.splitk > 1 && a.part ? a.splitk : 1;
@@ -455,8 +491,9 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
         if (force >= 0) pick = force;
         if (want_tile >= 0) pick = want_tile;
         if (a.epi == 1 && (pick == 5 || pick == 6 || pick == 9 || pick == 11 || pick == 13 || pick == 15 || pick == 17 || pick == 19 || pick == 21 || pick == 23 || pick == 26 || pick == 27)) pick = 1;   // GEGLU needs 64-wide wave tiles
-        if (pick >= 10 && (a.K % 64 != 0 || (conv && a.Cin % 64 != 0))) pick = 1;   // 64-deep stages
+        if (pick >= 10 && (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || !seg64)) pick = 1;   // 64-deep stages
 #define CTX_LAUNCH(WM_, WN_, MI_, NI_) do { if (conv) launch_gemm<WM_, WN_, MI_, NI_, true>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false>(a, s); } while (0)
+        g_last_tile = pick;
         switch (pick) {
         case 0: CTX_LAUNCH(4, 2, 2, 2); break;
         case 1: CTX_LAUNCH(2, 2, 2, 2); break;
@@ -506,6 +543,14 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
     return CTX_OK;
 }
 
+// Which kernel the last GEMM / conv dispatch of this process launched: *use8 as ctx_gemm_tune's second argument (0 = a tile of
+// gemm.hip, whose id goes to *tile; else *tile = -1).  For tests of the forcing and of the fall-through when a kernel declines.
+extern "C" void ctx_gemm_last_kernel(int32_t *tile, int32_t *use8)
+{
+    if (tile) *tile = g_last_tile;
+    if (use8) *use8 = g_last_use8;
+}
+
 extern "C" int32_t ctx_gemm_f16(const void *A, const void *Wt, const void *bias, const void *residual, int32_t M,
                                 int32_t N, int32_t K, void *C, ctx_stream_t stream)
 {
@@ -536,6 +581,36 @@ extern "C" int32_t ctx_conv3x3_f16(const void *x, const void *w, const void *bia
     a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.ups = upsample;
     a.tile = -1; a.use8 = -1;
     CTX_REQUIRE((int64_t)B * H * W * Cin < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31), "conv3x3: tensor too large for 32-bit offsets");
+    return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
+}
+
+// The resnet's second convolution with its 1x1 shortcut folded in as K segments (diffusers ResnetBlock2D.forward:
+// conv_shortcut(input_tensor) + conv2(hidden_states); reference call site src/stable_diffusion_depth.py:422-423):
+//   y = conv3x3(x; w) + xa wa^T (+ xb wb^T) + bias (+ bias2) (+ rowbias) (+ residual), fp32 sum, one rounding.
+// xa / xb: [B, H, W, Ca / Cb] on x's pixel grid; wa / wb: [Cout] rows of Ca / Cb weights, row strides ldwa / ldwb; xb null = one segment.
+// splitk: 1 none, > 1 that many slices, < 0 what the engine would plan for the 3x3 part; `part` holds splitk * M * Cout floats (with
+// splitk < 0: 32 * M * Cout) or is null (no split).  Honours ctx_gemm_tune.
+extern "C" int32_t ctx_conv3x3_seg_f16(const void *x, const void *w, const void *bias, const void *bias2, const void *rowbias,
+                                       const void *residual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, const void *xa,
+                                       const void *wa, int32_t Ca, int32_t ldwa, const void *xb, const void *wb, int32_t Cb, int32_t ldwb,
+                                       void *part, int32_t splitk, void *y, ctx_stream_t stream)
+{
+    CTX_REQUIRE(x && w && y && xa && wa, "conv3x3_seg: null pointer");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin % 32 == 0 && Cout % 8 == 0, "conv3x3_seg: need Cin%%32==0, Cout%%8==0 (Cin=%d Cout=%d)", Cin, Cout);
+    GemmArgs a = {};
+    a.Ho = H; a.Wo = W;
+    a.X = (const f16 *)x; a.Wt = (const f16 *)w; a.bias = (const f16 *)bias; a.bias2 = (const f16 *)bias2; a.rowbias = (const f16 *)rowbias;
+    a.residual = (const f16 *)residual; a.out = (f16 *)y;
+    a.M = B * H * W; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = H * W; a.ldrb = Cout;
+    a.H = H; a.W = W; a.Cin = Cin; a.stride = 1;
+    a.tile = -1; a.use8 = -1;
+    if (splitk < 0 && part) ctx_gemm_plan(a, true); else a.splitk = splitk;      // the plan of the 3x3 part's shape
+    a.part = (float *)part;
+    a.nseg = xb ? 2 : 1;
+    a.segX[0] = (const f16 *)xa; a.segW[0] = (const f16 *)wa; a.segC[0] = Ca; a.segLdw[0] = ldwa;
+    a.segX[1] = (const f16 *)xb; a.segW[1] = (const f16 *)wb; a.segC[1] = xb ? Cb : 0; a.segLdw[1] = ldwb;
+    a.K += a.segC[0] + a.segC[1];
+    CTX_REQUIRE((int64_t)a.M * (Cin > Ca + Cb ? Cin : Ca + Cb) < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31), "conv3x3_seg: tensor too large for 32-bit offsets");
     return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
 }
 

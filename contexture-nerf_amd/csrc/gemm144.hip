@@ -34,6 +34,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     constexpr int BM = 16 * BMB, NPX = BM / 8;                      // tile rows; activation pieces (8 rows x 128 B each)
     constexpr int NP = NPX + 20;                                    // DMA pieces per stage: activation + 20 weight
     constexpr int STAGE = (BM + G144_BN) * 64;                      // f16 per stage
+    static_assert(NPX % 2 == 0, "the K segments' chunk swizzle takes a weight piece's parity from its slot");
     static_assert(BMB % WM == 0 && (BMB == 9 || (BMB == 18 && VAR == 0)), "288-row tiles: lockstep schedule only");
     constexpr int SL = (NP + NW - 1) / NW;                          // piece slots per wave (the last one empty on some waves)
     static_assert(9 % WM == 0 && 10 % WN == 0, "wave grid must divide 9 x 10 blocks");
@@ -83,25 +84,55 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         } else {
             const bool ok = live && (n0 + s) < a.N;
             xok[i] = ok;
-            pp[i] = ok ? a.Wt + (size_t)(n0 + s) * a.K + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
+            pp[i] = ok ? a.Wt + (size_t)(n0 + s) * (CONV ? 9 * a.Cin : a.K) + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
             pst[i] = ok ? 64 : 0;
         }
     }
 
     int k_issue = kbeg * 64, issued = 0, tap_left = 0;
-    int cur_tap = CONV ? (kbeg * 64) / a.Cin : 0, cur_c0 = CONV ? kbeg * 64 - cur_tap * a.Cin : 0;   // FAST: tap and first channel of the next stage
+    // FAST: source (tap 0 .. 8, K segment 9 / 10), its channel count and the first channel of the next stage
+    int cur_tap = 0, cur_c0 = 0, cur_C = a.Cin;
+    if (CONV) { const ConvSrc cs = conv_stage_src(a, kbeg * 64); cur_tap = cs.src; cur_c0 = cs.c0; cur_C = cs.C; }
     auto retap = [&]() {                                            // CONV: new 3x3 tap -> recompute the activation pointers
         if (FAST) {
-            const int dy = cur_tap / 3 - 1 + a.poff, dx = cur_tap - (cur_tap / 3) * 3 - 1 + a.poff;
-            const int soff = (dy * a.W + dx) * a.Cin + cur_c0;     // scalar: the same for every lane
+            // A K segment (cur_tap 9 / 10): its tensor has the output's pixel grid, so the lane's pixel is row m of it and the segment
+            // is walked as a centre tap of that tensor; its weights are another matrix, so the weight pointers are formed anew.
+            // (Nothing behind a segment reads the earlier sources again.)  One assignment to pp[] serves taps and segments: a second
+            // definition of the pointers costs the kernel registers it does not have.  xcen[] itself is left as it is (a temporary per
+            // slot takes the segment's pointer): overwriting it put the array in scratch memory with this compiler.  The 288-row form
+            // now uses exactly 128 VGPRs, the limit of a 15-wave workgroup: it has no register left for the next change
+            // (`make resources` prints every kernel's registers and scratch).
+            const bool seg = cur_tap >= 9;
+            const int sg = cur_tap - 9, tap = seg ? 4 : cur_tap;    // bit 4 of xval: the row exists
+            if (seg) cur_C = sg ? a.segC[1] : a.segC[0];
+            const int dy = tap / 3 - 1 + a.poff, dx = tap - (tap / 3) * 3 - 1 + a.poff;
+            const int soff = seg ? cur_c0 : (dy * a.W + dx) * a.Cin + cur_c0;     // scalar: the same for every lane
+            // the weight pointers walk on from where they stand, in place
+            ConvWJump wj = {0, 0};
+            if (seg) wj = conv_seg_wjump(a, sg, cur_c0, k_issue, sg == 0 || issued == 0);
 #pragma unroll
             for (int i = 0; i < SL; ++i) {
-                if (wave + NW * i >= NPX) continue;
-                const bool v = (xval[i] >> cur_tap) & 1;
-                pp[i] = v ? xcen[i] + soff : zp;
+                const int p = wave + NW * i;
+                // lane's share of a segment offset: its row inside the 8-row piece times the row stride plus its swizzled chunk
+                // (NPX is even: a weight piece's rows have p's parity)
+                if (p >= NPX) {
+                    if (seg) {
+                        const int prow = conv_seg_lane(lane) >> 3;
+                        const long step = wj.jump + ((long)(n0 + 8 * (p - NPX)) * wj.dld + prow * wj.dld) * (long)sizeof(f16);
+                        pp[i] = (const f16 *)((const char *)pp[i] + (pst[i] ? step : 0));
+                    }
+                    continue;
+                }
+                const f16 *cen = xcen[i];
+                if (seg) {
+                    const int ln = conv_seg_lane(lane), prow = ln >> 3;
+                    cen = conv_seg_x(a, sg, m0 + 8 * p, 0) + (unsigned)(prow * cur_C + (((ln & 7) ^ (prow >> 1) ^ ((p & 1) << 2)) << 3));
+                }
+                const bool v = (xval[i] >> tap) & 1;
+                pp[i] = v ? cen + soff : zp;
                 pst[i] = v ? 64 : 0;
             }
-            tap_left = (a.Cin - cur_c0) >> 6;
+            tap_left = (cur_C - cur_c0) >> 6;
             return;
         }
         const ConvTap tap = conv_tap(a, k_issue);
@@ -129,7 +160,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     };
     auto issue_end = [&]() {
         k_issue += 64; ++issued;
-        if (FAST) { cur_c0 += 64; if (cur_c0 == a.Cin) { cur_c0 = 0; ++cur_tap; } }
+        if (FAST) { cur_c0 += 64; if (cur_c0 == cur_C) { cur_c0 = 0; ++cur_tap; } }
     };
     auto issue = [&](int buf) {
         issue_begin();
@@ -408,7 +439,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
                 if (m >= a.M || n >= a.N) continue;
                 const f32x4 v0 = *(const f32x4 *)(tile + row * RS + c8), v1 = *(const f32x4 *)(tile + row * RS + c8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if (a.bias) add8(v, *(const f16x8 *)(a.bias + n));
+                bias8(a, v, n);
                 store8(a, v, m, n);
             }
         }
@@ -429,7 +460,9 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         for (int j = 0; j < NI; ++j) {
             const int nn = nb + 16 * j + 4 * kg;
             if (nn >= a.N) continue;
-            store4(a, add4(acc[i][j], bs[j]), m, bidx, nn);
+            f32x4 v = add4(acc[i][j], bs[j]);
+            if (a.bias2) v = add4(v, *(const f16x4 *)(a.bias2 + nn));
+            store4(a, v, m, bidx, nn);
         }
     }
 }
@@ -440,6 +473,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
 int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
 {
     if (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || a.N % 4 != 0 || a.epi != 0 || a.res32 || a.out32 || a.zins) return 0;
+    for (int i = 0; i < a.nseg; ++i)
+        if (a.segC[i] % 64 != 0 || a.segLdw[i] % 64 != 0) return 0;  // K segments in whole stages, weight rows in whole swizzle periods
     if (a.ldc % 4 != 0 || (a.residual && a.ldr % 4 != 0) || (a.rowbias && a.ldrb % 4 != 0)) return 0;
     const int bm = form == 4 ? 288 : G144_BM;
     a.ntm = cdiv(a.M, bm);

@@ -286,6 +286,7 @@ int ctx_gemm8_try(GemmArgs &a, bool conv, bool force, hipStream_t s)
     const int min_tiles = ctx_env_int("CTX_GEMM8_MIN_TILES", 180);
     if (!en) return 0;
     if (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || a.N % 8 != 0) return 0;
+    if (a.nseg) return 0;                      // K segments: the kernels of gemm.hip / gemm144.hip
     if (a.epi == 1 && a.N % 64 != 0) return 0;
     const int ntm = cdiv(a.M, 256), ntn = cdiv(a.N, 256);
     const int S = (a.splitk > 1 && a.part) ? a.splitk : 1;

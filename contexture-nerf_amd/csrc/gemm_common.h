@@ -63,13 +63,62 @@ __device__ __forceinline__ ConvTap conv_tap(const GemmArgs &a, int k0)
 }
 // Source of one pixel for that tap; `off` as conv_pixel gives it.  ok: in, the pixel's row exists; out,
 // the tap reads the image (else the zero page: padding, or with ZINS the zero-inserted odd rows / columns of a.zins).
+// `cen`: a K segment's pixel pointer, read instead of the image (the caller passes the centre tap then: ok = the row exists)
 template <bool ZINS = false>
-__device__ __forceinline__ const f16 *conv_tap_src(const GemmArgs &a, const ConvTap &t, int oy, int ox, int off, bool &ok)
+__device__ __forceinline__ const f16 *conv_tap_src(const GemmArgs &a, const ConvTap &t, int oy, int ox, int off, bool &ok, const f16 *cen = nullptr)
 {
     const int iy = oy + t.dy, ix = ox + t.dx;
     ok = ok && iy >= 0 && iy < t.Hv && ix >= 0 && ix < t.Wv;
     if (ZINS) ok = ok && !(a.zins && ((iy | ix) & 1));
-    return ok ? a.X + off + (((iy >> a.ups) * a.W + (ix >> a.ups)) * a.Cin) + t.c0 : ctx_zero_page;
+    const f16 *src = a.X + off + (((iy >> a.ups) * a.W + (ix >> a.ups)) * a.Cin) + t.c0;
+    if (cen) src = cen;
+    return ok ? src : ctx_zero_page;
+}
+
+// K segments (GemmArgs::nseg): the source that the K stage starting at k0 reads.  src 0 .. 8: that tap of the 3x3 part; 9 / 10:
+// segment 0 / 1.  c0: first channel inside the source, C: the source's channel count (C - c0 is what is left of it), so a split-K
+// slice may start anywhere.  Weight rows of the 3x3 part are 9 Cin long whatever K is.
+struct ConvSrc { int src, c0, C; };
+__device__ __forceinline__ ConvSrc conv_stage_src(const GemmArgs &a, int k0)
+{
+    const int k9 = 9 * a.Cin;
+    if (k0 < k9) { const int tap = k0 / a.Cin; return {tap, k0 - tap * a.Cin, a.Cin}; }
+    const int k1 = k0 - k9;
+    if (k1 < a.segC[0]) return {9, k1, a.segC[0]};
+    return {10, k1 - a.segC[0], a.segC[1]};
+}
+// a segment's activation / weight source for output pixel m / feature n at the segment's channel c (the lane's chunk included);
+// selects, not indexing: a run-time index into the by-value argument block would put it in scratch memory
+// (element offsets fit 32 bits: the dispatcher checks M segC and N segLdw).  m / n / c here are the wave-uniform part (tile origin,
+// the piece's first row, the stage's first channel): scalar arithmetic; the callers add the lane's own row and chunk.
+__device__ __forceinline__ const f16 *conv_seg_x(const GemmArgs &a, int s, int m, int c)
+{
+    return (s ? a.segX[1] : a.segX[0]) + (unsigned)(m * (s ? a.segC[1] : a.segC[0]) + c);
+}
+__device__ __forceinline__ const f16 *conv_seg_w(const GemmArgs &a, int s, int n, int c)
+{
+    return (s ? a.segW[1] : a.segW[0]) + (unsigned)(n * (s ? a.segLdw[1] : a.segLdw[0]) + c);
+}
+// The segment switch runs once or twice per K loop.  Its per-lane arithmetic starts from a lane id taken through an empty volatile asm,
+// so that none of it is hoisted out of the loop into registers that would stay live across every stage.  The K loops' pointers get
+// no second definition either (that costs registers: the allocator keeps both): an activation pointer is still assigned in one
+// place per kernel, from the tap's or the segment's source, and a weight pointer walks on in place by conv_seg_wjump().
+__device__ __forceinline__ int conv_seg_lane(int lane)
+{
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
+// Weight pointers at a segment switch walk on from where they stand: in row n of the 3x3 matrix at K index k_issue (the end of the
+// 3x3 part, or a slice's start inside a segment: `fresh`) or at the end of segment 0's row; the lane's chunk is already in them.
+// -> bytes between the two matrices' origins (to the segment's channel c0) and the difference of the row strides (elements):
+// row n's pointer advances by jump + n * dld * sizeof(f16).
+struct ConvWJump { long jump; int dld; };
+__device__ __forceinline__ ConvWJump conv_seg_wjump(const GemmArgs &a, int sg, int c0, int k_issue, bool fresh)
+{
+    const f16 *from = fresh ? a.Wt + k_issue : a.segW[0] + a.segC[0];
+    const f16 *to = (sg ? a.segW[1] : a.segW[0]) + c0;
+    return {(long)((const char *)to - (const char *)from), (sg ? a.segLdw[1] : a.segLdw[0]) - (fresh ? 9 * a.Cin : a.segLdw[0])};
 }
 
 // ---- epilogue ------------------------------------------------------------------------------------------------------
@@ -98,7 +147,20 @@ __device__ __forceinline__ void add8(float (&v)[8], f16x8 b)
     for (int e = 0; e < 8; ++e) v[e] += (float)b[e];
 }
 
-// The operand order of every epilogue: accumulator, bias, row bias, residual, one rounding.  The bias is the caller's (some
+// the tile's bias for features n ..: bias (+ bias2), summed in fp32
+__device__ __forceinline__ f32x4 bias4(const GemmArgs &a, f32x4 v, int n)
+{
+    if (a.bias) v = add4(v, *(const f16x4 *)(a.bias + n));
+    if (a.bias2) v = add4(v, *(const f16x4 *)(a.bias2 + n));
+    return v;
+}
+__device__ __forceinline__ void bias8(const GemmArgs &a, float (&v)[8], int n)
+{
+    if (a.bias) add8(v, *(const f16x8 *)(a.bias + n));
+    if (a.bias2) add8(v, *(const f16x8 *)(a.bias2 + n));
+}
+
+// The operand order of every epilogue: accumulator, bias (+ bias2), row bias, residual, one rounding.  The bias is the caller's (some
 // kernels preload it per tile, some test a.bias per piece): store4 / store8 take v = accumulator + bias and do the rest.
 // F32: honour a.res32 / a.out32 (fp32 residual stream); the kernels that never see those flags do not test them.
 // store4: features nn .. nn + 3 of row m, whose row bias is row bidx.

@@ -30,7 +30,15 @@ struct GemmArgs {
     int tile, use8;        // plan: tile id of gemm.hip (-1 = heuristic); use8: -1 heuristic, 0 gemm.hip, 1 gemm8.hip, 2 / 3 conv_halo.hip (128 / 64 features), 4 .. 8 gemm144.hip (6 waves; 15 waves lockstep; pipelined; barrier per two stages; 288 x 160 lockstep)
     int stage_epi;         // 1: epilogue staged through LDS (whole-line stores / residual reads)
     int mfast;             // 1: consecutive workgroups walk M first (share the weight panel in their XCD's L2)
+    // conv, K segments: up to two centre-tap (1x1) products behind the 9 Cin part, each over another NHWC tensor of the output's pixel
+    // grid with its own weights: out += segX[s] . segW[s]^T.  K = 9 Cin + segC[0] + segC[1]; stride 1, no upsample, poff 0 only.
+    int nseg;              // 0 .. 2
+    const f16 *segX[2];    // [M, segC[s]]: the channel count is the pixel stride
+    const f16 *segW[2];    // [N] rows of segC[s] weights, row stride segLdw[s] (two column ranges of one [N][Ca + Cb] matrix)
+    int segC[2], segLdw[2];
+    const f16 *bias2;      // [N] or null: a second bias (the folded product's own), added in fp32 behind `bias`
 };
+#define CTX_GEMM_MAX_SEG 2
 
 int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s);
 // 256x256 8-wave kernel (gemm8.hip): launches and returns 1 when the problem suits it, else 0
@@ -53,9 +61,10 @@ int ctx_conv_out_f16(const f16 *x, const f16 *w, const f16 *bias, int B, int H, 
 int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int q_stride,
                        int kv_stride, float scale, f16 *O, int o_stride, hipStream_t s);
 extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
-// norms over the fp32 residual stream (x32 != 0) or fp16 activations; output fp16
+// norms over the fp32 residual stream (x32 != 0) or fp16 activations; output fp16.  x2 != null: the input is the channel concatenation
+// [x ; x2] read in place (x: channels 0 .. Ca with pixel stride Ca; x2: channels Ca .. C with pixel stride C - Ca; Ca % 8 == 0)
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
-                      void *y, void *stats_ws, hipStream_t stream);
+                      void *y, void *stats_ws, hipStream_t stream, const void *x2 = nullptr, int Ca = 0);
 // GroupNorm(+SiLU) backward, input gradient only, fp16 NHWC: dx = d(loss)/dx (+ add); ws of ctx_groupnorm_bwd_ws_bytes(B, groups)
 int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups);
 int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,

@@ -57,6 +57,17 @@ __device__ __forceinline__ Raw8<X32> ldraw(const void *base, size_t elem)
     return r;
 }
 
+// Two-source input (x2 != null): the tensor is the channel concatenation [x ; x2] that nobody materialised: channels 0 .. Ca lie in
+// x with pixel stride Ca, channels Ca .. C in x2 with pixel stride C - Ca (the up blocks' [hidden ; skip]).  A thread owns one
+// 8-channel column, so it picks its source once; thread-to-channel mapping and summation order are those of the one-source form,
+// which makes the result bit-identical to GroupNorm of the materialised concat.
+struct GnSrc { const void *p; int cs, col; };         // source, its pixel stride, the column's first channel inside it
+__device__ __forceinline__ GnSrc gn_src(const void *x, const void *x2, int Ca, int C, int ch)
+{
+    if (!x2) return {x, C, ch};
+    return ch < Ca ? GnSrc{x, Ca, ch} : GnSrc{x2, C - Ca, ch - Ca};
+}
+
 #define GN_MAX_GROUPS 64
 #define GN_MAX_SPLITS 128
 #define GN_MAX_C 4096
@@ -65,8 +76,8 @@ __device__ __forceinline__ Raw8<X32> ldraw(const void *base, size_t elem)
 #define GN_FOLD 8
 
 template <bool X32>
-__global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, int HW, int C, int G, int NS, int PL,
-                                                   float *__restrict__ part)
+__global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, const void *__restrict__ x2, int Ca, int HW, int C, int G,
+                                                   int NS, int PL, float *__restrict__ part)
 {
     extern __shared__ float s_part[];          // [PL][C][2]
     const int c8n = C / 8;
@@ -77,11 +88,12 @@ __global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, i
     float s[8], q[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
-    const size_t base = ((size_t)b * HW) * C + c8 * 8;
+    const GnSrc src = gn_src(x, x2, Ca, C, c8 * 8);
+    const size_t base = ((size_t)b * HW) * src.cs + src.col;
     for (int p = p0 + pl; p < p1; p += PL * GN_U) {
         Wide8 v[GN_U];
 #pragma unroll
-        for (int u = 0; u < GN_U; ++u) v[u] = ldraw<X32>(x, base + (size_t)min(p + u * PL, p1 - 1) * C).widen();   // unconditional
+        for (int u = 0; u < GN_U; ++u) v[u] = ldraw<X32>(src.p, base + (size_t)min(p + u * PL, p1 - 1) * src.cs).widen();   // unconditional
 #pragma unroll
         for (int u = 0; u < GN_U; ++u) {
             const bool live = p + u * PL < p1;
@@ -173,7 +185,7 @@ __device__ __forceinline__ void gn_store(const V8 &v, const float (&sa)[8], cons
 // four times the payload — tools/probes/stream_probe.hip: a copy-shaped kernel goes from 3.9 to 8.8 us on 12 MB with exactly that
 // table read added, and stays at 4.3 with the values in registers (SiLU and the index arithmetic cost nothing measurable).
 template <bool X32>
-__global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, const float *__restrict__ part,
+__global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, const void *__restrict__ x2, int Ca, const float *__restrict__ part,
                                                   const f16 *__restrict__ gamma, const f16 *__restrict__ beta, int HW, int C,
                                                   int G, int NS, int PL, float eps, int silu, f16 *__restrict__ y)
 {
@@ -183,11 +195,12 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
     const int c8n = C / 8;
     const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
     const int p0 = blockIdx.x * (PL * AU);
-    const size_t xb = (size_t)b * HW * C + c8 * 8;
+    const GnSrc src = gn_src(x, x2, Ca, C, c8 * 8);
+    const size_t xb = (size_t)b * HW * src.cs + src.col;
     f16 *yb = y + (size_t)b * HW * C + c8 * 8;
     Raw8<X32> v[AU];
 #pragma unroll
-    for (int u = 0; u < AU; ++u) v[u] = ldraw<X32>(x, xb + (size_t)min(p0 + u * PL + pl, HW - 1) * C);    // unconditional (clamped)
+    for (int u = 0; u < AU; ++u) v[u] = ldraw<X32>(src.p, xb + (size_t)min(p0 + u * PL + pl, HW - 1) * src.cs);    // unconditional (clamped)
     const f16x8 ga = *(const f16x8 *)(gamma + c8 * 8), be = *(const f16x8 *)(beta + c8 * 8);
     if (threadIdx.x < 256) {
         const int lpg = min(256 / G, 64);                                   // lanes per group: a power of two inside one wave (G < 4: idle lanes)
@@ -228,7 +241,7 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
 #define GN_FT 512
 #define GN_FU 12
 template <bool X32>
-__global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, const f16 *__restrict__ gamma,
+__global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, const void *__restrict__ x2, int Ca, const f16 *__restrict__ gamma,
                                                     const f16 *__restrict__ beta, int HW, int C, int G, int PLF, float eps, int silu,
                                                     f16 *__restrict__ y)
 {
@@ -239,12 +252,13 @@ __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, 
     const int cg = C / G, cpg = cg / 8;                // chunks per pixel in this group
     const int c = threadIdx.x % cpg, pl = threadIdx.x / cpg;
     const bool act = pl < PLF;                         // blockDim.x is rounded up to whole waves
-    const size_t xb = (size_t)b * HW * C + g * cg + c * 8;
+    const GnSrc src = gn_src(x, x2, Ca, C, g * cg + c * 8);    // two sources: the launcher takes this form only when no group straddles Ca
+    const size_t xb = (size_t)b * HW * src.cs + src.col;
     f16 *yb = y + (size_t)b * HW * C + g * cg + c * 8;
     const f16x8 ga = *(const f16x8 *)(gamma + g * cg + c * 8), be = *(const f16x8 *)(beta + g * cg + c * 8);
     Wide8 v[GN_FU];
 #pragma unroll
-    for (int u = 0; u < GN_FU; ++u) v[u] = ldraw<X32>(x, xb + (size_t)min(pl + PLF * u, HW - 1) * C).widen();     // unconditional (clamped), all in flight
+    for (int u = 0; u < GN_FU; ++u) v[u] = ldraw<X32>(src.p, xb + (size_t)min(pl + PLF * u, HW - 1) * src.cs).widen();     // unconditional (clamped), all in flight
     float s = 0.f, q = 0.f;
 #pragma unroll
     for (int u = 0; u < GN_FU; ++u)
@@ -280,11 +294,21 @@ extern "C" int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const voi
     return ctx_groupnorm_any(x, 0, gamma, beta, B, HW, C, groups, eps, silu, y, stats_ws, (hipStream_t)stream);
 }
 
+// GroupNorm(+SiLU) of the channel concatenation [xa ; xb] read in place: xa [B, HW, Ca], xb [B, HW, C - Ca]; y [B, HW, C].
+// Bit-identical to ctx_groupnorm_f16 of the materialised concat.
+extern "C" int32_t ctx_groupnorm2_f16(const void *xa, const void *xb, int32_t Ca, const void *gamma, const void *beta, int32_t B, int32_t HW,
+                                      int32_t C, int32_t groups, float eps, int32_t silu, void *y, void *stats_ws, ctx_stream_t stream)
+{
+    CTX_REQUIRE(xb, "groupnorm2: null pointer");
+    return ctx_groupnorm_any(xa, 0, gamma, beta, B, HW, C, groups, eps, silu, y, stats_ws, (hipStream_t)stream, xb, Ca);
+}
+
 // x32 != 0: the input is the fp32 residual stream (the output stays fp16: it is the next GEMM's operand)
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
-                      void *y, void *stats_ws, hipStream_t stream)
+                      void *y, void *stats_ws, hipStream_t stream, const void *x2, int Ca)
 {
     CTX_REQUIRE(x && gamma && beta && y && stats_ws, "groupnorm: null pointer");
+    CTX_REQUIRE(!x2 || (Ca > 0 && Ca < C && Ca % 8 == 0), "groupnorm: two sources need 0 < Ca < C in whole 8-channel columns (Ca=%d C=%d)", Ca, C);
     CTX_REQUIRE(B > 0 && HW > 0 && C % 8 == 0 && C % groups == 0 && groups <= GN_MAX_GROUPS && C <= GN_MAX_C &&
                     256 % groups == 0 && (256 / groups & (256 / groups - 1)) == 0,
                 "groupnorm: unsupported B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
@@ -293,9 +317,9 @@ int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *bet
         const int cg = C / groups;
         const int cpg = cg / 8;
         const int plf = cg % 8 == 0 ? GN_FT / cpg : 0;                  // pixel lanes of the one-kernel form
-        if (fuse && cg % 8 == 0 && cpg <= GN_FT && (HW + plf - 1) / plf <= GN_FU) {
+        if (fuse && cg % 8 == 0 && cpg <= GN_FT && (HW + plf - 1) / plf <= GN_FU && (!x2 || Ca % cg == 0)) {
             const int thr = (cpg * plf + 63) / 64 * 64;
-            CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(thr), 0, stream, x, (const f16 *)gamma, (const f16 *)beta, HW, C,
+            CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(thr), 0, stream, x, x2, Ca, (const f16 *)gamma, (const f16 *)beta, HW, C,
                                                    groups, plf, eps, silu, (f16 *)y));
             CTX_CHECK_LAUNCH("groupnorm");
             return CTX_OK;
@@ -327,13 +351,13 @@ int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *bet
         (void)hipFuncSetAttribute((const void *)k_gn_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         attr = true;
     }
-    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_stats<X>, dim3(NS, B), dim3(threads), lds, stream, x, HW, C, groups, NS, PL, part));
+    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_stats<X>, dim3(NS, B), dim3(threads), lds, stream, x, x2, Ca, HW, C, groups, NS, PL, part));
     // fat blocks (the per-block fold of the split partials is amortised), at least one batch each
     {
         const int apl = (256 + c8n - 1) / c8n;                      // pixel lanes: >= 256 threads (the fold uses 256), <= 512
         const int athreads = c8n * apl;
         const int nb = (HW + apl * GN_AU - 1) / (apl * GN_AU);
-        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(nb, B), dim3(athreads), 0, stream, x, part, (const f16 *)gamma, (const f16 *)beta, HW, C,
+        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(nb, B), dim3(athreads), 0, stream, x, x2, Ca, part, (const f16 *)gamma, (const f16 *)beta, HW, C,
                                                groups, NS, apl, eps, silu, (f16 *)y));
     }
     CTX_CHECK_LAUNCH("groupnorm");

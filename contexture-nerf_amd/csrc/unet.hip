@@ -370,16 +370,18 @@ static void op_gemm(ctx_unet *u, const f16 *X, size_t w, size_t bias, bool has_b
     engine_linear(*u, X, u->W + w, has_bias ? u->W + bias : nullptr, res, M, N, K, out, 0, epi, u->res32 && res_s && res, u->res32 && out_s);
 }
 static void op_conv(ctx_unet *u, const f16 *x, size_t w, size_t bias, const f16 *rowbias, int ldrb, const void *res, int B, int H,
-                    int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false)
+                    int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false, const ConvSegs *segs = nullptr)
 {
     engine_conv3(*u, x, u->W + w, u->W + bias, res, B, H, W, Cin, Cout, out, ConvGeom{stride, ups}, rowbias, ldrb, u->res32 && res_s && res,
-                 u->res32 && out_s);
+                 u->res32 && out_s, segs);
 }
 // x_s: x is a residual-stream tensor
-static void op_gn(ctx_unet *u, const void *x, size_t g, size_t b, int B, int HW, int C, float eps, int silu, f16 *y, void *stats, bool x_s = true)
+// x2 != null: the input is [x ; x2] along the channels, read in place (x has Ca of the C channels)
+static void op_gn(ctx_unet *u, const void *x, size_t g, size_t b, int B, int HW, int C, float eps, int silu, f16 *y, void *stats, bool x_s = true,
+                  const void *x2 = nullptr, int Ca = 0)
 {
     u->note(2, 0, 2);
-    RUN(ctx_groupnorm_any(x, (u->res32 && x_s) ? 1 : 0, u->W + g, u->W + b, B, HW, C, u->cfg.groups, eps, silu, y, stats, u->s));
+    RUN(ctx_groupnorm_any(x, (u->res32 && x_s) ? 1 : 0, u->W + g, u->W + b, B, HW, C, u->cfg.groups, eps, silu, y, stats, u->s, x2, Ca));
 }
 static void op_ln(ctx_unet *u, const void *x, size_t g, size_t b, int64_t rows, int C, f16 *y)
 {
@@ -409,20 +411,66 @@ struct FwdCtx {
     void *gn_stats;
 };
 
-static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void *x, int H, int W, void *out)
+// CTX_RESNET_FOLD (read once): 1 (default) the up blocks' [x ; skip] is read in place and the 1x1 shortcut runs as K segments of conv2;
+// 2 in-place concat only (norm1 reads the pair, the shortcut GEMM still gets a materialised copy); 0 neither: the graph as it was
+// before either existed, bit for bit.
+static int resnet_fold_mode(void)
+{
+    static const int m = ctx_env_int("CTX_RESNET_FOLD", 1);
+    return m;
+}
+// Shapes where the folded shortcut measured slower than conv2 with a residual + a separate shortcut GEMM keep the GEMM
+// (tools/bench_resnet_fold.py, the table in profiles/resnet_fold_by_kernel_and_grid.txt; CFG batch 2 at latent 96^2):
+//   M = 4608, 320 -> 640 (the first resnet of down block 1): folded 60.4 us; conv2 + residual 52.4 us + GEMM 7.2 us = 59.6 us
+// (a K = 320 GEMM is the cheapest of the shortcuts and its one segment is 5 of conv2's 95 stages on a split-K 2 plan).
+// The other nine shapes gain 3.7 - 9.2 us each.
+static bool resnet_fold_loses(int M, int cin, int cout) { return M == 4608 && cin == 320 && cout == 640; }
+
+// Ca > 0: the block's input is the channel concatenation [x ; x2] (an up block's hidden state and skip tensor), x having Ca
+// of its r.cin channels.  Only norm1 and the 1x1 shortcut ever read it: norm1 reads the pair in place, the shortcut becomes two K
+// segments of conv2 (one for a down block's cin != cout), and no concatenated tensor exists.  The fp32 residual stream (its operands
+// cannot be staged as fp16), channel counts no kernel takes as segments and CTX_RESNET_FOLD = 0 keep the materialised path.
+static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void *x, int H, int W, void *out, const void *x2 = nullptr, int Ca = 0)
 {
     const int B = f.B, HW = H * W, M = B * HW;
     size_t mark = u->top;
+    const int mode = u->res32 ? 0 : resnet_fold_mode();
+    const bool pair = Ca > 0;                      // (a dry run's pointers are all null)
+    const int Cb = r.cin - Ca;
+    const bool segs_ok = r.cout % 32 == 0 && (pair ? (Ca % 32 == 0 && Cb % 32 == 0) : r.cin % 32 == 0);
+    const bool fold = mode == 1 && r.cin != r.cout && segs_ok && !resnet_fold_loses(M, r.cin, r.cout);
+    const bool gn_pair = pair && mode != 0 && Ca % 8 == 0;
+    const void *xin = x;                           // what the shortcut GEMM / the residual reads: x, or the concatenated copy
+    if (pair) {
+        u->note(2, 0);                             // the concat: a copy, or the in-place reads that stand for it
+        if (!gn_pair || !fold) {
+            void *cat = u->allocS((size_t)M * r.cin);
+            if (u->res32) RUN(ctx_concat_f32((const float *)x, (const float *)x2, (int64_t)M, Ca, Cb, (float *)cat, u->s));
+            else RUN(ctx_concat_f16((const f16 *)x, (const f16 *)x2, (int64_t)M, Ca, Cb, (f16 *)cat, u->s));
+            xin = cat;
+        }
+    }
     f16 *t1 = u->allocH((size_t)M * r.cin);
-    op_gn(u, x, r.n1g, r.n1b, B, HW, r.cin, u->cfg.norm_eps, 1, t1, f.gn_stats);
+    if (gn_pair) op_gn(u, x, r.n1g, r.n1b, B, HW, r.cin, u->cfg.norm_eps, 1, t1, f.gn_stats, true, x2, Ca);
+    else op_gn(u, xin, r.n1g, r.n1b, B, HW, r.cin, u->cfg.norm_eps, 1, t1, f.gn_stats);
     f16 *h = u->allocH((size_t)M * r.cout);
     op_conv(u, t1, r.c1w, r.c1b, f.tproj ? f.tproj + r.temb_row : nullptr, u->temb_rows, nullptr, B, H, W, r.cin, r.cout, 1, 0, h);
     f16 *t2 = u->allocH((size_t)M * r.cout);
     op_gn(u, h, r.n2g, r.n2b, B, HW, r.cout, u->cfg.norm_eps, 1, t2, f.gn_stats, false);
-    const void *sc = x;
+    if (fold) {
+        // conv_shortcut(input) + conv2(t2) in one K loop: W_sc is [cout][cin], segment a reads its columns 0 .. Ca, segment b the rest
+        ConvSegs sg;
+        sg.n = pair ? 2 : 1; sg.bias2 = u->W + r.scb;
+        sg.x[0] = (const f16 *)x; sg.w[0] = u->W + r.scw; sg.C[0] = pair ? Ca : r.cin; sg.ldw[0] = r.cin;
+        if (pair) { sg.x[1] = (const f16 *)x2; sg.w[1] = u->W + r.scw + Ca; sg.C[1] = Cb; sg.ldw[1] = r.cin; }
+        op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, nullptr, B, H, W, r.cout, r.cout, 1, 0, out, true, true, &sg);
+        u->top = mark;
+        return out;
+    }
+    const void *sc = xin;
     if (r.cin != r.cout) {
         void *s2 = u->allocS((size_t)M * r.cout);
-        op_gemm(u, op_as16(u, x, (size_t)M * r.cin), r.scw, r.scb, true, nullptr, M, r.cout, r.cin, s2, 0, false, true);
+        op_gemm(u, op_as16(u, xin, (size_t)M * r.cin), r.scw, r.scb, true, nullptr, M, r.cout, r.cin, s2, 0, false, true);
         sc = s2;
     }
     op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, sc, B, H, W, r.cout, r.cout, 1, 0, out, true, true);
@@ -656,16 +704,14 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             int cin = cur + sk.C, cout = Lv.res[j].cout;
             void *o = u->allocS((size_t)B * h * w * cout);
             size_t mark = u->top;
-            void *cat = u->allocS((size_t)B * h * w * cin);
-            u->note(2, 0);
-            if (u->res32) RUN(ctx_concat_f32((const float *)x, (const float *)sk.p, (int64_t)B * h * w, cur, sk.C, (float *)cat, u->s));
-            else RUN(ctx_concat_f16((const f16 *)x, (const f16 *)sk.p, (int64_t)B * h * w, cur, sk.C, (f16 *)cat, u->s));
+            // the resnet reads [x ; skip] as a pair (a concatenated copy only on its fallback path)
+            if (cin != Lv.res[j].cin) { ctx_set_error("unet: up block input has %d channels, its resnet expects %d", cin, Lv.res[j].cin); return CTX_E_STATE; }
             if (Lv.has_attn) {
                 void *t = u->allocS((size_t)B * h * w * cout);
-                run_resnet(u, f, Lv.res[j], cat, h, w, t);
+                run_resnet(u, f, Lv.res[j], x, h, w, t, sk.p, cur);
                 u->tap(t, B * h * w, cout);
                 run_transformer(u, f, Lv.tr[j], t, h, w, o);
-            } else run_resnet(u, f, Lv.res[j], cat, h, w, o);
+            } else run_resnet(u, f, Lv.res[j], x, h, w, o, sk.p, cur);
             u->tap(o, B * h * w, cout);
             u->top = mark;
             x = o; cur = cout;

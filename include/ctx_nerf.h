@@ -404,11 +404,32 @@ int32_t ctx_gemm_f16(const void *A, const void *Wt, const void *bias, const void
 int32_t ctx_conv3x3_f16(const void *x, const void *w, const void *bias, const void *rowbias,
                         const void *residual, int32_t B, int32_t H, int32_t W, int32_t Cin,
                         int32_t Cout, int32_t stride, int32_t upsample, void *y, ctx_stream_t stream);
+/* The same stride-1 convolution with up to two K segments behind its 9 Cin part: centre-tap (1x1) products over tensors xa / xb
+   [B,H,W,Ca / Cb] of the same pixel grid, weights wa / wb [Cout] rows of Ca / Cb at row strides ldwa / ldwb (xb NULL: one segment):
+   y = conv3x3(x; w) + xa wa^T + xb wb^T + bias + bias2 (+rowbias) (+residual), summed in fp32 and rounded once.  This is
+   ResnetBlock2D's conv_shortcut(input_tensor) + conv2(hidden_states) under diffusers' UNet2DConditionModel (reference call site
+   src/stable_diffusion_depth.py:422-423) with the up blocks' torch.cat([hidden_states, skip]) read in place.  Channel counts in
+   multiples of 32.  splitk: 1 none, > 1 that many K slices, < 0 the engine's plan for the 3x3 part; part: splitk * M * Cout floats
+   (32 * M * Cout with splitk < 0) or NULL (no split). */
+int32_t ctx_conv3x3_seg_f16(const void *x, const void *w, const void *bias, const void *bias2, const void *rowbias,
+                            const void *residual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                            const void *xa, const void *wa, int32_t Ca, int32_t ldwa, const void *xb, const void *wb,
+                            int32_t Cb, int32_t ldwb, void *part, int32_t splitk, void *y, ctx_stream_t stream);
+/* The kernel that the last GEMM / convolution dispatch launched, in ctx_gemm_tune's terms (use8 0: gemm.hip's tile *tile): lets a test
+   of the cuBLAS / cuDNN replacements under UNet2DConditionModel (reference call site src/stable_diffusion_depth.py:422-423) see
+   that a forced kernel ran, or that the call fell through to another one when it declined. */
+void ctx_gemm_last_kernel(int32_t *tile, int32_t *use8);
 /* GroupNorm(+SiLU) over NHWC f16; stats_ws: ctx_groupnorm_ws_bytes(B, groups). */
 int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const void *beta, int32_t B, int32_t HW,
                           int32_t C, int32_t groups, float eps, int32_t silu, void *y, void *stats_ws,
                           ctx_stream_t stream);
+/* GroupNorm(+SiLU) of the channel concatenation [xa ; xb] (xa [B,HW,Ca], xb [B,HW,C-Ca], Ca % 8 == 0) read in place: norm1 of
+   the up blocks' ResnetBlock2D over torch.cat([hidden_states, res_hidden_states], dim=1) under diffusers' UNet2DConditionModel
+   (reference call site src/stable_diffusion_depth.py:422-423).  Bit-identical to ctx_groupnorm_f16 of the concatenated tensor. */
+int32_t ctx_groupnorm2_f16(const void *xa, const void *xb, int32_t Ca, const void *gamma, const void *beta, int32_t B,
+                           int32_t HW, int32_t C, int32_t groups, float eps, int32_t silu, void *y, void *stats_ws,
+                           ctx_stream_t stream);
 int32_t ctx_layernorm_f16(const void *x, const void *gamma, const void *beta, int64_t rows, int32_t C,
                           float eps, void *y, ctx_stream_t stream);
 /* softmax(Q K^T * scale) V; Q[B,Sq,heads*64], K[B,Skv,heads*64], V likewise (f16) -> O[B,Sq,heads*64];
