@@ -52,9 +52,10 @@ class _UvMlpFn(torch.autograd.Function):
         dev = blob.device
         Lf = (net.input_ch // 2 - 1) // 2
         # the activation store (8.8 GB for the 1024^2 atlas) is kept by the module and handed out to one forward at a time;
-        # allocating it per call makes the caching allocator split and re-malloc multi-GB blocks
+        # allocating it per call makes the caching allocator split and re-malloc multi-GB blocks.  The pool only grows: N changes
+        # from step to step on the occupancy path, and the kernels take the prefix of the length they need
         nbytes = lib.ctx_uvmlp_saved_bytes(N, net.D, net.W, net.input_ch)
-        saved = net._saved_pool if (net._saved_pool is not None and net._saved_pool.numel() == nbytes
+        saved = net._saved_pool if (net._saved_pool is not None and net._saved_pool.numel() >= nbytes
                                     and net._saved_pool.device == dev) else None
         net._saved_pool = None
         if saved is None:
@@ -75,7 +76,7 @@ class _UvMlpFn(torch.autograd.Function):
         gws = [torch.empty_like(l.weight) for l in layers]
         gbs = [torch.empty_like(l.bias) for l in layers]
         wsb = lib.ctx_uvmlp_bwd_ws_bytes(N, net.D, net.W)
-        if net._bwd_ws is None or net._bwd_ws.numel() != wsb or net._bwd_ws.device != dev:
+        if net._bwd_ws is None or net._bwd_ws.numel() < wsb or net._bwd_ws.device != dev:
             net._bwd_ws = None
             net._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)     # scratch, stream-ordered: reusable
         ws = net._bwd_ws
@@ -89,7 +90,10 @@ class _UvMlpFn(torch.autograd.Function):
         else:
             L.check(lib.ctx_uvmlp_bwd_idx(L.ptr(g_raw), L.ptr(g_tex), L.ptr(ctx.texels), ctx.res, L.ptr(raw), N, L.ptr(ctx.blob), net.D, net.W,
                                           net.multires, net.output_ch, net.skips[0], L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.stream()))
-        net._saved_pool, ctx.saved_acts = ctx.saved_acts, None          # back to the module for the next forward
+        back, ctx.saved_acts = ctx.saved_acts, None                     # back to the module for the next forward; of the
+        pool = net._saved_pool                                          # stores of two passes the module keeps the larger
+        if pool is None or pool.device != back.device or pool.numel() <= back.numel():
+            net._saved_pool = back
         grads = []
         for w, b in zip(gws, gbs):
             grads += [w, b]
@@ -366,8 +370,54 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
     return _composite_fwd(r, z, d, noise, white_bkgd)
 
 
+def _occ_expand(raw_c, idx, total):
+    lib = L.load()
+    raw = torch.empty(total, 4, device=idx.device)
+    n = idx.numel()
+    L.check(lib.ctx_occ_expand(L.ptr(raw_c, torch.float32, "raw_c") if n else None, L.ptr(idx, torch.int32, "idx") if n else None, n,
+                               total, L.ptr(raw), L.stream()))
+    return raw
+
+
+class _OccExpandFn(torch.autograd.Function):
+    """raw [total,4] = the fill with row idx[k] = raw_c[k] (`ctx_occ_expand`); the gradient to raw_c is the gather `ctx_occ_collect`."""
+
+    @staticmethod
+    def forward(ctx, raw_c, idx, total):
+        ctx.save_for_backward(idx)
+        ctx.total = total
+        return _occ_expand(raw_c, idx, total)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        idx, = ctx.saved_tensors
+        g = L.f32c(g)
+        grad_c = torch.empty(idx.numel(), 4, device=g.device)
+        L.check(lib.ctx_occ_collect(L.ptr(g), L.ptr(idx), idx.numel(), ctx.total, L.ptr(grad_c), L.stream()))
+        return grad_c, None, None
+
+
+def field_on_occupied(field, occupancy, ro, rd, z_vals):
+    """raw [R,S,4] of one pass with the field evaluated on the occupied samples only: occupancy.select (mark + compaction, one host
+    sync for n) -> ctx_occ_points -> field.forward_pts on the n points -> ctx_occ_expand.  Every other sample holds the fill
+    (0, 0, 0, -1e30): zero density for the compositing.  n = 0: the field is not called and raw is all fill (no autograd node)."""
+    lib = L.load()
+    R, S = z_vals.shape
+    idx = occupancy.select(ro, rd, z_vals)
+    n = idx.numel()
+    if n == 0:
+        return _occ_expand(None, idx, R * S).view(R, S, 4)
+    pts = torch.empty(n, 3, device=ro.device)
+    L.check(lib.ctx_occ_points(L.ptr(ro), L.ptr(rd), L.ptr(z_vals), R, S, L.ptr(idx), n, L.ptr(pts), L.stream()))
+    raw_c = L.f32c(field.forward_pts(pts))
+    if torch.is_grad_enabled() and raw_c.requires_grad:
+        return _OccExpandFn.apply(raw_c, idx, R * S).view(R, S, 4)
+    return _occ_expand(raw_c, idx, R * S).view(R, S, 4)
+
+
 def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None, perturb=0., raw_noise_std=0.,
-                N_importance=0, pytest=False, generator=None, return_extras=False):
+                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None):
     """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays —
     z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from sample_pdf), pts = o + d*z,
     raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused embed+MLP kernel, then
@@ -376,16 +426,25 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
     N_importance > 0 adds the hierarchical pass: sample_pdf (deterministic when perturb == 0) on the detached coarse weights,
     merged and sorted with the coarse samples and evaluated by the same field; the returned tuple is then the fine one.
     return_extras=True returns (outputs, extras) with extras = dict(z_vals) and, after a hierarchical pass, the coarse
-    rgb0 / disp0 / acc0 / weights0 / depth0 (part of the autograd graph) and z_fine."""
+    rgb0 / disp0 / acc0 / weights0 / depth0 (part of the autograd graph) and z_fine.
+    occupancy (volume_render.OccupancyGrid): the coarse and the hierarchical pass evaluate the field only on the samples inside
+    occupied cells (`field_on_occupied`); every other sample composites as empty space.  A listed sample's point, raw and gradient
+    carry the bits the same rows give in a dense-ordered launch of those n points; one host sync per pass.  With a grid that is
+    all occupied over a box holding every sample the results equal occupancy=None bit for bit."""
     ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
     if z_vals is None:
         t = torch.linspace(0., 1., steps=N_samples, device=ro.device)
         z_vals = (near * (1. - t) + far * t).expand(ro.shape[0], N_samples)
+    elif occupancy is not None and z_vals.requires_grad:
+        raise L.CtxError("render_rays(occupancy=): the sample selection has no gradient with respect to z_vals; detach them")
     if perturb > 0.:
         z_vals = perturb_z_vals(z_vals, pytest, generator)
     z_vals = L.f32c(z_vals)
-    pts = ro[:, None, :] + rd[:, None, :] * z_vals[:, :, None]          # [R,S,3]
-    raw = field.forward_pts(pts)                                         # [R,S,4]
+    if occupancy is None:
+        pts = ro[:, None, :] + rd[:, None, :] * z_vals[:, :, None]          # [R,S,3]
+        raw = field.forward_pts(pts)                                         # [R,S,4]
+    else:
+        raw = field_on_occupied(field, occupancy, ro, rd, z_vals)
     out = raw2outputs(raw, z_vals, rd, raw_noise_std, white_bkgd, pytest, generator)
     extras = {'z_vals': z_vals}
     if N_importance > 0:
@@ -395,6 +454,10 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
         z_all = z_all.contiguous()
         extras = {'z_vals': z_all, 'z_fine': z_fine, 'rgb0': out[0], 'disp0': out[1], 'acc0': out[2], 'weights0': out[3],
                   'depth0': out[4]}
-        pts = ro[:, None, :] + rd[:, None, :] * z_all[:, :, None]
-        out = raw2outputs(field.forward_pts(pts), z_all, rd, raw_noise_std, white_bkgd, pytest, generator)
+        if occupancy is None:
+            pts = ro[:, None, :] + rd[:, None, :] * z_all[:, :, None]
+            raw = field.forward_pts(pts)
+        else:
+            raw = field_on_occupied(field, occupancy, ro, rd, z_all)
+        out = raw2outputs(raw, z_all, rd, raw_noise_std, white_bkgd, pytest, generator)
     return (out, extras) if return_extras else out

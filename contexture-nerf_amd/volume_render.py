@@ -18,6 +18,7 @@ tiles); the refine step is one UNet denoise per image, i.e. replicas only.
 import numpy as np
 import torch
 import torch.distributed as dist
+from . import _lib as L
 from . import run_nerf_helpers as rnh
 
 
@@ -34,15 +35,98 @@ def shard_rows(H, rank, world):
     return r0, r0 + base + (1 if rank < rem else 0)
 
 
+class OccupancyGrid:
+    """Which cells of a G^3 grid over the box lo .. hi hold density: the ray path evaluates the field only on the samples inside
+    occupied cells (render_rays(occupancy=)), the ray-path counterpart of optim.field_texels = 'active'.
+    cells uint8 [G,G,G] (index [cz,cy,cx], 1 = occupied) and dens float32 [G,G,G], the decayed running maximum of the density
+    the field gave in each cell.  lo, hi: a number or three per axis; 1 <= G <= 256.  A new grid is all occupied with dens = 0,
+    so until the first `update` it only clips the samples to the box."""
+
+    def __init__(self, G, lo, hi, device):
+        G = int(G)
+        if not 1 <= G <= 256:
+            raise L.CtxError(f"OccupancyGrid: G={G} outside [1, 256]")
+        lo = np.broadcast_to(np.asarray(lo, np.float32), (3,)).copy()
+        hi = np.broadcast_to(np.asarray(hi, np.float32), (3,)).copy()
+        if not bool(np.all(lo < hi)) or not bool(np.all(np.isfinite(hi - lo))):
+            raise L.CtxError(f"OccupancyGrid: the box needs finite lo < hi on every axis, got lo={lo.tolist()}, hi={hi.tolist()}")
+        self.G, self.lo, self.hi = G, lo, hi
+        ext = hi - lo                                       # binary32, once: the kernels and the restatement take these by value
+        self.inv = np.float32(G) / ext
+        self.h = ext / np.float32(G)
+        self.device = torch.device(device)
+        self.cells = torch.ones(G, G, G, dtype=torch.uint8, device=self.device)
+        self.dens = torch.zeros(G, G, G, dtype=torch.float32, device=self.device)
+
+    @classmethod
+    def from_mask(cls, mask, lo, hi):
+        """A grid with the given occupied cells: mask bool [G,G,G] (index [cz,cy,cx]) on the device the grid lives on."""
+        if not isinstance(mask, torch.Tensor) or mask.dim() != 3 or len(set(mask.shape)) != 1:
+            raise L.CtxError(f"OccupancyGrid.from_mask: want a [G,G,G] tensor, got {tuple(getattr(mask, 'shape', ()))}")
+        grid = cls(mask.shape[0], lo, hi, mask.device)
+        grid.cells = (mask != 0).to(torch.uint8).contiguous()
+        return grid
+
+    def select(self, rays_o, rays_d, z_vals):
+        """-> idx int32 [n], ascending: the samples r*S + s of z_vals [R,S] whose point rays_o + rays_d * z lies in an occupied
+        cell (`ctx_occ_mark`, then the ordered compaction `ctx_texel_compact`).  R*S < 2^31.  Reading n back SYNCS the host: one
+        sync per pass of render_rays."""
+        if isinstance(z_vals, torch.Tensor) and z_vals.requires_grad:
+            raise L.CtxError("OccupancyGrid.select: the selection has no gradient with respect to z_vals; detach them")
+        p_o, p_d = L.ptr(rays_o, torch.float32, "rays_o"), L.ptr(rays_d, torch.float32, "rays_d")
+        p_z = L.ptr(z_vals, torch.float32, "z_vals")
+        if z_vals.dim() != 2 or rays_o.numel() != 3 * z_vals.shape[0] or rays_d.numel() != 3 * z_vals.shape[0]:
+            raise L.CtxError(f"OccupancyGrid.select: want rays_o, rays_d [R,3] and z_vals [R,S]; got {tuple(rays_o.shape)}, "
+                             f"{tuple(rays_d.shape)}, {tuple(z_vals.shape)}")
+        lib = L.load()
+        R, S = z_vals.shape
+        dev = z_vals.device
+        n_ws = lib.ctx_texel_compact_ws_bytes(R * S)
+        if n_ws < 0:
+            raise L.CtxError(f"OccupancyGrid.select: {R} rays x {S} samples: want 1 <= R*S < 2^31 (int32 sample indices); split the batch")
+        mask = torch.empty(R * S, dtype=torch.uint8, device=dev)
+        L.check(lib.ctx_occ_mark(p_o, p_d, p_z, R, S, L.ptr(self.cells, torch.uint8, "cells"), self.G, *map(float, self.lo),
+                                 *map(float, self.inv), L.ptr(mask), L.stream()))
+        ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+        idx = torch.empty(R * S, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        L.check(lib.ctx_texel_compact(L.ptr(mask), R * S, L.ptr(idx), L.ptr(count), L.ptr(ws), L.stream()))
+        return idx[:int(count.item())].clone()
+
+    def cell_points(self, generator=None):
+        """-> pts [G^3,3]: per cell lo + (c + u) * h with u = 0.5 (the centre) or, with a generator, one uniform draw per axis."""
+        lib = L.load()
+        n = self.G ** 3
+        u = torch.rand(n, 3, device=self.cells.device, generator=generator) if generator is not None else None
+        pts = torch.empty(n, 3, device=self.cells.device)
+        L.ptr(self.cells, torch.uint8, "cells")
+        L.check(lib.ctx_occ_cell_points(self.G, *map(float, self.lo), *map(float, self.h), L.ptr(u), L.ptr(pts), L.stream()))
+        return pts
+
+    @torch.no_grad()
+    def update(self, field, thresh, decay=0.95, generator=None):
+        """Refresh from the field: one point per cell (jittered inside it when a generator is given), field.forward_pts without
+        gradients, then dens = max(dens * decay, relu(sigma)) and cells = dens > thresh (`ctx_occ_update`)."""
+        lib = L.load()
+        raw = L.f32c(field.forward_pts(self.cell_points(generator)))
+        L.check(lib.ctx_occ_update(L.ptr(raw, torch.float32, "raw"), L.ptr(self.dens, torch.float32, "dens"),
+                                   L.ptr(self.cells, torch.uint8, "cells"), self.G ** 3, float(decay), float(thresh), L.stream()))
+
+    def fraction(self):
+        """The share of occupied cells, a host float (syncs)."""
+        return float(self.cells.count_nonzero().item()) / self.G ** 3
+
+
 @torch.no_grad()
-def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0):
+def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None):
     """-> dict(rgb [h,W,3], depth [h,W], acc [h,W], disp [h,W]) for the row range `rows` (default: all).
     N_importance > 0 adds nerf-pytorch's hierarchical pass (render_rays: sample_pdf(det=True) on the coarse weights, merged
-    and sorted with the coarse samples, evaluated by the same field)."""
+    and sorted with the coarse samples, evaluated by the same field).  occupancy: an OccupancyGrid, see render_rays."""
     ro, rd = rnh.get_rays(H, W, K, c2w)
     r0, r1 = (0, H) if rows is None else rows
     ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
-    rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance)
+    rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance,
+                                                 occupancy=occupancy)
     h = r1 - r0
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
@@ -78,10 +162,11 @@ def depth_for_diffusion(depth, acc, thresh=0.5):
 
 @torch.no_grad()
 def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples=128, guidance_scale=7.5, strength=1.0,
-                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None):
-    """configs[4] end to end on this rank's rows; every rank returns the refined image [1,3,S,S] and the gathered render."""
+                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None):
+    """configs[4] end to end on this rank's rows; every rank returns the refined image [1,3,S,S] and the gathered render.
+    occupancy: an OccupancyGrid for the render (render_rays)."""
     K = pinhole(H, W)
-    tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world))
+    tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world), occupancy=occupancy)
     rgb = gather_rows(tile['rgb'], H, group)
     depth = gather_rows(tile['depth'], H, group)
     acc = gather_rows(tile['acc'], H, group)
@@ -95,31 +180,40 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None):
+               white_bkgd=False, generator=None, occupancy=None):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
-    rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync."""
+    rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
+    occupancy: an OccupancyGrid (render_rays): the field runs, and keeps activations, on the occupied samples only, at one
+    host sync per pass.  A batch in which no pass has an occupied sample has a loss without a graph: backward and the
+    optimizer step are skipped and loss / psnr are still returned."""
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
-                                  return_extras=True)
+                                  return_extras=True, occupancy=occupancy)
     target = target_rgb.reshape(-1, 3)
     img_loss = rnh.img2mse(out[0], target)
     loss = img_loss
     if 'rgb0' in extras:
         loss = loss + rnh.img2mse(extras['rgb0'], target)
-    loss.backward()
-    optimizer.step()
+    if occupancy is None or loss.requires_grad:
+        loss.backward()
+        optimizer.step()
     return {'loss': loss.detach(), 'psnr': rnh.mse2psnr(img_loss.detach()).reshape(())}
 
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
-              perturb=1., raw_noise_std=0., white_bkgd=False):
+              perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
+              occupancy_thresh=0.01):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
     The views can be renders of a painted mesh: TexturedMeshModel.render on a white background (pass white_bkgd=True then)
-    with the camera-to-world matrices of the same poses."""
+    with the camera-to-world matrices of the same poses.
+    occupancy: an OccupancyGrid handed to every train_step.  It stays as given for the first occupancy_warmup iterations; from
+    then on occupancy.update(field, occupancy_thresh) runs before iterations occupancy_warmup, occupancy_warmup + occupancy_every,
+    ...  The jitter of the cell points comes from the same generator, so a run still repeats exactly.  occupancy_thresh is a
+    density (the default 0.01 is instant-ngp's minimum optical thickness per unit length)."""
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -130,9 +224,12 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     gen = torch.Generator(device=dev).manual_seed(seed)
     opt = torch.optim.Adam(field.parameters(), lr=lr)
     hist = []
-    for _ in range(iters):
+    for it in range(iters):
+        if occupancy is not None and it >= occupancy_warmup and (it - occupancy_warmup) % occupancy_every == 0:
+            occupancy.update(field, occupancy_thresh, generator=gen)
         idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
         step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
-                          perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen)
+                          perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
+                          occupancy=occupancy)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()

@@ -280,6 +280,34 @@ int32_t ctx_raymarch_composite_bwd(const float *raw, const float *z_vals, const 
                                    const float *g_rgb, const float *g_disp, const float *g_acc, const float *g_weights,
                                    const float *g_depth, float *grad_raw, ctx_stream_t stream);
 
+/* ---- occupancy grid of the ray path: evaluate the field only on the samples that lie in occupied cells ---- */
+/* The grid: cells uint8 [G,G,G] (flat index (cz*G + cy)*G + cx, 1 = occupied) and dens float32 [G,G,G] over the box lo .. hi,
+   1 <= G <= 256.  The host computes inv = G / (hi - lo) and h = (hi - lo) / G once per axis in binary32 and passes them by value.
+   All arithmetic below is binary32 in the order written (no contraction).
+   ctx_occ_mark: for every sample of z_vals [R,S]: p = o + d*z (one product, one sum per axis: the bits of the torch expression
+   rays_o + rays_d * z), t = (p - lo)*inv; the sample is inside when t >= 0 && t < G on the three axes (false for NaN); then
+   mask = cells[(int)t], else 0.  Every byte of mask [R*S] is written.  1 <= R*S < 2^31 (the rule of ctx_texel_compact, which turns the
+   mask into the ascending list idx). */
+int32_t ctx_occ_mark(const float *rays_o, const float *rays_d, const float *z_vals, int64_t R, int32_t S, const uint8_t *cells,
+                     int32_t G, float lo_x, float lo_y, float lo_z, float inv_x, float inv_y, float inv_z, uint8_t *mask,
+                     ctx_stream_t stream);
+/* pts [n,3]: row k = o + d*z of sample idx[k] (ray idx[k] / S), the same expression.  1 <= n <= R*S. */
+int32_t ctx_occ_points(const float *rays_o, const float *rays_d, const float *z_vals, int64_t R, int32_t S, const int32_t *idx,
+                       int64_t n, float *pts, ctx_stream_t stream);
+/* raw [total,4]: row idx[k] = raw_c[k], every other row the fill (0, 0, 0, -1e30f): zero density after the compositing's ReLU, with
+   density noise too, and finite.  n = 0 is legal (all fill; raw_c and idx may be null).  Two launches: the fill, then the listed rows. */
+int32_t ctx_occ_expand(const float *raw_c, const int32_t *idx, int64_t n, int64_t total, float *raw, ctx_stream_t stream);
+/* Backward of ctx_occ_expand: grad_c [n,4], row k = grad[idx[k]].  n >= 1.
+   In these three list kernels an idx entry outside [0, total) is skipped: nothing is read or stored through it (ctx_occ_points and
+   ctx_occ_expand leave its row alone, ctx_occ_collect writes zeros to it). */
+int32_t ctx_occ_collect(const float *grad, const int32_t *idx, int64_t n, int64_t total, float *grad_c, ctx_stream_t stream);
+/* pts [G^3,3]: the point of cell c the field is asked at, per axis lo + ((float)c_axis + u)*h with u [G^3,3] in [0,1) (nullable: 0.5). */
+int32_t ctx_occ_cell_points(int32_t G, float lo_x, float lo_y, float lo_z, float h_x, float h_y, float h_z,
+                            const float *u /*nullable*/, float *pts, ctx_stream_t stream);
+/* The refresh from raw [n,4] = the field on those points (n = G^3): sigma = raw.w > 0 ? raw.w : 0, dens = fmaxf(dens*decay, sigma),
+   cells = dens > thresh (equality is not occupied).  A NaN raw.w leaves sigma 0 and marks the cell occupied. */
+int32_t ctx_occ_update(const float *raw, float *dens, uint8_t *cells, int64_t n, float decay, float thresh, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
