@@ -71,6 +71,10 @@ SIGNATURES = {
     "ctx_occ_collect": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "ctx_occ_cell_points": (_i32, [_i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "ctx_occ_update": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp]),
+    "ctx_occ_voxelize": (_i32, [_vp, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
+    "ctx_occ_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_occ_ray_spans": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                 _vp, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),
     "ctx_unet_param_count": (_i32, [_vp]),

@@ -1,0 +1,226 @@
+// Occupancy grid from the mesh, and what a ray needs of it: the conservative triangle-to-cell voxeliser (voxelize), the cube dilation of
+// the byte grid (dilate), and per ray the span between its first and its last occupied cell (ray_spans).
+// Built with -ffp-contract=off: every product, sum and quotient below rounds on its own, in the order written, so the numpy
+// restatements (tests/test_occupancy_mesh_cpu.py) give the same bits; they are the definition, this file follows them line by line.
+// No atomics.  The voxeliser only ever stores the byte 1 (as k_texel_mark / k_vc_seen do): racing stores write the same value, the
+// caller zeroes the grid, several calls accumulate a union.  Every other output element has one writer.
+#include "common.h"
+#include <math.h>
+
+#define OCM_BLK 256
+#define OCM_CAP 2048          // blocks of a grid-stride launch: 8 per CU
+
+#define OCM_E 0.0078125f      // 2^-7 of a cell: the inflation of the cell's box on every side
+#define OCM_DELTA 1.015625f   // 1 + 2e, the side of the inflated box
+
+struct ocm3 { float x, y, z; };
+
+__device__ __forceinline__ bool ocm_finite(float x) { return fabsf(x) < INFINITY; }          // false for NaN
+
+// ---- voxeliser: one wave per triangle, the lanes stride over the candidate cells of its bounding box, x fastest --------------------
+// The triangle index is wave-uniform, so the vertex loads are scalar loads and the set-up (normal, plane terms, nine edge terms) is done
+// once per wave, outside the cell loop (gfx950 has no scalar float arithmetic: the values are uniform, in vector registers);
+// per cell a lane evaluates the plane pair and nine edge functions of Schwarz and Seidel's conservative test on the inflated box.
+__global__ __launch_bounds__(OCM_BLK) void k_occ_voxelize(const float *__restrict__ vtx, const int64_t *__restrict__ faces, int64_t V, int64_t F, int G,
+                                                          ocm3 lo, ocm3 inv, uint8_t *__restrict__ cells)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * OCM_BLK + threadIdx.x) >> 6));
+    const int64_t nwaves = ((int64_t)gridDim.x * OCM_BLK) >> 6;
+    const float Gm1 = (float)(G - 1);
+    for (int64_t f = wave0; f < F; f += nwaves) {
+        const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) continue;
+        float g[3][3];                                                // g[vertex][axis], grid coordinates: the expression of ctx_occ_mark
+        const int64_t iv[3] = {i0, i1, i2};
+        bool fin = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            g[k][0] = (vtx[iv[k] * 3 + 0] - lo.x) * inv.x;
+            g[k][1] = (vtx[iv[k] * 3 + 1] - lo.y) * inv.y;
+            g[k][2] = (vtx[iv[k] * 3 + 2] - lo.z) * inv.z;
+            fin = fin && ocm_finite(g[k][0]) && ocm_finite(g[k][1]) && ocm_finite(g[k][2]);
+        }
+        if (!fin) continue;
+        int c0[3], cn[3];                                             // first candidate and count per axis
+        bool empty = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float mn = fminf(fminf(g[0][a], g[1][a]), g[2][a]), mx = fmaxf(fmaxf(g[0][a], g[1][a]), g[2][a]);
+            const float fa = floorf(mn - OCM_E), fb = floorf(mx + OCM_E);
+            empty = empty || fb < 0.f || fa > Gm1;
+            c0[a] = (int)fmaxf(fa, 0.f);                              // in [0, G - 1] unless empty (then unused)
+            cn[a] = (int)fminf(fb, Gm1) - c0[a] + 1;
+        }
+        if (empty) continue;
+        const int total = cn[0] * cn[1] * cn[2];                      // <= 256^3
+
+        float ea[3], eb[3], e1[3], e2[3], n[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            ea[a] = g[1][a] - g[0][a]; eb[a] = g[2][a] - g[0][a];
+            e1[a] = g[2][a] - g[1][a]; e2[a] = g[0][a] - g[2][a];
+        }
+        n[0] = ea[1] * eb[2] - ea[2] * eb[1];
+        n[1] = ea[2] * eb[0] - ea[0] * eb[2];
+        n[2] = ea[0] * eb[1] - ea[1] * eb[0];
+        const bool degenerate = n[0] == 0.f && n[1] == 0.f && n[2] == 0.f;
+        float crit[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) crit[a] = n[a] > 0.f ? OCM_DELTA : 0.f;
+        const float d1 = (n[0] * (crit[0] - g[0][0]) + n[1] * (crit[1] - g[0][1])) + n[2] * (crit[2] - g[0][2]);
+        const float d2 = (n[0] * ((OCM_DELTA - crit[0]) - g[0][0]) + n[1] * ((OCM_DELTA - crit[1]) - g[0][1])) + n[2] * ((OCM_DELTA - crit[2]) - g[0][2]);
+        float neu[9], nev[9], de[9];                                  // [plane * 3 + edge]; planes xy, yz, zx
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            const int u = pl, v = (pl + 1) % 3, w = (pl + 2) % 3;
+#pragma unroll
+            for (int ed = 0; ed < 3; ++ed) {
+                const float eu = ed == 0 ? ea[u] : ed == 1 ? e1[u] : e2[u];
+                const float ev = ed == 0 ? ea[v] : ed == 1 ? e1[v] : e2[v];
+                const float a_u = n[w] >= 0.f ? -ev : ev, a_v = n[w] >= 0.f ? eu : -eu;
+                neu[pl * 3 + ed] = a_u; nev[pl * 3 + ed] = a_v;
+                de[pl * 3 + ed] = (-(a_u * g[ed][u] + a_v * g[ed][v]) + fmaxf(0.f, OCM_DELTA * a_u)) + fmaxf(0.f, OCM_DELTA * a_v);
+            }
+        }
+
+        for (int i = lane; i < total; i += 64) {
+            const int ix = i % cn[0], t = i / cn[0];
+            const int cx = c0[0] + ix, cy = c0[1] + t % cn[1], cz = c0[2] + t / cn[1];
+            bool ok = true;
+            if (!degenerate) {
+                const float p[3] = {(float)cx - OCM_E, (float)cy - OCM_E, (float)cz - OCM_E};
+                const float npd = (n[0] * p[0] + n[1] * p[1]) + n[2] * p[2];
+                const float s1 = npd + d1, s2 = npd + d2;
+                ok = (s1 <= 0.f && s2 >= 0.f) || (s1 >= 0.f && s2 <= 0.f);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    const int u = pl, v = (pl + 1) % 3;
+#pragma unroll
+                    for (int ed = 0; ed < 3; ++ed)
+                        ok = ok && ((neu[pl * 3 + ed] * p[u] + nev[pl * 3 + ed] * p[v]) + de[pl * 3 + ed]) >= 0.f;
+                }
+            }
+            if (ok) cells[((int64_t)cz * G + cy) * G + cx] = 1;       // 0 <= c < G on the three axes by the clamps above
+        }
+    }
+}
+
+extern "C" int32_t ctx_occ_voxelize(const float *vertices, const int64_t *faces, int64_t V, int64_t F, int32_t G, float lo_x, float lo_y, float lo_z,
+                                    float inv_x, float inv_y, float inv_z, uint8_t *cells, ctx_stream_t stream)
+{
+    CTX_REQUIRE(vertices && faces && cells, "occ_voxelize: null pointer");
+    CTX_REQUIRE(G >= 1 && G <= 256, "occ_voxelize: G=%d outside [1, 256]", (int)G);
+    CTX_REQUIRE(V >= 1 && F >= 1, "occ_voxelize: V=%lld, F=%lld: want at least one vertex and one face", (long long)V, (long long)F);
+    CTX_REQUIRE(V <= INT32_MAX && F <= INT32_MAX, "occ_voxelize: V=%lld, F=%lld: want both below 2^31", (long long)V, (long long)F);
+    const ocm3 lo = {lo_x, lo_y, lo_z}, inv = {inv_x, inv_y, inv_z};
+    hipLaunchKernelGGL(k_occ_voxelize, dim3(capped_blocks(F, OCM_BLK / 64, OCM_CAP)), dim3(OCM_BLK), 0, (hipStream_t)stream, vertices, faces, V, F,
+                       (int)G, lo, inv, cells);
+    CTX_CHECK_LAUNCH("occ_voxelize");
+    return CTX_OK;
+}
+
+// ---- dilation: one pass per axis, dst[c] = any of src within +-k along that axis (clamped to the grid) -------------------------------
+__global__ __launch_bounds__(OCM_BLK) void k_occ_dilate_axis(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int G, int k, int64_t stride,
+                                                             int64_t n)
+{
+    for (int64_t c = (int64_t)blockIdx.x * OCM_BLK + threadIdx.x; c < n; c += (int64_t)gridDim.x * OCM_BLK) {
+        const int a = (int)((c / stride) % G);
+        const int j0 = a - k > 0 ? a - k : 0, j1 = a + k < G - 1 ? a + k : G - 1;
+        uint8_t any = 0;
+        for (int j = j0; j <= j1; ++j) any |= src[c + (int64_t)(j - a) * stride];          // same line and column: inside [0, n)
+        dst[c] = any ? 1 : 0;
+    }
+}
+
+extern "C" int32_t ctx_occ_dilate(const uint8_t *src, int32_t G, int32_t k, uint8_t *dst, uint8_t *ws, ctx_stream_t stream)
+{
+    CTX_REQUIRE(src && dst, "occ_dilate: null pointer");
+    CTX_REQUIRE(G >= 1 && G <= 256, "occ_dilate: G=%d outside [1, 256]", (int)G);
+    CTX_REQUIRE(k >= 0, "occ_dilate: k=%d: want k >= 0", (int)k);
+    if (k > G) k = G;                                                 // the grid has G cells per axis: a wider cube reaches no further
+    CTX_REQUIRE(src != dst, "occ_dilate: dst must not be src");
+    CTX_REQUIRE(k == 0 || (ws && ws != src && ws != dst), "occ_dilate: k=%d needs a workspace of G^3 bytes that is neither src nor dst", (int)k);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)G * G * G;
+    const dim3 grid(capped_blocks(n, OCM_BLK, OCM_CAP)), blk(OCM_BLK);
+    if (k == 0) {
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, blk, 0, s, src, dst, (int)G, 0, (int64_t)1, n);              // the copy (non-zero -> 1)
+    } else {
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, blk, 0, s, src, dst, (int)G, (int)k, (int64_t)1, n);         // x
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, blk, 0, s, (const uint8_t *)dst, ws, (int)G, (int)k, (int64_t)G, n);          // y
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, blk, 0, s, (const uint8_t *)ws, dst, (int)G, (int)k, (int64_t)G * G, n);      // z
+    }
+    CTX_CHECK_LAUNCH("occ_dilate");
+    return CTX_OK;
+}
+
+// ---- spans: one lane per ray, a cell walk whose exit parameters come from the integer cell index at every step (no drift) --------------
+__global__ __launch_bounds__(OCM_BLK) void k_occ_ray_spans(const float *__restrict__ ro, const float *__restrict__ rd, int64_t R, float near, float far,
+                                                           const uint8_t *__restrict__ cells, int G, ocm3 lo, ocm3 hi, ocm3 inv, ocm3 h,
+                                                           float2 *__restrict__ span, uint8_t *__restrict__ hit)
+{
+    const float Gm1 = (float)(G - 1);
+    const int max_cells = 3 * G + 3;
+    for (int64_t r = (int64_t)blockIdx.x * OCM_BLK + threadIdx.x; r < R; r += (int64_t)gridDim.x * OCM_BLK) {
+        const float ox = ro[r * 3 + 0], oy = ro[r * 3 + 1], oz = ro[r * 3 + 2];
+        const float dx = rd[r * 3 + 0], dy = rd[r * 3 + 1], dz = rd[r * 3 + 2];
+        bool ok = ocm_finite(ox) && ocm_finite(oy) && ocm_finite(oz) && ocm_finite(dx) && ocm_finite(dy) && ocm_finite(dz);
+        float ta = near, tb = far;
+        if (ok) {                                                     // slab clip; a zero component compares the origin with its slab
+            if (dx == 0.f) ok = ok && ox >= lo.x && ox <= hi.x;
+            else { const float t1 = (lo.x - ox) / dx, t2 = (hi.x - ox) / dx; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
+            if (dy == 0.f) ok = ok && oy >= lo.y && oy <= hi.y;
+            else { const float t1 = (lo.y - oy) / dy, t2 = (hi.y - oy) / dy; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
+            if (dz == 0.f) ok = ok && oz >= lo.z && oz <= hi.z;
+            else { const float t1 = (lo.z - oz) / dz, t2 = (hi.z - oz) / dz; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
+            ok = ok && ta <= tb;
+        }
+        float s0 = near, s1 = far;
+        bool found = false;
+        if (ok) {
+            int cx = (int)fminf(fmaxf(((ox + dx * ta) - lo.x) * inv.x, 0.f), Gm1);
+            int cy = (int)fminf(fmaxf(((oy + dy * ta) - lo.y) * inv.y, 0.f), Gm1);
+            int cz = (int)fminf(fmaxf(((oz + dz * ta) - lo.z) * inv.z, 0.f), Gm1);
+            float tin = ta;
+            for (int step = 0; step < max_cells; ++step) {
+                const float ex = dx == 0.f ? INFINITY : ((lo.x + (float)(cx + (dx > 0.f ? 1 : 0)) * h.x) - ox) / dx;
+                const float ey = dy == 0.f ? INFINITY : ((lo.y + (float)(cy + (dy > 0.f ? 1 : 0)) * h.y) - oy) / dy;
+                const float ez = dz == 0.f ? INFINITY : ((lo.z + (float)(cz + (dz > 0.f ? 1 : 0)) * h.z) - oz) / dz;
+                int ax = 0;
+                float te = ex;
+                if (ey < te) { ax = 1; te = ey; }
+                if (ez < te) { ax = 2; te = ez; }
+                const float tout = fminf(fmaxf(te, tin), tb);
+                if (cells[((int64_t)cz * G + cy) * G + cx]) {         // 0 <= c < G: clamped at the start, checked at every step
+                    if (!found) { s0 = tin; found = true; }
+                    s1 = tout;
+                }
+                if (te >= tb) break;
+                if (ax == 0) { cx += dx > 0.f ? 1 : -1; if (cx < 0 || cx > G - 1) break; }
+                else if (ax == 1) { cy += dy > 0.f ? 1 : -1; if (cy < 0 || cy > G - 1) break; }
+                else { cz += dz > 0.f ? 1 : -1; if (cz < 0 || cz > G - 1) break; }
+                tin = tout;
+            }
+        }
+        span[r] = make_float2(s0, s1);
+        hit[r] = found ? 1 : 0;
+    }
+}
+
+extern "C" int32_t ctx_occ_ray_spans(const float *rays_o, const float *rays_d, int64_t R, float near, float far, const uint8_t *cells, int32_t G,
+                                     float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
+                                     float h_x, float h_y, float h_z, float *span, uint8_t *hit, ctx_stream_t stream)
+{
+    CTX_REQUIRE(rays_o && rays_d && cells && span && hit, "occ_ray_spans: null pointer");
+    CTX_REQUIRE(G >= 1 && G <= 256, "occ_ray_spans: G=%d outside [1, 256]", (int)G);
+    CTX_REQUIRE(R >= 1 && R <= INT32_MAX, "occ_ray_spans: R=%lld outside [1, 2^31)", (long long)R);
+    CTX_REQUIRE(near < far && fabsf(near) < INFINITY && fabsf(far) < INFINITY, "occ_ray_spans: want finite near < far, got %g, %g", (double)near,
+                (double)far);
+    CTX_REQUIRE(((uintptr_t)span % 8) == 0, "occ_ray_spans: span must be 8-byte aligned");
+    const ocm3 lo = {lo_x, lo_y, lo_z}, hi = {hi_x, hi_y, hi_z}, inv = {inv_x, inv_y, inv_z}, h = {h_x, h_y, h_z};
+    hipLaunchKernelGGL(k_occ_ray_spans, dim3(capped_blocks(R, OCM_BLK, OCM_CAP)), dim3(OCM_BLK), 0, (hipStream_t)stream, rays_o, rays_d, R, near, far,
+                       cells, (int)G, lo, hi, inv, h, (float2 *)span, hit);
+    CTX_CHECK_LAUNCH("occ_ray_spans");
+    return CTX_OK;
+}

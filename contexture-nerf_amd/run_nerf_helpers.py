@@ -417,7 +417,7 @@ def field_on_occupied(field, occupancy, ro, rd, z_vals):
 
 
 def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None, perturb=0., raw_noise_std=0.,
-                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None):
+                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None, clip=False):
     """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays —
     z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from sample_pdf), pts = o + d*z,
     raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused embed+MLP kernel, then
@@ -430,9 +430,21 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
     occupancy (volume_render.OccupancyGrid): the coarse and the hierarchical pass evaluate the field only on the samples inside
     occupied cells (`field_on_occupied`); every other sample composites as empty space.  A listed sample's point, raw and gradient
     carry the bits the same rows give in a dense-ordered launch of those n points; one host sync per pass.  With a grid that is
-    all occupied over a box holding every sample the results equal occupancy=None bit for bit."""
+    all occupied over a box holding every sample the results equal occupancy=None bit for bit.
+    clip=True (needs occupancy, and no z_vals of the caller's): every ray spreads its N_samples over its own span, from where it enters
+    its first to where it leaves its last occupied cell (occupancy.ray_spans): z_vals = t0*(1-t) + t1*t with the same linspace t.  The
+    jitter, the hierarchical pass and the compositing then run on those z_vals as they do on any.  A ray that meets no occupied cell
+    keeps near .. far, where the selection finds nothing for it.  No further host sync."""
+    if clip and occupancy is None:
+        raise L.CtxError("render_rays: clip=True needs an occupancy grid (occupancy=): the spans are those of its occupied cells")
+    if clip and z_vals is not None:
+        raise L.CtxError("render_rays: clip=True places the samples itself; it cannot be combined with given z_vals")
     ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
-    if z_vals is None:
+    if clip:
+        span, _ = occupancy.ray_spans(ro, rd, near, far)
+        t = torch.linspace(0., 1., steps=N_samples, device=ro.device)
+        z_vals = span[:, :1] * (1. - t) + span[:, 1:] * t
+    elif z_vals is None:
         t = torch.linspace(0., 1., steps=N_samples, device=ro.device)
         z_vals = (near * (1. - t) + far * t).expand(ro.shape[0], N_samples)
     elif occupancy is not None and z_vals.requires_grad:

@@ -35,6 +35,22 @@ def shard_rows(H, rank, world):
     return r0, r0 + base + (1 if rank < rem else 0)
 
 
+def _check_mesh(vertices, faces, dilate, who):
+    """Shapes, dtypes and counts of a mesh handed to the voxeliser, looked at before any pointer is taken."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise L.CtxError(f"{who}: want vertices float32 [V,3], got {getattr(vertices, 'dtype', type(vertices).__name__)} "
+                         f"{tuple(getattr(vertices, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise L.CtxError(f"{who}: want faces int64 [F,3] (the dtype Mesh.faces has), got {getattr(faces, 'dtype', type(faces).__name__)} "
+                         f"{tuple(getattr(faces, 'shape', ()))}")
+    if vertices.shape[0] == 0:
+        raise L.CtxError(f"{who}: the mesh has no vertex")
+    if faces.shape[0] == 0:
+        raise L.CtxError(f"{who}: the mesh has no face (F = 0): nothing to voxelise")
+    if int(dilate) != dilate or dilate < 0:
+        raise L.CtxError(f"{who}: dilate={dilate}: want a whole number of cells >= 0")
+
+
 class OccupancyGrid:
     """Which cells of a G^3 grid over the box lo .. hi hold density: the ray path evaluates the field only on the samples inside
     occupied cells (render_rays(occupancy=)), the ray-path counterpart of optim.field_texels = 'active'.
@@ -66,6 +82,67 @@ class OccupancyGrid:
         grid = cls(mask.shape[0], lo, hi, mask.device)
         grid.cells = (mask != 0).to(torch.uint8).contiguous()
         return grid
+
+    @classmethod
+    def from_mesh(cls, vertices, faces, G, lo, hi, dilate=1):
+        """A grid whose occupied cells are the mesh's surface: every cell a triangle touches (`ctx_occ_voxelize`, conservative: no
+        touched cell is missed), grown by `dilate` cells on every side (`ctx_occ_dilate`); dens = 0.  vertices float32 [V,3] and faces
+        int64 [F,3] (the dtype Mesh.faces has) are device tensors; the grid lives on their device.
+        The vertices are taken as given: they must be in the world frame of the rays.  For a TexturedMeshModel that is
+        model.mesh.vertices after its normalisation, together with the c2w of the renderer's poses.
+        A trained field blurs the surface over a cell or two, hence dilate=1 by default.  Such a grid is meant to stay as it is:
+        fit_views(occupancy_every=0) never refreshes it from the student's density."""
+        _check_mesh(vertices, faces, dilate, "OccupancyGrid.from_mesh")
+        grid = cls(G, lo, hi, vertices.device)
+        grid.cells.zero_()
+        grid.voxelize(vertices, faces, dilate=dilate)
+        return grid
+
+    def voxelize(self, vertices, faces, dilate=0):
+        """Adds a mesh to this grid: the union of what is occupied with the cells the triangles touch, those grown by `dilate` cells.
+        vertices float32 [V,3], faces int64 [F,3], device tensors in the world frame of the rays (from_mesh).  A face with an index
+        outside [0, V) or a non-finite vertex marks nothing.  After `update`, this gives mesh + learned density."""
+        _check_mesh(vertices, faces, dilate, "OccupancyGrid.voxelize")
+        p_v, p_f = L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces")
+        L.ptr(self.cells, torch.uint8, "cells")
+        lib = L.load()
+        target = self.cells if dilate == 0 else torch.zeros_like(self.cells)       # grown alone, then united: what is there does not grow
+        L.check(lib.ctx_occ_voxelize(p_v, p_f, vertices.shape[0], faces.shape[0], self.G, *map(float, self.lo), *map(float, self.inv),
+                                     L.ptr(target), L.stream()))
+        if dilate > 0:
+            grown, ws = torch.empty_like(target), torch.empty_like(target)
+            L.check(lib.ctx_occ_dilate(L.ptr(target), self.G, min(int(dilate), self.G), L.ptr(grown), L.ptr(ws), L.stream()))
+            self.cells |= grown
+
+    def dilate(self, k):
+        """Grows the occupied cells by k cells on every side (a cube: a cell is occupied when one within k on the three axes was)."""
+        k = int(k)
+        if k < 0:
+            raise L.CtxError(f"OccupancyGrid.dilate: k={k}: want k >= 0")
+        p_c = L.ptr(self.cells, torch.uint8, "cells")
+        out, ws = torch.empty_like(self.cells), torch.empty_like(self.cells)
+        L.check(L.load().ctx_occ_dilate(p_c, self.G, min(k, self.G), L.ptr(out), L.ptr(ws), L.stream()))
+        self.cells = out
+
+    def ray_spans(self, rays_o, rays_d, near, far):
+        """-> (span float32 [R,2], hit bool [R]): per ray the parameters at which it enters its first and leaves its last occupied
+        cell within [near, far] clipped to the box (`ctx_occ_ray_spans`); (near, far) and hit = False for a ray that meets none.
+        rays_o, rays_d: float32 [R,3] device tensors.  No host sync."""
+        near, far = float(near), float(far)
+        if not (near < far and np.isfinite(near) and np.isfinite(far)):
+            raise L.CtxError(f"OccupancyGrid.ray_spans: want finite near < far, got {near}, {far}")
+        if not (isinstance(rays_o, torch.Tensor) and isinstance(rays_d, torch.Tensor) and rays_o.dim() == 2 and rays_o.shape[1] == 3
+                and rays_o.shape[0] >= 1 and rays_d.shape == rays_o.shape):
+            raise L.CtxError(f"OccupancyGrid.ray_spans: want rays_o, rays_d [R,3] with R >= 1; got {tuple(getattr(rays_o, 'shape', ()))}, "
+                             f"{tuple(getattr(rays_d, 'shape', ()))}")
+        p_o, p_d = L.ptr(rays_o, torch.float32, "rays_o"), L.ptr(rays_d, torch.float32, "rays_d")
+        R = rays_o.shape[0]
+        span = torch.empty(R, 2, dtype=torch.float32, device=rays_o.device)
+        hit = torch.empty(R, dtype=torch.uint8, device=rays_o.device)
+        L.check(L.load().ctx_occ_ray_spans(p_o, p_d, R, near, far, L.ptr(self.cells, torch.uint8, "cells"), self.G, *map(float, self.lo),
+                                           *map(float, self.hi), *map(float, self.inv), *map(float, self.h), L.ptr(span), L.ptr(hit),
+                                           L.stream()))
+        return span, hit != 0
 
     def select(self, rays_o, rays_d, z_vals):
         """-> idx int32 [n], ascending: the samples r*S + s of z_vals [R,S] whose point rays_o + rays_d * z lies in an occupied
@@ -118,15 +195,16 @@ class OccupancyGrid:
 
 
 @torch.no_grad()
-def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None):
+def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None, clip=False):
     """-> dict(rgb [h,W,3], depth [h,W], acc [h,W], disp [h,W]) for the row range `rows` (default: all).
     N_importance > 0 adds nerf-pytorch's hierarchical pass (render_rays: sample_pdf(det=True) on the coarse weights, merged
-    and sorted with the coarse samples, evaluated by the same field).  occupancy: an OccupancyGrid, see render_rays."""
+    and sorted with the coarse samples, evaluated by the same field).  occupancy: an OccupancyGrid; clip: samples between each
+    ray's first and last occupied cell; see render_rays."""
     ro, rd = rnh.get_rays(H, W, K, c2w)
     r0, r1 = (0, H) if rows is None else rows
     ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
     rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance,
-                                                 occupancy=occupancy)
+                                                 occupancy=occupancy, clip=clip)
     h = r1 - r0
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
@@ -162,11 +240,12 @@ def depth_for_diffusion(depth, acc, thresh=0.5):
 
 @torch.no_grad()
 def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples=128, guidance_scale=7.5, strength=1.0,
-                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None):
+                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None, clip=False):
     """configs[4] end to end on this rank's rows; every rank returns the refined image [1,3,S,S] and the gathered render.
-    occupancy: an OccupancyGrid for the render (render_rays)."""
+    occupancy, clip: an OccupancyGrid for the render and whether the samples are placed inside its spans (render_rays)."""
     K = pinhole(H, W)
-    tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world), occupancy=occupancy)
+    tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world), occupancy=occupancy,
+                        clip=clip)
     rgb = gather_rows(tile['rgb'], H, group)
     depth = gather_rows(tile['depth'], H, group)
     acc = gather_rows(tile['acc'], H, group)
@@ -180,17 +259,18 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None):
+               white_bkgd=False, generator=None, occupancy=None, clip=False):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
     occupancy: an OccupancyGrid (render_rays): the field runs, and keeps activations, on the occupied samples only, at one
     host sync per pass.  A batch in which no pass has an occupied sample has a loss without a graph: backward and the
-    optimizer step are skipped and loss / psnr are still returned."""
+    optimizer step are skipped and loss / psnr are still returned.  clip=True places the samples between each ray's first and
+    last occupied cell (render_rays)."""
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
-                                  return_extras=True, occupancy=occupancy)
+                                  return_extras=True, occupancy=occupancy, clip=clip)
     target = target_rgb.reshape(-1, 3)
     img_loss = rnh.img2mse(out[0], target)
     loss = img_loss
@@ -204,7 +284,7 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01):
+              occupancy_thresh=0.01, clip=False):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -213,7 +293,10 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     occupancy: an OccupancyGrid handed to every train_step.  It stays as given for the first occupancy_warmup iterations; from
     then on occupancy.update(field, occupancy_thresh) runs before iterations occupancy_warmup, occupancy_warmup + occupancy_every,
     ...  The jitter of the cell points comes from the same generator, so a run still repeats exactly.  occupancy_thresh is a
-    density (the default 0.01 is instant-ngp's minimum optical thickness per unit length)."""
+    density (the default 0.01 is instant-ngp's minimum optical thickness per unit length).
+    occupancy_every=0: a static grid, never refreshed.  This is how a grid made from the mesh (OccupancyGrid.from_mesh) is used: the
+    surface is known before the first iteration and must not be overwritten by the student's density.  clip=True places every ray's
+    samples between its first and last occupied cell (render_rays)."""
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -225,11 +308,11 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     opt = torch.optim.Adam(field.parameters(), lr=lr)
     hist = []
     for it in range(iters):
-        if occupancy is not None and it >= occupancy_warmup and (it - occupancy_warmup) % occupancy_every == 0:
+        if occupancy is not None and occupancy_every != 0 and it >= occupancy_warmup and (it - occupancy_warmup) % occupancy_every == 0:
             occupancy.update(field, occupancy_thresh, generator=gen)
         idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
         step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                           perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                          occupancy=occupancy)
+                          occupancy=occupancy, clip=clip)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()

@@ -308,6 +308,37 @@ int32_t ctx_occ_cell_points(int32_t G, float lo_x, float lo_y, float lo_z, float
    cells = dens > thresh (equality is not occupied).  A NaN raw.w leaves sigma 0 and marks the cell occupied. */
 int32_t ctx_occ_update(const float *raw, float *dens, uint8_t *cells, int64_t n, float decay, float thresh, ctx_stream_t stream);
 
+/* ---- occupancy grid from the mesh, and the span of occupied cells along a ray (definitions: tests/test_occupancy_mesh_cpu.py) ---- */
+/* ctx_occ_voxelize: stores the byte 1 into every cell a triangle of the mesh touches; never clears (the caller zeroes cells; calls
+   accumulate a union); plain byte stores, no atomics.  vertices float32 [V,3] in the frame of the box, faces int64 [F,3].  Binary32 in
+   the order written: g = (v - lo)*inv per vertex (the expression of ctx_occ_mark), so cell c is the cube [c, c+1]^3; the test runs on
+   the cube inflated by e = 2^-7 of a cell on every side (minimum corner p = c - e, side D = 1 + 2e), which makes the binary32 result a
+   superset of the exact overlap and lets a triangle on a cell face mark both layers.  Candidates per axis: max(0, floor(min - e)) ..
+   min(G - 1, floor(max + e)) of the triangle's bounding box.  A triangle with a face index outside [0, V) or a non-finite grid
+   coordinate marks nothing.  Test (Schwarz and Seidel 2010): n = (g1 - g0) x (g2 - g0); n == 0: every candidate is marked.  Plane:
+   crit = D where n > 0 else 0 per axis, d1 = n.(crit - g0), d2 = n.((D - crit) - g0), s1 = n.p + d1, s2 = n.p + d2, passes when s1 and
+   s2 do not have the same strict sign (s1*s2 <= 0, written with comparisons).  Edges: for the planes xy, yz, zx and the edges
+   e_i = g_{i+1} - g_i: ne = (-e.v, e.u), negated when n's third component there is < 0; de = -(ne.g_i) + max(0, D*ne.u) + max(0, D*ne.v);
+   passes when ne.p + de >= 0.  Dots sum left to right.  1 <= G <= 256, 1 <= V, F < 2^31. */
+int32_t ctx_occ_voxelize(const float *vertices, const int64_t *faces, int64_t V, int64_t F, int32_t G, float lo_x, float lo_y, float lo_z,
+                         float inv_x, float inv_y, float inv_z, uint8_t *cells, ctx_stream_t stream);
+/* Cube (Chebyshev) dilation: dst[c] = 1 when any cell of src within k on the three axes is non-zero, else 0.  Separable: x (src -> dst),
+   y (dst -> ws), z (ws -> dst), each a running maximum over +-k clamped to the grid.  k >= 0 (above G - 1 it reaches no further); k = 0 copies (non-zero -> 1) and takes
+   no workspace.  src, dst and ws [G^3] bytes, pairwise distinct. */
+int32_t ctx_occ_dilate(const uint8_t *src, int32_t G, int32_t k, uint8_t *dst, uint8_t *ws /*nullable for k = 0*/, ctx_stream_t stream);
+/* span [R,2], hit [R]: where the ray o + d*t enters its first and leaves its last occupied cell within [near, far] clipped to the box;
+   (near, far) and hit = 0 for a ray without one.  One lane per ray, binary32 in the order written.  A non-finite o or d: no hit.
+   Clip: t_a = near, t_b = far; per axis with d != 0: t1 = (lo - o)/d, t2 = (hi - o)/d, t_a = max(t_a, min(t1, t2)), t_b = min(t_b,
+   max(t1, t2)); with d == 0 the ray misses unless lo <= o <= hi; it misses unless t_a <= t_b.  Start cell per axis:
+   (int)clamp(((o + d*t_a) - lo)*inv, 0, G - 1).  Walk: at every cell the exit parameter per axis is ((lo + (float)(c + (d > 0))*h) - o)/d
+   from the integer cell index (+inf for d == 0; no running sum, no drift); te = the smallest, ties to x before y before z; the cell is
+   left at t_out = min(max(te, t_in), t_b), the next cell's t_in (the first one's is t_a); an occupied cell sets span1 = t_out and, if it
+   is the first, span0 = t_in.  The walk ends when te >= t_b, when the step along te's axis leaves the grid, or after 3G + 3 cells.
+   Finite near < far; 1 <= R < 2^31; span 8-byte aligned. */
+int32_t ctx_occ_ray_spans(const float *rays_o, const float *rays_d, int64_t R, float near, float far, const uint8_t *cells, int32_t G,
+                          float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
+                          float h_x, float h_y, float h_z, float *span, uint8_t *hit, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
