@@ -8,6 +8,7 @@
 #include <math.h>
 
 #pragma clang fp contract(off)
+#include "composite.h"
 
 // ------------------------------------------------------------------------------------------------
 // prepare_vertices: two tiny kernels (vertex transform, then per-face gather + normal).
@@ -908,7 +909,7 @@ extern "C" int32_t ctx_get_rays(int32_t H, int32_t W, float fx, float fy, float 
     return CTX_OK;
 }
 
-// Per-sample terms of nerf-pytorch raw2outputs, shared by the forward and the backward so both see the same bits.
+// The sample's distance to the next one, the dense layout's part of the per-sample terms; what follows it is composite_rest (composite.h).
 // zx: lane 63's next depth (the first depth of the following chunk); noise is added to the density before the ReLU.
 template <bool NOISE>
 __device__ __forceinline__ void composite_sample(float qw, float nz, float zv, float zx, int s, int S, bool ok, float nrm,
@@ -918,34 +919,7 @@ __device__ __forceinline__ void composite_sample(float qw, float nz, float zv, f
     float zn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, zx), __builtin_bit_cast(int, zv), 0x130, 0xf, 0xf, false));
     dist = (s + 1 < S) ? (zn - zv) : 1e10f;
     dist = dist * nrm;
-    float pre = NOISE ? qw + nz : qw;
-    float sigma = pre > 0.f ? pre : 0.f;
-    e = __builtin_amdgcn_exp2f(-1.4426950408889634f * sigma * dist);
-    alpha = ok ? 1.0f - e : 0.f;
-    t = ok ? (1.0f - alpha) + 1e-10f : 1.0f;
-}
-
-// inclusive prefix product over the 64 lanes on the DPP path (no LDS crossbar): Hillis-Steele inside the 16-lane
-// rows (row_shr 1, 2, 4, 8; lanes without a source multiply by `old` = 1), then row_bcast 15 / 31 across rows;
-// exc = inclusive shifted right by one lane (wave_shr:1; lane 0 keeps `old` = 1)
-__device__ __forceinline__ void composite_prefix(float t, float &inc, float &exc)
-{
-    inc = t;
-    const int one = 0x3f800000;
-#define CTX_SCAN_STEP(ctrl, rmask) inc = inc * __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
-    CTX_SCAN_STEP(0x111, 0xf);
-    CTX_SCAN_STEP(0x112, 0xf);
-    CTX_SCAN_STEP(0x114, 0xf);
-    CTX_SCAN_STEP(0x118, 0xf);
-    CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
-    CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
-#undef CTX_SCAN_STEP
-    exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ float composite_sigmoid(float x)
-{
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+    composite_rest<NOISE>(qw, nz, dist, ok, e, alpha, t);
 }
 
 // One wavefront per ray: lane s holds sample s of the current 64-sample chunk.  Transmittance is an
@@ -1003,17 +977,8 @@ __global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ ra
         dep += w * zv;
         a += w;
         Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
-        if (ch + 1 == nch) {
-            float s0 = wave_sum_dpp(c0), s1 = wave_sum_dpp(c1), s2 = wave_sum_dpp(c2), sd = wave_sum_dpp(dep), sa = wave_sum_dpp(a);
-            if (lane == 0) {
-                if (white) { s0 += 1.0f - sa; s1 += 1.0f - sa; s2 += 1.0f - sa; }
-                rgb[r * 3 + 0] = s0; rgb[r * 3 + 1] = s1; rgb[r * 3 + 2] = s2;
-                depth[r] = sd; acc[r] = sa;
-                float qd = sd / sa;
-                float dv = 1.0f / (qd > 1e-10f ? qd : 1e-10f);
-                disp[r] = (qd != qd) ? qd : dv;
-            }
-        }
+        if (ch + 1 == nch)
+            composite_finish(lane, r, white, c0, c1, c2, dep, a, rgb, disp, acc, depth);
         r = rn; ch = cn;
     }
 }
@@ -1054,7 +1019,6 @@ extern "C" int32_t ctx_raymarch_composite_fwd(const float *raw, const float *z_v
 // recomputes the chunk, carries the suffix sum of G_k w_k over the chunks behind it and adds a true in-wave suffix scan (row_shl
 // inside the 16-lane rows, the three row totals behind a row by readlane), so a sample deep behind an opaque one keeps its
 // relative accuracy.  No atomics, one fixed summation order; every element of grad_raw is written.
-#define COMPOSITE_BWD_MAX_S 4096
 template <bool NOISE>
 __global__ __launch_bounds__(256) void k_composite_bwd(const float4 *__restrict__ raw, const float *__restrict__ z,
                                                        const float *__restrict__ rays_d, const float *__restrict__ noise,
@@ -1090,12 +1054,8 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float4 *__restrict_
             Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
         }
         const float sd = wave_sum_dpp(dep), sa = wave_sum_dpp(a);
-        const float g0 = g_rgb ? g_rgb[r * 3 + 0] : 0.f, g1 = g_rgb ? g_rgb[r * 3 + 1] : 0.f, g2 = g_rgb ? g_rgb[r * 3 + 2] : 0.f;
-        const float qd = sd / sa;
-        const bool hasq = qd > 1e-10f;                                  // false on the acc == 0 ray (0 / 0): both gq terms drop
-        const float gq = (hasq && g_disp) ? -g_disp[r] / (qd * qd) : 0.f;
-        const float gd = (g_depth ? g_depth[r] : 0.f) + (hasq ? gq / sa : 0.f);
-        const float ga = ((g_acc ? g_acc[r] : 0.f) - (hasq ? gq * sd / (sa * sa) : 0.f)) - (white ? (g0 + g1) + g2 : 0.f);
+        float g0, g1, g2, gd, ga;
+        composite_bwd_upstream(r, white, sd, sa, g_rgb, g_disp, g_acc, g_depth, g0, g1, g2, gd, ga);
         float carry = 0.f;                                              // sum of G_k w_k over the chunks behind this one
         for (int ch = nch - 1; ch >= 0; --ch) {
             const int s = ch * 64 + lane;
@@ -1109,33 +1069,8 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float4 *__restrict_
             composite_sample<NOISE>(q.w, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
             composite_prefix(t, inc, exc);
             const float T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tcv), ch)) * exc;
-            const float w = alpha * T;
-            const float c0 = composite_sigmoid(q.x), c1 = composite_sigmoid(q.y), c2 = composite_sigmoid(q.z);
-            const float G = ((((g0 * c0 + g1 * c1) + g2 * c2) + gd * zv) + ga) + gw;          // dL/dw_s
-            // inclusive suffix sum of G_k w_k over the lanes at and behind this one
-            float suf = ok ? G * w : 0.f;
-#define CTX_SUFFIX_STEP(ctrl) suf = suf + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), ctrl, 0xf, 0xf, false))
-            CTX_SUFFIX_STEP(0x101);                   // row_shl 1, 2, 4, 8: lanes without a source add `old` = 0
-            CTX_SUFFIX_STEP(0x102);
-            CTX_SUFFIX_STEP(0x104);
-            CTX_SUFFIX_STEP(0x108);
-#undef CTX_SUFFIX_STEP
-            const int si = __builtin_bit_cast(int, suf);
-            const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16)), r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 32));
-            const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 48));
-            const int row = lane >> 4;
-            suf = suf + (row == 0 ? (r1 + (r2 + r3)) : row == 1 ? (r2 + r3) : row == 2 ? r3 : 0.f);
-            // exclusive: the inclusive sum of the next lane (wave_shl:1; lane 63 keeps `old` = 0)
-            const float X = carry + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), 0x130, 0xf, 0xf, false));
-            carry = carry + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, suf), 0));
-            // dL/dalpha_s * dist_s * e_s with e_s folded in before the division: e / t <= 1 and dist * e stays finite at dist = 1e10
-            const float da = (G * T) * (dist * e) - (X * (e * __builtin_amdgcn_rcpf(t))) * dist;
             const float pre = NOISE ? q.w + nz : q.w;
-            float4 o;
-            o.x = (w * g0) * (c0 * (1.0f - c0));
-            o.y = (w * g1) * (c1 * (1.0f - c1));
-            o.z = (w * g2) * (c2 * (1.0f - c2));
-            o.w = pre > 0.f ? da : 0.f;                // the ReLU mask is a select: dist is 1e10 on the last sample
+            const float4 o = composite_bwd_sample(q, pre, zv, gw, ok, lane, dist, e, alpha, t, T, g0, g1, g2, gd, ga, carry);
             if (ok) grad_raw[r * S + s] = o;
         }
     }

@@ -4,18 +4,13 @@
 // restatements (tests/test_occupancy_mesh_cpu.py) give the same bits; they are the definition, this file follows them line by line.
 // No atomics.  The voxeliser only ever stores the byte 1 (as k_texel_mark / k_vc_seen do): racing stores write the same value, the
 // caller zeroes the grid, several calls accumulate a union.  Every other output element has one writer.
-#include "common.h"
-#include <math.h>
+#include "occ_walk.h"
 
 #define OCM_BLK 256
 #define OCM_CAP 2048          // blocks of a grid-stride launch: 8 per CU
 
 #define OCM_E 0.0078125f      // 2^-7 of a cell: the inflation of the cell's box on every side
 #define OCM_DELTA 1.015625f   // 1 + 2e, the side of the inflated box
-
-struct ocm3 { float x, y, z; };
-
-__device__ __forceinline__ bool ocm_finite(float x) { return fabsf(x) < INFINITY; }          // false for NaN
 
 // ---- voxeliser: one wave per triangle, the lanes stride over the candidate cells of its bounding box, x fastest --------------------
 // The triangle index is wave-uniform, so the vertex loads are scalar loads and the set-up (normal, plane terms, nine edge terms) is done
@@ -155,54 +150,21 @@ extern "C" int32_t ctx_occ_dilate(const uint8_t *src, int32_t G, int32_t k, uint
     return CTX_OK;
 }
 
-// ---- spans: one lane per ray, a cell walk whose exit parameters come from the integer cell index at every step (no drift) --------------
+// ---- spans: one lane per ray; the cell walk is occ_walk (occ_walk.h), shared with the march kernels -------------------------------------
 __global__ __launch_bounds__(OCM_BLK) void k_occ_ray_spans(const float *__restrict__ ro, const float *__restrict__ rd, int64_t R, float near, float far,
                                                            const uint8_t *__restrict__ cells, int G, ocm3 lo, ocm3 hi, ocm3 inv, ocm3 h,
                                                            float2 *__restrict__ span, uint8_t *__restrict__ hit)
 {
-    const float Gm1 = (float)(G - 1);
-    const int max_cells = 3 * G + 3;
     for (int64_t r = (int64_t)blockIdx.x * OCM_BLK + threadIdx.x; r < R; r += (int64_t)gridDim.x * OCM_BLK) {
-        const float ox = ro[r * 3 + 0], oy = ro[r * 3 + 1], oz = ro[r * 3 + 2];
-        const float dx = rd[r * 3 + 0], dy = rd[r * 3 + 1], dz = rd[r * 3 + 2];
-        bool ok = ocm_finite(ox) && ocm_finite(oy) && ocm_finite(oz) && ocm_finite(dx) && ocm_finite(dy) && ocm_finite(dz);
-        float ta = near, tb = far;
-        if (ok) {                                                     // slab clip; a zero component compares the origin with its slab
-            if (dx == 0.f) ok = ok && ox >= lo.x && ox <= hi.x;
-            else { const float t1 = (lo.x - ox) / dx, t2 = (hi.x - ox) / dx; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
-            if (dy == 0.f) ok = ok && oy >= lo.y && oy <= hi.y;
-            else { const float t1 = (lo.y - oy) / dy, t2 = (hi.y - oy) / dy; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
-            if (dz == 0.f) ok = ok && oz >= lo.z && oz <= hi.z;
-            else { const float t1 = (lo.z - oz) / dz, t2 = (hi.z - oz) / dz; ta = fmaxf(ta, fminf(t1, t2)); tb = fminf(tb, fmaxf(t1, t2)); }
-            ok = ok && ta <= tb;
-        }
         float s0 = near, s1 = far;
         bool found = false;
-        if (ok) {
-            int cx = (int)fminf(fmaxf(((ox + dx * ta) - lo.x) * inv.x, 0.f), Gm1);
-            int cy = (int)fminf(fmaxf(((oy + dy * ta) - lo.y) * inv.y, 0.f), Gm1);
-            int cz = (int)fminf(fmaxf(((oz + dz * ta) - lo.z) * inv.z, 0.f), Gm1);
-            float tin = ta;
-            for (int step = 0; step < max_cells; ++step) {
-                const float ex = dx == 0.f ? INFINITY : ((lo.x + (float)(cx + (dx > 0.f ? 1 : 0)) * h.x) - ox) / dx;
-                const float ey = dy == 0.f ? INFINITY : ((lo.y + (float)(cy + (dy > 0.f ? 1 : 0)) * h.y) - oy) / dy;
-                const float ez = dz == 0.f ? INFINITY : ((lo.z + (float)(cz + (dz > 0.f ? 1 : 0)) * h.z) - oz) / dz;
-                int ax = 0;
-                float te = ex;
-                if (ey < te) { ax = 1; te = ey; }
-                if (ez < te) { ax = 2; te = ez; }
-                const float tout = fminf(fmaxf(te, tin), tb);
-                if (cells[((int64_t)cz * G + cy) * G + cx]) {         // 0 <= c < G: clamped at the start, checked at every step
-                    if (!found) { s0 = tin; found = true; }
-                    s1 = tout;
-                }
-                if (te >= tb) break;
-                if (ax == 0) { cx += dx > 0.f ? 1 : -1; if (cx < 0 || cx > G - 1) break; }
-                else if (ax == 1) { cy += dy > 0.f ? 1 : -1; if (cy < 0 || cy > G - 1) break; }
-                else { cz += dz > 0.f ? 1 : -1; if (cz < 0 || cz > G - 1) break; }
-                tin = tout;
-            }
-        }
+        occ_walk(ro[r * 3 + 0], ro[r * 3 + 1], ro[r * 3 + 2], rd[r * 3 + 0], rd[r * 3 + 1], rd[r * 3 + 2], near, far, cells, G, lo, hi, inv, h,
+                 [&](bool occ, float tin, float tout) {
+                     if (occ) {
+                         if (!found) { s0 = tin; found = true; }
+                         s1 = tout;
+                     }
+                 });
         span[r] = make_float2(s0, s1);
         hit[r] = found ? 1 : 0;
     }

@@ -370,6 +370,78 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
     return _composite_fwd(r, z, d, noise, white_bkgd)
 
 
+def _packed_fwd(r, t, dt, d, noise, ray_off, white_bkgd):
+    lib = L.load()
+    n, R, dev = r.shape[0], d.shape[0], d.device
+    rgb = torch.empty(R, 3, device=dev); disp = torch.empty(R, device=dev); acc = torch.empty(R, device=dev)
+    w = torch.empty(n, device=dev); depth = torch.empty(R, device=dev)
+    L.check(lib.ctx_raymarch_packed_fwd(L.ptr(r, torch.float32, "raw"), L.ptr(t, torch.float32, "t"), L.ptr(dt, torch.float32, "dt"),
+                                        L.ptr(d, torch.float32, "rays_d"), L.ptr(noise), L.ptr(ray_off, torch.int64, "ray_off"), R, n,
+                                        int(white_bkgd), L.ptr(rgb), L.ptr(disp), L.ptr(acc), L.ptr(w), L.ptr(depth), L.stream()))
+    return rgb, disp, acc, w, depth
+
+
+class _PackedCompositeFn(torch.autograd.Function):
+    """raw2outputs_packed with the gradient to raw (`ctx_raymarch_packed_bwd`): as _CompositeFn, only the inputs are saved."""
+
+    @staticmethod
+    def forward(ctx, raw, t, dt, d, noise, ray_off, white_bkgd):
+        out = _packed_fwd(raw, t, dt, d, noise, ray_off, white_bkgd)
+        ctx.save_for_backward(raw, t, dt, d, noise, ray_off)
+        ctx.white = int(white_bkgd)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
+        lib = L.load()
+        raw, t, dt, d, noise, ray_off = ctx.saved_tensors
+        gs = [None if g is None else L.f32c(g) for g in (g_rgb, g_disp, g_acc, g_w, g_depth)]
+        grad = torch.empty_like(raw)
+        L.check(lib.ctx_raymarch_packed_bwd(L.ptr(raw), L.ptr(t), L.ptr(dt), L.ptr(d), L.ptr(noise), L.ptr(ray_off), d.shape[0], raw.shape[0],
+                                            ctx.white, L.ptr(gs[0]), L.ptr(gs[1]), L.ptr(gs[2]), L.ptr(gs[3]), L.ptr(gs[4]), L.ptr(grad),
+                                            L.stream()))
+        return grad, None, None, None, None, None, None
+
+
+def raw2outputs_packed(raw, t, dt, rays_d, ray_off, raw_noise_std=0, white_bkgd=False, generator=None):
+    """raw2outputs on ragged per-ray sample lists (OccupancyGrid.march): ray r holds the samples ray_off[r] .. ray_off[r+1] of raw [n,4],
+    t [n] and dt [n]; rays_d [R,3], ray_off int64 [R+1] -> (rgb [R,3], disp [R], acc [R], weights [n], depth [R]).
+    It is the dense kernel with a per-ray sample count and the given distance dt * |rays_d|: no sample gets the 1e10 distance, so the
+    background shows through what the lists leave, and a ray without samples gets acc = depth = 0, rgb 0 (or white) and the 0 / 0
+    disparity of a dense ray of zero density.  raw_noise_std > 0 adds randn(n) * std to the density before the ReLU.  Gradients go
+    to raw only (`ctx_raymarch_packed_bwd`, at most 4096 samples per ray): a t, dt or rays_d that requires grad is refused."""
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and any(isinstance(x, torch.Tensor) and x.requires_grad for x in (t, dt, rays_d)):
+        raise L.CtxError("raw2outputs_packed: the HIP path has no gradient with respect to t / dt / rays_d; detach them")
+    r, t, dt, d = L.f32c(raw), L.f32c(t), L.f32c(dt), L.f32c(rays_d).reshape(-1, 3)
+    n = r.shape[0]
+    if r.dim() != 2 or r.shape[1] != 4 or t.shape != (n,) or dt.shape != (n,) or ray_off.shape != (d.shape[0] + 1,):
+        raise L.CtxError(f"raw2outputs_packed: want raw [n,4], t [n], dt [n], rays_d [R,3], ray_off [R+1]; got {tuple(r.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(dt.shape)}, {tuple(d.shape)}, {tuple(ray_off.shape)}")
+    noise = torch.randn(n, device=r.device, generator=generator) * raw_noise_std if raw_noise_std > 0 else None
+    if grad_mode and r.requires_grad:
+        return _PackedCompositeFn.apply(r, t, dt, d, noise, ray_off, white_bkgd)
+    return _packed_fwd(r, t, dt, d, noise, ray_off, white_bkgd)
+
+
+def render_rays_marched(field, rays_o, rays_d, near, far, occupancy, step, white_bkgd=False, perturb=0., raw_noise_std=0., generator=None,
+                        return_extras=False):
+    """The ray path on ragged per-ray sample lists, as instant-ngp and nerfacc march: occupancy.march places samples `step` apart (a
+    world length) inside each ray's runs of occupied cells and nowhere else, field.forward_pts runs on exactly those n points, and
+    raw2outputs_packed composites the lists directly: no expansion, no fill, no [R,S] tensor; one host sync (n).
+    -> (rgb [R,3], disp [R], acc [R], weights [n], depth [R]); return_extras=True adds dict(ray_off, ray_id, t, dt, pts).
+    perturb > 0 draws one uniform offset per sample inside its interval.  n = 0: the field is not called, every ray is empty and
+    the outputs carry no autograd graph."""
+    if occupancy is None:
+        raise L.CtxError("render_rays_marched: march needs an occupancy grid (occupancy=): the samples lie in its occupied cells")
+    ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
+    ray_off, ray_id, t, dt, pts = occupancy.march(ro, rd, near, far, step, perturb=perturb > 0., generator=generator)
+    raw = L.f32c(field.forward_pts(pts)) if t.numel() else torch.empty(0, 4, device=ro.device)
+    out = raw2outputs_packed(raw, t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
+    return (out, {'ray_off': ray_off, 'ray_id': ray_id, 't': t, 'dt': dt, 'pts': pts}) if return_extras else out
+
+
 def _occ_expand(raw_c, idx, total):
     lib = L.load()
     raw = torch.empty(total, 4, device=idx.device)
@@ -417,7 +489,7 @@ def field_on_occupied(field, occupancy, ro, rd, z_vals):
 
 
 def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None, perturb=0., raw_noise_std=0.,
-                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None, clip=False):
+                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None, clip=False, march=None):
     """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays —
     z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from sample_pdf), pts = o + d*z,
     raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused embed+MLP kernel, then
@@ -434,7 +506,20 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
     clip=True (needs occupancy, and no z_vals of the caller's): every ray spreads its N_samples over its own span, from where it enters
     its first to where it leaves its last occupied cell (occupancy.ray_spans): z_vals = t0*(1-t) + t1*t with the same linspace t.  The
     jitter, the hierarchical pass and the compositing then run on those z_vals as they do on any.  A ray that meets no occupied cell
-    keeps near .. far, where the selection finds nothing for it.  No further host sync."""
+    keeps near .. far, where the selection finds nothing for it.  No further host sync.
+    march=step (needs occupancy; refuses clip=True, N_importance > 0, given z_vals and pytest=True, because it places and draws the samples itself): the
+    pass is render_rays_marched with that world-space step, N_samples is unused and weights is the flat list [n]."""
+    if march is not None:
+        if clip:
+            raise L.CtxError("render_rays: march= places the samples itself; it cannot be combined with clip=True")
+        if N_importance > 0:
+            raise L.CtxError("render_rays: march= has no hierarchical pass; it cannot be combined with N_importance > 0")
+        if z_vals is not None:
+            raise L.CtxError("render_rays: march= places the samples itself; it cannot be combined with given z_vals")
+        if pytest:
+            raise L.CtxError("render_rays: march= draws its jitter and noise from torch (generator=); it cannot be combined with pytest=True")
+        return render_rays_marched(field, rays_o, rays_d, near, far, occupancy, march, white_bkgd=white_bkgd, perturb=perturb,
+                                   raw_noise_std=raw_noise_std, generator=generator, return_extras=return_extras)
     if clip and occupancy is None:
         raise L.CtxError("render_rays: clip=True needs an occupancy grid (occupancy=): the spans are those of its occupied cells")
     if clip and z_vals is not None:

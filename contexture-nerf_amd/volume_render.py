@@ -144,6 +144,52 @@ class OccupancyGrid:
                                            L.stream()))
         return span, hit != 0
 
+    def march_bound(self, step):
+        """An upper bound on the samples `march` places on one ray: floor(D / step * (1 + 2^-15)) + (3G + 4) // 2 + 1 with D the box
+        diagonal (the path inside the box over step, one per run from ceil, and the rounding)."""
+        D = float(np.sqrt(np.sum((self.hi.astype(np.float64) - self.lo.astype(np.float64)) ** 2)))
+        return int(np.floor(D / float(step) * (1.0 + 2.0 ** -15))) + (3 * self.G + 4) // 2 + 1
+
+    def march(self, rays_o, rays_d, near, far, step, perturb=False, generator=None):
+        """-> (ray_off int64 [R+1], ray_id int32 [n], t [n], dt [n], pts [n,3]): every ray walks the grid once and gets samples `step`
+        apart (a WORLD length, whatever |rays_d| is) inside its runs of occupied cells and nowhere else (`ctx_occ_march_count`, the
+        exclusive scan, `ctx_occ_march_write`).  Ray r owns ray_off[r] .. ray_off[r+1], ascending in t; sample j of a run [a, b] cut into k
+        intervals of width dt sits at a + (j + u) * dt with u = 0.5, or with perturb one uniform draw per sample (drawn after the count,
+        which does not depend on it: a seeded generator repeats exactly).  n = 0 is legal: empty lists.  Reading n back SYNCS the host,
+        the path's one sync.  A (G, box, step) whose per-ray bound `march_bound` exceeds 4096, the most the compositing backward holds,
+        is refused."""
+        near, far, step = float(near), float(far), float(step)
+        if not (near < far and np.isfinite(near) and np.isfinite(far)):
+            raise L.CtxError(f"OccupancyGrid.march: want finite near < far, got {near}, {far}")
+        if not (step > 0 and np.isfinite(step)):
+            raise L.CtxError(f"OccupancyGrid.march: step={step}: want a finite world length > 0")
+        bound = self.march_bound(step)
+        if bound > 4096:
+            raise L.CtxError(f"OccupancyGrid.march: step={step:g} with G={self.G} over the box {self.lo.tolist()} .. {self.hi.tolist()} can put "
+                             f"{bound} samples on one ray; the compositing backward holds 4096: use a longer step")
+        if not (isinstance(rays_o, torch.Tensor) and isinstance(rays_d, torch.Tensor) and rays_o.dim() == 2 and rays_o.shape[1] == 3
+                and rays_o.shape[0] >= 1 and rays_d.shape == rays_o.shape):
+            raise L.CtxError(f"OccupancyGrid.march: want rays_o, rays_d [R,3] with R >= 1; got {tuple(getattr(rays_o, 'shape', ()))}, "
+                             f"{tuple(getattr(rays_d, 'shape', ()))}")
+        p_o, p_d = L.ptr(rays_o, torch.float32, "rays_o"), L.ptr(rays_d, torch.float32, "rays_d")
+        lib = L.load()
+        R, dev = rays_o.shape[0], rays_o.device
+        grid = (L.ptr(self.cells, torch.uint8, "cells"), self.G, *map(float, self.lo), *map(float, self.hi), *map(float, self.inv),
+                *map(float, self.h), step)
+        count = torch.empty(R, dtype=torch.int32, device=dev)
+        L.check(lib.ctx_occ_march_count(p_o, p_d, R, near, far, *grid, L.ptr(count), L.stream()))
+        ray_off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(count, 0, dtype=torch.int64, out=ray_off[1:])
+        n = int(ray_off[R].item())                                                         # the one host sync
+        if n >= 2 ** 31:
+            raise L.CtxError(f"OccupancyGrid.march: {n} samples on {R} rays: want n < 2^31; split the batch")
+        u = torch.rand(n, device=dev, generator=generator) if perturb else None
+        ray_id = torch.empty(n, dtype=torch.int32, device=dev)
+        t, dt, pts = torch.empty(n, device=dev), torch.empty(n, device=dev), torch.empty(n, 3, device=dev)
+        L.check(lib.ctx_occ_march_write(p_o, p_d, R, near, far, *grid, L.ptr(ray_off), L.ptr(u), n, L.ptr(ray_id), L.ptr(t), L.ptr(dt),
+                                        L.ptr(pts), L.stream()))
+        return ray_off, ray_id, t, dt, pts
+
     def select(self, rays_o, rays_d, z_vals):
         """-> idx int32 [n], ascending: the samples r*S + s of z_vals [R,S] whose point rays_o + rays_d * z lies in an occupied
         cell (`ctx_occ_mark`, then the ordered compaction `ctx_texel_compact`).  R*S < 2^31.  Reading n back SYNCS the host: one
@@ -195,16 +241,18 @@ class OccupancyGrid:
 
 
 @torch.no_grad()
-def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None, clip=False):
+def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None, clip=False,
+                 march=None):
     """-> dict(rgb [h,W,3], depth [h,W], acc [h,W], disp [h,W]) for the row range `rows` (default: all).
     N_importance > 0 adds nerf-pytorch's hierarchical pass (render_rays: sample_pdf(det=True) on the coarse weights, merged
     and sorted with the coarse samples, evaluated by the same field).  occupancy: an OccupancyGrid; clip: samples between each
-    ray's first and last occupied cell; see render_rays."""
+    ray's first and last occupied cell; see render_rays.  march: a world-space step; the samples are then the ragged lists of
+    occupancy.march (render_rays_marched) and N_samples is unused."""
     ro, rd = rnh.get_rays(H, W, K, c2w)
     r0, r1 = (0, H) if rows is None else rows
     ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
     rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance,
-                                                 occupancy=occupancy, clip=clip)
+                                                 occupancy=occupancy, clip=clip, march=march)
     h = r1 - r0
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
@@ -240,12 +288,14 @@ def depth_for_diffusion(depth, acc, thresh=0.5):
 
 @torch.no_grad()
 def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples=128, guidance_scale=7.5, strength=1.0,
-                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None, clip=False):
+                      num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None, clip=False,
+                      march=None):
     """configs[4] end to end on this rank's rows; every rank returns the refined image [1,3,S,S] and the gathered render.
-    occupancy, clip: an OccupancyGrid for the render and whether the samples are placed inside its spans (render_rays)."""
+    occupancy, clip: an OccupancyGrid for the render and whether the samples are placed inside its spans (render_rays).
+    march: a world-space step for the render's ragged sample lists (render_rays_marched); N_samples is then unused."""
     K = pinhole(H, W)
     tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world), occupancy=occupancy,
-                        clip=clip)
+                        clip=clip, march=march)
     rgb = gather_rows(tile['rgb'], H, group)
     depth = gather_rows(tile['depth'], H, group)
     acc = gather_rows(tile['acc'], H, group)
@@ -259,18 +309,20 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None, clip=False):
+               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
     occupancy: an OccupancyGrid (render_rays): the field runs, and keeps activations, on the occupied samples only, at one
     host sync per pass.  A batch in which no pass has an occupied sample has a loss without a graph: backward and the
     optimizer step are skipped and loss / psnr are still returned.  clip=True places the samples between each ray's first and
-    last occupied cell (render_rays)."""
+    last occupied cell (render_rays).  march: a world-space step; the batch is rendered from the ragged lists of occupancy.march
+    (render_rays_marched: no [R,S] tensor, one host sync), N_samples is unused, and a batch with n = 0 skips backward and the step
+    in the same way."""
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
-                                  return_extras=True, occupancy=occupancy, clip=clip)
+                                  return_extras=True, occupancy=occupancy, clip=clip, march=march)
     target = target_rgb.reshape(-1, 3)
     img_loss = rnh.img2mse(out[0], target)
     loss = img_loss
@@ -284,7 +336,7 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False):
+              occupancy_thresh=0.01, clip=False, march=None):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -296,7 +348,9 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     density (the default 0.01 is instant-ngp's minimum optical thickness per unit length).
     occupancy_every=0: a static grid, never refreshed.  This is how a grid made from the mesh (OccupancyGrid.from_mesh) is used: the
     surface is known before the first iteration and must not be overwritten by the student's density.  clip=True places every ray's
-    samples between its first and last occupied cell (render_rays)."""
+    samples between its first and last occupied cell (render_rays).  march: a world-space step handed to every train_step: the
+    samples are the ragged lists of occupancy.march, N_samples is unused, and the refresh schedule stays as it is (the grid may
+    change between iterations and the march follows it)."""
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -313,6 +367,6 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
         idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
         step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                           perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                          occupancy=occupancy, clip=clip)
+                          occupancy=occupancy, clip=clip, march=march)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()

@@ -339,6 +339,43 @@ int32_t ctx_occ_ray_spans(const float *rays_o, const float *rays_d, int64_t R, f
                           float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
                           float h_x, float h_y, float h_z, float *span, uint8_t *hit, ctx_stream_t stream);
 
+/* ---- marching the grid into ragged per-ray sample lists, and the compositing on them (definition: tests/march_rule.py) ---- */
+/* count [R]: how many samples the march places on each ray.  The finite check, the clip, the start cell and the walk are those of
+   ctx_occ_ray_spans, expression for expression (one device function).  A run is a maximal sequence of consecutive occupied cells of the
+   walk: a = t_in of its first cell, b = t_out of its last; an empty cell closes the open run (also an empty cell of zero length between two
+   occupied ones), and so do the end of the walk and a step that leaves the grid.  step > 0 is a WORLD length.  A closed run [a, b]:
+   nrm = sqrtf((dx*dx + dy*dy) + dz*dz), len = (b - a)*nrm; no sample unless len > 0 (false for NaN); else
+   k = (int)min(max(ceilf(len / step), 1), 4097), dt = (b - a) / (float)k, and sample j = 0 .. k-1 sits at t_j = a + ((float)j + u)*dt with
+   interval width dt: the intervals tile the run.  count = the sum of k over the ray's runs; 0 for a ray that is non-finite, misses the box
+   or meets no occupied cell.  Binary32 in the order written; sqrtf and / correctly rounded.  Arguments as ctx_occ_ray_spans. */
+int32_t ctx_occ_march_count(const float *rays_o, const float *rays_d, int64_t R, float near, float far, const uint8_t *cells, int32_t G,
+                            float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
+                            float h_x, float h_y, float h_z, float step, int32_t *count, ctx_stream_t stream);
+/* The same walk, writing the lists: ray r stores its samples, in walk order (ascending t), at ray_off[r] .. ray_off[r+1] of ray_id int32 [n],
+   t [n], dt [n] and pts [n,3] with p = o + d*t_j (one product, one sum per axis: the bits of ctx_occ_points).  ray_off int64 [R+1] is the
+   exclusive scan of count, n = ray_off[R] < 2^31.  u [n] (nullable: 0.5, the midpoints) holds one draw in [0,1) per sample.  A ray never
+   stores past ray_off[r+1] nor outside [0, n), whatever it computes; n = 0 is legal (nothing is launched, the lists may be null). */
+int32_t ctx_occ_march_write(const float *rays_o, const float *rays_d, int64_t R, float near, float far, const uint8_t *cells, int32_t G,
+                            float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
+                            float h_x, float h_y, float h_z, float step, const int64_t *ray_off, const float *u /*nullable*/, int64_t n,
+                            int32_t *ray_id, float *t, float *dt, float *pts, ctx_stream_t stream);
+/* ctx_raymarch_composite_fwd_noise on ragged lists: ray r holds the samples ray_off[r] .. ray_off[r+1] of raw [n,4], t [n], dt [n]
+   (noise [n] nullable), and sample s has the distance dist = dt_s * |rays_d| in place of (z_{s+1} - z_s) * |rays_d|: no sample gets the
+   1e10 distance, the background shows through what the lists leave.  Everything after dist is the dense kernel's code, so a rectangular
+   layout (ray_off = r*S, dt = z_{s+1} - z_s with 1e10 last) gives the dense kernel's bits.  depth = sum w*t.  A ray without samples:
+   acc = depth = 0, rgb 0 (1 with white_bkgd), disp = 0/0 as the dense kernel gives a ray of zero density.  weights [n] nullable.
+   0 <= n < 2^31; a ray whose ray_off leaves [0, n] or descends is taken as empty. */
+int32_t ctx_raymarch_packed_fwd(const float *raw, const float *t, const float *dt, const float *rays_d, const float *noise /*nullable*/,
+                                const int64_t *ray_off, int64_t R, int64_t n, int32_t white_bkgd, float *rgb, float *disp, float *acc,
+                                float *weights /*nullable*/, float *depth, ctx_stream_t stream);
+/* Backward with respect to raw, the closed form of ctx_raymarch_composite_bwd on the lists: grad_raw [n,4], every row of every ray
+   written, nothing for a ray without samples; upstream gradients each nullable (g_weights [n]).  No atomics, one summation order.  A ray
+   with more than 4096 samples (which the march never makes: only a caller's own ray_off can) gets NaN in its rows; other rays are
+   unaffected.  No gradient with respect to t, dt or rays_d. */
+int32_t ctx_raymarch_packed_bwd(const float *raw, const float *t, const float *dt, const float *rays_d, const float *noise /*nullable*/,
+                                const int64_t *ray_off, int64_t R, int64_t n, int32_t white_bkgd, const float *g_rgb, const float *g_disp,
+                                const float *g_acc, const float *g_weights, const float *g_depth, float *grad_raw, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
