@@ -36,6 +36,22 @@ __device__ __forceinline__ void composite_prefix(float t, float &inc, float &exc
     exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
 }
 
+// inclusive prefix sum over the 64 lanes: the same DPP controls with `old` = 0, so lanes without a source and rows outside the mask add 0;
+// exc = inclusive shifted right by one lane (lane 0 keeps 0).  Lane i adds its 16-lane row left to right in a 4-level tree, then the rows.
+__device__ __forceinline__ void composite_prefix_sum(float v, float &inc, float &exc)
+{
+    inc = v;
+#define CTX_SCAN_STEP(ctrl, rmask) inc = inc + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
+    CTX_SCAN_STEP(0x111, 0xf);
+    CTX_SCAN_STEP(0x112, 0xf);
+    CTX_SCAN_STEP(0x114, 0xf);
+    CTX_SCAN_STEP(0x118, 0xf);
+    CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
+    CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
+#undef CTX_SCAN_STEP
+    exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
+}
+
 __device__ __forceinline__ float composite_sigmoid(float x)
 {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));

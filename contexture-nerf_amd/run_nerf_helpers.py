@@ -425,6 +425,68 @@ def raw2outputs_packed(raw, t, dt, rays_d, ray_off, raw_noise_std=0, white_bkgd=
     return _packed_fwd(r, t, dt, d, noise, ray_off, white_bkgd)
 
 
+def _distortion_fwd(w, t, dt, d, ray_off):
+    lib = L.load()
+    R, n = d.shape[0], w.shape[0]
+    loss = torch.empty(R, device=d.device)
+    L.check(lib.ctx_distortion_packed_fwd(L.ptr(w, torch.float32, "weights"), L.ptr(t, torch.float32, "t"), L.ptr(dt, torch.float32, "dt"),
+                                          L.ptr(d, torch.float32, "rays_d"), L.ptr(ray_off, torch.int64, "ray_off"), R, n, L.ptr(loss),
+                                          L.stream()))
+    return loss
+
+
+class _DistortionFn(torch.autograd.Function):
+    """distortion_loss with the gradient to the weights (`ctx_distortion_packed_bwd`): only the inputs are saved, no double backward."""
+
+    @staticmethod
+    def forward(ctx, w, t, dt, d, ray_off):
+        ctx.save_for_backward(w, t, dt, d, ray_off)
+        return _distortion_fwd(w, t, dt, d, ray_off)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        lib = L.load()
+        w, t, dt, d, ray_off = ctx.saved_tensors
+        grad = torch.empty_like(w)
+        L.check(lib.ctx_distortion_packed_bwd(L.ptr(w), L.ptr(t), L.ptr(dt), L.ptr(d), L.ptr(ray_off), d.shape[0], w.shape[0],
+                                              L.ptr(L.f32c(g_loss)), L.ptr(grad), L.stream()))
+        return grad, None, None, None, None
+
+
+def distortion_loss(weights, t, dt, rays_d, ray_off=None):
+    """mip-NeRF 360's distortion loss of each ray's weights, as nerfacc's distortion(weights, t_starts, t_ends, packed_info), by two
+    wave-per-ray HIP kernels on the ragged lists of OccupancyGrid.march: weights [n], t [n], dt [n], rays_d [R,3], ray_off int64 [R+1]
+    -> loss [R] with loss[r] = sum_i sum_j w_i w_j |x_i - x_j| + (1/3) sum_i w_i^2 delta_i over the ray's samples, x = (t - t_0) * |rays_d|
+    and delta = dt * |rays_d|: world lengths, so the value does not depend on |rays_d|.  The position is the sample's own t, where the
+    density was evaluated.  t ascending inside a ray is a precondition (the march and z_vals satisfy it).  A ray without samples and a
+    zero direction give 0; a non-finite weight poisons its own ray only; any number of samples per ray.
+    ray_off=None takes the rectangular layout of the dense path: weights [R,S], t = z_vals [R,S], and dt is ignored and taken as
+    z[:,1:] - z[:,:-1] with 0 for the last sample, whose interval is the unbounded one and has no width to spread over.
+    Gradients go to weights only (`ctx_distortion_packed_bwd`): a t, dt or rays_d that requires grad is refused."""
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and any(isinstance(x, torch.Tensor) and x.requires_grad for x in (t, dt, rays_d)):
+        raise L.CtxError("distortion_loss: the HIP path has no gradient with respect to t / dt / rays_d; detach them")
+    w, t, d = L.f32c(weights), L.f32c(t), L.f32c(rays_d).reshape(-1, 3)
+    R = d.shape[0]
+    if ray_off is None:
+        if w.dim() != 2 or w.shape[0] != R or t.shape != w.shape:
+            raise L.CtxError(f"distortion_loss: without ray_off want weights [R,S], t [R,S], rays_d [R,3]; got {tuple(w.shape)}, "
+                             f"{tuple(t.shape)}, {tuple(d.shape)}")
+        S = w.shape[1]
+        ray_off = torch.arange(R + 1, device=w.device, dtype=torch.int64) * S
+        dt = torch.cat([t[:, 1:] - t[:, :-1], torch.zeros(R, 1, device=w.device)], -1)
+        w, t = w.reshape(-1), t.reshape(-1)
+    dt = L.f32c(dt).reshape(-1)
+    n = w.shape[0]
+    if w.dim() != 1 or t.shape != (n,) or dt.shape != (n,) or ray_off.shape != (R + 1,):
+        raise L.CtxError(f"distortion_loss: want weights [n], t [n], dt [n], rays_d [R,3], ray_off [R+1]; got {tuple(w.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(dt.shape)}, {tuple(d.shape)}, {tuple(ray_off.shape)}")
+    if grad_mode and w.requires_grad:
+        return _DistortionFn.apply(w, t, dt, d, ray_off)
+    return _distortion_fwd(w, t, dt, d, ray_off)
+
+
 def render_rays_marched(field, rays_o, rays_d, near, far, occupancy, step, white_bkgd=False, perturb=0., raw_noise_std=0., generator=None,
                         return_extras=False):
     """The ray path on ragged per-ray sample lists, as instant-ngp and nerfacc march: occupancy.march places samples `step` apart (a

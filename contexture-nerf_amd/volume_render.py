@@ -309,7 +309,7 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None):
+               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0.):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
@@ -318,7 +318,12 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
     optimizer step are skipped and loss / psnr are still returned.  clip=True places the samples between each ray's first and
     last occupied cell (render_rays).  march: a world-space step; the batch is rendered from the ragged lists of occupancy.march
     (render_rays_marched: no [R,S] tensor, one host sync), N_samples is unused, and a batch with n = 0 skips backward and the step
-    in the same way."""
+    in the same way.
+    distortion > 0 adds distortion * mean over the rays of rnh.distortion_loss (mip-NeRF 360's regulariser, which pulls each ray's
+    weights together): on the march path of the weights and lists the render returned, otherwise of the fine pass's weights and final
+    z_vals.  The dict then gains 'distortion', the unweighted mean, detached.  distortion = 0 (the default) runs nothing new."""
+    if not distortion >= 0.:
+        raise L.CtxError(f"train_step: distortion={distortion}: want a weight >= 0")
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
@@ -328,15 +333,25 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
     loss = img_loss
     if 'rgb0' in extras:
         loss = loss + rnh.img2mse(extras['rgb0'], target)
+    dloss = None
+    if distortion > 0.:
+        if march is not None:
+            dloss = rnh.distortion_loss(out[3], extras['t'], extras['dt'], rays_d, extras['ray_off']).mean()
+        else:
+            dloss = rnh.distortion_loss(out[3], extras['z_vals'], None, rays_d).mean()
+        loss = loss + distortion * dloss
     if occupancy is None or loss.requires_grad:
         loss.backward()
         optimizer.step()
-    return {'loss': loss.detach(), 'psnr': rnh.mse2psnr(img_loss.detach()).reshape(())}
+    res = {'loss': loss.detach(), 'psnr': rnh.mse2psnr(img_loss.detach()).reshape(())}
+    if dloss is not None:
+        res['distortion'] = dloss.detach()
+    return res
 
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False, march=None):
+              occupancy_thresh=0.01, clip=False, march=None, distortion=0.):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -350,7 +365,7 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     surface is known before the first iteration and must not be overwritten by the student's density.  clip=True places every ray's
     samples between its first and last occupied cell (render_rays).  march: a world-space step handed to every train_step: the
     samples are the ragged lists of occupancy.march, N_samples is unused, and the refresh schedule stays as it is (the grid may
-    change between iterations and the march follows it)."""
+    change between iterations and the march follows it).  distortion: the weight of the distortion loss, handed to every train_step."""
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -367,6 +382,6 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
         idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
         step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                           perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                          occupancy=occupancy, clip=clip, march=march)
+                          occupancy=occupancy, clip=clip, march=march, distortion=distortion)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()

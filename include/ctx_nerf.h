@@ -375,6 +375,21 @@ int32_t ctx_raymarch_packed_fwd(const float *raw, const float *t, const float *d
 int32_t ctx_raymarch_packed_bwd(const float *raw, const float *t, const float *dt, const float *rays_d, const float *noise /*nullable*/,
                                 const int64_t *ray_off, int64_t R, int64_t n, int32_t white_bkgd, const float *g_rgb, const float *g_disp,
                                 const float *g_acc, const float *g_weights, const float *g_depth, float *grad_raw, ctx_stream_t stream);
+/* mip-NeRF 360's distortion loss of the weights on the same lists (definition: tests/distortion_rule.py).  With |d| = the norm of ray r's
+   direction as the compositing forms it, x_i = (t_i - t_0) * |d| and delta_i = dt_i * |d| (world lengths, centred on the ray's first sample):
+   loss[r] = sum_i sum_j w_i w_j |x_i - x_j| + (1/3) sum_i w_i^2 delta_i, evaluated by prefix sums as
+   sum_i w_i * (2 * (x_i * W_<i - V_<i) + delta_i * w_i / 3) with W_<i = sum_{j<i} w_j, V_<i = sum_{j<i} w_j x_j: t ascending inside a ray is a
+   precondition and is not checked.  loss [R]: every element written, 0 for a ray without samples and for a zero direction; a non-finite
+   weight poisons its own ray only.  n = 0 zero-fills loss (the lists may be null).  ray_off as ctx_raymarch_packed_fwd.  The chunks of a
+   ray are chained by two carried scalars, so there is no 4096-sample limit. */
+int32_t ctx_distortion_packed_fwd(const float *weights, const float *t, const float *dt, const float *rays_d, const int64_t *ray_off, int64_t R,
+                                  int64_t n, float *loss, ctx_stream_t stream);
+/* Backward with respect to weights: grad_w[i] = g_loss[r] * (2 * (x_i * (W_<i - W_>i) - (V_<i - V_>i)) + 2 * w_i * delta_i / 3) with the
+   suffix sums taken as total minus inclusive prefix.  grad_w [n]: every row of every ray written, nothing for a ray without samples.
+   Recomputed from the inputs, nothing saved; no atomics, one summation order; no 4096-sample limit.  No gradient with respect to t, dt
+   or rays_d. */
+int32_t ctx_distortion_packed_bwd(const float *weights, const float *t, const float *dt, const float *rays_d, const int64_t *ray_off, int64_t R,
+                                  int64_t n, const float *g_loss, float *grad_w, ctx_stream_t stream);
 
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
