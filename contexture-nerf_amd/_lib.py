@@ -81,6 +81,7 @@ SIGNATURES = {
     "ctx_raymarch_packed_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctx_distortion_packed_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "ctx_distortion_packed_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "ctx_resample_packed": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),
     "ctx_unet_param_count": (_i32, [_vp]),

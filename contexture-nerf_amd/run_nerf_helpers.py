@@ -487,21 +487,88 @@ def distortion_loss(weights, t, dt, rays_d, ray_off=None):
     return _distortion_fwd(w, t, dt, d, ray_off)
 
 
+RESAMPLE_MAX_K = 4096          # the fine lists are composited too: what the compositing backward holds per ray
+
+
+def _check_resample(resample, who):
+    """resample= as an int: 0 (off) or the fine samples per hit ray in [1, 4096]; anything else is refused."""
+    if isinstance(resample, bool) or not isinstance(resample, (int, np.integer)) or not 0 <= resample <= RESAMPLE_MAX_K:
+        raise L.CtxError(f"{who}: resample={resample!r}: want 0 (off) or an int in [1, {RESAMPLE_MAX_K}], the fine samples per hit ray")
+    return int(resample)
+
+
+def resample_packed(weights, ts, dt, ray_off, rays_o, rays_d, K, perturb=False, generator=None):
+    """Importance resampling of ragged per-ray sample lists, as nerf-pytorch's sample_pdf and nerfacc's resampling do it, by one
+    wave-per-ray HIP kernel (`ctx_resample_packed`; the rule: tests/resample_rule.py).  weights [n], ts [n] (interval
+    starts: OccupancyGrid.march(starts=True)), dt [n], ray_off int64 [R+1], rays_o / rays_d [R,3]
+    -> (ray_off' int64 [R+1], ray_id' int32 [n'], t' [n'], dt' [n'], pts' [n',3]): every ray with samples gets exactly K fine samples
+    (ray_off' = K * cumsum(count > 0), n' = K * hit rays), a ray without samples none.  Fine sample k sits where the ray's CDF of
+    m = min(max(w, 0), 1) + 1e-5 reaches (k + xi_k)/K, xi = 0.5 or with perturb one uniform draw per fine sample (stratified), always
+    inside a coarse interval; the widths dt' are the strata's occupied lengths, so they tile what the coarse widths tile.
+    Reading n' back SYNCS the host: a second sync after the march's, kept apart because the march returns before the weights exist.
+    Nothing here has a gradient: a weights, ts or dt that requires grad is refused."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= RESAMPLE_MAX_K:
+        raise L.CtxError(f"resample_packed: K={K!r}: want an int in [1, {RESAMPLE_MAX_K}]")
+    if any(isinstance(x, torch.Tensor) and x.requires_grad for x in (weights, ts, dt)):
+        raise L.CtxError("resample_packed: the resampling has no gradient with respect to weights / ts / dt; detach them")
+    if not all(isinstance(x, torch.Tensor) for x in (weights, ts, dt, ray_off, rays_o, rays_d)):
+        raise L.CtxError("resample_packed: want tensors weights [n], ts [n], dt [n], ray_off [R+1], rays_o [R,3], rays_d [R,3]")
+    n = weights.shape[0] if weights.dim() == 1 else -1
+    R = rays_d.shape[0] if rays_d.dim() == 2 else -1
+    if (n < 0 or R < 1 or ts.shape != (n,) or dt.shape != (n,) or ray_off.shape != (R + 1,) or tuple(rays_o.shape) != (R, 3)
+            or tuple(rays_d.shape) != (R, 3)):
+        raise L.CtxError(f"resample_packed: want weights [n], ts [n], dt [n], ray_off [R+1], rays_o [R,3], rays_d [R,3]; got "
+                         f"{tuple(weights.shape)}, {tuple(ts.shape)}, {tuple(dt.shape)}, {tuple(ray_off.shape)}, {tuple(rays_o.shape)}, "
+                         f"{tuple(rays_d.shape)}")
+    K = int(K)
+    p = (L.ptr(weights, torch.float32, "weights"), L.ptr(ts, torch.float32, "ts"), L.ptr(dt, torch.float32, "dt"),
+         L.ptr(ray_off, torch.int64, "ray_off"), L.ptr(rays_o, torch.float32, "rays_o"), L.ptr(rays_d, torch.float32, "rays_d"))
+    dev = rays_d.device
+    fine_off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(ray_off[1:] > ray_off[:-1], 0, dtype=torch.int64, out=fine_off[1:])
+    fine_off *= K
+    n1 = int(fine_off[R].item())                                                           # the second host sync
+    if n1 >= 2 ** 31:
+        raise L.CtxError(f"resample_packed: {n1} fine samples on {R} rays: want n' < 2^31; split the batch")
+    xi = torch.rand(n1, device=dev, generator=generator) if perturb else None
+    ray_id = torch.empty(n1, dtype=torch.int32, device=dev)
+    t1, dt1, pts = torch.empty(n1, device=dev), torch.empty(n1, device=dev), torch.empty(n1, 3, device=dev)
+    L.check(L.load().ctx_resample_packed(*p, R, n, K, L.ptr(fine_off), L.ptr(xi), n1, L.ptr(ray_id), L.ptr(t1), L.ptr(dt1), L.ptr(pts),
+                                         L.stream()))
+    return fine_off, ray_id, t1, dt1, pts
+
+
 def render_rays_marched(field, rays_o, rays_d, near, far, occupancy, step, white_bkgd=False, perturb=0., raw_noise_std=0., generator=None,
-                        return_extras=False):
+                        return_extras=False, resample=0):
     """The ray path on ragged per-ray sample lists, as instant-ngp and nerfacc march: occupancy.march places samples `step` apart (a
     world length) inside each ray's runs of occupied cells and nowhere else, field.forward_pts runs on exactly those n points, and
     raw2outputs_packed composites the lists directly: no expansion, no fill, no [R,S] tensor; one host sync (n).
     -> (rgb [R,3], disp [R], acc [R], weights [n], depth [R]); return_extras=True adds dict(ray_off, ray_id, t, dt, pts).
     perturb > 0 draws one uniform offset per sample inside its interval.  n = 0: the field is not called, every ray is empty and
-    the outputs carry no autograd graph."""
+    the outputs carry no autograd graph.
+    resample=K > 0 adds the hierarchical pass on the lists: march(starts=True), the field on the n coarse points, raw2outputs_packed,
+    resample_packed on the detached coarse weights (perturb > 0: stratified draws), the field on the n' = K * (hit rays) fine points,
+    raw2outputs_packed on (t', dt', ray_off').  The returned tuple is the fine one (weights [n']); the extras' ray_off / ray_id / t / dt /
+    pts are the fine lists, the coarse pass is kept as rgb0 / disp0 / acc0 / weights0 / depth0 (part of the autograd graph) and
+    ray_off0 / ray_id0 / t0 / dt0 / pts0.  The generator is drawn from in a fixed order: the march's u, the coarse noise, xi, the fine
+    noise.  Two host syncs (n, n').  n = 0: no field call and no fine pass; the coarse keys hold the same empty-ray outputs."""
+    K = _check_resample(resample, "render_rays_marched")
     if occupancy is None:
         raise L.CtxError("render_rays_marched: march needs an occupancy grid (occupancy=): the samples lie in its occupied cells")
     ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
-    ray_off, ray_id, t, dt, pts = occupancy.march(ro, rd, near, far, step, perturb=perturb > 0., generator=generator)
+    ray_off, ray_id, t, dt, pts, *ts = occupancy.march(ro, rd, near, far, step, perturb=perturb > 0., generator=generator, starts=K > 0)
     raw = L.f32c(field.forward_pts(pts)) if t.numel() else torch.empty(0, 4, device=ro.device)
     out = raw2outputs_packed(raw, t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
-    return (out, {'ray_off': ray_off, 'ray_id': ray_id, 't': t, 'dt': dt, 'pts': pts}) if return_extras else out
+    extras = {}
+    if K > 0:
+        extras = {'rgb0': out[0], 'disp0': out[1], 'acc0': out[2], 'weights0': out[3], 'depth0': out[4], 'ray_off0': ray_off,
+                  'ray_id0': ray_id, 't0': t, 'dt0': dt, 'pts0': pts}
+        if t.numel():
+            ray_off, ray_id, t, dt, pts = resample_packed(out[3].detach(), ts[0], dt, ray_off, ro, rd, K, perturb=perturb > 0.,
+                                                          generator=generator)
+            out = raw2outputs_packed(L.f32c(field.forward_pts(pts)), t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
+    extras.update({'ray_off': ray_off, 'ray_id': ray_id, 't': t, 'dt': dt, 'pts': pts})
+    return (out, extras) if return_extras else out
 
 
 def _occ_expand(raw_c, idx, total):
@@ -551,7 +618,7 @@ def field_on_occupied(field, occupancy, ro, rd, z_vals):
 
 
 def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z_vals=None, perturb=0., raw_noise_std=0.,
-                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None, clip=False, march=None):
+                N_importance=0, pytest=False, generator=None, return_extras=False, occupancy=None, clip=False, march=None, resample=0):
     """The ray path north_star names (absent in the reference): nerf-pytorch's render_rays —
     z_vals = near*(1-t)+far*t for t = linspace(0,1,N_samples) (or the given z_vals, e.g. from sample_pdf), pts = o + d*z,
     raw = field(pts) with field = NeRF2D(input_ch = 3*(1+2L), output_ch = 4) evaluated by the fused embed+MLP kernel, then
@@ -570,7 +637,11 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
     jitter, the hierarchical pass and the compositing then run on those z_vals as they do on any.  A ray that meets no occupied cell
     keeps near .. far, where the selection finds nothing for it.  No further host sync.
     march=step (needs occupancy; refuses clip=True, N_importance > 0, given z_vals and pytest=True, because it places and draws the samples itself): the
-    pass is render_rays_marched with that world-space step, N_samples is unused and weights is the flat list [n]."""
+    pass is render_rays_marched with that world-space step, N_samples is unused and weights is the flat list [n].
+    resample=K (an int in [1, 4096]; needs march): the march becomes the coarse pass and every hit ray gets K fine samples drawn from its
+    coarse weights, the hierarchical pass of the lists (render_rays_marched); the returned tuple is the fine one.  0: off."""
+    if _check_resample(resample, "render_rays") and march is None:
+        raise L.CtxError("render_rays: resample= resamples the marched lists; it needs march=")
     if march is not None:
         if clip:
             raise L.CtxError("render_rays: march= places the samples itself; it cannot be combined with clip=True")
@@ -581,7 +652,7 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
         if pytest:
             raise L.CtxError("render_rays: march= draws its jitter and noise from torch (generator=); it cannot be combined with pytest=True")
         return render_rays_marched(field, rays_o, rays_d, near, far, occupancy, march, white_bkgd=white_bkgd, perturb=perturb,
-                                   raw_noise_std=raw_noise_std, generator=generator, return_extras=return_extras)
+                                   raw_noise_std=raw_noise_std, generator=generator, return_extras=return_extras, resample=resample)
     if clip and occupancy is None:
         raise L.CtxError("render_rays: clip=True needs an occupancy grid (occupancy=): the spans are those of its occupied cells")
     if clip and z_vals is not None:

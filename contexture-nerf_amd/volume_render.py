@@ -150,14 +150,15 @@ class OccupancyGrid:
         D = float(np.sqrt(np.sum((self.hi.astype(np.float64) - self.lo.astype(np.float64)) ** 2)))
         return int(np.floor(D / float(step) * (1.0 + 2.0 ** -15))) + (3 * self.G + 4) // 2 + 1
 
-    def march(self, rays_o, rays_d, near, far, step, perturb=False, generator=None):
+    def march(self, rays_o, rays_d, near, far, step, perturb=False, generator=None, starts=False):
         """-> (ray_off int64 [R+1], ray_id int32 [n], t [n], dt [n], pts [n,3]): every ray walks the grid once and gets samples `step`
         apart (a WORLD length, whatever |rays_d| is) inside its runs of occupied cells and nowhere else (`ctx_occ_march_count`, the
         exclusive scan, `ctx_occ_march_write`).  Ray r owns ray_off[r] .. ray_off[r+1], ascending in t; sample j of a run [a, b] cut into k
         intervals of width dt sits at a + (j + u) * dt with u = 0.5, or with perturb one uniform draw per sample (drawn after the count,
         which does not depend on it: a seeded generator repeats exactly).  n = 0 is legal: empty lists.  Reading n back SYNCS the host,
         the path's one sync.  A (G, box, step) whose per-ray bound `march_bound` exceeds 4096, the most the compositing backward holds,
-        is refused."""
+        is refused.  starts=True adds a sixth tensor ts [n] = t - u * dt, the start of each sample's interval (what rnh.resample_packed
+        takes): one binary32 torch expression, u = 0.5 without perturb."""
         near, far, step = float(near), float(far), float(step)
         if not (near < far and np.isfinite(near) and np.isfinite(far)):
             raise L.CtxError(f"OccupancyGrid.march: want finite near < far, got {near}, {far}")
@@ -188,6 +189,8 @@ class OccupancyGrid:
         t, dt, pts = torch.empty(n, device=dev), torch.empty(n, device=dev), torch.empty(n, 3, device=dev)
         L.check(lib.ctx_occ_march_write(p_o, p_d, R, near, far, *grid, L.ptr(ray_off), L.ptr(u), n, L.ptr(ray_id), L.ptr(t), L.ptr(dt),
                                         L.ptr(pts), L.stream()))
+        if starts:
+            return ray_off, ray_id, t, dt, pts, t - (u if perturb else 0.5) * dt
         return ray_off, ray_id, t, dt, pts
 
     def select(self, rays_o, rays_d, z_vals):
@@ -242,17 +245,18 @@ class OccupancyGrid:
 
 @torch.no_grad()
 def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None, clip=False,
-                 march=None):
+                 march=None, resample=0):
     """-> dict(rgb [h,W,3], depth [h,W], acc [h,W], disp [h,W]) for the row range `rows` (default: all).
     N_importance > 0 adds nerf-pytorch's hierarchical pass (render_rays: sample_pdf(det=True) on the coarse weights, merged
     and sorted with the coarse samples, evaluated by the same field).  occupancy: an OccupancyGrid; clip: samples between each
     ray's first and last occupied cell; see render_rays.  march: a world-space step; the samples are then the ragged lists of
-    occupancy.march (render_rays_marched) and N_samples is unused."""
+    occupancy.march (render_rays_marched) and N_samples is unused.  resample: with march, the fine samples per hit ray of the
+    importance-resampled second pass (render_rays_marched); 0: none."""
     ro, rd = rnh.get_rays(H, W, K, c2w)
     r0, r1 = (0, H) if rows is None else rows
     ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
     rgb, disp, acc, wts, depth = rnh.render_rays(field, ro, rd, near, far, N_samples, white_bkgd=white_bkgd, N_importance=N_importance,
-                                                 occupancy=occupancy, clip=clip, march=march)
+                                                 occupancy=occupancy, clip=clip, march=march, resample=resample)
     h = r1 - r0
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
@@ -289,13 +293,14 @@ def depth_for_diffusion(depth, acc, thresh=0.5):
 @torch.no_grad()
 def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples=128, guidance_scale=7.5, strength=1.0,
                       num_inference_steps=50, fixed_seed=0, image_size=512, rank=0, world=1, group=None, occupancy=None, clip=False,
-                      march=None):
+                      march=None, resample=0):
     """configs[4] end to end on this rank's rows; every rank returns the refined image [1,3,S,S] and the gathered render.
     occupancy, clip: an OccupancyGrid for the render and whether the samples are placed inside its spans (render_rays).
-    march: a world-space step for the render's ragged sample lists (render_rays_marched); N_samples is then unused."""
+    march: a world-space step for the render's ragged sample lists (render_rays_marched); N_samples is then unused.  resample: with
+    march, the fine samples per hit ray of the resampled second pass."""
     K = pinhole(H, W)
     tile = render_image(field, H, W, K, c2w, near, far, N_samples, rows=shard_rows(H, rank, world), occupancy=occupancy,
-                        clip=clip, march=march)
+                        clip=clip, march=march, resample=resample)
     rgb = gather_rows(tile['rgb'], H, group)
     depth = gather_rows(tile['depth'], H, group)
     acc = gather_rows(tile['acc'], H, group)
@@ -309,7 +314,7 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0.):
+               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0., resample=0):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
@@ -321,13 +326,16 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
     in the same way.
     distortion > 0 adds distortion * mean over the rays of rnh.distortion_loss (mip-NeRF 360's regulariser, which pulls each ray's
     weights together): on the march path of the weights and lists the render returned, otherwise of the fine pass's weights and final
-    z_vals.  The dict then gains 'distortion', the unweighted mean, detached.  distortion = 0 (the default) runs nothing new."""
+    z_vals.  The dict then gains 'distortion', the unweighted mean, detached.  distortion = 0 (the default) runs nothing new.
+    resample=K > 0 (needs march): the march is the coarse pass and every hit ray gets K fine samples drawn from its detached coarse
+    weights (render_rays_marched); the loss is img2mse(fine) + img2mse(coarse), the distortion loss acts on the fine weights and lists,
+    and the step costs a second host sync."""
     if not distortion >= 0.:
         raise L.CtxError(f"train_step: distortion={distortion}: want a weight >= 0")
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
-                                  return_extras=True, occupancy=occupancy, clip=clip, march=march)
+                                  return_extras=True, occupancy=occupancy, clip=clip, march=march, resample=resample)
     target = target_rgb.reshape(-1, 3)
     img_loss = rnh.img2mse(out[0], target)
     loss = img_loss
@@ -351,7 +359,7 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False, march=None, distortion=0.):
+              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -365,7 +373,8 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     surface is known before the first iteration and must not be overwritten by the student's density.  clip=True places every ray's
     samples between its first and last occupied cell (render_rays).  march: a world-space step handed to every train_step: the
     samples are the ragged lists of occupancy.march, N_samples is unused, and the refresh schedule stays as it is (the grid may
-    change between iterations and the march follows it).  distortion: the weight of the distortion loss, handed to every train_step."""
+    change between iterations and the march follows it).  distortion: the weight of the distortion loss, handed to every train_step.
+    resample: with march, the fine samples per hit ray of the resampled second pass, handed to every train_step."""
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -382,6 +391,6 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
         idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
         step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                           perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                          occupancy=occupancy, clip=clip, march=march, distortion=distortion)
+                          occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()

@@ -391,6 +391,21 @@ int32_t ctx_distortion_packed_fwd(const float *weights, const float *t, const fl
 int32_t ctx_distortion_packed_bwd(const float *weights, const float *t, const float *dt, const float *rays_d, const int64_t *ray_off, int64_t R,
                                   int64_t n, const float *g_loss, float *grad_w, ctx_stream_t stream);
 
+/* Importance resampling of the same lists (definition: tests/resample_rule.py).  Ray r's S = ray_off[r+1] - ray_off[r]
+   coarse samples arrive as interval start ts [n], width dt [n] >= 0 and weight weights [n]; it gets the K fine samples fine_off[r] ..
+   fine_off[r+1] (fine_off int64 [R+1] = K * the exclusive scan of S > 0; n_fine = fine_off[R]).  Mass m_i = min(max(w_i, 0), 1) + 1e-5 (a NaN
+   weight counts as 0, +inf as 1); C, l = the exclusive prefix sums of m and dt, W, L their totals.  At u in [0, 1]: tau = u*W, i = the last
+   interval with C_i <= tau, f = clamp((tau - C_i)/m_i, 0, 1).  Fine sample k < K: u = ((float)k + xi_k)/(float)K with xi [n_fine]
+   (nullable: 0.5) one draw in [0, 1) per fine sample; t' = ts_i + f*dt_i (always inside a coarse interval, never in a gap between runs);
+   dt' = l((k+1)/K) - l(k/K) with l(u) = min(l_i + f*dt_i, l_{i+1}), l(0) = 0 and l(1) = L, so the widths are >= 0 and tile the ray's
+   occupied length; p = o + d*t' (the bits of ctx_occ_points); ray_id = r.  The prefix sums are made non-descending by a running maximum
+   (the identity on sequential sums).  Every element of a hit ray's fine span is written, nothing for a ray without samples; whatever a
+   ray computes it stores only inside [fine_off[r], fine_off[r+1]) and [0, n_fine), at most K entries.  No atomics, one summation order;
+   any S <= 2^31 - 64 (a longer ray is taken as empty).  1 <= K <= 4096 (what the compositing backward holds); n = 0 or n_fine = 0 launches nothing (the lists may be null). */
+int32_t ctx_resample_packed(const float *weights, const float *ts, const float *dt, const int64_t *ray_off, const float *rays_o,
+                            const float *rays_d, int64_t R, int64_t n, int32_t K, const int64_t *fine_off, const float *xi /*nullable*/,
+                            int64_t n_fine, int32_t *ray_id_out, float *t_out, float *dt_out, float *pts_out, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
