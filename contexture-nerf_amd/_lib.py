@@ -102,6 +102,7 @@ SIGNATURES = {
     "ctx_unet_forward_ref": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "ctx_unet_set_residual_fp32": (_i32, [_vp, _i32]),
     "ctx_unet_stats": (_i32, [_vp, _i32, _vp, _vp]),
+    "ctx_unet_gn_epilogue_counts": (_i32, [_vp, _vp, _vp]),
     "ctx_unet_set_taps": (_i32, [_vp, _vp, _i64]),
     "ctx_unet_tap_count": (_i32, [_vp]),
     "ctx_unet_tap_info": (_i32, [_vp, _i32, _vp, _vp, _vp]),
@@ -126,9 +127,12 @@ SIGNATURES = {
     "ctx_conv3x3_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ctx_conv3x3_seg_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32,
                                    _vp, _i32, _vp, _vp]),
+    "ctx_conv3x3_gn_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ctx_gemm_last_kernel": (None, [_vp, _vp]),
     "ctx_groupnorm_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_groupnorm2_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "ctx_groupnorm_apply_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "ctx_groupnorm_slabs_f16": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "ctx_layernorm_f16": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
     "ctx_attention_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "ctx_attention_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp]),

@@ -44,6 +44,13 @@ struct Engine {
     int64_t launches[3] = {0, 0, 0};
     double flops[3] = {0, 0, 0};
 
+    // GroupNorm partials that a producer's epilogue has written (engine_linear / engine_conv3 with a GnReq): the tensor they belong to
+    // and its GroupNorm shape.  A graph's GroupNorm op takes them only for exactly this tensor and shape, and every GroupNorm op
+    // clears the tag, so partials never outlive the next GroupNorm.  Counters of the current run: GroupNorms that ran on a
+    // producer's partials / that read split-K slabs in place of a reduced tensor.
+    struct GnTag { const void *x = nullptr; int B = 0, HW = 0, C = 0, groups = 0, NS = 0; } gn_tag;
+    int64_t gn_from_producer = 0, gn_from_slabs = 0;
+
     size_t walloc(size_t n) { size_t o = wtop; wtop += (n + 127) / 128 * 128; return o; }
     size_t add(const std::string &name, std::vector<int64_t> shp, int kind, size_t dst, int a = 0, int b = 0)
     {
@@ -65,7 +72,11 @@ struct Engine {
     }
     f16 *allocH(size_t n) { return (f16 *)alloc(n * 2); }
 
-    void begin() { top = 0; peak = 0; rc = 0; for (int k = 0; k < 3; ++k) { launches[k] = 0; flops[k] = 0; } }   // a run from an empty arena
+    void begin()                                               // a run from an empty arena
+    {
+        top = 0; peak = 0; rc = 0; gn_tag = GnTag(); gn_from_producer = 0; gn_from_slabs = 0;
+        for (int k = 0; k < 3; ++k) { launches[k] = 0; flops[k] = 0; }
+    }
     void note(int klass, double fl, int n = 1) { launches[klass] += n; flops[klass] += fl; }
     bool live() const { return !dry && rc == 0; }
     // device-to-device copies on the run's stream
@@ -78,9 +89,13 @@ struct Engine {
 #define ENGINE_RUN(e, expr) do { if ((e)->live()) { int r__ = (expr); if (r__ != 0) (e)->rc = r__; } } while (0)
 #define ENGINE_LAUNCH(e, kernel, grid, block, lds, ...) do { if ((e)->live()) hipLaunchKernelGGL(kernel, grid, block, lds, (e)->s, __VA_ARGS__); } while (0)
 
+// A request that the producer of `out` also write the GroupNorm partials of a following GroupNorm(groups) over samples of HW rows, into
+// `part` (ctx_groupnorm_ws_bytes).  Honoured (a live run only): e.gn_tag names `out`; declined: the tag stays empty and the GroupNorm
+// op computes its statistics itself.
+struct GnReq { float *part = nullptr; int groups = 0, HW = 0; };
 // out[M, ldc] = X[M,K] Wt[N,K]^T (+ bias[N]) (+ res[M,N]); ldc 0 = dense; epi 1 = GEGLU (out has N/2 columns); res32 / out32: res / out are fp32
 void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, const void *res, int M, int N, int K, void *out, int ldc = 0,
-                   int epi = 0, bool res32 = false, bool out32 = false);
+                   int epi = 0, bool res32 = false, bool out32 = false, const GnReq *gn = nullptr);
 // a 3x3 convolution's geometry beyond "stride 1, padding 1" (GemmArgs has each meaning); Ho = ((H << ups) - 1) / stride + 1, Wo alike
 struct ConvGeom { int stride = 1, ups = 0, poff = 0, zins = 0; };
 // K segments of a convolution (GemmArgs::nseg): n 1x1 products over tensors x[s] [B,H,W,C[s]] of the output's pixel grid, weights
@@ -90,7 +105,11 @@ struct ConvSegs { int n = 0; const f16 *x[2] = {nullptr, nullptr}; const f16 *w[
 // The segments' product is counted as a class-0 op of its own (the 1x1 convolution it stands for).
 void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
                   ConvGeom g = ConvGeom(), const f16 *rowbias = nullptr, int ldrb = 0, bool res32 = false, bool out32 = false,
-                  const ConvSegs *segs = nullptr);
+                  const ConvSegs *segs = nullptr, const GnReq *gn = nullptr, GnSlabs *slabs = nullptr);
+// Split-K factor that engine_conv3 will run this stride-1 convolution with when asked to keep its slabs (1: it does not split).
+// slabs != null in engine_conv3: the reduce launch is skipped, `out` is not written (pass null) and *slabs describes the fp32 slabs,
+// which stay allocated above the caller's arena mark; only where this function returns > 1.
+int engine_conv3_split(int B, int H, int W, int Cin, int Cout);
 
 // `run` as a dry run: nothing is launched, the arena only measures (e.peak), the counters count; -> the run's return code
 template <class F> int engine_dry_run(Engine *e, F run)

@@ -24,7 +24,7 @@ int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace
 }
 
 // one GEMM / implicit-GEMM conv of a fully described problem: plan, split-K scratch above the arena mark, dispatch, release
-static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs = nullptr)
+static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs = nullptr, const GnReq *gn = nullptr, GnSlabs *slabs = nullptr)
 {
     e.note(0, 2.0 * a.M * a.N * a.K);
     size_t mark = e.top;
@@ -41,22 +41,36 @@ static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs 
     }
     if (a.zins) a.use8 = 0;        // the zero-inserted grid is an addressing mode of gemm.hip only
     if (a.splitk > 1) a.part = (float *)e.alloc((size_t)a.splitk * a.M * a.N * 4);
+    if (gn && gn->part && gn->groups > 0 && a.N % gn->groups == 0) { a.gn_part = gn->part; a.gn_cg = a.N / gn->groups; a.gn_hw = gn->HW; }
+    if (slabs) {
+        a.keep_slabs = 1;
+        *slabs = GnSlabs{a.part, a.splitk, (size_t)a.M * a.N, a.bias, a.bias2, a.rowbias, a.ldrb};
+    }
     ENGINE_RUN(&e, ctx_gemm_dispatch(a, conv, e.s));
-    e.top = mark;
+    if (e.live() && a.gn_part) e.gn_tag = Engine::GnTag{a.out, a.M / a.gn_hw, a.gn_hw, a.N, gn->groups, a.gn_ns};
+    if (!slabs) e.top = mark;
+}
+
+int engine_conv3_split(int B, int H, int W, int Cin, int Cout)
+{
+    GemmArgs a = {};
+    a.Ho = H; a.Wo = W; a.M = B * H * W; a.N = Cout; a.K = 9 * Cin; a.H = H; a.W = W; a.Cin = Cin; a.stride = 1;
+    ctx_gemm_plan(a, true);
+    return (a.splitk > 1 && a.splitk <= a.K / 64) ? a.splitk : 1;       // (gemm144.hip clips the factor to K / 64)
 }
 
 void engine_linear(Engine &e, const f16 *X, const f16 *Wt, const f16 *bias, const void *res, int M, int N, int K, void *out, int ldc, int epi,
-                   bool res32, bool out32)
+                   bool res32, bool out32, const GnReq *gn)
 {
     GemmArgs a = {};
     a.X = X; a.Wt = Wt; a.bias = bias; a.residual = (const f16 *)res; a.out = (f16 *)out;
     a.M = M; a.N = N; a.K = K; a.ldc = ldc ? ldc : epi == 1 ? N / 2 : N; a.ldr = N; a.rows_per_batch = 1; a.ldrb = N; a.epi = epi;
     a.res32 = res32; a.out32 = out32;
-    engine_gemm(e, a, false);
+    engine_gemm(e, a, false, nullptr, gn);
 }
 
 void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const void *res, int B, int H, int W, int Cin, int Cout, void *out,
-                  ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32, const ConvSegs *segs)
+                  ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32, const ConvSegs *segs, const GnReq *gn, GnSlabs *slabs)
 {
     GemmArgs a = {};
     a.Ho = ((H << g.ups) - 1) / g.stride + 1; a.Wo = ((W << g.ups) - 1) / g.stride + 1;
@@ -64,7 +78,7 @@ void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = ldrb;
     a.H = H; a.W = W; a.Cin = Cin; a.stride = g.stride; a.ups = g.ups; a.poff = g.poff; a.zins = g.zins;
     a.res32 = res32; a.out32 = out32;
-    engine_gemm(e, a, true, segs);
+    engine_gemm(e, a, true, segs, gn, slabs);
 }
 
 int engine_finish(Engine *e, const char *who)

@@ -340,6 +340,55 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(GemmArgs a)
     }
 }
 
+// The same second pass with a GroupNorm partials request (GemmArgs::gn_part): grid (slots, samples), a block owns RB whole rows of one
+// sample and a thread one 4-feature column of them (c4n columns x PL row lanes; blockDim is rounded up to whole waves), so that it can
+// sum the fp16 values it stores.  Operand order and rounding are k_splitk_reduce's: the output is bit-identical.  Fold, fixed order:
+// thread sums [PL][4][c4n] -> channel sums [N] -> 8 lanes per group and a shuffle tree -> part[b][slot][g].
+__global__ __launch_bounds__(1024) void k_splitk_reduce_gn(GemmArgs a, int RB, int PL)
+{
+    extern __shared__ float2 s_gn[];                               // [PL][4][c4n], then [N]
+    const int c4n = a.N / 4, tid = threadIdx.x;
+    const int c4 = tid % c4n, pl = tid / c4n, nn = c4 * 4;
+    const int b = blockIdx.y, slot = blockIdx.x;
+    const size_t MN = (size_t)a.M * a.N;
+    float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
+    if (pl < PL) {
+        for (int r = pl; r < RB; r += PL) {
+            const int m = b * a.gn_hw + slot * RB + r;
+            f32x4 v = *(const f32x4 *)(a.part + (size_t)m * a.N + nn);
+            for (int sidx = 1; sidx < a.splitk; ++sidx) {
+                f32x4 p = *(const f32x4 *)(a.part + sidx * MN + (size_t)m * a.N + nn);
+                v += p;
+            }
+            v = bias4(a, v, nn);
+            const f16x4 o = store4<true>(a, v, m, a.rowbias ? m / a.rows_per_batch : 0, nn);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float f = (float)o[j]; gs[j] += f; gq[j] += f * f; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_gn[(pl * 4 + j) * c4n + c4] = make_float2(gs[j], gq[j]);
+    }
+    __syncthreads();
+    float2 *s_ch = s_gn + PL * 4 * c4n;
+    for (int c = tid; c < a.N; c += blockDim.x) {
+        const int cell = (c & 3) * c4n + (c >> 2);
+        float ss = 0.f, qq = 0.f;
+        for (int l = 0; l < PL; ++l) { const float2 t = s_gn[l * 4 * c4n + cell]; ss += t.x; qq += t.y; }
+        s_ch[c] = make_float2(ss, qq);
+    }
+    __syncthreads();
+    const int cg = a.gn_cg, G = a.N / cg, octs = (int)blockDim.x >> 3;
+    for (int g0 = 0; g0 < G; g0 += octs) {
+        const int g = g0 + (tid >> 3), l8 = tid & 7;
+        float ss = 0.f, qq = 0.f;
+        if (g < G)
+            for (int k = l8; k < cg; k += 8) { const float2 t = s_ch[g * cg + k]; ss += t.x; qq += t.y; }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, 64); qq += __shfl_xor(qq, o, 64); }
+        if (g < G && l8 == 0) *(float2 *)(a.gn_part + (((size_t)b * a.gn_ns + slot) * G + g) * 2) = make_float2(ss, qq);
+    }
+}
+
 // tile ids (CTX_GEMM_TILE / ctx_gemm_tune): WM x WN waves of MI x NI 32x32 blocks
 //   0: 256x128 8w   1: 128x128 4w   2: 256x64 4w   3: 128x64 2w   4: 64x64 1w
 //   5: 64x64 4w (32x32 per wave)   6: 64x64 2w (64x32)   7: 128x128 8w (32x64)   8: 64x128 4w (32x64)   9: 128x64 4w (64x32)
@@ -377,6 +426,29 @@ static void launch_gemm(GemmArgs &a, hipStream_t s)
 
 static void launch_reduce(GemmArgs &a, hipStream_t s)
 {
+    if (a.gn_part) {
+        // rows per block: the smallest divisor of the sample that leaves <= CTX_GN_MAX_SLOTS slots and ~256 blocks in all
+        const int c4n = a.N / 4, hw = a.gn_hw;
+        bool ok = !a.res32 && !a.out32 && a.N % 4 == 0 && c4n <= 1024 && hw > 0 && a.M % hw == 0 && a.gn_cg >= 1 && a.N % a.gn_cg == 0 && a.ldc == a.N;
+        if (ok) {
+            const int B = a.M / hw, want = B >= 2 ? (CTX_GN_MAX_SLOTS < cdiv(256, B) ? CTX_GN_MAX_SLOTS : cdiv(256, B)) : CTX_GN_MAX_SLOTS;
+            int rb = cdiv(hw, want);
+            while (hw % rb) ++rb;
+            const int pl = rb < 1024 / c4n ? rb : 1024 / c4n, threads = cdiv(c4n * pl, 64) * 64;
+            a.gn_ns = hw / rb;
+            const size_t lds = ((size_t)pl * 4 * c4n + a.N) * sizeof(float2);
+            static bool attr = false;
+            if (!attr) { (void)hipFuncSetAttribute((const void *)k_splitk_reduce_gn, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); attr = true; }
+            if (ctx_prof_on()) {
+                hipEvent_t e0, e1;
+                ctx_prof_events(0, &e0, &e1);
+                hipExtLaunchKernelGGL(k_splitk_reduce_gn, dim3(a.gn_ns, B), dim3(threads), lds, s, e0, e1, 0, a, rb, pl);
+            } else
+                hipLaunchKernelGGL(k_splitk_reduce_gn, dim3(a.gn_ns, B), dim3(threads), lds, s, a, rb, pl);
+            return;
+        }
+        a.gn_part = nullptr;                                       // declined: the plain reduce below
+    }
     size_t total = (size_t)a.M * (a.N / 4);
     unsigned nb = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     ctx_launch<k_splitk_reduce>(0, dim3(nb), dim3(256), 0, s, a);
@@ -534,7 +606,14 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
         }
 #undef CTX_LAUNCH
     }
-    if (a.splitk > 1) launch_reduce(a, s);                                   // every kernel above leaves fp32 partials then
+    // a GroupNorm partials request: served by a gemm144.hip tile's epilogue (it accepted or cleared the request itself) or, behind
+    // split-K, by the reduce; no other tile takes it
+    if (a.gn_part && a.splitk <= 1 && !(launched && want8 >= 4)) a.gn_part = nullptr;
+    if (a.keep_slabs && a.splitk <= 1) {
+        ctx_set_error("gemm: the slabs were to be kept but the launch did not split K");
+        return CTX_E_STATE;
+    }
+    if (a.splitk > 1 && !a.keep_slabs) launch_reduce(a, s);                  // every kernel above leaves fp32 partials then
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         ctx_set_error("gemm launch failed: %s", hipGetErrorString(e));
@@ -612,6 +691,37 @@ extern "C" int32_t ctx_conv3x3_seg_f16(const void *x, const void *w, const void 
     a.K += a.segC[0] + a.segC[1];
     CTX_REQUIRE((int64_t)a.M * (Cin > Ca + Cb ? Cin : Ca + Cb) < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31), "conv3x3_seg: tensor too large for 32-bit offsets");
     return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
+}
+
+// The resnet's first convolution as the engine runs it in front of norm2 (diffusers ResnetBlock2D.forward: conv1, + time embedding,
+// norm2; reference call site src/stable_diffusion_depth.py:422-423): a stride-1 conv3x3 with either
+//   gn_part != null: a request for the partials of GroupNorm(groups) over its output (GemmArgs::gn_part); *slots = slots per sample
+//                    that were written (ctx_groupnorm_apply_f16 takes them), 0 = the launched kernel declined; or
+//   keep_slabs != 0: split-K without the reduce launch; y is not written (may be null) and ctx_groupnorm_slabs_f16 reads `part`
+//                    (*slots, when given, = the split factor that ran).
+// splitk / part as ctx_conv3x3_seg_f16.  Honours ctx_gemm_tune.
+extern "C" int32_t ctx_conv3x3_gn_f16(const void *x, const void *w, const void *bias, const void *bias2, const void *rowbias, const void *residual,
+                                      int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void *part, int32_t splitk, int32_t keep_slabs,
+                                      int32_t groups, void *gn_part, int32_t *slots, void *y, ctx_stream_t stream)
+{
+    CTX_REQUIRE(x && w && (y || keep_slabs), "conv3x3_gn: null pointer");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && Cout % 8 == 0 && splitk != 0, "conv3x3_gn: need Cin%%64==0, Cout%%8==0 (Cin=%d Cout=%d)", Cin, Cout);
+    CTX_REQUIRE(!gn_part || (slots && groups > 0 && Cout % groups == 0 && !keep_slabs), "conv3x3_gn: a partials request needs slots, groups dividing Cout, and no kept slabs");
+    CTX_REQUIRE(!keep_slabs || (part && (splitk > 1 || splitk < 0)), "conv3x3_gn: kept slabs need split-K");
+    GemmArgs a = {};
+    a.Ho = H; a.Wo = W;
+    a.X = (const f16 *)x; a.Wt = (const f16 *)w; a.bias = (const f16 *)bias; a.bias2 = (const f16 *)bias2; a.rowbias = (const f16 *)rowbias;
+    a.residual = (const f16 *)residual; a.out = (f16 *)y;
+    a.M = B * H * W; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = H * W; a.ldrb = Cout;
+    a.H = H; a.W = W; a.Cin = Cin; a.stride = 1;
+    a.tile = -1; a.use8 = -1;
+    if (splitk < 0 && part) ctx_gemm_plan(a, true); else a.splitk = part ? splitk : 1;      // < 0: the engine's plan (kernel and split)
+    a.part = (float *)part; a.keep_slabs = keep_slabs ? 1 : 0;
+    if (gn_part) { a.gn_part = (float *)gn_part; a.gn_cg = Cout / groups; a.gn_hw = H * W; }
+    CTX_REQUIRE((int64_t)a.M * Cin < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31), "conv3x3_gn: tensor too large for 32-bit offsets");
+    const int rc = ctx_gemm_dispatch(a, true, (hipStream_t)stream);
+    if (slots) *slots = rc != CTX_OK ? 0 : keep_slabs ? a.splitk : a.gn_part ? a.gn_ns : 0;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

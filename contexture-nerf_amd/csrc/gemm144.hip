@@ -27,7 +27,9 @@
 // offset from the lane's centre-tap pointer and a bit of a 9-bit in-bounds mask
 // BMB: token rows of the tile in 16-row blocks: 9 (144 x 160) or 18 (288 x 160: 103 instead of 76 FLOP per staged byte, for problems
 // with >= ~512 such tiles, i.e. the lockstep batch; its 56 KB stages leave room for a ring of 2 only, so it runs the lockstep schedule)
-template <int WM, int WN, bool CONV, int NS, int VAR, bool UPS = false, int BMB = 9>
+// GNP: the GroupNorm partials request (GemmArgs::gn_part) is honoured in the LDS-staged epilogue; instantiated for the 15-wave forms
+// only, and the kernels without it compile to what they were
+template <int WM, int WN, bool CONV, int NS, int VAR, bool UPS = false, int BMB = 9, bool GNP = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
 {
     constexpr int NW = WM * WN, MI = BMB / WM, NI = 10 / WN;        // waves; 16x16 blocks per wave along tokens / features
@@ -420,6 +422,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         ctx_barrier();                               // every wave is done with the ring
         constexpr int NT = 64 * NW, CPR = G144_BN / 8;              // chunks of 8 features per row
+        // GNP: NT is a whole number of rows of chunks, so a thread keeps its 8-channel column over every pass of the walk below and
+        // sums what it stores (the values as rounded to fp16: what k_gn_apply will read); nothing is masked (the launcher checks)
+        static_assert(!GNP || (NT % CPR == 0 && NT % G144_BN == 0 && (NT / CPR) % (NT / G144_BN) == 0), "GroupNorm partials: whole chunk rows per pass");
+        float gs[8], gq[8];
+        if constexpr (GNP) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { gs[j] = 0.f; gq[j] = 0.f; }
+        }
         // 144 rows at a time (the 288-row tile takes two passes through the same patch)
 #pragma unroll
         for (int half = 0; half < BMB / 9; ++half) {
@@ -440,7 +450,49 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
                 const f32x4 v0 = *(const f32x4 *)(tile + row * RS + c8), v1 = *(const f32x4 *)(tile + row * RS + c8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 bias8(a, v, n);
-                store8(a, v, m, n);
+                const f16x8 o = store8(a, v, m, n);
+                if constexpr (GNP) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { const float f = (float)o[j]; gs[j] += f; gq[j] += f * f; }
+                }
+            }
+        }
+        if constexpr (GNP) {
+            // Fold to one (sum, sum of squares) per group of the tile, in a fixed order, through the patch's LDS (read out by now):
+            // thread sums [PLN pixel lanes][8][CPR] (8-byte cells, consecutive lanes consecutive cells) -> A: channel sums over NA
+            // slices of the pixel lanes [NA][160] -> B: 8 lanes walk a group's NA x cg cells, then a shuffle tree (as k_gn_stats).
+            constexpr int PLN = NT / CPR, NA = NT / G144_BN, LPA = PLN / NA;
+            float2 *sp = (float2 *)smem, *sc = sp + PLN * 8 * CPR;
+            const int c8 = tid % CPR, pl = tid / CPR;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            ctx_barrier();                                          // everybody has read the patch out
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sp[(pl * 8 + j) * CPR + c8] = make_float2(gs[j], gq[j]);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            ctx_barrier();
+            {
+                const int sl = tid / G144_BN, ci = tid - sl * G144_BN;      // cell ci = j * CPR + c8 of a pixel lane: channel c8 * 8 + j
+                float ss = 0.f, qq = 0.f;
+#pragma unroll
+                for (int l = 0; l < LPA; ++l) { const float2 t = sp[(sl * LPA + l) * G144_BN + ci]; ss += t.x; qq += t.y; }
+                sc[sl * G144_BN + (ci % CPR) * 8 + ci / CPR] = make_float2(ss, qq);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            ctx_barrier();
+            const int cg = a.gn_cg, ng = G144_BN / cg, cells = NA * cg;
+            const int oc = tid >> 3, l8 = tid & 7;                  // NT / 8 = 120 octets >= the tile's groups (cg >= 2)
+            float ss = 0.f, qq = 0.f;
+            if (oc < ng)
+                for (int k = l8; k < cells; k += 8) {
+                    const int sl = k / cg;
+                    const float2 t = sc[sl * G144_BN + oc * cg + (k - sl * cg)];
+                    ss += t.x; qq += t.y;
+                }
+#pragma unroll
+            for (int o = 4; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, 64); qq += __shfl_xor(qq, o, 64); }
+            if (oc < ng && l8 == 0) {
+                const int b = m0 / a.gn_hw, slot = (m0 - b * a.gn_hw) / BM;
+                *(float2 *)(a.gn_part + (((size_t)b * a.gn_ns + slot) * (a.N / cg) + n0 / cg + oc) * 2) = make_float2(ss, qq);
             }
         }
         return;
@@ -486,9 +538,27 @@ int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
     static const int stg = ctx_env_int("CTX_G144_STAGE", 1);
     a.stage_epi = stg && form != 0 && a.N % 8 == 0 && a.ldc % 8 == 0 && (!a.residual || a.ldr % 8 == 0) && (!a.rowbias || a.ldrb % 8 == 0);
     const dim3 grid(a.ntm * a.ntn * S);
+    // GroupNorm partials: a tile lies inside one sample and holds whole groups, nothing is masked, and the rows are walked through
+    // LDS (the 15-wave forms).  With split-K the request is the reduce kernel's (gemm.hip); otherwise a request this tile cannot
+    // serve is cleared: the caller sees the decline.
+    bool gnp = false;
+    if (a.gn_part && S == 1) {
+        gnp = a.stage_epi && !(conv && a.ups) && a.gn_hw > 0 && a.gn_cg >= 2 && a.M % a.gn_hw == 0 && a.gn_hw % bm == 0 && a.gn_hw / bm <= CTX_GN_MAX_SLOTS &&
+              a.N % G144_BN == 0 && G144_BN % a.gn_cg == 0 && a.ldc == a.N;
+        if (gnp) a.gn_ns = a.gn_hw / bm; else a.gn_part = nullptr;
+    }
     // threads, ring depth, then the kernel's template arguments
 #define G144_GO(NT_, NS_, ...) ctx_launch<k_gemm144<__VA_ARGS__>>(0, grid, dim3(NT_), (size_t)NS_ * (bm + G144_BN) * 64 * sizeof(f16), s, a)
     const bool ups = conv && a.ups;
+    if (gnp) {                                                       // the same forms with the partials in the epilogue
+        switch (form) {
+        case 4: if (conv) G144_GO(960, 2, 3, 5, true, 2, 0, false, 18, true); else G144_GO(960, 2, 3, 5, false, 2, 0, false, 18, true); break;
+        case 1: if (conv) G144_GO(960, 3, 3, 5, true, 3, 0, false, 9, true); else G144_GO(960, 3, 3, 5, false, 3, 0, false, 9, true); break;
+        case 2: if (conv) G144_GO(960, 4, 3, 5, true, 4, 1, false, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 1, false, 9, true); break;
+        default: if (conv) G144_GO(960, 4, 3, 5, true, 4, 2, false, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 2, false, 9, true); break;
+        }
+        return 1;
+    }
     switch (form) {
     case 4:                                                          // 288 x 160, 15 waves, lockstep, ring of 2
         if (!conv) G144_GO(960, 2, 3, 5, false, 2, 0, false, 18);

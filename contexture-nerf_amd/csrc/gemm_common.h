@@ -163,9 +163,10 @@ __device__ __forceinline__ void bias8(const GemmArgs &a, float (&v)[8], int n)
 // The operand order of every epilogue: accumulator, bias (+ bias2), row bias, residual, one rounding.  The bias is the caller's (some
 // kernels preload it per tile, some test a.bias per piece): store4 / store8 take v = accumulator + bias and do the rest.
 // F32: honour a.res32 / a.out32 (fp32 residual stream); the kernels that never see those flags do not test them.
-// store4: features nn .. nn + 3 of row m, whose row bias is row bidx.
+// store4: features nn .. nn + 3 of row m, whose row bias is row bidx.  -> the fp16 values as stored (zeros behind a.out32), for the
+// callers that also sum them (GroupNorm partials)
 template <bool F32 = false>
-__device__ __forceinline__ void store4(const GemmArgs &a, f32x4 v, size_t m, int bidx, int nn)
+__device__ __forceinline__ f16x4 store4(const GemmArgs &a, f32x4 v, size_t m, int bidx, int nn)
 {
     if (a.rowbias) v = add4(v, *(const f16x4 *)(a.rowbias + (size_t)bidx * a.ldrb + nn));
     if (a.residual) {
@@ -174,16 +175,17 @@ __device__ __forceinline__ void store4(const GemmArgs &a, f32x4 v, size_t m, int
     }
     if (F32 && a.out32) {
         *(f32x4 *)((float *)a.out + m * a.ldc + nn) = v;
-        return;
+        return (f16x4){0, 0, 0, 0};
     }
     f16x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (f16)v[e];
     *(f16x4 *)(a.out + m * a.ldc + nn) = o;
+    return o;
 }
 // store8: features n .. n + 7 of row m (the row walk of the LDS-staged epilogues: 16 bytes of fp16 per lane)
 template <bool F32 = false>
-__device__ __forceinline__ void store8(const GemmArgs &a, float (&v)[8], int m, int n)
+__device__ __forceinline__ f16x8 store8(const GemmArgs &a, float (&v)[8], int m, int n)
 {
     if (a.rowbias) add8(v, *(const f16x8 *)(a.rowbias + (size_t)(m / a.rows_per_batch) * a.ldrb + n));
     if (a.residual) {
@@ -198,12 +200,13 @@ __device__ __forceinline__ void store8(const GemmArgs &a, float (&v)[8], int m, 
     if (F32 && a.out32) {
         float *op = (float *)a.out + (size_t)m * a.ldc + n;
         *(f32x4 *)op = (f32x4){v[0], v[1], v[2], v[3]}; *(f32x4 *)(op + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-        return;
+        return (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
     }
     f16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (f16)v[e];
     *(f16x8 *)(a.out + (size_t)m * a.ldc + n) = o;
+    return o;
 }
 // fp32 split-K partial: features nn .. nn + 3 of a row of the slice's [M][N] slab (masked along N)
 __device__ __forceinline__ void store_part4(const GemmArgs &a, float *row, int nn, f32x4 v)

@@ -37,7 +37,18 @@ struct GemmArgs {
     const f16 *segW[2];    // [N] rows of segC[s] weights, row stride segLdw[s] (two column ranges of one [N][Ca + Cb] matrix)
     int segC[2], segLdw[2];
     const f16 *bias2;      // [N] or null: a second bias (the folded product's own), added in fp32 behind `bias`
+    // GroupNorm partials request (gn_part null: none).  The kernel that rounds the output (a gemm144.hip tile, or the split-K reduce)
+    // also writes the (sum x, sum x^2) of the fp16 values it stores, per (sample, slot, group), in k_gn_apply's layout
+    // part[b][gn_ns][N / gn_cg][2]; every slot has exactly one writer.  The launcher fills gn_ns when it accepts and clears gn_part
+    // when it declines (the caller then runs k_gn_stats as before).
+    float *gn_part;
+    int gn_cg, gn_hw;      // channels per group; pixels per sample (M = B gn_hw)
+    int gn_ns;             // out: slots per sample
+    int keep_slabs;        // 1 (with splitk > 1): no reduce launch; `out` is not written and the reader sums the fp32 slabs itself, in the
+                           // reduce's operand order (k_gn_fused's slab source).  The dispatch fails if the launch did not split.
 };
+// slots per sample a GroupNorm partials buffer holds (ctx_groupnorm_ws_bytes is sized for it)
+#define CTX_GN_MAX_SLOTS 128
 #define CTX_GEMM_MAX_SEG 2
 
 int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s);
@@ -65,6 +76,16 @@ extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 // [x ; x2] read in place (x: channels 0 .. Ca with pixel stride Ca; x2: channels Ca .. C with pixel stride C - Ca; Ca % 8 == 0)
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
                       void *y, void *stats_ws, hipStream_t stream, const void *x2 = nullptr, int Ca = 0);
+// 1: a one-source GroupNorm of this shape takes the two-pass form (k_gn_stats + k_gn_apply), 0: the one-kernel form
+int ctx_groupnorm_two_pass(int HW, int C, int groups);
+// the apply half of the two-pass form on partials part[B][NS][groups][2] that a producer wrote (GemmArgs::gn_part), fp16 input
+int ctx_groupnorm_apply(const void *x, const float *part, int NS, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps,
+                        int silu, void *y, hipStream_t stream);
+// a split-K convolution's unreduced output (GemmArgs::keep_slabs): S fp32 slabs of [M][C] at stride MN, and the epilogue operands the
+// reduce would have added; the one-kernel GroupNorm reads it in place of the reduced fp16 tensor, bit-identically
+struct GnSlabs { const float *part; int S; size_t MN; const f16 *bias, *bias2, *rowbias; int ldrb; };
+int ctx_groupnorm_slabs(const GnSlabs &sl, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu, void *y,
+                        hipStream_t stream);
 // GroupNorm(+SiLU) backward, input gradient only, fp16 NHWC: dx = d(loss)/dx (+ add); ws of ctx_groupnorm_bwd_ws_bytes(B, groups)
 int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups);
 int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,

@@ -69,7 +69,7 @@ __device__ __forceinline__ GnSrc gn_src(const void *x, const void *x2, int Ca, i
 }
 
 #define GN_MAX_GROUPS 64
-#define GN_MAX_SPLITS 128
+#define GN_MAX_SPLITS CTX_GN_MAX_SLOTS
 #define GN_MAX_C 4096
 #define GN_U 4
 #define GN_AU 6
@@ -238,12 +238,36 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
 // (batch, group) slab fits a workgroup's registers (<= GN_FT x GN_FU chunks), a workgroup loads its slab once, reduces
 // it (fixed order: lane partials -> DPP wave sums -> 8 wave partials), and writes the normalised slab from registers.
 // At the UNet's two deepest levels this replaces two latency-bound launches and one re-read of the tensor.
+// SLAB: the input is a split-K convolution's fp32 slabs (GnSlabs) that no reduce launch has summed: a thread forms the fp16 value the
+// reduce would have stored, in its operand order (slabs ascending, bias, bias2, row bias, one rounding: store4 of gemm_common.h), and
+// normalises that, bit for bit what it would read from the reduced tensor.
 #define GN_FT 512
 #define GN_FU 12
-template <bool X32>
+__device__ __forceinline__ Wide8 gn_slab_chunk(const GnSlabs &sl, size_t m, int b, int C, int ch)
+{
+    const float *row = sl.part + m * C + ch;
+    f32x4 lo = *(const f32x4 *)row, hi = *(const f32x4 *)(row + 4);
+    for (int s = 1; s < sl.S; ++s) { lo += *(const f32x4 *)(row + s * sl.MN); hi += *(const f32x4 *)(row + s * sl.MN + 4); }
+    Wide8 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { r.v[j] = lo[j]; r.v[4 + j] = hi[j]; }
+    if (sl.bias) { const f16x8 t = *(const f16x8 *)(sl.bias + ch);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r.v[j] += (float)t[j]; }
+    if (sl.bias2) { const f16x8 t = *(const f16x8 *)(sl.bias2 + ch);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r.v[j] += (float)t[j]; }
+    if (sl.rowbias) { const f16x8 t = *(const f16x8 *)(sl.rowbias + (size_t)b * sl.ldrb + ch);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r.v[j] += (float)t[j]; }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.v[j] = (float)(f16)r.v[j];
+    return r;
+}
+template <bool X32, bool SLAB = false>
 __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, const void *__restrict__ x2, int Ca, const f16 *__restrict__ gamma,
                                                     const f16 *__restrict__ beta, int HW, int C, int G, int PLF, float eps, int silu,
-                                                    f16 *__restrict__ y)
+                                                    f16 *__restrict__ y, GnSlabs sl)
 {
     // threads = cpg chunk columns x PLF pixel lanes: a thread keeps one column, so gamma / beta are 16 registers (an LDS table read per
     // chunk at a 32-byte lane stride is bank-conflicted and was the slowest part of the apply kernels: tools/probes/stream_probe.hip)
@@ -258,7 +282,10 @@ __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, 
     const f16x8 ga = *(const f16x8 *)(gamma + g * cg + c * 8), be = *(const f16x8 *)(beta + g * cg + c * 8);
     Wide8 v[GN_FU];
 #pragma unroll
-    for (int u = 0; u < GN_FU; ++u) v[u] = ldraw<X32>(src.p, xb + (size_t)min(pl + PLF * u, HW - 1) * src.cs).widen();     // unconditional (clamped), all in flight
+    for (int u = 0; u < GN_FU; ++u) {                                                                                     // unconditional (clamped), all in flight
+        if constexpr (SLAB) v[u] = gn_slab_chunk(sl, (size_t)b * HW + min(pl + PLF * u, HW - 1), b, C, g * cg + c * 8);
+        else v[u] = ldraw<X32>(src.p, xb + (size_t)min(pl + PLF * u, HW - 1) * src.cs).widen();
+    }
     float s = 0.f, q = 0.f;
 #pragma unroll
     for (int u = 0; u < GN_FU; ++u)
@@ -283,6 +310,33 @@ __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, 
     }
 }
 
+// what every GroupNorm launcher requires of a shape
+static bool gn_shape_ok(int B, int HW, int C, int groups)
+{
+    return B > 0 && HW > 0 && groups > 0 && C % 8 == 0 && C % groups == 0 && groups <= GN_MAX_GROUPS && C <= GN_MAX_C && 256 % groups == 0 &&
+           (256 / groups & (256 / groups - 1)) == 0;
+}
+// pixel lanes of the one-kernel form when the shape takes it (a group's channels are whole chunks and a (sample, group) slab fits
+// a workgroup's registers), else 0: the two-pass form
+static int gn_one_kernel_lanes(int HW, int C, int groups)
+{
+    static const int fuse = ctx_env_int("CTX_GN_FUSED", 1);
+    const int cg = C / groups, cpg = cg / 8;
+    const int plf = cg % 8 == 0 ? GN_FT / cpg : 0;
+    return (fuse && plf > 0 && cpg <= GN_FT && (HW + plf - 1) / plf <= GN_FU) ? plf : 0;
+}
+// pass 2 on NS partials per (sample, group): fat blocks (the per-block fold of the split partials is amortised), at least one batch each
+static void gn_launch_apply(const void *x, int x32, const void *x2, int Ca, const float *part, int NS, const void *gamma, const void *beta, int B, int HW,
+                            int C, int groups, float eps, int silu, void *y, hipStream_t stream)
+{
+    const int c8n = C / 8;
+    const int apl = (256 + c8n - 1) / c8n;                      // pixel lanes: >= 256 threads (the fold uses 256), <= 512
+    const int athreads = c8n * apl;
+    const int nb = (HW + apl * GN_AU - 1) / (apl * GN_AU);
+    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(nb, B), dim3(athreads), 0, stream, x, x2, Ca, part, (const f16 *)gamma, (const f16 *)beta, HW, C,
+                                           groups, NS, apl, eps, silu, (f16 *)y));
+}
+
 extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups)
 {
     return ((int64_t)B * GN_MAX_SPLITS * groups * 2 + (int64_t)B * 2 * GN_MAX_C) * 4;
@@ -303,27 +357,33 @@ extern "C" int32_t ctx_groupnorm2_f16(const void *xa, const void *xb, int32_t Ca
     return ctx_groupnorm_any(xa, 0, gamma, beta, B, HW, C, groups, eps, silu, y, stats_ws, (hipStream_t)stream, xb, Ca);
 }
 
+extern "C" int32_t ctx_groupnorm_apply_f16(const void *x, const void *part, int32_t slots, const void *gamma, const void *beta, int32_t B, int32_t HW,
+                                           int32_t C, int32_t groups, float eps, int32_t silu, void *y, ctx_stream_t stream)
+{
+    return ctx_groupnorm_apply(x, (const float *)part, slots, gamma, beta, B, HW, C, groups, eps, silu, y, (hipStream_t)stream);
+}
+
+extern "C" int32_t ctx_groupnorm_slabs_f16(const void *part, int32_t splitk, const void *bias, const void *bias2, const void *rowbias, int32_t ldrb,
+                                           const void *gamma, const void *beta, int32_t B, int32_t HW, int32_t C, int32_t groups, float eps,
+                                           int32_t silu, void *y, ctx_stream_t stream)
+{
+    const GnSlabs sl = {(const float *)part, splitk, (size_t)B * HW * C, (const f16 *)bias, (const f16 *)bias2, (const f16 *)rowbias, ldrb};
+    return ctx_groupnorm_slabs(sl, gamma, beta, B, HW, C, groups, eps, silu, y, (hipStream_t)stream);
+}
+
 // x32 != 0: the input is the fp32 residual stream (the output stays fp16: it is the next GEMM's operand)
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
                       void *y, void *stats_ws, hipStream_t stream, const void *x2, int Ca)
 {
     CTX_REQUIRE(x && gamma && beta && y && stats_ws, "groupnorm: null pointer");
     CTX_REQUIRE(!x2 || (Ca > 0 && Ca < C && Ca % 8 == 0), "groupnorm: two sources need 0 < Ca < C in whole 8-channel columns (Ca=%d C=%d)", Ca, C);
-    CTX_REQUIRE(B > 0 && HW > 0 && C % 8 == 0 && C % groups == 0 && groups <= GN_MAX_GROUPS && C <= GN_MAX_C &&
-                    256 % groups == 0 && (256 / groups & (256 / groups - 1)) == 0,
-                "groupnorm: unsupported B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
-    {
-        static const int fuse = ctx_env_int("CTX_GN_FUSED", 1);
-        const int cg = C / groups;
-        const int cpg = cg / 8;
-        const int plf = cg % 8 == 0 ? GN_FT / cpg : 0;                  // pixel lanes of the one-kernel form
-        if (fuse && cg % 8 == 0 && cpg <= GN_FT && (HW + plf - 1) / plf <= GN_FU && (!x2 || Ca % cg == 0)) {
-            const int thr = (cpg * plf + 63) / 64 * 64;
-            CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(thr), 0, stream, x, x2, Ca, (const f16 *)gamma, (const f16 *)beta, HW, C,
-                                                   groups, plf, eps, silu, (f16 *)y));
-            CTX_CHECK_LAUNCH("groupnorm");
-            return CTX_OK;
-        }
+    CTX_REQUIRE(gn_shape_ok(B, HW, C, groups), "groupnorm: unsupported B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
+    if (const int plf = gn_one_kernel_lanes(HW, C, groups); plf && (!x2 || Ca % (C / groups) == 0)) {
+        const int thr = (C / groups / 8 * plf + 63) / 64 * 64;
+        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(thr), 0, stream, x, x2, Ca, (const f16 *)gamma, (const f16 *)beta, HW, C,
+                                               groups, plf, eps, silu, (f16 *)y, GnSlabs{}));
+        CTX_CHECK_LAUNCH("groupnorm");
+        return CTX_OK;
     }
     int c8n = C / 8;
     int PL = 1024 / c8n;                                      // pixel lanes: ~1000 threads per block
@@ -352,15 +412,36 @@ int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *bet
         attr = true;
     }
     CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_stats<X>, dim3(NS, B), dim3(threads), lds, stream, x, x2, Ca, HW, C, groups, NS, PL, part));
-    // fat blocks (the per-block fold of the split partials is amortised), at least one batch each
-    {
-        const int apl = (256 + c8n - 1) / c8n;                      // pixel lanes: >= 256 threads (the fold uses 256), <= 512
-        const int athreads = c8n * apl;
-        const int nb = (HW + apl * GN_AU - 1) / (apl * GN_AU);
-        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(nb, B), dim3(athreads), 0, stream, x, x2, Ca, part, (const f16 *)gamma, (const f16 *)beta, HW, C,
-                                               groups, NS, apl, eps, silu, (f16 *)y));
-    }
+    gn_launch_apply(x, x32, x2, Ca, part, NS, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
     CTX_CHECK_LAUNCH("groupnorm");
+    return CTX_OK;
+}
+
+int ctx_groupnorm_two_pass(int HW, int C, int groups) { return gn_one_kernel_lanes(HW, C, groups) == 0; }
+
+// The apply half alone, on partials somebody else wrote (a GEMM / convolution epilogue or the split-K reduce: GemmArgs::gn_part):
+// part[B][NS][groups][2], every slot of it written.
+int ctx_groupnorm_apply(const void *x, const float *part, int NS, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps,
+                        int silu, void *y, hipStream_t stream)
+{
+    CTX_REQUIRE(x && part && gamma && beta && y, "groupnorm apply: null pointer");
+    CTX_REQUIRE(gn_shape_ok(B, HW, C, groups) && NS >= 1 && NS <= GN_MAX_SPLITS, "groupnorm apply: unsupported B=%d HW=%d C=%d groups=%d NS=%d", B, HW, C, groups, NS);
+    gn_launch_apply(x, 0, nullptr, 0, part, NS, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
+    CTX_CHECK_LAUNCH("groupnorm apply");
+    return CTX_OK;
+}
+
+// One-kernel GroupNorm(+SiLU) of a split-K convolution's unreduced slabs (k_gn_fused's slab source); the shape must take the one-kernel form.
+int ctx_groupnorm_slabs(const GnSlabs &sl, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu, void *y,
+                        hipStream_t stream)
+{
+    CTX_REQUIRE(sl.part && sl.S >= 1 && gamma && beta && y, "groupnorm slabs: bad arguments");
+    const int plf = gn_shape_ok(B, HW, C, groups) ? gn_one_kernel_lanes(HW, C, groups) : 0;
+    CTX_REQUIRE(plf > 0 && (!sl.rowbias || sl.ldrb % 8 == 0), "groupnorm slabs: B=%d HW=%d C=%d groups=%d does not take the one-kernel form", B, HW, C, groups);
+    const int thr = (C / groups / 8 * plf + 63) / 64 * 64;
+    hipLaunchKernelGGL((k_gn_fused<false, true>), dim3(groups, B), dim3(thr), 0, stream, (const void *)nullptr, (const void *)nullptr, 0, (const f16 *)gamma,
+                       (const f16 *)beta, HW, C, groups, plf, eps, silu, (f16 *)y, sl);
+    CTX_CHECK_LAUNCH("groupnorm slabs");
     return CTX_OK;
 }
 

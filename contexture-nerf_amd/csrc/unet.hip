@@ -363,24 +363,59 @@ __global__ __launch_bounds__(256) void k_add_scaled_f16(f16 *__restrict__ dst, c
 // ---- op wrappers: the shared op layer (engine.h) on this engine's weight offsets and residual-stream flags ------
 #define RUN(expr) ENGINE_RUN(u, expr)
 
+// CTX_GN_EPI (read once): 2 (default) the producer of a tensor that a two-pass GroupNorm reads next writes that GroupNorm's partials
+// from its epilogue (no k_gn_stats launch); 1 that, and the one-kernel GroupNorm behind a split-K conv1 reads the fp32 slabs itself (no
+// reduce launch, no fp16 tensor between them); 3 the slabs only (bit-identical to 0: it moves no rounding point); 0 neither: the graph
+// as it was before either existed, bit for bit.
+// The slabs are not in the default because they lose at every shape of the UNet (tools/bench_gn_epilogue.py, CFG batch 2 at latent
+// 96^2, table in profiles/gn_epilogue_by_kernel_and_grid.txt): conv1 + reduce + one-kernel GroupNorm 39.3 - 83.8 us at M = 1152 and
+// 27.9 / 36.6 us at M = 288, against 48.4 - 93.4 and 44.2 / 70.6 us on the slabs: the 64 workgroups of the one-kernel form (one per
+// sample and group) then read 4 - 16 fp32 slabs where the reduce spreads the same bytes over the whole chip.  The partials gain
+// 4.3 - 9.6 us at each of the eight producer shapes measured; no shape keeps the old path.
+static int gn_epi_mode(void)
+{
+    static const int m = ctx_env_int("CTX_GN_EPI", 2);
+    return m;
+}
+// The request a producer of [B, HW, C] passes on when the next reader of its output is a one-source GroupNorm that takes the two-pass
+// form (else: no request).  A producer that cannot serve it declines, and op_gn then runs k_gn_stats as it always did.
+static GnReq gn_request(ctx_unet *u, void *stats, int HW, int C, bool want)
+{
+    GnReq r;
+    if (want && (gn_epi_mode() == 1 || gn_epi_mode() == 2) && !u->res32 && C % u->cfg.groups == 0 && ctx_groupnorm_two_pass(HW, C, u->cfg.groups)) {
+        r.part = (float *)stats; r.groups = u->cfg.groups; r.HW = HW;
+    }
+    return r;
+}
+
 // res / out are residual-stream tensors (fp32 when u->res32) iff res_s / out_s
 static void op_gemm(ctx_unet *u, const f16 *X, size_t w, size_t bias, bool has_bias, const void *res, int M, int N, int K, void *out,
-                    int epi = 0, bool res_s = false, bool out_s = false)
+                    int epi = 0, bool res_s = false, bool out_s = false, const GnReq *gn = nullptr)
 {
-    engine_linear(*u, X, u->W + w, has_bias ? u->W + bias : nullptr, res, M, N, K, out, 0, epi, u->res32 && res_s && res, u->res32 && out_s);
+    engine_linear(*u, X, u->W + w, has_bias ? u->W + bias : nullptr, res, M, N, K, out, 0, epi, u->res32 && res_s && res, u->res32 && out_s, gn);
 }
 static void op_conv(ctx_unet *u, const f16 *x, size_t w, size_t bias, const f16 *rowbias, int ldrb, const void *res, int B, int H,
-                    int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false, const ConvSegs *segs = nullptr)
+                    int W, int Cin, int Cout, int stride, int ups, void *out, bool res_s = false, bool out_s = false, const ConvSegs *segs = nullptr,
+                    const GnReq *gn = nullptr, GnSlabs *slabs = nullptr)
 {
     engine_conv3(*u, x, u->W + w, u->W + bias, res, B, H, W, Cin, Cout, out, ConvGeom{stride, ups}, rowbias, ldrb, u->res32 && res_s && res,
-                 u->res32 && out_s, segs);
+                 u->res32 && out_s, segs, gn, slabs);
 }
 // x_s: x is a residual-stream tensor
 // x2 != null: the input is [x ; x2] along the channels, read in place (x has Ca of the C channels)
+// Partials that x's producer left in `stats` (Engine::gn_tag) replace the statistics launch when they are for exactly this tensor and
+// shape; in every other case (two sources, the fp32 stream, a declined or absent request) both launches run.
 static void op_gn(ctx_unet *u, const void *x, size_t g, size_t b, int B, int HW, int C, float eps, int silu, f16 *y, void *stats, bool x_s = true,
                   const void *x2 = nullptr, int Ca = 0)
 {
     u->note(2, 0, 2);
+    const Engine::GnTag t = u->gn_tag;
+    u->gn_tag = Engine::GnTag();
+    if (t.x && t.x == x && !x2 && !(u->res32 && x_s) && t.B == B && t.HW == HW && t.C == C && t.groups == u->cfg.groups) {
+        ++u->gn_from_producer;
+        RUN(ctx_groupnorm_apply(x, (const float *)stats, t.NS, u->W + g, u->W + b, B, HW, C, u->cfg.groups, eps, silu, y, u->s));
+        return;
+    }
     RUN(ctx_groupnorm_any(x, (u->res32 && x_s) ? 1 : 0, u->W + g, u->W + b, B, HW, C, u->cfg.groups, eps, silu, y, stats, u->s, x2, Ca));
 }
 static void op_ln(ctx_unet *u, const void *x, size_t g, size_t b, int64_t rows, int C, f16 *y)
@@ -430,7 +465,9 @@ static bool resnet_fold_loses(int M, int cin, int cout) { return M == 4608 && ci
 // of its r.cin channels.  Only norm1 and the 1x1 shortcut ever read it: norm1 reads the pair in place, the shortcut becomes two K
 // segments of conv2 (one for a down block's cin != cout), and no concatenated tensor exists.  The fp32 residual stream (its operands
 // cannot be staged as fp16), channel counts no kernel takes as segments and CTX_RESNET_FOLD = 0 keep the materialised path.
-static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void *x, int H, int W, void *out, const void *x2 = nullptr, int Ca = 0)
+// gn_next: the next reader of `out` is a one-source GroupNorm and nothing changes `out` before it (conv2 then takes its partials request).
+static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void *x, int H, int W, void *out, bool gn_next, const void *x2 = nullptr,
+                        int Ca = 0)
 {
     const int B = f.B, HW = H * W, M = B * HW;
     size_t mark = u->top;
@@ -453,17 +490,37 @@ static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void 
     f16 *t1 = u->allocH((size_t)M * r.cin);
     if (gn_pair) op_gn(u, x, r.n1g, r.n1b, B, HW, r.cin, u->cfg.norm_eps, 1, t1, f.gn_stats, true, x2, Ca);
     else op_gn(u, xin, r.n1g, r.n1b, B, HW, r.cin, u->cfg.norm_eps, 1, t1, f.gn_stats);
-    f16 *h = u->allocH((size_t)M * r.cout);
-    op_conv(u, t1, r.c1w, r.c1b, f.tproj ? f.tproj + r.temb_row : nullptr, u->temb_rows, nullptr, B, H, W, r.cin, r.cout, 1, 0, h);
-    f16 *t2 = u->allocH((size_t)M * r.cout);
-    op_gn(u, h, r.n2g, r.n2b, B, HW, r.cout, u->cfg.norm_eps, 1, t2, f.gn_stats, false);
+    // conv1's output has one reader, norm2.  Where conv1 runs split-K and norm2 takes the one-kernel form (the two deepest levels),
+    // norm2 sums the slabs itself: no reduce launch and no fp16 tensor between them.  Else conv1 is asked for norm2's partials.
+    const f16 *trow = f.tproj ? f.tproj + r.temb_row : nullptr;
+    const bool slab = (gn_epi_mode() == 1 || gn_epi_mode() == 3) && !u->res32 && r.cout % u->cfg.groups == 0 && !ctx_groupnorm_two_pass(HW, r.cout, u->cfg.groups) &&
+                      r.temb_row % 8 == 0 && u->temb_rows % 8 == 0 && engine_conv3_split(B, H, W, r.cin, r.cout) > 1;
+    f16 *t2 = nullptr;
+    if (slab) {
+        t2 = u->allocH((size_t)M * r.cout);
+        const size_t m2 = u->top;
+        GnSlabs sl = {};
+        op_conv(u, t1, r.c1w, r.c1b, trow, u->temb_rows, nullptr, B, H, W, r.cin, r.cout, 1, 0, nullptr, false, false, nullptr, nullptr, &sl);
+        u->note(2, 0, 2);                          // norm2, counted as the GroupNorm op it is
+        u->gn_tag = Engine::GnTag();
+        if (u->live()) ++u->gn_from_slabs;
+        RUN(ctx_groupnorm_slabs(sl, u->W + r.n2g, u->W + r.n2b, B, HW, r.cout, u->cfg.groups, u->cfg.norm_eps, 1, t2, u->s));
+        u->top = m2;
+    } else {
+        f16 *h = u->allocH((size_t)M * r.cout);
+        const GnReq rq = gn_request(u, f.gn_stats, HW, r.cout, true);
+        op_conv(u, t1, r.c1w, r.c1b, trow, u->temb_rows, nullptr, B, H, W, r.cin, r.cout, 1, 0, h, false, false, nullptr, &rq);
+        t2 = u->allocH((size_t)M * r.cout);
+        op_gn(u, h, r.n2g, r.n2b, B, HW, r.cout, u->cfg.norm_eps, 1, t2, f.gn_stats, false);
+    }
+    const GnReq rq2 = gn_request(u, f.gn_stats, HW, r.cout, gn_next);
     if (fold) {
         // conv_shortcut(input) + conv2(t2) in one K loop: W_sc is [cout][cin], segment a reads its columns 0 .. Ca, segment b the rest
         ConvSegs sg;
         sg.n = pair ? 2 : 1; sg.bias2 = u->W + r.scb;
         sg.x[0] = (const f16 *)x; sg.w[0] = u->W + r.scw; sg.C[0] = pair ? Ca : r.cin; sg.ldw[0] = r.cin;
         if (pair) { sg.x[1] = (const f16 *)x2; sg.w[1] = u->W + r.scw + Ca; sg.C[1] = Cb; sg.ldw[1] = r.cin; }
-        op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, nullptr, B, H, W, r.cout, r.cout, 1, 0, out, true, true, &sg);
+        op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, nullptr, B, H, W, r.cout, r.cout, 1, 0, out, true, true, &sg, &rq2);
         u->top = mark;
         return out;
     }
@@ -473,12 +530,13 @@ static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void 
         op_gemm(u, op_as16(u, xin, (size_t)M * r.cin), r.scw, r.scb, true, nullptr, M, r.cout, r.cin, s2, 0, false, true);
         sc = s2;
     }
-    op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, sc, B, H, W, r.cout, r.cout, 1, 0, out, true, true);
+    op_conv(u, t2, r.c2w, r.c2b, nullptr, 0, sc, B, H, W, r.cout, r.cout, 1, 0, out, true, true, nullptr, &rq2);
     u->top = mark;
     return out;
 }
 
-static void *run_transformer(ctx_unet *u, const FwdCtx &f, const TrP &t, const void *x, int H, int W, void *out)
+// gn_next: as run_resnet's (proj_out then takes the partials request)
+static void *run_transformer(ctx_unet *u, const FwdCtx &f, const TrP &t, const void *x, int H, int W, void *out, bool gn_next)
 {
     const int B = f.B, S = H * W, M = B * S, C = t.C, cd = u->cfg.cross_attention_dim;
     size_t mark = u->top;
@@ -542,7 +600,8 @@ static void *run_transformer(ctx_unet *u, const FwdCtx &f, const TrP &t, const v
     op_gemm(u, l, t.f1w, t.f1b, true, nullptr, M, 8 * C, C, ff, 1);
     void *h3 = h1;
     op_gemm(u, ff, t.f2w, t.f2b, true, h2, M, C, 4 * C, h3, 0, true, true);
-    op_gemm(u, op_as16(u, h3, (size_t)M * C), t.pow_, t.pob, true, x, M, C, C, out, 0, true, true);
+    const GnReq rq = gn_request(u, f.gn_stats, S, C, gn_next);
+    op_gemm(u, op_as16(u, h3, (size_t)M * C), t.pow_, t.pob, true, x, M, C, C, out, 0, true, true, &rq);
     u->top = mark;
     return out;
 }
@@ -633,11 +692,11 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             if (Lv.has_attn) {
                 size_t mark = u->top;
                 void *t = u->allocS((size_t)B * h * w * cout);
-                run_resnet(u, f, Lv.res[j], x, h, w, t);
+                run_resnet(u, f, Lv.res[j], x, h, w, t, true);                       // read next by the transformer's norm
                 u->tap(t, B * h * w, cout);
-                run_transformer(u, f, Lv.tr[j], t, h, w, o);
+                run_transformer(u, f, Lv.tr[j], t, h, w, o, j + 1 < lpb);             // ... by the level's next resnet (norm1)
                 u->top = mark;
-            } else run_resnet(u, f, Lv.res[j], x, h, w, o);
+            } else run_resnet(u, f, Lv.res[j], x, h, w, o, j + 1 < lpb);
             u->tap(o, B * h * w, cout);
             x = o; cur = cout;
             skips.push_back({x, cur, h, w});
@@ -679,13 +738,13 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     }
     {
         void *o1 = u->allocS((size_t)B * h * w * cur);
-        run_resnet(u, f, u->mid.res[0], x, h, w, o1);
+        run_resnet(u, f, u->mid.res[0], x, h, w, o1, true);
         u->tap(o1, B * h * w, cur);
         void *o2 = u->allocS((size_t)B * h * w * cur);
-        run_transformer(u, f, u->mid.tr[0], o1, h, w, o2);
+        run_transformer(u, f, u->mid.tr[0], o1, h, w, o2, true);
         u->tap(o2, B * h * w, cur);
         void *o3 = u->allocS((size_t)B * h * w * cur);
-        run_resnet(u, f, u->mid.res[1], o2, h, w, o3);
+        run_resnet(u, f, u->mid.res[1], o2, h, w, o3, false);
         u->tap(o3, B * h * w, cur);
         x = o3;
     }
@@ -706,12 +765,14 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             size_t mark = u->top;
             // the resnet reads [x ; skip] as a pair (a concatenated copy only on its fallback path)
             if (cin != Lv.res[j].cin) { ctx_set_error("unet: up block input has %d channels, its resnet expects %d", cin, Lv.res[j].cin); return CTX_E_STATE; }
+            // the up path's resnets read [x ; skip] (two sources); only the last block's output goes to a one-source GroupNorm (conv_norm_out)
+            const bool last = i == n - 1 && j == lpb && !Lv.has_sampler;
             if (Lv.has_attn) {
                 void *t = u->allocS((size_t)B * h * w * cout);
-                run_resnet(u, f, Lv.res[j], x, h, w, t, sk.p, cur);
+                run_resnet(u, f, Lv.res[j], x, h, w, t, true, sk.p, cur);
                 u->tap(t, B * h * w, cout);
-                run_transformer(u, f, Lv.tr[j], t, h, w, o);
-            } else run_resnet(u, f, Lv.res[j], x, h, w, o, sk.p, cur);
+                run_transformer(u, f, Lv.tr[j], t, h, w, o, last);
+            } else run_resnet(u, f, Lv.res[j], x, h, w, o, last, sk.p, cur);
             u->tap(o, B * h * w, cout);
             u->top = mark;
             x = o; cur = cout;
@@ -870,6 +931,14 @@ extern "C" int32_t ctx_unet_tap_info(const ctx_unet_t *u, int32_t i, int64_t *of
 {
     CTX_REQUIRE(u && offset && rows && channels && i >= 0 && i < (int32_t)u->taps.size(), "unet_tap_info: bad args");
     *offset = (int64_t)u->taps[i].off; *rows = u->taps[i].rows; *channels = u->taps[i].C;
+    return CTX_OK;
+}
+
+extern "C" int32_t ctx_unet_gn_epilogue_counts(const ctx_unet_t *u, int64_t *from_producer, int64_t *from_slabs)
+{
+    CTX_REQUIRE(u && from_producer && from_slabs, "unet_gn_epilogue_counts: bad args");
+    *from_producer = u->gn_from_producer;
+    *from_slabs = u->gn_from_slabs;
     return CTX_OK;
 }
 

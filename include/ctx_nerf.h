@@ -473,6 +473,9 @@ int32_t ctx_unet_set_residuals(ctx_unet_t *u, const void *residuals /*nullable*/
    passes).  The workspace grows: query ctx_unet_workspace_bytes again after switching. */
 int32_t ctx_unet_set_residual_fp32(ctx_unet_t *u, int32_t on);
 int32_t ctx_unet_stats(const ctx_unet_t *u, int32_t klass, int64_t *launches, double *flops);
+/* GroupNorms of the last forward that ran without a statistics launch on partials from their producer's epilogue, and GroupNorms
+   that read a split-K convolution's slabs in place of a reduced tensor (CTX_GN_EPI; no reference counterpart). */
+int32_t ctx_unet_gn_epilogue_counts(const ctx_unet_t *u, int64_t *from_producer, int64_t *from_slabs);
 /* Measurement aid (tools/precision_attribution.py; no reference counterpart): buf (fp16 device memory of `capacity` elements, NULL =
    off) receives a copy of every block's output (fp16 NHWC [rows, channels]) of the following plain forwards, in execution order:
    conv_in; per down level resnet (, transformer) x layers, downsampler; mid resnet, transformer, resnet; per up level resnet
@@ -541,6 +544,19 @@ int32_t ctx_conv3x3_seg_f16(const void *x, const void *w, const void *bias, cons
                             const void *residual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                             const void *xa, const void *wa, int32_t Ca, int32_t ldwa, const void *xb, const void *wb,
                             int32_t Cb, int32_t ldwb, void *part, int32_t splitk, void *y, ctx_stream_t stream);
+/* The resnet's conv1 as the UNet engine runs it in front of norm2 (ResnetBlock2D.forward: conv1, + time embedding, norm2, under
+   diffusers' UNet2DConditionModel; reference call site src/stable_diffusion_depth.py:422-423): stride-1 conv3x3 + bias + bias2
+   (+rowbias) (+residual), and one of
+     gn_part != NULL: the kernel that rounds the output also writes the (sum, sum of squares) partials of GroupNorm(groups) over it
+       into gn_part (ctx_groupnorm_ws_bytes(B, groups)); *slots = slots per sample written, for ctx_groupnorm_apply_f16, or 0 when
+       the launched kernel declined the request (y is the same either way);
+     keep_slabs != 0 (needs splitk > 1): the split-K reduce is not launched; y is not written (may be NULL) and part holds the splitk
+       fp32 slabs [B*H*W][Cout] for ctx_groupnorm_slabs_f16 (*slots, when given, = the split factor that ran).
+   splitk and part as ctx_conv3x3_seg_f16 (< 0: the engine's plan, kernel and split).  Honours ctx_gemm_tune. */
+int32_t ctx_conv3x3_gn_f16(const void *x, const void *w, const void *bias, const void *bias2, const void *rowbias,
+                           const void *residual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void *part,
+                           int32_t splitk, int32_t keep_slabs, int32_t groups, void *gn_part, int32_t *slots, void *y,
+                           ctx_stream_t stream);
 /* The kernel that the last GEMM / convolution dispatch launched, in ctx_gemm_tune's terms (use8 0: gemm.hip's tile *tile): lets a test
    of the cuBLAS / cuDNN replacements under UNet2DConditionModel (reference call site src/stable_diffusion_depth.py:422-423) see
    that a forced kernel ran, or that the call fell through to another one when it declined. */
@@ -556,6 +572,17 @@ int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const void *beta, in
 int32_t ctx_groupnorm2_f16(const void *xa, const void *xb, int32_t Ca, const void *gamma, const void *beta, int32_t B,
                            int32_t HW, int32_t C, int32_t groups, float eps, int32_t silu, void *y, void *stats_ws,
                            ctx_stream_t stream);
+/* The second pass of GroupNorm(+SiLU) alone, on partials part[B][slots][groups][2] that the producer of x wrote
+   (ctx_conv3x3_gn_f16 with gn_part); same reference call site as ctx_groupnorm2_f16. */
+int32_t ctx_groupnorm_apply_f16(const void *x, const void *part, int32_t slots, const void *gamma, const void *beta, int32_t B,
+                                int32_t HW, int32_t C, int32_t groups, float eps, int32_t silu, void *y, ctx_stream_t stream);
+/* One-kernel GroupNorm(+SiLU) of a split-K convolution's unreduced output (ctx_conv3x3_gn_f16 with keep_slabs): the value it
+   normalises is (f16)(sum_s slab_s + bias + bias2 + rowbias[b]) in the reduce kernel's operand order, so the result is bit-identical
+   to the reduce followed by ctx_groupnorm_f16.  The shape must take the one-kernel form (C / groups a multiple of 8, small HW);
+   same reference call site as ctx_groupnorm2_f16. */
+int32_t ctx_groupnorm_slabs_f16(const void *part, int32_t splitk, const void *bias, const void *bias2, const void *rowbias,
+                                int32_t ldrb, const void *gamma, const void *beta, int32_t B, int32_t HW, int32_t C,
+                                int32_t groups, float eps, int32_t silu, void *y, ctx_stream_t stream);
 int32_t ctx_layernorm_f16(const void *x, const void *gamma, const void *beta, int64_t rows, int32_t C,
                           float eps, void *y, ctx_stream_t stream);
 /* softmax(Q K^T * scale) V; Q[B,Sq,heads*64], K[B,Skv,heads*64], V likewise (f16) -> O[B,Sq,heads*64];
