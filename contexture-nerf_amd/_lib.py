@@ -129,6 +129,15 @@ SIGNATURES = {
                                    _vp, _i32, _vp, _vp]),
     "ctx_conv3x3_gn_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ctx_gemm_last_kernel": (None, [_vp, _vp]),
+    "ctx_conv3x3_geom_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "ctx_pack_conv3_dgrad_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_pack_mat_dgrad_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_groupnorm_bwd_ws_bytes": (_i64, [_i32, _i32]),
+    "ctx_groupnorm_bwd_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "ctx_softmax_rows_f16": (_i32, [_vp, _i32, _i32, _f32, _vp, _vp]),
+    "ctx_softmax_bwd_rows_f16": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp]),
+    "ctx_quant_bwd_f16": (_i32, [_vp, _vp, _i32, _i32, _i64, _f32, _vp, _vp]),
+    "ctx_conv_in_bwd_f16": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ctx_groupnorm_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_groupnorm2_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_groupnorm_apply_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),

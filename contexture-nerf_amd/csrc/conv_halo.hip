@@ -191,11 +191,11 @@ __global__ __launch_bounds__(512) void k_conv_halo(GemmArgs a)
     }
 }
 
-// Launch when the problem fits (returns 1): stride 1, no upsample, H and W multiples of 16, Cin multiple of 64, epi 0.
+// Launch when the problem fits (returns 1): stride 1, no upsample, symmetric padding (poff 0), H and W multiples of 16, Cin multiple of 64, epi 0.
 int ctx_conv_halo_try(GemmArgs &a, int ni, hipStream_t s)
 {
     if (a.nseg) return 0;                      // K segments: the kernels of gemm.hip / gemm144.hip
-    if (a.stride != 1 || a.ups != 0 || (a.H & 15) || (a.W & 15) || a.Cin % 64 != 0 || a.epi != 0 || a.N % 8 != 0) return 0;
+    if (a.stride != 1 || a.ups != 0 || a.poff != 0 || (a.H & 15) || (a.W & 15) || a.Cin % 64 != 0 || a.epi != 0 || a.N % 8 != 0) return 0;
     const int B = a.M / (a.H * a.W);
     const int BN = 64 * ni;
     a.ntm = B * (a.H >> 4) * (a.W >> 4);

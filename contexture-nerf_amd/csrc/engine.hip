@@ -73,10 +73,9 @@ void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const
                   ConvGeom g, const f16 *rowbias, int ldrb, bool res32, bool out32, const ConvSegs *segs, const GnReq *gn, GnSlabs *slabs)
 {
     GemmArgs a = {};
-    a.Ho = ((H << g.ups) - 1) / g.stride + 1; a.Wo = ((W << g.ups) - 1) / g.stride + 1;
+    ctx_conv3_problem(a, B, H, W, Cin, Cout, g.stride, g.ups, g.poff, g.zins);
     a.X = x; a.Wt = Wt; a.bias = bias; a.rowbias = rowbias; a.residual = (const f16 *)res; a.out = (f16 *)out;
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo; a.ldrb = ldrb;
-    a.H = H; a.W = W; a.Cin = Cin; a.stride = g.stride; a.ups = g.ups; a.poff = g.poff; a.zins = g.zins;
+    a.ldrb = ldrb;
     a.res32 = res32; a.out32 = out32;
     engine_gemm(e, a, true, segs, gn, slabs);
 }
@@ -135,6 +134,13 @@ __global__ void k_pack_mat_T(const float *__restrict__ s, int out, int in, int l
     }
 }
 
+// grid of a repack launch over a parameter of n source elements (grid-stride kernels)
+static unsigned pack_blocks(int64_t n)
+{
+    const int64_t nbk = cdiv64(n, 256);
+    return (unsigned)(nbk > 4096 ? 4096 : nbk);
+}
+
 int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t stream, const char *who)
 {
     CTX_REQUIRE(e && e->W && src && i >= 0 && i < (int)e->params.size(), "%s: bad args / not bound", who);
@@ -143,8 +149,7 @@ int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t st
     int64_t n = 1;
     for (int k = 0; k < p.ndim; ++k) n *= p.shape[k];
     f16 *d = e->W + p.dst;
-    int64_t nbk = cdiv64(n, 256);
-    unsigned nb = (unsigned)(nbk > 4096 ? 4096 : nbk);
+    const unsigned nb = pack_blocks(n);
     switch (p.kind) {
     case PK_COPY: hipLaunchKernelGGL(k_pack_copy, dim3(nb), dim3(256), 0, s, src, n, d); break;
     case PK_CONV3: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b, d); break;
@@ -155,5 +160,24 @@ int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t st
     if (p.kind2 == 1) hipLaunchKernelGGL(k_pack_conv3_T, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.pad2, e->W + p.dst2);
     else if (p.kind2 == 2) hipLaunchKernelGGL(k_pack_mat_T, dim3(nb), dim3(256), 0, s, src, (int)p.shape[0], (int)p.shape[1], p.ld2, p.col2, e->W + p.dst2);
     CTX_CHECK_LAUNCH(who);
+    return CTX_OK;
+}
+
+// ---- test seams: the two backward packs alone, with engine_set_param's launch geometry -----------------------------
+extern "C" int32_t ctx_pack_conv3_dgrad_f16(const float *src, int32_t Cout, int32_t Cin, int32_t pad, void *dst, ctx_stream_t stream)
+{
+    CTX_REQUIRE(src && dst, "pack_conv3_dgrad: null pointer");
+    CTX_REQUIRE(Cout > 0 && Cin > 0 && pad >= Cout && (int64_t)Cin * 9 * pad < (1ll << 31), "pack_conv3_dgrad: need 0 < Cout <= pad (Cout=%d Cin=%d pad=%d)", Cout, Cin, pad);
+    hipLaunchKernelGGL(k_pack_conv3_T, dim3(pack_blocks((int64_t)Cout * Cin * 9)), dim3(256), 0, (hipStream_t)stream, src, Cout, Cin, pad, (f16 *)dst);
+    CTX_CHECK_LAUNCH("pack_conv3_dgrad");
+    return CTX_OK;
+}
+extern "C" int32_t ctx_pack_mat_dgrad_f16(const float *src, int32_t out, int32_t in, int32_t ld, int32_t col, void *dst, ctx_stream_t stream)
+{
+    CTX_REQUIRE(src && dst, "pack_mat_dgrad: null pointer");
+    CTX_REQUIRE(out > 0 && in > 0 && col >= 0 && (int64_t)col + out <= ld && (int64_t)in * ld < (1ll << 31),
+                "pack_mat_dgrad: columns col .. col + out must lie inside ld (out=%d in=%d ld=%d col=%d)", out, in, ld, col);
+    hipLaunchKernelGGL(k_pack_mat_T, dim3(pack_blocks((int64_t)out * in)), dim3(256), 0, (hipStream_t)stream, src, out, in, ld, col, (f16 *)dst);
+    CTX_CHECK_LAUNCH("pack_mat_dgrad");
     return CTX_OK;
 }

@@ -693,6 +693,33 @@ extern "C" int32_t ctx_conv3x3_seg_f16(const void *x, const void *w, const void 
     return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
 }
 
+// A 3x3 convolution in any geometry the engines use (test seam): GemmArgs as engine_conv3 fills them, so the VAE's downsampler
+// forward (stride 2, poff 1: diffusers' F.pad(x, (0,1,0,1))) and its input gradient (upsample 1, zins 1, poff -1: the zero-inserted
+// grid) can be run one kernel at a time.  splitk / part as ctx_conv3x3_seg_f16 (no part: no split).  Honours ctx_gemm_tune.
+extern "C" int32_t ctx_conv3x3_geom_f16(const void *x, const void *w, const void *bias, const void *residual, int32_t B, int32_t H, int32_t W,
+                                        int32_t Cin, int32_t Cout, int32_t stride, int32_t upsample, int32_t poff, int32_t zins, void *part,
+                                        int32_t splitk, void *y, ctx_stream_t stream)
+{
+    CTX_REQUIRE(x && w && y, "conv3x3_geom: null pointer");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 8 == 0 && (stride == 1 || stride == 2) &&
+                    (upsample == 0 || upsample == 1) && !(upsample && stride == 2),
+                "conv3x3_geom: need Cin%%64==0, Cout%%8==0, stride 1|2 (B=%d H=%d W=%d Cin=%d Cout=%d s=%d up=%d)", B, H, W, Cin, Cout, stride, upsample);
+    CTX_REQUIRE(zins == 0 || (zins == 1 && upsample == 1 && stride == 1), "conv3x3_geom: the zero-inserted grid needs upsample 1 and stride 1");
+    CTX_REQUIRE(poff >= -1 && poff <= 1, "conv3x3_geom: poff %d is outside -1 .. 1", poff);
+    CTX_REQUIRE(poff != 1 || (H % 2 == 0 && W % 2 == 0), "conv3x3_geom: poff 1 (padding on the bottom / right only) needs even H and W (H=%d W=%d)", H, W);
+    CTX_REQUIRE(splitk != 0 && splitk <= 32 && (splitk <= 1 || splitk <= 9 * Cin / 64), "conv3x3_geom: splitk %d (1 .. min(32, K / 64), or < 0 for the plan)", splitk);
+    GemmArgs a = {};
+    ctx_conv3_problem(a, B, H, W, Cin, Cout, stride, upsample, poff, zins);
+    a.X = (const f16 *)x; a.Wt = (const f16 *)w; a.bias = (const f16 *)bias; a.residual = (const f16 *)residual; a.out = (f16 *)y;
+    a.ldrb = Cout;
+    a.tile = -1; a.use8 = -1;
+    CTX_REQUIRE((int64_t)B * H * W * Cin < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31) && (int64_t)B * a.Ho * a.Wo * Cout < (1ll << 31),
+                "conv3x3_geom: tensor too large for 32-bit offsets");
+    if (splitk < 0 && part) ctx_gemm_plan(a, true); else a.splitk = part && splitk > 1 ? splitk : 1;
+    a.part = (float *)part;
+    return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
+}
+
 // The resnet's first convolution as the engine runs it in front of norm2 (diffusers ResnetBlock2D.forward: conv1, + time embedding,
 // norm2; reference call site src/stable_diffusion_depth.py:422-423): a stride-1 conv3x3 with either
 //   gn_part != null: a request for the partials of GroupNorm(groups) over its output (GemmArgs::gn_part); *slots = slots per sample

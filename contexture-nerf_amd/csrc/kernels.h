@@ -51,6 +51,15 @@ struct GemmArgs {
 #define CTX_GN_MAX_SLOTS 128
 #define CTX_GEMM_MAX_SEG 2
 
+// the problem of a 3x3 convolution over x [B,H,W,Cin] in the given geometry (stride, x2 grid, poff, zins): output grid, GEMM extents and
+// leading dimensions.  engine_conv3 and the test seam ctx_conv3x3_geom_f16 both fill their arguments here.
+static inline void ctx_conv3_problem(GemmArgs &a, int B, int H, int W, int Cin, int Cout, int stride, int ups, int poff, int zins)
+{
+    a.Ho = ((H << ups) - 1) / stride + 1; a.Wo = ((W << ups) - 1) / stride + 1;
+    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo;
+    a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.ups = ups; a.poff = poff; a.zins = zins;
+}
+
 int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s);
 // 256x256 8-wave kernel (gemm8.hip): launches and returns 1 when the problem suits it, else 0
 int ctx_gemm8_try(GemmArgs &a, bool conv, bool force, hipStream_t s);
@@ -87,9 +96,7 @@ struct GnSlabs { const float *part; int S; size_t MN; const f16 *bias, *bias2, *
 int ctx_groupnorm_slabs(const GnSlabs &sl, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu, void *y,
                         hipStream_t stream);
 // GroupNorm(+SiLU) backward, input gradient only, fp16 NHWC: dx = d(loss)/dx (+ add); ws of ctx_groupnorm_bwd_ws_bytes(B, groups)
-int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups);
-int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,
-                          float eps, int silu, f16 *dx, void *ws, hipStream_t s);
+// (ctx_groupnorm_bwd_ws_bytes / ctx_groupnorm_bwd_f16: declared in include/ctx_nerf.h, the unit tests call them too)
 int ctx_layernorm_any(const void *x, int x32, const void *gamma, const void *beta, int64_t rows, int C, float eps, void *y, hipStream_t stream);
 int ctx_concat_f32(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s);
 int ctx_f16_to_f32(const f16 *x, int64_t n, float *y, hipStream_t s);

@@ -550,13 +550,20 @@ __global__ __launch_bounds__(256) void k_gnb_apply(const f16 *__restrict__ x, co
     }
 }
 
-int64_t ctx_groupnorm_bwd_ws_bytes(int B, int groups) { return ((int64_t)B * GNB_MAX_SPLITS * groups * 2 + (int64_t)B * groups * 4) * 4; }
+extern "C" int64_t ctx_groupnorm_bwd_ws_bytes(int32_t B, int32_t groups)
+{
+    return ((int64_t)B * GNB_MAX_SPLITS * groups * 2 + (int64_t)B * groups * 4) * 4;
+}
 
 // dx = d(loss)/dx (+ add) of y = GroupNorm(x) (SiLU after it when `silu`), fp16 NHWC; ws: ctx_groupnorm_bwd_ws_bytes(B, groups)
-int ctx_groupnorm_bwd_f16(const f16 *x, const f16 *dy, const f16 *gamma, const f16 *beta, const f16 *add, int B, int HW, int C, int groups,
-                          float eps, int silu, f16 *dx, void *ws, hipStream_t s)
+extern "C" int32_t ctx_groupnorm_bwd_f16(const void *xv, const void *dyv, const void *gammav, const void *betav, const void *addv, int32_t B,
+                                         int32_t HW, int32_t C, int32_t groups, float eps, int32_t silu, void *dxv, void *ws, ctx_stream_t stream)
 {
+    const f16 *x = (const f16 *)xv, *dy = (const f16 *)dyv, *gamma = (const f16 *)gammav, *beta = (const f16 *)betav, *add = (const f16 *)addv;
+    f16 *dx = (f16 *)dxv;
+    hipStream_t s = (hipStream_t)stream;
     CTX_REQUIRE(x && dy && gamma && beta && dx && ws, "groupnorm backward: null pointer");
+    CTX_REQUIRE(B > 0 && HW > 0 && C >= 8 && groups > 0, "groupnorm backward: B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
     const int G = groups, c8n = C / 8;
     CTX_REQUIRE(C % 8 == 0 && 256 % c8n == 0 && C % G == 0, "groupnorm backward: C=%d groups=%d is outside the kernel's envelope", C, G);
     const int PL = 256 / c8n;

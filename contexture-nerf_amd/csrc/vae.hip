@@ -270,6 +270,8 @@ static void vrows(ctx_vae *v, const f16 *src, int S, int top, f16 *dst)
 {
     v->copy2d(dst, (size_t)top * 2, src, (size_t)3 * top * 2, (size_t)top * 2, S);
 }
+// k_softmax_rows takes its scale times log2(e) (it exponentiates with exp2)
+static float softmax_scale_log2e(float scale) { return 1.4426950408889634f * scale; }
 // probabilities pr = softmax(q k^T scale) [S, S] of dense q, k [S, top]; the scores sc are materialised
 static void vprobs(ctx_vae *v, const f16 *qb, const f16 *kb, int S, int top, float scale_log2e, f16 *sc, f16 *pr)
 {
@@ -298,7 +300,7 @@ static void vattn(ctx_vae *v, const VAttn &at, const f16 *o, f16 *x, int B, int 
         vrows(v, base, S, top, qb);
         vrows(v, base ? base + top : nullptr, S, top, kb);
         VRUN(ctx_transpose_v_f16(base + 2 * top, 1, S, 3 * top, top / 64, S, vt, v->s));     // V^T through the head-transpose kernel
-        vprobs(v, qb, kb, S, top, 1.4426950408889634f / sqrtf((float)top), sc, pr);
+        vprobs(v, qb, kb, S, top, softmax_scale_log2e(1.0f / sqrtf((float)top)), sc, pr);
         engine_linear(*v, pr, vt, nullptr, nullptr, S, top, S, att ? att + (size_t)b * S * top : nullptr);
     }
     f16 *o2 = v->allocH((size_t)M * top);
@@ -515,6 +517,11 @@ __global__ __launch_bounds__(256) void k_conv_in_bwd(const f16 *__restrict__ dy,
     }
 }
 
+// launch geometry of the three kernels above: the engine's backward and the test seams at the end of this file both take it from here
+static unsigned quant_bwd_blocks(int64_t npix) { return (unsigned)cdiv64(npix, 256); }
+static unsigned conv_in_bwd_blocks(int64_t npix) { return (unsigned)std::min<int64_t>(cdiv64(npix, 256), 8192); }
+static size_t conv_in_bwd_lds(int C) { return (size_t)9 * 4 * C * sizeof(float); }
+
 // a data-gradient conv: the transposed / flipped pack by pointer, no bias
 static void vconv_bwd(ctx_vae *v, const f16 *x, size_t wT, int B, int H, int W, int Cin, int Cout, f16 *out, ConvGeom g = ConvGeom())
 {
@@ -565,7 +572,7 @@ static void vattn_bwd(ctx_vae *v, const VAttn &at, const f16 *o, const f16 *qkv,
         vrows(v, base, S, top, qb);
         vrows(v, base ? base + top : nullptr, S, top, kb);
         vrows(v, base ? base + 2 * top : nullptr, S, top, vb);
-        vprobs(v, qb, kb, S, top, 1.4426950408889634f * scale, sc, pr);                             // P (recomputed)
+        vprobs(v, qb, kb, S, top, softmax_scale_log2e(scale), sc, pr);                               // P (recomputed)
         engine_linear(*v, da, vb, nullptr, nullptr, S, S, top, dp);                                 // dP = dAtt V^T
         // dV = P^T dAtt : X = P^T [S,S], Wt = dAtt^T [top,S]
         VRUN(ctx_transpose_v_f16(pr, 1, S, S, S / 64, S, tr, v->s));
@@ -597,7 +604,7 @@ static int vae_encode_bwd_run(ctx_vae *v, const float *gmom, float gscale, float
     void *gws = v->alloc((size_t)ctx_groupnorm_bwd_ws_bytes(B, c.groups));
     const size_t Ml = (size_t)B * h * w;
     f16 *dm = v->allocH(Ml * 64);
-    ENGINE_LAUNCH(v, k_quant_bwd, dim3((unsigned)cdiv64((int64_t)Ml, 256)), dim3(256), 0, gmom, v->W + v->qw, B, L2, (int64_t)h * w, gscale, dm);
+    ENGINE_LAUNCH(v, k_quant_bwd, dim3(quant_bwd_blocks((int64_t)Ml)), dim3(256), 0, gmom, v->W + v->qw, B, L2, (int64_t)h * w, gscale, dm);
     // two rotating gradient buffers sized for the largest activation of the encoder
     size_t big = 0;
     { int hh = H, ww = W; for (int i = 0; i < n; ++i) { big = std::max(big, (size_t)B * hh * ww * c.block_out_channels[i]); if (i != n - 1) { hh /= 2; ww /= 2; } } }
@@ -620,7 +627,7 @@ static int vae_encode_bwd_run(ctx_vae *v, const float *gmom, float gscale, float
         for (int j = (int)v->down[i].size() - 1; j >= 0; --j) { vres_bwd(v, v->down[i][j], tape_at(ri--), ga, B, h, w, gb, gws); std::swap(ga, gb); }
     }
     const int C0 = c.block_out_channels[0];
-    ENGINE_LAUNCH(v, k_conv_in_bwd, dim3((unsigned)std::min<int64_t>(cdiv64((int64_t)B * H * W, 256), 8192)), dim3(256), (size_t)9 * 4 * C0 * sizeof(float),
+    ENGINE_LAUNCH(v, k_conv_in_bwd, dim3(conv_in_bwd_blocks((int64_t)B * H * W)), dim3(256), conv_in_bwd_lds(C0),
                   ga, v->W + v->enc.ciw, B, H, W, C0, c.out_channels, 1.0f / gscale, dimg);
     return engine_finish(v, "vae_encode_bwd");
 }
@@ -664,3 +671,41 @@ extern "C" int32_t ctx_vae_encode_bwd(ctx_vae_t *v, const float *grad_moments, f
 
 /* GEMM and convolution FLOPs of the last run (a training forward's count carries on through its backward) */
 extern "C" double ctx_vae_flops(const ctx_vae_t *v) { return v ? v->flops[0] : 0.0; }
+
+// ---- test seams: the row kernels and the two ends of the encoder backward alone, launched as the engine launches them -------------
+extern "C" int32_t ctx_softmax_rows_f16(const void *s, int32_t rows, int32_t n, float scale, void *p, ctx_stream_t stream)
+{
+    CTX_REQUIRE(s && p, "softmax_rows: null pointer");
+    CTX_REQUIRE(rows > 0 && n > 0 && n % 8 == 0, "softmax_rows: need n %% 8 == 0 (rows=%d n=%d)", rows, n);
+    hipLaunchKernelGGL(k_softmax_rows, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16 *)s, n, softmax_scale_log2e(scale), (f16 *)p);
+    CTX_CHECK_LAUNCH("softmax_rows");
+    return CTX_OK;
+}
+extern "C" int32_t ctx_softmax_bwd_rows_f16(const void *P, const void *dP, int32_t rows, int32_t n, float scale, void *dS, ctx_stream_t stream)
+{
+    CTX_REQUIRE(P && dP && dS, "softmax_bwd_rows: null pointer");
+    CTX_REQUIRE(rows > 0 && n > 0 && n % 8 == 0, "softmax_bwd_rows: need n %% 8 == 0 (rows=%d n=%d)", rows, n);
+    hipLaunchKernelGGL(k_softmax_bwd_rows, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16 *)P, (const f16 *)dP, n, scale, (f16 *)dS);
+    CTX_CHECK_LAUNCH("softmax_bwd_rows");
+    return CTX_OK;
+}
+extern "C" int32_t ctx_quant_bwd_f16(const float *g, const void *w, int32_t B, int32_t C, int64_t HW, float gscale, void *d, ctx_stream_t stream)
+{
+    CTX_REQUIRE(g && w && d, "quant_bwd: null pointer");
+    CTX_REQUIRE(B > 0 && HW > 0 && C > 0 && C <= 16 && (int64_t)B * HW < (1ll << 31), "quant_bwd: need 1 <= C <= 16 (B=%d C=%d HW=%lld)", B, C, (long long)HW);
+    hipLaunchKernelGGL(k_quant_bwd, dim3(quant_bwd_blocks((int64_t)B * HW)), dim3(256), 0, (hipStream_t)stream, g, (const f16 *)w, B, C, HW, gscale, (f16 *)d);
+    CTX_CHECK_LAUNCH("quant_bwd");
+    return CTX_OK;
+}
+extern "C" int32_t ctx_conv_in_bwd_f16(const void *dy, const void *w_pack, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cimg, float inv_gscale,
+                                       float *dimg, ctx_stream_t stream)
+{
+    CTX_REQUIRE(dy && w_pack && dimg, "conv_in_bwd: null pointer");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && Cimg >= 1 && Cimg <= 4 && conv_in_bwd_lds(C) <= 64 * 1024 &&
+                    (int64_t)B * H * W * C < (1ll << 31),
+                "conv_in_bwd: need C %% 8 == 0, C <= 448, 1 <= Cimg <= 4 (B=%d H=%d W=%d C=%d Cimg=%d)", B, H, W, C, Cimg);
+    hipLaunchKernelGGL(k_conv_in_bwd, dim3(conv_in_bwd_blocks((int64_t)B * H * W)), dim3(256), conv_in_bwd_lds(C), (hipStream_t)stream, (const f16 *)dy,
+                       (const f16 *)w_pack, B, H, W, C, Cimg, inv_gscale, dimg);
+    CTX_CHECK_LAUNCH("conv_in_bwd");
+    return CTX_OK;
+}

@@ -561,6 +561,40 @@ int32_t ctx_conv3x3_gn_f16(const void *x, const void *w, const void *bias, const
    of the cuBLAS / cuDNN replacements under UNet2DConditionModel (reference call site src/stable_diffusion_depth.py:422-423) see
    that a forced kernel ran, or that the call fell through to another one when it declined. */
 void ctx_gemm_last_kernel(int32_t *tile, int32_t *use8);
+/* ---- test-only seams of the VAE encoder's training path (ctx_vae_encode_train / ctx_vae_encode_bwd: autograd of `vae.encode`,
+   src/training/trainer.py:732, 866).  Each validates and then launches what the engine launches; tests/vae_train_rule.py holds the
+   float64 references and the error bounds.  Not for product code. ---- */
+/* A 3x3 convolution in any geometry the engines use, GemmArgs filled as the engines fill them: Ho = ((H << upsample) - 1) / stride + 1.
+   poff: input-coordinate offset, 0 = symmetric padding 1; 1 = padding on the bottom / right only (diffusers' Downsample2D of the VAE:
+   F.pad(x, (0,1,0,1)) and a stride-2 conv; needs even H and W).  zins = 1 (needs upsample 1, stride 1): the x2 grid is zero-inserted,
+   not nearest-upsampled; with poff -1 and the pack of ctx_pack_conv3_dgrad_f16 this is that downsampler's input gradient.
+   w [Cout][3][3][Cin]; splitk / part as ctx_conv3x3_seg_f16 (part NULL: no split; splitk <= min(32, 9 Cin / 64)).  Honours
+   ctx_gemm_tune.  CTX_E_ARG, nothing launched: zins without upsample 1 and stride 1, poff outside -1 .. 1, poff 1 with odd H or W. */
+int32_t ctx_conv3x3_geom_f16(const void *x, const void *w, const void *bias, const void *residual, int32_t B, int32_t H, int32_t W,
+                             int32_t Cin, int32_t Cout, int32_t stride, int32_t upsample, int32_t poff, int32_t zins, void *part,
+                             int32_t splitk, void *y, ctx_stream_t stream);
+/* The weight packs of the data gradients, as ctx_vae_set_param writes them next to the forward packs.
+   conv: src f32 [Cout,Cin,3,3] -> dst f16 [Cin][t' = 3 (2 - ky) + (2 - kx)][pad], zero in the columns Cout .. pad (pad >= Cout): the
+   weights [N = Cin][3][3][K-channels = pad] of the convolution that maps a cotangent of pad channels to the input gradient.
+   matrix: src f32 [out,in] -> dst f16 [in][ld] at columns col .. col + out (the rest of dst is not written). */
+int32_t ctx_pack_conv3_dgrad_f16(const float *src, int32_t Cout, int32_t Cin, int32_t pad, void *dst, ctx_stream_t stream);
+int32_t ctx_pack_mat_dgrad_f16(const float *src, int32_t out, int32_t in, int32_t ld, int32_t col, void *dst, ctx_stream_t stream);
+/* GroupNorm(+SiLU) backward, input gradient only, NHWC f16: dx = d loss / d x (+ add, nullable) of y = GroupNorm(x) (SiLU behind it
+   when silu) for the cotangent dy.  Deterministic.  ws: ctx_groupnorm_bwd_ws_bytes(B, groups).  C % 8 == 0, 256 % (C / 8) == 0,
+   C % groups == 0, else CTX_E_ARG. */
+int64_t ctx_groupnorm_bwd_ws_bytes(int32_t B, int32_t groups);
+int32_t ctx_groupnorm_bwd_f16(const void *x, const void *dy, const void *gamma, const void *beta, const void *add, int32_t B, int32_t HW,
+                              int32_t C, int32_t groups, float eps, int32_t silu, void *dx, void *ws, ctx_stream_t stream);
+/* The row kernels of the mid-block attention: p = softmax(s * scale) over rows of n f16 scores, and its backward
+   dS = P * (dP - sum_j P_j dP_j) * scale.  n % 8 == 0. */
+int32_t ctx_softmax_rows_f16(const void *s, int32_t rows, int32_t n, float scale, void *p, ctx_stream_t stream);
+int32_t ctx_softmax_bwd_rows_f16(const void *P, const void *dP, int32_t rows, int32_t n, float scale, void *dS, ctx_stream_t stream);
+/* The two ends of the encoder backward.  quant_conv: g f32 NCHW [B,C,HW], w f16 [C,C] -> d f16 NHWC [B*HW,64] =
+   gscale * sum_o g_o w[o][c], zero in the channels C .. 64 (C <= 16).  conv_in: dy f16 NHWC [B,H,W,C], w_pack f16 [C][3][3][8] (the
+   forward pack, image channels padded to 8) -> dimg f32 NCHW [B,Cimg,H,W] = inv_gscale * the input gradient (Cimg <= 4, C <= 448). */
+int32_t ctx_quant_bwd_f16(const float *g, const void *w, int32_t B, int32_t C, int64_t HW, float gscale, void *d, ctx_stream_t stream);
+int32_t ctx_conv_in_bwd_f16(const void *dy, const void *w_pack, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cimg, float inv_gscale,
+                            float *dimg, ctx_stream_t stream);
 /* GroupNorm(+SiLU) over NHWC f16; stats_ws: ctx_groupnorm_ws_bytes(B, groups). */
 int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const void *beta, int32_t B, int32_t HW,
