@@ -56,6 +56,8 @@ SIGNATURES = {
     "ctx_uvmlp_fwd_save": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ctx_uvmlp_bwd_ws_bytes": (_i64, [_i64, _i32, _i32]),
     "ctx_uvmlp_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_uvmlp_fwd_emb": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_uvmlp_bwd_emb": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctx_texel_active_mark": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ctx_texel_compact_ws_bytes": (_i64, [_i64]),
     "ctx_texel_compact": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
@@ -82,6 +84,9 @@ SIGNATURES = {
     "ctx_distortion_packed_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "ctx_distortion_packed_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "ctx_resample_packed": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_hashgrid_fwd": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_hashgrid_bwd_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "ctx_hashgrid_bwd": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),
     "ctx_unet_param_count": (_i32, [_vp]),

@@ -1,0 +1,228 @@
+// Multiresolution hash-grid encoding (instant-ngp): xyz -> Lv levels x F trainable features, trilinear in each level's grid.
+// The rule is tests/hashgrid_rule.py; this file is built with -ffp-contract=off and is array_equal to it.
+//
+//   ctx_hashgrid_fwd : emb[n, l*F + f] = sum over the 8 corners of the point's cell at level l of w_c * table[l, idx_c, f]
+//   ctx_hashgrid_bwd : g_table[l, idx_c, f] += w_c * g_emb[n, l*F + f], summed as 64-bit integers (a fixed-point accumulator scaled from
+//                      max|g_emb|), so the result does not depend on the order the adds arrive in: bit-reproducible
+//
+// Mapping of both: one thread per (point, level), blockIdx.y = level.  Workgroups are dispatched x-fastest, so the chip works on one
+// level at a time and that level's T*F*4 (forward) or T*F*8 (backward) bytes stay hot in L2 - instant-ngp's mapping.  A thread
+// gathers (adds to) 8 entries of F floats (F int64) and stores (loads) its F floats of the point's row.
+// Positions get no gradient.  No transcendental runs here: the level resolutions are integers computed on the host.
+#include "common.h"
+#include <math.h>
+
+#define HG_MAX_LEVELS 16
+#define HG_BLOCK 256
+
+struct HgGrid {
+    float lo[3], hi[3];
+    int res[HG_MAX_LEVELS];
+    int Lv, log2T;
+};
+
+// what every entry point accepts
+static int32_t hg_check(const char *who, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res, const float *lo, const float *hi, HgGrid &g)
+{
+    CTX_REQUIRE(res && lo && hi, "%s: null res / lo / hi", who);
+    CTX_REQUIRE(Lv >= 1 && Lv <= HG_MAX_LEVELS, "%s: Lv=%d outside [1, %d]", who, Lv, HG_MAX_LEVELS);
+    CTX_REQUIRE(F == 1 || F == 2 || F == 4, "%s: F=%d (1, 2 or 4 features per entry)", who, F);
+    CTX_REQUIRE(Lv * F <= 64, "%s: Lv*F=%d above 64, the width of the field's embedding", who, Lv * F);
+    CTX_REQUIRE(log2T >= 4 && log2T <= 22, "%s: log2T=%d outside [4, 22]", who, log2T);
+    for (int a = 0; a < 3; ++a) {
+        CTX_REQUIRE(isfinite(lo[a]) && isfinite(hi[a]) && lo[a] < hi[a], "%s: box axis %d: want finite lo < hi (lo=%g hi=%g)", who, a, lo[a], hi[a]);
+        g.lo[a] = lo[a]; g.hi[a] = hi[a];
+    }
+    for (int l = 0; l < Lv; ++l) {
+        CTX_REQUIRE(res[l] >= 1 && res[l] <= (1 << 20), "%s: res[%d]=%d outside [1, 2^20]", who, l, res[l]);
+        g.res[l] = res[l];
+    }
+    g.Lv = Lv; g.log2T = log2T;
+    return CTX_OK;
+}
+
+// A point's cell at one level: entry index and weight of the 8 corners, c = cx + 2 cy + 4 cz.  NaN clamps to 0, so every index is in range.
+struct HgCell { uint32_t idx[8]; float w[8]; };
+__device__ __forceinline__ HgCell hg_cell(const float *__restrict__ pts, int64_t n, const HgGrid &g, int l)
+{
+    const int res = g.res[l];
+    const uint32_t T = 1u << g.log2T;
+    const int64_t side = (int64_t)res + 1;
+    const bool dense = side * side * side <= (int64_t)T;
+    int i[3];
+    float w[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float x = (pts[n * 3 + a] - g.lo[a]) / (g.hi[a] - g.lo[a]);
+        x = fminf(fmaxf(x, 0.0f), 1.0f);
+        const float pos = x * (float)res;
+        i[a] = min((int)floorf(pos), res - 1);
+        w[a] = pos - (float)i[a];
+    }
+    HgCell c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
+        const uint32_t gx = (uint32_t)(i[0] + bx), gy = (uint32_t)(i[1] + by), gz = (uint32_t)(i[2] + bz);
+        c.idx[k] = dense ? gx + (uint32_t)side * (gy + (uint32_t)side * gz) : ((gx ^ (gy * 2654435761u) ^ (gz * 805459861u)) & (T - 1));
+        const float sx = bx ? w[0] : 1.0f - w[0], sy = by ? w[1] : 1.0f - w[1], sz = bz ? w[2] : 1.0f - w[2];
+        c.w[k] = (sx * sy) * sz;
+    }
+    return c;
+}
+
+template <int F> struct HgVec;
+template <> struct HgVec<1> { typedef float type; };
+template <> struct HgVec<2> { typedef float2 type; };
+template <> struct HgVec<4> { typedef float4 type; };
+
+template <int F>
+__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_fwd(const float *__restrict__ pts, int64_t n, const float *__restrict__ table, HgGrid g,
+                                                           float *__restrict__ emb)
+{
+    typedef typename HgVec<F>::type V;
+    const int l = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const HgCell c = hg_cell(pts, p, g, l);
+    const float *tl = table + ((int64_t)l << g.log2T) * F;
+    float t[8][F];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) *(V *)t[k] = *(const V *)(tl + (int64_t)c.idx[k] * F);   // the 8 gathers in flight together
+    float o[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s = s + c.w[k] * t[k][f];
+        o[f] = s;
+    }
+    *(V *)(emb + p * ((int64_t)g.Lv * F) + l * F) = *(const V *)o;
+}
+
+extern "C" int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *table, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
+                                    const float *lo, const float *hi, float *emb, ctx_stream_t stream)
+{
+    HgGrid g;
+    if (int32_t rc = hg_check("hashgrid_fwd", Lv, F, log2T, res, lo, hi, g)) return rc;
+    CTX_REQUIRE(pts && table && emb, "hashgrid_fwd: null pointer");
+    CTX_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "hashgrid_fwd: n=%lld outside [1, 2^31)", (long long)n);
+    const dim3 grid((unsigned)cdiv64(n, HG_BLOCK), Lv);
+    hipStream_t s = (hipStream_t)stream;
+    if (F == 1) hipLaunchKernelGGL(k_hashgrid_fwd<1>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
+    else if (F == 2) hipLaunchKernelGGL(k_hashgrid_fwd<2>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
+    else hipLaunchKernelGGL(k_hashgrid_fwd<4>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
+    CTX_CHECK_LAUNCH("hashgrid_fwd");
+    return CTX_OK;
+}
+
+// ---- backward to the table -------------------------------------------------------------------------------------------------------
+// absmax: bits of max|g_emb| (the order of non-negative floats is the order of their bits; inf and NaN sort above every finite value);
+// status: 0 = accumulate, 1 = all zero, 2 = a non-finite gradient poisons the table's gradient;  x: 2^x is the smallest power of two above m
+struct HgCtl { uint32_t absmax; int32_t status; int32_t x; int32_t pad; };
+
+__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_absmax(const float *__restrict__ g, int64_t count, HgCtl *__restrict__ ctl)
+{
+    uint32_t m = 0;
+    const int64_t stride = (int64_t)gridDim.x * HG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x; i < count; i += stride) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
+    for (int o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    __shared__ uint32_t s_m[HG_BLOCK / 64];
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {                        // one atomic per workgroup
+        for (int k = 1; k < HG_BLOCK / 64; ++k) m = max(m, s_m[k]);
+        if (m) atomicMax(&ctl->absmax, m);
+    }
+}
+
+__global__ void k_hashgrid_scale(HgCtl *ctl)
+{
+    const uint32_t b = ctl->absmax;
+    int status = 0, x = 0;
+    if (b == 0) status = 1;
+    else if (b >= 0x7f800000u) status = 2;
+    else if (b >> 23) x = (int)(b >> 23) - 126;    // m = 1.f * 2^(e - 127) < 2^(e - 126)
+    else x = (31 - __clz((int)b)) - 148;           // subnormal: top bit p is worth 2^(p - 149)
+    ctl->status = status;
+    ctl->x = x;
+}
+
+// the exact power of two 2^e as a double, -1022 <= e <= 1023
+__device__ __forceinline__ double hg_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }
+
+template <int F>
+__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd(const float *__restrict__ pts, int64_t n, const float *__restrict__ g_emb, HgGrid g, int E,
+                                                           const HgCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
+{
+    typedef typename HgVec<F>::type V;
+    if (ctl->status != 0) return;
+    const int l = blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const double scale = hg_pow2(E - ctl->x);
+    float ge[F];
+    *(V *)ge = *(const V *)(g_emb + p * ((int64_t)g.Lv * F) + l * F);
+    const HgCell c = hg_cell(pts, p, g, l);
+    unsigned long long *al = acc + ((int64_t)l << g.log2T) * F;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const float prod = c.w[k] * ge[f];                                  // one rounding
+            const long long q = __double2ll_rn((double)prod * scale);           // |prod| < 2^x: |q| <= 2^E, exact scaling, nearest even
+            if (q) atomicAdd(al + (int64_t)c.idx[k] * F + f, (unsigned long long)q);
+        }
+}
+
+__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_convert(const long long *__restrict__ acc, int64_t count, int E, const HgCtl *__restrict__ ctl,
+                                                               float *__restrict__ g_table)
+{
+    const int status = ctl->status;
+    const double inv = hg_pow2(ctl->x - E);
+    const int64_t stride = (int64_t)gridDim.x * HG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x; i < count; i += stride)
+        g_table[i] = status == 2 ? __uint_as_float(0x7fc00000u) : (status == 1 ? 0.0f : (float)((double)acc[i] * inv));
+}
+
+static inline int64_t hg_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+extern "C" int64_t ctx_hashgrid_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T)
+{
+    if (Lv < 1 || Lv > HG_MAX_LEVELS || !(F == 1 || F == 2 || F == 4) || Lv * F > 64 || log2T < 4 || log2T > 22) return -1;
+    return hg_align(((int64_t)Lv << log2T) * F * 8) + 256;      // the int64 accumulator [Lv, T, F], then the control words
+}
+
+extern "C" int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
+                                    const float *lo, const float *hi, int32_t stages, void *ws, float *g_table, ctx_stream_t stream)
+{
+    HgGrid g;
+    if (int32_t rc = hg_check("hashgrid_bwd", Lv, F, log2T, res, lo, hi, g)) return rc;
+    CTX_REQUIRE(pts && g_emb && ws && g_table, "hashgrid_bwd: null pointer");
+    CTX_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "hashgrid_bwd: n=%lld outside [1, 2^31)", (long long)n);
+    CTX_REQUIRE(stages >= 1 && stages <= 7, "hashgrid_bwd: stages=%d (bits: 1 zero, 2 accumulate, 4 convert; 7 is the backward)", stages);
+    const int64_t count = ((int64_t)Lv << log2T) * F;
+    unsigned long long *acc = (unsigned long long *)ws;
+    HgCtl *ctl = (HgCtl *)((char *)ws + hg_align(count * 8));
+    int c8n = 3;                                   // ceil(log2(8 n)): an entry receives at most 8 n terms, each at most 2^E
+    while (((int64_t)1 << (c8n - 3)) < n) ++c8n;
+    const int E = 62 - c8n;
+    hipStream_t s = (hipStream_t)stream;
+    if (stages & 1) {
+        (void)hipMemsetAsync(acc, 0, count * 8, s);
+        (void)hipMemsetAsync(ctl, 0, sizeof(HgCtl), s);
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(k_hashgrid_absmax, dim3(capped_blocks(n * Lv * F, HG_BLOCK * 4, 1024)), dim3(HG_BLOCK), 0, s, g_emb, n * Lv * F, ctl);
+        hipLaunchKernelGGL(k_hashgrid_scale, dim3(1), dim3(1), 0, s, ctl);
+        const dim3 grid((unsigned)cdiv64(n, HG_BLOCK), Lv);
+        if (F == 1) hipLaunchKernelGGL(k_hashgrid_bwd<1>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
+        else if (F == 2) hipLaunchKernelGGL(k_hashgrid_bwd<2>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
+        else hipLaunchKernelGGL(k_hashgrid_bwd<4>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
+    }
+    if (stages & 4)
+        hipLaunchKernelGGL(k_hashgrid_convert, dim3(capped_blocks(count, HG_BLOCK * 4, 4096)), dim3(HG_BLOCK), 0, s, (const long long *)acc, count, E,
+                           ctl, g_table);
+    CTX_CHECK_LAUNCH("hashgrid_bwd");
+    return CTX_OK;
+}

@@ -7,6 +7,8 @@
 //     operands (k_uvmlp_fwd16 / k_uvmlp_dgrad16: every operand is two fp16 numbers, 22 bits of mantissa);
 //   * every other shape, the weight gradients, and everything under CTX_UVMLP_EXACT_F32=1 run on the exact-f32 pipe
 //     (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, 157 TFLOP/s peak on MI355X).
+// ctx_uvmlp_fwd_emb / ctx_uvmlp_bwd_emb take a precomputed embedding of any width up to 64 (the hash-grid field) through the same
+// exact-f32 kernels and add the gradient to that embedding (k_uvmlp_grad_emb, after the dZ chain).
 //
 // In all four chain kernels one workgroup = 64 texels x W hidden units; wave w owns hidden columns [64w, 64w+64) as 2x2
 // accumulator tiles of 32x32.  Activations never leave the CU: the f32 kernels keep them in LDS as act[64][STRIDE] floats
@@ -668,8 +670,10 @@ static int32_t uvm_check_list(const char *who, const int32_t *idx, int64_t N, in
 }
 
 // idx == nullptr: the points are uv / emb / the whole grid and the atlas plane is N long
+// input_ch: the embedding's width, dims * (1 + 2L) where the kernel computes it; any width in [1, 64] on the `emb` seam
 static int32_t uvm_fwd(const float *uv, const float *emb, const int32_t *idx, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
-                       int32_t dims, int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved_v, ctx_stream_t stream)
+                       int32_t dims, int32_t L, int32_t input_ch, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved_v,
+                       ctx_stream_t stream)
 {
     float *saved = (float *)saved_v;
     UvmPlan p; int64_t total = 0;
@@ -678,9 +682,8 @@ static int32_t uvm_fwd(const float *uv, const float *emb, const int32_t *idx, in
     CTX_REQUIRE(dims == 2 || dims == 3, "uvmlp_fwd: dims=%d (2: uv, 3: xyz)", dims);
     CTX_REQUIRE(uv || emb || idx || (dims == 2 && res > 1 && (int64_t)res * res == N),
                 "uvmlp_fwd: no inputs needs dims == 2 and N == res*res (N=%lld res=%d)", (long long)N, res);
-    int input_ch = dims * (1 + 2 * L);
     CTX_REQUIRE(uvm_build_plan(D, W, input_ch, output_ch, skip, p, total) == 0,
-                "uvmlp_fwd: unsupported D=%d W=%d dims=%d L=%d output_ch=%d", D, W, dims, L, output_ch);
+                "uvmlp_fwd: unsupported D=%d W=%d dims=%d L=%d input_ch=%d output_ch=%d", D, W, dims, L, input_ch, output_ch);
     p.dims = dims;
     hipStream_t s = (hipStream_t)stream;
     const float *pk = (const float *)packed;
@@ -705,21 +708,31 @@ extern "C" int32_t ctx_uvmlp_fwd_save(const float *uv, const float *emb, int64_t
                                       int32_t dims, int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved,
                                       ctx_stream_t stream)
 {
-    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, dims, L, output_ch, skip, raw, tex_chw, saved, stream);
+    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, dims, L, dims * (1 + 2 * L), output_ch, skip, raw, tex_chw, saved, stream);
 }
 
 extern "C" int32_t ctx_uvmlp_fwd_save_idx(const int32_t *idx, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W, int32_t L,
                                           int32_t output_ch, int32_t skip, float *raw, float *tex_chw, void *saved, ctx_stream_t stream)
 {
     if (int32_t rc = uvm_check_list("uvmlp_fwd_save_idx", idx, N, res)) return rc;
-    return uvm_fwd(nullptr, nullptr, idx, N, res, packed, D, W, 2, L, output_ch, skip, raw, tex_chw, saved, stream);
+    return uvm_fwd(nullptr, nullptr, idx, N, res, packed, D, W, 2, L, 2 * (1 + 2 * L), output_ch, skip, raw, tex_chw, saved, stream);
 }
 
 extern "C" int32_t ctx_uvmlp_fwd(const float *uv, const float *emb, int64_t N, int32_t res, const void *packed, int32_t D, int32_t W,
                                  int32_t L, int32_t output_ch, int32_t skip, float *raw, float *tex_chw,
                                  ctx_stream_t stream)
 {
-    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, 2, L, output_ch, skip, raw, tex_chw, nullptr, stream);
+    return uvm_fwd(uv, emb, nullptr, N, res, packed, D, W, 2, L, 2 * (1 + 2 * L), output_ch, skip, raw, tex_chw, nullptr, stream);
+}
+
+// The `emb` seam on its own: a precomputed embedding of any width input_ch in [1, 64] (the hash-grid field's Lv * F features).  dims = 3 keeps it
+// on the exact-f32 chain whatever W is; with input_ch = 63 it is the launch ctx_uvmlp_fwd_save(emb, dims = 3, L = 10) makes.
+extern "C" int32_t ctx_uvmlp_fwd_emb(const float *emb, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
+                                     int32_t skip, float *raw, void *saved, ctx_stream_t stream)
+{
+    CTX_REQUIRE(emb, "uvmlp_fwd_emb: null embedding");
+    CTX_REQUIRE(input_ch >= 1 && input_ch <= UVM_EPAD3, "uvmlp_fwd_emb: input_ch=%d outside [1, %d]", input_ch, UVM_EPAD3);
+    return uvm_fwd(nullptr, emb, nullptr, N, 0, packed, D, W, 3, 0, input_ch, output_ch, skip, raw, nullptr, saved, stream);
 }
 
 // =====================================================================================================================
@@ -1191,6 +1204,63 @@ __global__ __launch_bounds__(256) void k_uvm_reduce(const float *__restrict__ sl
     }
 }
 
+// ---- gradient of the `emb` seam: grad_emb[n][e] = sum_j dZ_0[n][j] W_0[j][e] + sum_j dZ_s[n][j] W_s[j][e], s = skip + 1, e < in_ch --------
+// (the skip layer's first in_ch weight columns are its embedding part).  Reads the dZ rows k_uvmlp_dgrad left in the workspace and the
+// forward's packed weights (k_uvm_pack's fragment order: element (j, k) of a layer sits in block (k / 8, j / 32), lane (j % 32) + 32 (k % 8 / 4),
+// slot k % 4; both layers hold the padded embedding in k < epad).  One workgroup = 64 points x 64 columns as a register-tiled product on the
+// VALU: thread (pg, eg) owns points 4 pg .. 4 pg + 3 and columns 4 eg .. 4 eg + 3, and walks K = 2 W in chunks of 64 staged through LDS.
+// HBM floor: the 2 N W 4 bytes of dZ it reads (+ N in_ch 4 written).
+#define UVM_GE_LD 68      // floats per staged row: 16-byte aligned, 4 x odd
+__global__ __launch_bounds__(256) void k_uvmlp_grad_emb(const float *__restrict__ dz0, const float *__restrict__ dzs, int64_t N, int W,
+                                                        const float *__restrict__ w0, const float *__restrict__ wsk, int in_ch, int epad,
+                                                        float *__restrict__ grad_emb)
+{
+    __shared__ __attribute__((aligned(16))) float dzt[UVM_TM * UVM_GE_LD];   // [point][j]
+    __shared__ __attribute__((aligned(16))) float wt[64 * UVM_GE_LD];        // [j][e]
+    const int tid = threadIdx.x, eg = tid & 15, pg = tid >> 4;
+    const int64_t n0 = (int64_t)blockIdx.x * UVM_TM;
+    const bool live = eg * 4 < in_ch;
+    float acc[4][4] = {};
+    for (int src = 0; src < 2; ++src) {
+        const float *dz = src ? dzs : dz0;
+        const float *wp = src ? wsk : w0;
+        for (int jc = 0; jc < W / 64; ++jc) {
+            __syncthreads();                       // the previous chunk has been consumed
+            for (int q = tid; q < UVM_TM * 16; q += 256) {
+                const int row = q >> 4, c4 = q & 15;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (n0 + row < N) v = *(const float4 *)(dz + (n0 + row) * W + jc * 64 + c4 * 4);
+                *(float4 *)(dzt + row * UVM_GE_LD + c4 * 4) = v;
+            }
+            for (int q = tid; q < 1024; q += 256) {
+                const int lane = q & 63, nbl = (q >> 6) & 1, kb = q >> 7;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (kb * 8 < epad) v = *(const float4 *)(wp + (((int64_t)kb * (W / 32) + jc * 2 + nbl) * 64 + lane) * 4);
+                *(float4 *)(wt + (nbl * 32 + (lane & 31)) * UVM_GE_LD + kb * 8 + 4 * (lane >> 5)) = v;
+            }
+            __syncthreads();
+            if (live) {
+#pragma unroll 8
+                for (int j = 0; j < 64; ++j) {
+                    const float4 b = *(const float4 *)(wt + j * UVM_GE_LD + eg * 4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float a = dzt[(pg * 4 + i) * UVM_GE_LD + j];
+                        acc[i][0] += a * b.x; acc[i][1] += a * b.y; acc[i][2] += a * b.z; acc[i][3] += a * b.w;
+                    }
+                }
+            }
+        }
+    }
+    if (live)
+        for (int i = 0; i < 4; ++i) {
+            const int64_t n = n0 + pg * 4 + i;
+            if (n < N)
+                for (int c = 0; c < 4; ++c)
+                    if (eg * 4 + c < in_ch) grad_emb[n * in_ch + eg * 4 + c] = acc[i][c];
+        }
+}
+
 static inline int64_t uvm_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // The backward's workspace: byte offsets of its parts and the total.  ctx_uvmlp_bwd_ws_bytes and ctx_uvmlp_bwd both take it from here.
@@ -1228,8 +1298,8 @@ static void uvm_launch_wgrad(int G, const float *dz, const float *in, int64_t N,
 
 // idx == nullptr: grad_tex is [output_ch][N]; else [output_ch][res^2], read at the listed nodes
 static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32_t *idx, int32_t res, const float *raw, int64_t N, const void *packed,
-                       int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip, const void *saved_v, void *ws,
-                       float *const *gws, float *const *gbs, ctx_stream_t stream)
+                       int32_t D, int32_t W, int32_t dims, int32_t L, int32_t input_ch, int32_t output_ch, int32_t skip, const void *saved_v,
+                       void *ws, float *const *gws, float *const *gbs, float *grad_emb, ctx_stream_t stream)
 {
     UvmPlan p; int64_t total = 0;
     const UvmList list = {idx, idx ? (int64_t)res * res : N};
@@ -1237,9 +1307,8 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
     CTX_REQUIRE(grad_raw || grad_tex, "uvmlp_bwd: need grad_raw and / or grad_tex");
     CTX_REQUIRE(!grad_tex || raw, "uvmlp_bwd: grad_tex needs raw (the tanh argument)");
     CTX_REQUIRE(dims == 2 || dims == 3, "uvmlp_bwd: dims=%d (2: uv, 3: xyz)", dims);
-    int input_ch = dims * (1 + 2 * L);
     CTX_REQUIRE(uvm_build_plan(D, W, input_ch, output_ch, skip, p, total) == 0,
-                "uvmlp_bwd: unsupported D=%d W=%d dims=%d L=%d output_ch=%d", D, W, dims, L, output_ch);
+                "uvmlp_bwd: unsupported D=%d W=%d dims=%d L=%d input_ch=%d output_ch=%d", D, W, dims, L, input_ch, output_ch);
     p.dims = dims;
     CTX_REQUIRE(skip >= 0 && skip + 1 < D, "uvmlp_bwd: skip=%d outside [0, D-2]", skip);
     for (int i = 0; i <= D; ++i) CTX_REQUIRE(gws[i] && gbs[i], "uvmlp_bwd: null gradient pointer for layer %d", i);
@@ -1317,6 +1386,11 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
         }
         CTX_CHECK_LAUNCH("uvmlp_wgrad_reduce");
     }
+    if (grad_emb) {   // the input gradient, from the dZ rows of the two layers that read the embedding
+        hipLaunchKernelGGL(k_uvmlp_grad_emb, dim3((unsigned)ntiles), dim3(256), 0, s, dz, dz + (int64_t)(skip + 1) * N * W, N, W, pk + p.layer[0].w_off,
+                           pk + p.layer[skip + 1].w_off, input_ch, p.epad, grad_emb);
+        CTX_CHECK_LAUNCH("uvmlp_grad_emb");
+    }
     return CTX_OK;
 }
 
@@ -1324,7 +1398,7 @@ extern "C" int32_t ctx_uvmlp_bwd(const float *grad_raw, const float *grad_tex, c
                                  int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip, const void *saved, void *ws,
                                  float *const *gws, float *const *gbs, ctx_stream_t stream)
 {
-    return uvm_bwd(grad_raw, grad_tex, nullptr, 0, raw, N, packed, D, W, dims, L, output_ch, skip, saved, ws, gws, gbs, stream);
+    return uvm_bwd(grad_raw, grad_tex, nullptr, 0, raw, N, packed, D, W, dims, L, dims * (1 + 2 * L), output_ch, skip, saved, ws, gws, gbs, nullptr, stream);
 }
 
 extern "C" int32_t ctx_uvmlp_bwd_idx(const float *grad_raw, const float *grad_tex, const int32_t *idx, int32_t res, const float *raw, int64_t N,
@@ -1332,5 +1406,15 @@ extern "C" int32_t ctx_uvmlp_bwd_idx(const float *grad_raw, const float *grad_te
                                      void *ws, float *const *gws, float *const *gbs, ctx_stream_t stream)
 {
     if (int32_t rc = uvm_check_list("uvmlp_bwd_idx", idx, N, res)) return rc;
-    return uvm_bwd(grad_raw, grad_tex, idx, res, raw, N, packed, D, W, 2, L, output_ch, skip, saved, ws, gws, gbs, stream);
+    return uvm_bwd(grad_raw, grad_tex, idx, res, raw, N, packed, D, W, 2, L, 2 * (1 + 2 * L), output_ch, skip, saved, ws, gws, gbs, nullptr, stream);
+}
+
+// ctx_uvmlp_bwd of the `emb` seam (ctx_uvmlp_fwd_emb's `saved`), with the gradient to the embedding: grad_emb [N][input_ch], nullptr skips it
+extern "C" int32_t ctx_uvmlp_bwd_emb(const float *grad_raw, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
+                                     int32_t skip, const void *saved, void *ws, float *const *gws, float *const *gbs, float *grad_emb,
+                                     ctx_stream_t stream)
+{
+    CTX_REQUIRE(grad_raw, "uvmlp_bwd_emb: null grad_raw");
+    CTX_REQUIRE(input_ch >= 1 && input_ch <= UVM_EPAD3, "uvmlp_bwd_emb: input_ch=%d outside [1, %d]", input_ch, UVM_EPAD3);
+    return uvm_bwd(grad_raw, nullptr, nullptr, 0, nullptr, N, packed, D, W, 3, 0, input_ch, output_ch, skip, saved, ws, gws, gbs, grad_emb, stream);
 }

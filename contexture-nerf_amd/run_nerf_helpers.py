@@ -8,6 +8,8 @@ uv -> embed -> MLP -> (tanh+1)/2 path used by TexturedMeshModel.get_texture_map.
 When gradients are enabled and a parameter requires them, the forward keeps the activations
 (`ctx_uvmlp_fwd_save`) and `backward` runs `ctx_uvmlp_bwd` (the texture side of the SDS loop,
 src/training/trainer.py:644-907): parameter gradients only — uv / the embedding are not trainable inputs.
+`NeRF2D.forward_features(emb)` is the exception: the `emb` seam for any width up to 64 (`ctx_uvmlp_fwd_emb`), whose backward
+(`ctx_uvmlp_bwd_emb`) also carries the gradient to the embedding; hashgrid.HashGridField trains its table through it.
 """
 import ctypes as C
 import numpy as np
@@ -41,6 +43,29 @@ def get_embedder(multires, i=0):
     return (lambda x, eo=eo: eo.embed(x)), eo.out_dim
 
 
+def _take_saved(net, nbytes, dev):
+    """The module's activation store if it is large enough (then the module gives it up until the backward hands it back), else a new one."""
+    saved = net._saved_pool if (net._saved_pool is not None and net._saved_pool.numel() >= nbytes
+                                and net._saved_pool.device == dev) else None
+    net._saved_pool = None
+    return saved if saved is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _return_saved(net, back):
+    """Of the stores of two passes the module keeps the larger."""
+    pool = net._saved_pool
+    if pool is None or pool.device != back.device or pool.numel() <= back.numel():
+        net._saved_pool = back
+
+
+def _bwd_scratch(net, N, dev):
+    wsb = L.load().ctx_uvmlp_bwd_ws_bytes(N, net.D, net.W)
+    if net._bwd_ws is None or net._bwd_ws.numel() < wsb or net._bwd_ws.device != dev:
+        net._bwd_ws = None
+        net._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)     # scratch, stream-ordered: reusable
+    return net._bwd_ws
+
+
 class _UvMlpFn(torch.autograd.Function):
     """(raw [N,C], tex [C,N] or None) = field(uv | emb | grid(res)); gradients flow to the nn.Linear parameters.
     texels (int32 [N], nodes of the res x res grid): the field on those nodes only; tex is then [C,res*res], zero off the list."""
@@ -54,12 +79,7 @@ class _UvMlpFn(torch.autograd.Function):
         # the activation store (8.8 GB for the 1024^2 atlas) is kept by the module and handed out to one forward at a time;
         # allocating it per call makes the caching allocator split and re-malloc multi-GB blocks.  The pool only grows: N changes
         # from step to step on the occupancy path, and the kernels take the prefix of the length they need
-        nbytes = lib.ctx_uvmlp_saved_bytes(N, net.D, net.W, net.input_ch)
-        saved = net._saved_pool if (net._saved_pool is not None and net._saved_pool.numel() >= nbytes
-                                    and net._saved_pool.device == dev) else None
-        net._saved_pool = None
-        if saved is None:
-            saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        saved = _take_saved(net, lib.ctx_uvmlp_saved_bytes(N, net.D, net.W, net.input_ch), dev)
         raw, tex = net._launch_fwd(uv, emb, N, res, want_tex, texels, blob, saved)
         ctx.net, ctx.N, ctx.saved_acts, ctx.blob, ctx.texels, ctx.res = net, N, saved, blob, texels, res
         ctx.save_for_backward(raw)          # an output: kept through save_for_backward so the graph holds no reference cycle
@@ -75,11 +95,7 @@ class _UvMlpFn(torch.autograd.Function):
         layers = list(net.pts_linears) + [net.output_linear]
         gws = [torch.empty_like(l.weight) for l in layers]
         gbs = [torch.empty_like(l.bias) for l in layers]
-        wsb = lib.ctx_uvmlp_bwd_ws_bytes(N, net.D, net.W)
-        if net._bwd_ws is None or net._bwd_ws.numel() < wsb or net._bwd_ws.device != dev:
-            net._bwd_ws = None
-            net._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)     # scratch, stream-ordered: reusable
-        ws = net._bwd_ws
+        ws = _bwd_scratch(net, N, dev)
         gwp = (C.c_void_p * len(gws))(*[L.ptr(g).value for g in gws])
         gbp = (C.c_void_p * len(gbs))(*[L.ptr(g).value for g in gbs])
         g_raw = None if g_raw is None else L.f32c(g_raw)
@@ -90,14 +106,52 @@ class _UvMlpFn(torch.autograd.Function):
         else:
             L.check(lib.ctx_uvmlp_bwd_idx(L.ptr(g_raw), L.ptr(g_tex), L.ptr(ctx.texels), ctx.res, L.ptr(raw), N, L.ptr(ctx.blob), net.D, net.W,
                                           net.multires, net.output_ch, net.skips[0], L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.stream()))
-        back, ctx.saved_acts = ctx.saved_acts, None                     # back to the module for the next forward; of the
-        pool = net._saved_pool                                          # stores of two passes the module keeps the larger
-        if pool is None or pool.device != back.device or pool.numel() <= back.numel():
-            net._saved_pool = back
+        back, ctx.saved_acts = ctx.saved_acts, None                     # back to the module for the next forward
+        _return_saved(net, back)
         grads = []
         for w, b in zip(gws, gbs):
             grads += [w, b]
         return (None, None, None, None, None, None, None, *grads)
+
+
+class _FeatureMlpFn(torch.autograd.Function):
+    """raw [N,C] = field(emb [N,input_ch]) on the `emb` seam (`ctx_uvmlp_fwd_emb`); gradients flow to the nn.Linear parameters and, where
+    it requires one, to emb (`ctx_uvmlp_bwd_emb`).  Same activation pool and backward scratch as _UvMlpFn."""
+
+    @staticmethod
+    def forward(ctx, net, emb, *params):
+        lib = L.load()
+        blob = net.packed()
+        N = emb.shape[0]
+        saved = _take_saved(net, lib.ctx_uvmlp_saved_bytes(N, net.D, net.W, net.input_ch), blob.device)
+        raw = net._launch_features(emb, blob, saved)
+        ctx.net, ctx.N, ctx.saved_acts, ctx.blob = net, N, saved, blob
+        ctx.set_materialize_grads(False)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        lib = L.load()
+        net, N = ctx.net, ctx.N
+        dev = ctx.blob.device
+        layers = list(net.pts_linears) + [net.output_linear]
+        nparam = 2 * len(layers)
+        if g_raw is None:
+            return (None,) * (2 + nparam)
+        gws = [torch.empty_like(l.weight) for l in layers]
+        gbs = [torch.empty_like(l.bias) for l in layers]
+        ws = _bwd_scratch(net, N, dev)
+        gwp = (C.c_void_p * len(gws))(*[L.ptr(g).value for g in gws])
+        gbp = (C.c_void_p * len(gbs))(*[L.ptr(g).value for g in gbs])
+        g_emb = torch.empty(N, net.input_ch, device=dev) if ctx.needs_input_grad[1] else None
+        L.check(lib.ctx_uvmlp_bwd_emb(L.ptr(L.f32c(g_raw)), N, L.ptr(ctx.blob), net.D, net.W, net.input_ch, net.output_ch, net.skips[0],
+                                      L.ptr(ctx.saved_acts), L.ptr(ws), gwp, gbp, L.ptr(g_emb), L.stream()))
+        back, ctx.saved_acts = ctx.saved_acts, None
+        _return_saved(net, back)
+        grads = []
+        for w, b in zip(gws, gbs):
+            grads += [w, b]
+        return (None, g_emb, *grads)
 
 
 class NeRF2D(nn.Module):
@@ -204,6 +258,29 @@ class NeRF2D(nn.Module):
         e = L.f32c(x).reshape(-1, self.input_ch)
         raw, _ = self._run(None, e, e.shape[0], 0, False)
         return raw.reshape(*x.shape[:-1], self.output_ch)
+
+    def _launch_features(self, emb, blob, saved):
+        raw = torch.empty(emb.shape[0], self.output_ch, device=blob.device)
+        L.check(L.load().ctx_uvmlp_fwd_emb(L.ptr(emb, torch.float32, "emb"), emb.shape[0], L.ptr(blob), self.D, self.W, self.input_ch,
+                                           self.output_ch, self.skips[0], L.ptr(raw), L.ptr(saved), L.stream()))
+        return raw
+
+    def forward_features(self, emb):
+        """emb [..., input_ch]: a precomputed embedding of any width input_ch <= 64 (a hash-grid encoding's features) -> [..., output_ch].
+        Differentiable in the parameters and in emb; always the exact-f32 kernels.  With input_ch = 63 it is forward(emb) bit for bit."""
+        if self.input_ch > 64:
+            raise L.CtxError(f"NeRF2D.forward_features: input_ch={self.input_ch} is wider than the fused kernel's 64-column embedding")
+        if not isinstance(emb, torch.Tensor) or emb.shape[-1] != self.input_ch:
+            raise L.CtxError(f"NeRF2D.forward_features: want emb [..., {self.input_ch}], got {tuple(getattr(emb, 'shape', ()))}")
+        e = L.f32c(emb).reshape(-1, self.input_ch)
+        L.ptr(e, torch.float32, "emb")
+        if e.shape[0] == 0:
+            return torch.zeros(*emb.shape[:-1], self.output_ch, device=e.device)
+        if torch.is_grad_enabled() and (e.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raw = _FeatureMlpFn.apply(self, e, *self._params())
+        else:
+            raw = self._launch_features(e, self.packed(), None)
+        return raw.reshape(*emb.shape[:-1], self.output_ch)
 
     def forward_pts(self, pts):
         """Fused embed+MLP on raw points [..., dims] (dims 2: uv, 3: xyz) -> [..., output_ch]."""

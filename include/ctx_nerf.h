@@ -226,6 +226,18 @@ int32_t ctx_uvmlp_bwd(const float *grad_raw /*nullable*/, const float *grad_tex 
                       int64_t N, const void *packed, int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip,
                       const void *saved, void *ws, float *const *gws, float *const *gbs, ctx_stream_t stream);
 
+/* The `emb` seam on its own, with the gradient to the embedding (the hash-grid field): ctx_uvmlp_fwd_save / ctx_uvmlp_bwd
+   with the embedding's width given instead of derived from (dims, L): emb [N, input_ch], 1 <= input_ch <= 64, raw [N, output_ch], no atlas.
+   Always the exact-f32 chain; with input_ch = 63 the launches, and so the bits, are those of ctx_uvmlp_fwd_save(emb, dims = 3, L = 10) /
+   ctx_uvmlp_bwd.  saved (nullable: plain forward): ctx_uvmlp_saved_bytes(N, D, W, input_ch); ws: ctx_uvmlp_bwd_ws_bytes(N, D, W).
+   grad_emb [N, input_ch] (nullable: skipped) = dZ_0 . W_0 + dZ_{skip+1} . W_{skip+1}[:, :input_ch], one kernel after the dZ chain that
+   reads the dZ rows the chain left in ws.  Deterministic. */
+int32_t ctx_uvmlp_fwd_emb(const float *emb, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
+                          int32_t skip, float *raw, void *saved /*nullable*/, ctx_stream_t stream);
+int32_t ctx_uvmlp_bwd_emb(const float *grad_raw, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
+                          int32_t skip, const void *saved, void *ws, float *const *gws, float *const *gbs, float *grad_emb /*nullable*/,
+                          ctx_stream_t stream);
+
 /* ---- texture field on the texels the views sample (TexturedMeshModel.get_texture_map_only_valid_areas,
    src/models/textured_mesh.py:303-347, queries the MLP on chosen texels only; here the choice is what a cached raster can read) ---- */
 /* The active set of a raster, in binary32 in the order ctx_texture_mapping_fwd / _bwd use: for every pixel of uv [B,H,W,2] with
@@ -405,6 +417,25 @@ int32_t ctx_distortion_packed_bwd(const float *weights, const float *t, const fl
 int32_t ctx_resample_packed(const float *weights, const float *ts, const float *dt, const int64_t *ray_off, const float *rays_o,
                             const float *rays_d, int64_t R, int64_t n, int32_t K, const int64_t *fine_off, const float *xi /*nullable*/,
                             int64_t n_fine, int32_t *ray_id_out, float *t_out, float *dt_out, float *pts_out, ctx_stream_t stream);
+
+/* ---- multiresolution hash-grid encoding (instant-ngp; definition: tests/hashgrid_rule.py) ---- */
+/* pts [n,3] in the box lo .. hi (host float[3] each, finite, lo < hi) -> emb [n, Lv*F].  table float32 [Lv, T, F], T = 2^log2T, 4 <= log2T <= 22;
+   1 <= Lv <= 16, F in {1, 2, 4}, Lv*F <= 64; res int32 [Lv] (host), 1 <= res[l] <= 2^20, computed by the caller in float64.  Per level and
+   axis, in binary32 in this order: x = (p - lo)/(hi - lo), x = fminf(fmaxf(x, 0), 1) (NaN -> 0: every index is in range), pos = x*(float)res,
+   i = min((int)floorf(pos), res - 1), w = pos - (float)i.  Corner c = cx + 2 cy + 4 cz at node g = i + bit: idx = gx + (res+1)*(gy + (res+1)*gz)
+   where (res+1)^3 <= T (dense level), else (gx ^ gy*2654435761u ^ gz*805459861u) & (T - 1) in uint32; weight (sx*sy)*sz with s = bit ? w : 1 - w;
+   emb[n, l*F + f] = the left-to-right sum over c ascending of w_c * table[l, idx_c, f], starting from 0.  1 <= n < 2^31. */
+int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *table, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
+                         const float *lo, const float *hi, float *emb, ctx_stream_t stream);
+/* The gradient to the table, g_table [Lv, T, F], every element written; positions get none.  An integer accumulator, so the result does not
+   depend on the order of the adds: m = max|g_emb|, 2^x the smallest power of two above m, E = 62 - ceil(log2(8n)); every contribution
+   w_c * g_emb[n, l*F + f] (one float rounding) is scaled by 2^(E-x) in double (exact), rounded to nearest even into int64 and added to
+   acc[l, idx_c, f] with a 64-bit integer atomic; g_table = (float)((double)acc * 2^(x-E)).  m = 0 writes zeros; a non-finite g_emb turns all
+   of g_table into NaN.  ws: ctx_hashgrid_bwd_ws_bytes(Lv, F, log2T) bytes (-1: refused): the accumulator and the control words.
+   stages: bits 1 = zero the accumulator, 2 = reduce m and accumulate, 4 = convert; 7 is the backward, the parts exist to be timed apart. */
+int64_t ctx_hashgrid_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T);
+int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
+                         const float *lo, const float *hi, int32_t stages, void *ws, float *g_table, ctx_stream_t stream);
 
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
