@@ -1,8 +1,8 @@
-// Volume-render compositing: everything that follows a sample's distance, shared by the dense kernels (geometry.hip: k_composite,
-// k_composite_bwd) and the packed ones (march.hip), so that a packed ray and a dense ray with the same distances give the same bits.
-// One wavefront per ray, lane s of chunk c holds sample 64c + s.  Both files are built without FMA contraction.
+// Volume-render compositing, the per-sample and per-chunk pieces (kernels and entry points: composite.hip).  Everything here is written
+// over a ray layout, dense or packed, so that a packed ray and a dense ray with the same distances give the same bits.
+// One wavefront per ray, lane s of chunk c holds sample 64c + s (ray_wave.h).  Built without FMA contraction.
 #pragma once
-#include "common.h"
+#include "ray_wave.h"
 
 #define COMPOSITE_BWD_MAX_S 4096      // the backward keeps chunk c's entry transmittance in lane c of one register: 64 chunks
 
@@ -18,43 +18,69 @@ __device__ __forceinline__ void composite_rest(float qw, float nz, float dist, b
     t = ok ? (1.0f - alpha) + 1e-10f : 1.0f;
 }
 
-// inclusive prefix product over the 64 lanes on the DPP path (no LDS crossbar): Hillis-Steele inside the 16-lane
-// rows (row_shr 1, 2, 4, 8; lanes without a source multiply by `old` = 1), then row_bcast 15 / 31 across rows;
-// exc = inclusive shifted right by one lane (wave_shr:1; lane 0 keeps `old` = 1)
-__device__ __forceinline__ void composite_prefix(float t, float &inc, float &exc)
-{
-    inc = t;
-    const int one = 0x3f800000;
-#define CTX_SCAN_STEP(ctrl, rmask) inc = inc * __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
-    CTX_SCAN_STEP(0x111, 0xf);
-    CTX_SCAN_STEP(0x112, 0xf);
-    CTX_SCAN_STEP(0x114, 0xf);
-    CTX_SCAN_STEP(0x118, 0xf);
-    CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
-    CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
-#undef CTX_SCAN_STEP
-    exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(one, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
-}
-
-// inclusive prefix sum over the 64 lanes: the same DPP controls with `old` = 0, so lanes without a source and rows outside the mask add 0;
-// exc = inclusive shifted right by one lane (lane 0 keeps 0).  Lane i adds its 16-lane row left to right in a 4-level tree, then the rows.
-__device__ __forceinline__ void composite_prefix_sum(float v, float &inc, float &exc)
-{
-    inc = v;
-#define CTX_SCAN_STEP(ctrl, rmask) inc = inc + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, inc), ctrl, rmask, 0xf, false))
-    CTX_SCAN_STEP(0x111, 0xf);
-    CTX_SCAN_STEP(0x112, 0xf);
-    CTX_SCAN_STEP(0x114, 0xf);
-    CTX_SCAN_STEP(0x118, 0xf);
-    CTX_SCAN_STEP(0x142, 0xa);                    // row_bcast:15 into rows 1 and 3
-    CTX_SCAN_STEP(0x143, 0xc);                    // row_bcast:31 into rows 2 and 3
-#undef CTX_SCAN_STEP
-    exc = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, inc), 0x138, 0xf, 0xf, false));
-}
-
 __device__ __forceinline__ float composite_sigmoid(float x)
 {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+
+// The two ray layouts.  Each says where ray r's samples start and how many there are (count), where a sample's depth lies (depth[i]) and
+// what its distance to the next one is: dist_in is what that takes from memory, loaded with the sample, dist the arithmetic on it.  The
+// distance is split in two so that k_composite_prefetch can issue the load a chunk ahead and do the arithmetic when it reduces the chunk;
+// both take the union of what the two layouts need, so each ignores some arguments.
+// RAGGED: a ray may be empty or hold more than COMPOSITE_BWD_MAX_S samples (the dense entry points refuse both).
+struct dense_rays {                               // R x S samples, ray r at r * S; dist = z[s+1] - z[s], 1e10 on the last sample
+    static constexpr bool RAGGED = false;
+    const float *__restrict__ depth;
+    int S;
+    __device__ __forceinline__ int count(int64_t r, int64_t &off) const { off = r * S; return S; }
+    // lane 63's next depth: the first depth of the following chunk (the other lanes take theirs from the lane above)
+    __device__ __forceinline__ float dist_in(int64_t off, int s, int n, bool ok, int lane) const
+    {
+        return (lane == 63 && s + 1 < n) ? depth[off + s + 1] : 0.f;
+    }
+    __device__ __forceinline__ float dist(float zv, float zx, int s, int n, float nrm) const
+    {
+        const float zn = wave_shl1(zv, zx);
+        return ((s + 1 < n) ? (zn - zv) : 1e10f) * nrm;
+    }
+};
+struct packed_rays {                              // ray r holds samples ray_off[r] .. ray_off[r+1] of n; dist = dt * |d|, no 1e10 distance:
+    static constexpr bool RAGGED = true;          // the background shows through what the runs leave
+    const float *__restrict__ depth, *__restrict__ dt;
+    const int64_t *__restrict__ ray_off;
+    int64_t n;
+    __device__ __forceinline__ int count(int64_t r, int64_t &off) const { return packed_count(ray_off, r, n, off); }
+    __device__ __forceinline__ float dist_in(int64_t off, int s, int, bool ok, int) const { return ok ? dt[off + s] : 0.f; }
+    __device__ __forceinline__ float dist(float, float dtv, int, int, float nrm) const { return dtv * nrm; }
+};
+
+// The sample's weight under its chunk's entry transmittance Tc (call it in every lane: it scans across the wave); Tc <- the next chunk's.
+template <bool NOISE>
+__device__ __forceinline__ float composite_weight(float qw, float nz, float dist, bool ok, float &Tc)
+{
+    float e, alpha, t;
+    composite_rest<NOISE>(qw, nz, dist, ok, e, alpha, t);
+    const float inc = wave_scan<scan_prod>(t);
+    const float w = alpha * (Tc * wave_shr1(inc, 1.0f));
+    Tc = Tc * wave_lane(inc, 63);
+    return w;
+}
+
+// Forward, one chunk of a ray: the weight (stored when asked for) and the lane's share of the five sums.
+struct composite_sums {
+    float Tc = 1.0f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dep = 0.f, a = 0.f;
+};
+template <bool NOISE>
+__device__ __forceinline__ void composite_chunk(float4 q, float zv, float nz, float dist, bool ok, float *__restrict__ weights, int64_t i,
+                                                composite_sums &m)
+{
+    const float w = composite_weight<NOISE>(q.w, nz, dist, ok, m.Tc);
+    if (weights && ok) weights[i] = w;
+    m.c0 += w * composite_sigmoid(q.x);
+    m.c1 += w * composite_sigmoid(q.y);
+    m.c2 += w * composite_sigmoid(q.z);
+    m.dep += w * zv;
+    m.a += w;
 }
 
 // The ray's outputs from the lanes' partial sums (wave-uniform call): the wave sums, the white background, disp = 1 / max(depth / acc, 1e-10)
@@ -97,22 +123,9 @@ __device__ __forceinline__ float4 composite_bwd_sample(float4 q, float pre, floa
     const float w = alpha * T;
     const float c0 = composite_sigmoid(q.x), c1 = composite_sigmoid(q.y), c2 = composite_sigmoid(q.z);
     const float G = ((((g0 * c0 + g1 * c1) + g2 * c2) + gd * zv) + ga) + gw;          // dL/dw_s
-    // inclusive suffix sum of G_k w_k over the lanes at and behind this one
-    float suf = ok ? G * w : 0.f;
-#define CTX_SUFFIX_STEP(ctrl) suf = suf + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), ctrl, 0xf, 0xf, false))
-    CTX_SUFFIX_STEP(0x101);                   // row_shl 1, 2, 4, 8: lanes without a source add `old` = 0
-    CTX_SUFFIX_STEP(0x102);
-    CTX_SUFFIX_STEP(0x104);
-    CTX_SUFFIX_STEP(0x108);
-#undef CTX_SUFFIX_STEP
-    const int si = __builtin_bit_cast(int, suf);
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 16)), r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(si, 48));
-    const int row = lane >> 4;
-    suf = suf + (row == 0 ? (r1 + (r2 + r3)) : row == 1 ? (r2 + r3) : row == 2 ? r3 : 0.f);
-    // exclusive: the inclusive sum of the next lane (wave_shl:1; lane 63 keeps `old` = 0)
-    const float X = carry + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, suf), 0x130, 0xf, 0xf, false));
-    carry = carry + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, suf), 0));
+    const float suf = wave_suffix_sum(ok ? G * w : 0.f, lane);          // of G_k w_k over the lanes at and behind this one
+    const float X = carry + wave_shl1(suf, 0.f);                         // exclusive: the inclusive sum of the next lane
+    carry = carry + wave_lane(suf, 0);
     // dL/dalpha_s * dist_s * e_s with e_s folded in before the division: e / t <= 1 and dist * e stays finite at dist = 1e10
     const float da = (G * T) * (dist * e) - (X * (e * __builtin_amdgcn_rcpf(t))) * dist;
     float4 o;

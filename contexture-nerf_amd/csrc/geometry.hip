@@ -8,7 +8,6 @@
 #include <math.h>
 
 #pragma clang fp contract(off)
-#include "composite.h"
 
 // ------------------------------------------------------------------------------------------------
 // prepare_vertices: two tiny kernels (vertex transform, then per-face gather + normal).
@@ -882,7 +881,7 @@ extern "C" int32_t ctx_embed_fwd(const float *x, int64_t N, int32_t d, int32_t L
 }
 
 // ------------------------------------------------------------------------------------------------
-// Rays + volume-render compositing.
+// Camera rays.
 __global__ __launch_bounds__(256) void k_get_rays(int H, int W, float fx, float fy, float cx, float cy,
                                                   const float *__restrict__ c2w, float *__restrict__ ro,
                                                   float *__restrict__ rd)
@@ -906,189 +905,5 @@ extern "C" int32_t ctx_get_rays(int32_t H, int32_t W, float fx, float fy, float 
     hipLaunchKernelGGL(k_get_rays, dim3((unsigned)cdiv64((int64_t)H * W, 256)), dim3(256), 0, (hipStream_t)stream,
                        H, W, fx, fy, cx, cy, c2w, rays_o, rays_d);
     CTX_CHECK_LAUNCH("get_rays");
-    return CTX_OK;
-}
-
-// The sample's distance to the next one, the dense layout's part of the per-sample terms; what follows it is composite_rest (composite.h).
-// zx: lane 63's next depth (the first depth of the following chunk); noise is added to the density before the ReLU.
-template <bool NOISE>
-__device__ __forceinline__ void composite_sample(float qw, float nz, float zv, float zx, int s, int S, bool ok, float nrm,
-                                                 float &dist, float &e, float &alpha, float &t)
-{
-    // next sample's depth: wave_shl:1 on the DPP path (lane 63 keeps `old` = the first depth of the following chunk)
-    float zn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, zx), __builtin_bit_cast(int, zv), 0x130, 0xf, 0xf, false));
-    dist = (s + 1 < S) ? (zn - zv) : 1e10f;
-    dist = dist * nrm;
-    composite_rest<NOISE>(qw, nz, dist, ok, e, alpha, t);
-}
-
-// One wavefront per ray: lane s holds sample s of the current 64-sample chunk.  Transmittance is an
-// exclusive prefix product across lanes (6 DPP steps), colour/depth/acc are wave sums on the DPP path.  The next chunk's (or next
-// ray's first) loads are issued before the current chunk is reduced, so HBM latency overlaps the shuffle chain.
-template <bool NOISE>
-__global__ __launch_bounds__(256) void k_composite(const float4 *__restrict__ raw, const float *__restrict__ z,
-                                                   const float *__restrict__ rays_d, const float *__restrict__ noise,
-                                                   int64_t R, int S, int white,
-                                                   float *__restrict__ rgb, float *__restrict__ disp,
-                                                   float *__restrict__ acc, float *__restrict__ weights,
-                                                   float *__restrict__ depth)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
-    const int nch = (S + 63) >> 6;
-    // software pipeline over the flattened (ray, chunk) sequence of this wave
-    int64_t r = wave;
-    int ch = 0;
-    float4 q_n = make_float4(0.f, 0.f, 0.f, 0.f);
-    float z_n = 0.f, zx_n = 0.f, nz_n = 0.f;
-    auto fetch = [&](int64_t rr, int cc) {
-        int s = cc * 64 + lane;
-        bool ok = rr < R && s < S;
-        q_n = ok ? raw[rr * S + s] : make_float4(0.f, 0.f, 0.f, 0.f);
-        z_n = ok ? z[rr * S + s] : 0.f;
-        zx_n = (rr < R && lane == 63 && s + 1 < S) ? z[rr * S + s + 1] : 0.f;      // first depth of the following chunk
-        if (NOISE) nz_n = ok ? noise[rr * S + s] : 0.f;
-    };
-    if (r < R) fetch(r, 0);
-    float Tc = 1.0f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dep = 0.f, a = 0.f, nrm = 0.f;
-    while (r < R) {
-        float4 q = q_n;
-        float zv = z_n, zx = zx_n, nz = nz_n;
-        const int s = ch * 64 + lane;
-        const bool ok = s < S;
-        if (ch == 0) {
-            float d0 = rays_d[r * 3 + 0], d1 = rays_d[r * 3 + 1], d2 = rays_d[r * 3 + 2];
-            nrm = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-            Tc = 1.0f; c0 = c1 = c2 = dep = a = 0.f;
-        }
-        // issue the next (ray, chunk) loads now
-        int64_t rn = r; int cn = ch + 1;
-        if (cn == nch) { cn = 0; rn = r + nwaves; }
-        fetch(rn, cn);
-        float dist, e, alpha, t, inc, exc;
-        composite_sample<NOISE>(q.w, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
-        composite_prefix(t, inc, exc);
-        float w = alpha * (Tc * exc);
-        if (weights && ok) weights[r * S + s] = w;
-        c0 += w * composite_sigmoid(q.x);
-        c1 += w * composite_sigmoid(q.y);
-        c2 += w * composite_sigmoid(q.z);
-        dep += w * zv;
-        a += w;
-        Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
-        if (ch + 1 == nch)
-            composite_finish(lane, r, white, c0, c1, c2, dep, a, rgb, disp, acc, depth);
-        r = rn; ch = cn;
-    }
-}
-
-static int composite_blocks(int64_t R)
-{
-    int64_t nb = cdiv64(R, 4);
-    static int cap = -1;
-    if (cap < 0) { const char *e = getenv("CTX_COMPOSITE_BLOCKS"); cap = e ? atoi(e) : 262144; }   // one ray per wave up to 1 M rays: 136.8 us vs 142.6 at 32768 blocks (512^2 x 128)
-    return (int)(nb > cap ? cap : nb);
-}
-
-extern "C" int32_t ctx_raymarch_composite_fwd_noise(const float *raw, const float *z_vals, const float *rays_d, const float *noise,
-                                                    int64_t R, int32_t S, int32_t white_bkgd, float *rgb, float *disp, float *acc,
-                                                    float *weights, float *depth, ctx_stream_t stream)
-{
-    CTX_REQUIRE(raw && z_vals && rays_d && rgb && disp && acc && depth && R > 0 && S > 0, "raymarch: bad args");
-    if (noise)
-        hipLaunchKernelGGL(k_composite<true>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
-                           z_vals, rays_d, noise, R, S, white_bkgd, rgb, disp, acc, weights, depth);
-    else
-        hipLaunchKernelGGL(k_composite<false>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
-                           z_vals, rays_d, noise, R, S, white_bkgd, rgb, disp, acc, weights, depth);
-    CTX_CHECK_LAUNCH("raymarch_composite");
-    return CTX_OK;
-}
-
-extern "C" int32_t ctx_raymarch_composite_fwd(const float *raw, const float *z_vals, const float *rays_d, int64_t R,
-                                              int32_t S, int32_t white_bkgd, float *rgb, float *disp, float *acc,
-                                              float *weights, float *depth, ctx_stream_t stream)
-{
-    return ctx_raymarch_composite_fwd_noise(raw, z_vals, rays_d, nullptr, R, S, white_bkgd, rgb, disp, acc, weights, depth, stream);
-}
-
-// Backward of k_composite with respect to raw (closed form: DESIGN section 4d).  One wavefront per ray, two sweeps over the
-// ray's 64-sample chunks.  Sweep 1 (front to back) re-runs the forward's alpha / transmittance sequence for acc and depth and
-// leaves chunk c's entry transmittance in lane c of one register, which bounds S at 64 chunks.  Sweep 2 (back to front)
-// recomputes the chunk, carries the suffix sum of G_k w_k over the chunks behind it and adds a true in-wave suffix scan (row_shl
-// inside the 16-lane rows, the three row totals behind a row by readlane), so a sample deep behind an opaque one keeps its
-// relative accuracy.  No atomics, one fixed summation order; every element of grad_raw is written.
-template <bool NOISE>
-__global__ __launch_bounds__(256) void k_composite_bwd(const float4 *__restrict__ raw, const float *__restrict__ z,
-                                                       const float *__restrict__ rays_d, const float *__restrict__ noise,
-                                                       int64_t R, int S, int white,
-                                                       const float *__restrict__ g_rgb, const float *__restrict__ g_disp,
-                                                       const float *__restrict__ g_acc, const float *__restrict__ g_weights,
-                                                       const float *__restrict__ g_depth, float4 *__restrict__ grad_raw)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
-    const int nch = (S + 63) >> 6;
-    for (int64_t r = wave; r < R; r += nwaves) {
-        const float d0 = rays_d[r * 3 + 0], d1 = rays_d[r * 3 + 1], d2 = rays_d[r * 3 + 2];
-        const float nrm = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-        const float4 *rawr = raw + r * S;
-        const float *zr = z + r * S, *nr = NOISE ? noise + r * S : nullptr;
-        float Tc = 1.0f, tcv = 1.0f, dep = 0.f, a = 0.f;
-        for (int ch = 0; ch < nch; ++ch) {
-            const int s = ch * 64 + lane;
-            const bool ok = s < S;
-            float qw = ok ? rawr[s].w : 0.f;
-            float zv = ok ? zr[s] : 0.f;
-            float zx = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
-            float nz = (NOISE && ok) ? nr[s] : 0.f;
-            float dist, e, alpha, t, inc, exc;
-            composite_sample<NOISE>(qw, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
-            composite_prefix(t, inc, exc);
-            if (lane == ch) tcv = Tc;
-            float w = alpha * (Tc * exc);
-            dep += w * zv;
-            a += w;
-            Tc = Tc * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 63));
-        }
-        const float sd = wave_sum_dpp(dep), sa = wave_sum_dpp(a);
-        float g0, g1, g2, gd, ga;
-        composite_bwd_upstream(r, white, sd, sa, g_rgb, g_disp, g_acc, g_depth, g0, g1, g2, gd, ga);
-        float carry = 0.f;                                              // sum of G_k w_k over the chunks behind this one
-        for (int ch = nch - 1; ch >= 0; --ch) {
-            const int s = ch * 64 + lane;
-            const bool ok = s < S;
-            float4 q = ok ? rawr[s] : make_float4(0.f, 0.f, 0.f, 0.f);
-            float zv = ok ? zr[s] : 0.f;
-            float zx = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
-            float nz = (NOISE && ok) ? nr[s] : 0.f;
-            float gw = (g_weights && ok) ? g_weights[r * S + s] : 0.f;
-            float dist, e, alpha, t, inc, exc;
-            composite_sample<NOISE>(q.w, nz, zv, zx, s, S, ok, nrm, dist, e, alpha, t);
-            composite_prefix(t, inc, exc);
-            const float T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tcv), ch)) * exc;
-            const float pre = NOISE ? q.w + nz : q.w;
-            const float4 o = composite_bwd_sample(q, pre, zv, gw, ok, lane, dist, e, alpha, t, T, g0, g1, g2, gd, ga, carry);
-            if (ok) grad_raw[r * S + s] = o;
-        }
-    }
-}
-
-extern "C" int32_t ctx_raymarch_composite_bwd(const float *raw, const float *z_vals, const float *rays_d, const float *noise,
-                                              int64_t R, int32_t S, int32_t white_bkgd, const float *g_rgb, const float *g_disp,
-                                              const float *g_acc, const float *g_weights, const float *g_depth, float *grad_raw,
-                                              ctx_stream_t stream)
-{
-    CTX_REQUIRE(raw && z_vals && rays_d && grad_raw && R > 0 && S > 0, "raymarch_bwd: bad args");
-    CTX_REQUIRE(S <= COMPOSITE_BWD_MAX_S, "raymarch_bwd: S exceeds the 4096 samples per ray the backward supports");
-    if (noise)
-        hipLaunchKernelGGL(k_composite_bwd<true>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
-                           z_vals, rays_d, noise, R, S, white_bkgd, g_rgb, g_disp, g_acc, g_weights, g_depth, (float4 *)grad_raw);
-    else
-        hipLaunchKernelGGL(k_composite_bwd<false>, dim3((unsigned)composite_blocks(R)), dim3(256), 0, (hipStream_t)stream, (const float4 *)raw,
-                           z_vals, rays_d, noise, R, S, white_bkgd, g_rgb, g_disp, g_acc, g_weights, g_depth, (float4 *)grad_raw);
-    CTX_CHECK_LAUNCH("raymarch_composite_bwd");
     return CTX_OK;
 }

@@ -1,12 +1,12 @@
 // Importance resampling of the marched sample lists (definition: tests/resample_rule.py): every hit ray gets K fine
 // samples placed by the inverse CDF of its own coarse weights, and K fine widths that tile its occupied length.
-// The layout is k_composite_packed's and k_distortion_packed's: one wavefront per ray, grid-stride; lane s of coarse chunk c holds interval
+// One wavefront per ray, grid-stride (ray_wave.h); lane s of coarse chunk c holds interval
 // ray_off[r] + 64c + s, lane k of output chunk q owns fine sample fine_off[r] + 64q + k.  Sweep one takes the totals W (mass) and L (occupied
 // length) by chunked prefix sums chained by two carried scalars, so any S <= 2^31 - 64 works without a chunk table (the chunk and sample
 // indices are int).  Sweep two, per output chunk, walks the coarse chunks again with the same sums; a lane whose target falls into the chunk's mass range finds its interval by a six-step
 // lane-indexed search on the chunk's exclusive sums (ds_bpermute, no LDS allocation) and fetches that lane's C, l, m, ts, dt.
 // Built with -ffp-contract=off.  No atomics; every output element has one writer.
-#include "composite.h"
+#include "ray_wave.h"
 
 #define RESAMPLE_MAX_K 4096           // the fine lists are composited too: what the compositing backward holds per ray (COMPOSITE_BWD_MAX_S)
 
@@ -15,31 +15,15 @@ __device__ __forceinline__ float resample_lane(float v, int src)          // v o
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
 }
 
-// inclusive prefix maximum over the 64 lanes of values >= 0: composite_prefix_sum's DPP controls (`old` = 0 is the neutral element).
-// A tree-ordered prefix sum of non-negative terms can step down by an ulp between neighbouring lanes; the maximum makes it non-descending,
-// which the search, the order of t' and dt' >= 0 rest on.  On sequential sums (the restatement) it is the identity.
-__device__ __forceinline__ float resample_prefix_max(float v)
-{
-#define CTX_SCAN_STEP(ctrl, rmask) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false)))
-    CTX_SCAN_STEP(0x111, 0xf);
-    CTX_SCAN_STEP(0x112, 0xf);
-    CTX_SCAN_STEP(0x114, 0xf);
-    CTX_SCAN_STEP(0x118, 0xf);
-    CTX_SCAN_STEP(0x142, 0xa);
-    CTX_SCAN_STEP(0x143, 0xc);
-#undef CTX_SCAN_STEP
-    return v;
-}
-
 // non-descending prefix sums of v >= 0 continued from carry: in = max over the lanes up to this one of carry + (inclusive sum), ex = the
-// lane before's `in` (lane 0: carry); carry <- lane 63's `in`.
+// lane before's `in` (lane 0: carry); carry <- lane 63's `in`.  A tree-ordered prefix sum of non-negative terms can step down by an ulp
+// between neighbouring lanes; the prefix maximum makes it non-descending, which the search, the order of t' and dt' >= 0 rest on.  On
+// sequential sums (the restatement) it is the identity.
 __device__ __forceinline__ void resample_prefix(float v, float &carry, float &ex, float &in)
 {
-    float inc, exc;
-    composite_prefix_sum(v, inc, exc);
-    in = resample_prefix_max(carry + inc);
-    ex = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, carry), __builtin_bit_cast(int, in), 0x138, 0xf, 0xf, false));
-    carry = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, in), 63));
+    in = wave_scan<scan_max>(carry + wave_scan<scan_sum>(v));
+    ex = wave_shr1(in, carry);
+    carry = wave_lane(in, 63);
 }
 
 // One chunk of coarse intervals: the lane's mass m = min(max(w, 0), 1) + 1e-5 (a NaN weight counts as 0, +inf as 1), start and width (all 0
@@ -91,14 +75,12 @@ __global__ __launch_bounds__(256) void k_resample_packed(const float *__restrict
                                                          int32_t *__restrict__ ray_id, float *__restrict__ t_out, float *__restrict__ dt_out,
                                                          float *__restrict__ pts)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
+    const ray_wave rw = ray_wave_here();
+    const int lane = rw.lane;
     const float Kf = (float)K;
-    for (int64_t r = wave; r < R; r += nwaves) {
-        const int64_t off = ray_off[r], end = ray_off[r + 1];
-        // n < 2^31; a ray_off outside the lists reads nothing, nor does a ray whose 64 * chunks would leave an int
-        const int S = (off >= 0 && end >= off && end <= n && end - off <= INT32_MAX - 63) ? (int)(end - off) : 0;
+    for (int64_t r = rw.first; r < R; r += rw.stride) {
+        int64_t off;
+        const int S = packed_count(ray_off, r, n, off);
         if (S == 0) continue;                                           // an empty ray (most rays of a render): nothing, without its origin
         const int64_t foff = fine_off[r];
         const int64_t fend = fine_off[r + 1] < n_fine ? fine_off[r + 1] : n_fine;
@@ -173,7 +155,7 @@ extern "C" int32_t ctx_resample_packed(const float *weights, const float *ts, co
     if (n == 0 || n_fine == 0) return CTX_OK;
     CTX_REQUIRE(weights && ts && dt && ray_off && rays_o && rays_d && fine_off, "resample_packed: null input with n=%lld", (long long)n);
     CTX_REQUIRE(ray_id_out && t_out && dt_out && pts_out, "resample_packed: null output with n_fine=%lld", (long long)n_fine);
-    hipLaunchKernelGGL(k_resample_packed, dim3(capped_blocks(R, 4, 262144)), dim3(256), 0, (hipStream_t)stream, weights, ts, dt, ray_off, rays_o,
+    hipLaunchKernelGGL(k_resample_packed, dim3(ray_blocks(R)), dim3(256), 0, (hipStream_t)stream, weights, ts, dt, ray_off, rays_o,
                        rays_d, R, n, (int)K, fine_off, xi, n_fine, ray_id_out, t_out, dt_out, pts_out);
     CTX_CHECK_LAUNCH("resample_packed");
     return CTX_OK;

@@ -34,7 +34,7 @@ def clamped(w):
 
 
 def _wave_scan(v):
-    """Inclusive sum of 64 binary32 values in the order of composite_prefix_sum (row_shr 1, 2, 4, 8, row_bcast 15, row_bcast 31)."""
+    """Inclusive sum of 64 binary32 values in the order of wave_scan<scan_sum> (row_shr 1, 2, 4, 8, row_bcast 15, row_bcast 31)."""
     x = v.astype(f32).copy()
     lane = np.arange(64)
     for s in (1, 2, 4, 8):
