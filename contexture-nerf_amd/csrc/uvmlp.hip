@@ -1303,7 +1303,9 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
 {
     UvmPlan p; int64_t total = 0;
     const UvmList list = {idx, idx ? (int64_t)res * res : N};
-    CTX_REQUIRE(packed && saved_v && ws && gws && gbs && N > 0, "uvmlp_bwd: bad args");
+    // gws and gbs both null with a grad_emb: the input gradient alone (the dZ chain and k_uvmlp_grad_emb), no weight-gradient launch
+    const bool want_w = gws || gbs || !grad_emb;
+    CTX_REQUIRE(packed && saved_v && ws && (!want_w || (gws && gbs)) && N > 0, "uvmlp_bwd: bad args");
     CTX_REQUIRE(grad_raw || grad_tex, "uvmlp_bwd: need grad_raw and / or grad_tex");
     CTX_REQUIRE(!grad_tex || raw, "uvmlp_bwd: grad_tex needs raw (the tanh argument)");
     CTX_REQUIRE(dims == 2 || dims == 3, "uvmlp_bwd: dims=%d (2: uv, 3: xyz)", dims);
@@ -1311,7 +1313,7 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
                 "uvmlp_bwd: unsupported D=%d W=%d dims=%d L=%d input_ch=%d output_ch=%d", D, W, dims, L, input_ch, output_ch);
     p.dims = dims;
     CTX_REQUIRE(skip >= 0 && skip + 1 < D, "uvmlp_bwd: skip=%d outside [0, D-2]", skip);
-    for (int i = 0; i <= D; ++i) CTX_REQUIRE(gws[i] && gbs[i], "uvmlp_bwd: null gradient pointer for layer %d", i);
+    for (int i = 0; want_w && i <= D; ++i) CTX_REQUIRE(gws[i] && gbs[i], "uvmlp_bwd: null gradient pointer for layer %d", i);
     hipStream_t s = (hipStream_t)stream;
     const float *pk = (const float *)packed;
     const float *saved = (const float *)saved_v;
@@ -1341,10 +1343,12 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
         });
     }
     CTX_CHECK_LAUNCH("uvmlp_dgrad");
-    hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(output_ch * W / 4, 64)), dim3(256), 0, s, part_w, dg, (int64_t)4 * W, output_ch, W, W,
-                       gws[D], W, 0);
-    hipLaunchKernelGGL(k_uvm_reduce, dim3(1), dim3(256), 0, s, part_b, dg, (int64_t)4, 1, 4, output_ch, gbs[D], 4, 0);
-    CTX_CHECK_LAUNCH("uvmlp_reduce_out");
+    if (want_w) {
+        hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(output_ch * W / 4, 64)), dim3(256), 0, s, part_w, dg, (int64_t)4 * W, output_ch, W, W,
+                           gws[D], W, 0);
+        hipLaunchKernelGGL(k_uvm_reduce, dim3(1), dim3(256), 0, s, part_b, dg, (int64_t)4, 1, 4, output_ch, gbs[D], 4, 0);
+        CTX_CHECK_LAUNCH("uvmlp_reduce_out");
+    }
 
     // ---- phase 2: weight / bias gradients ----
     int64_t chunk = cdiv64(N, UVM_WG_GROUPS);
@@ -1356,7 +1360,7 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
     const float *emb = saved;
     const float *acts = saved + N * p.epad;
     static const int wg8 = [] { const char *e = getenv("CTX_UVM_WG8"); return e ? atoi(e) : 0; }();
-    for (int li = D - 1; li >= 0; --li) {
+    for (int li = D - 1; want_w && li >= 0; --li) {
         const float *dzl = dz + (int64_t)li * N * W;
         const int kin = li == 0 ? input_ch : (li == skip + 1 ? input_ch + W : W);
         const bool has_emb = li == 0 || li == skip + 1;

@@ -282,6 +282,25 @@ class NeRF2D(nn.Module):
             raw = self._launch_features(e, self.packed(), None)
         return raw.reshape(*emb.shape[:-1], self.output_ch)
 
+    @torch.no_grad()
+    def features_input_gradient(self, emb, g_raw):
+        """(raw [N, output_ch], g_emb [N, input_ch]) for emb [N, input_ch] and g_raw [N, output_ch], float32 contiguous device tensors:
+        forward_features' launch with the activation store, then `ctx_uvmlp_bwd_emb` for the input gradient alone (no weight-gradient
+        launch).  No autograd graph, no .grad; the activation pool goes back to the module as after a backward."""
+        lib = L.load()
+        blob = self.packed()
+        N = emb.shape[0]
+        saved = _take_saved(self, lib.ctx_uvmlp_saved_bytes(N, self.D, self.W, self.input_ch), blob.device)
+        try:
+            raw = self._launch_features(emb, blob, saved)
+            g_emb = torch.empty(N, self.input_ch, device=blob.device)
+            L.check(lib.ctx_uvmlp_bwd_emb(L.ptr(g_raw, torch.float32, "g_raw"), N, L.ptr(blob), self.D, self.W, self.input_ch, self.output_ch,
+                                          self.skips[0], L.ptr(saved), L.ptr(_bwd_scratch(self, N, blob.device)), None, None, L.ptr(g_emb),
+                                          L.stream()))
+        finally:
+            _return_saved(self, saved)
+        return raw, g_emb
+
     def forward_pts(self, pts):
         """Fused embed+MLP on raw points [..., dims] (dims 2: uv, 3: xyz) -> [..., output_ch]."""
         x = L.f32c(pts).reshape(-1, self.dims)
@@ -562,6 +581,30 @@ def distortion_loss(weights, t, dt, rays_d, ray_off=None):
     if grad_mode and w.requires_grad:
         return _DistortionFn.apply(w, t, dt, d, ray_off)
     return _distortion_fwd(w, t, dt, d, ray_off)
+
+
+def weighted_sum_packed(weights, values, ray_off):
+    """Per-ray weighted sums on ragged per-ray sample lists (`ctx_weighted_sum_packed`, one wavefront per ray): weights [n], values [n,C]
+    with 1 <= C <= 4, ray_off int64 [R+1] -> out [R,C] with out[r] = sum_i weights[i] * values[i] over the ray's samples, zeros for a ray
+    without samples.  What torch.zeros(R, C).index_add_(0, ray_id, weights[:, None] * values) computes, without float atomics: one summation
+    order, so two runs give the same bits.  No autograd: an input that requires grad is refused."""
+    if not all(isinstance(x, torch.Tensor) for x in (weights, values, ray_off)):
+        raise L.CtxError("weighted_sum_packed: want tensors weights [n], values [n,C], ray_off [R+1]")
+    if weights.requires_grad or values.requires_grad:
+        raise L.CtxError("weighted_sum_packed: the sum has no gradient with respect to weights / values; detach them")
+    n = weights.shape[0] if weights.dim() == 1 else -1
+    if n < 0 or values.dim() != 2 or values.shape[0] != n or ray_off.dim() != 1 or ray_off.shape[0] < 2:
+        raise L.CtxError(f"weighted_sum_packed: want weights [n], values [n,C], ray_off [R+1] with R >= 1; got {tuple(weights.shape)}, "
+                         f"{tuple(values.shape)}, {tuple(ray_off.shape)}")
+    Cn, R = values.shape[1], ray_off.shape[0] - 1
+    if not 1 <= Cn <= 4:
+        raise L.CtxError(f"weighted_sum_packed: values has C={Cn} columns: want 1 <= C <= 4")
+    if n >= 2 ** 31:
+        raise L.CtxError(f"weighted_sum_packed: n={n}: want n < 2^31; split the batch")
+    p = (L.ptr(weights, torch.float32, "weights"), L.ptr(values, torch.float32, "values"), L.ptr(ray_off, torch.int64, "ray_off"))
+    out = torch.empty(R, Cn, device=ray_off.device)
+    L.check(L.load().ctx_weighted_sum_packed(*p, R, n, Cn, L.ptr(out), L.stream()))
+    return out
 
 
 RESAMPLE_MAX_K = 4096          # the fine lists are composited too: what the compositing backward holds per ray

@@ -261,6 +261,38 @@ def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, ro
     return {'rgb': rgb.reshape(h, W, 3), 'depth': depth.reshape(h, W), 'acc': acc.reshape(h, W), 'disp': disp.reshape(h, W)}
 
 
+@torch.no_grad()
+def render_normals(field, H, W, K, c2w, near, far, occupancy, march, rows=None):
+    """-> dict(normal [h,W,3], z_normal [h,W], acc [h,W], depth [h,W]) for the row range `rows` (default: all): the normals of the field's
+    density, rendered as the colour is, on the marched lists only (occupancy and march as render_rays_marched takes them, no jitter).
+    field: anything with density_gradient(pts, return_raw=True) -> (raw [n,4], grad [n,3]), e.g. a HashGridField.
+    Per sample n_i = -grad_i / max(|grad_i|, 1e-12); per ray N = sum_i w_i n_i with the compositing weights (rnh.weighted_sum_packed: one
+    summation order, no atomics) and normal = N / max(|N|, 1e-12), in the world frame; 0 where the ray has no samples.
+    z_normal = clamp((c2w[:3,:3]^T normal)_z, 0, 1): the camera looks down -z (get_rays), so a surface that faces the camera has a positive
+    value, the convention the painting side's z_normals follow.  One host sync (the march's n).  No gradient flows through any of it."""
+    if not callable(getattr(field, 'density_gradient', None)):
+        raise L.CtxError(f"render_normals: {type(field).__name__} has no density_gradient(pts, return_raw=True): the normals are the field's "
+                         "gradient with respect to the positions, which this field does not give (a HashGridField does)")
+    if occupancy is None or march is None:
+        raise L.CtxError("render_normals: the marched path only: want an occupancy grid (occupancy=) and a world-space step (march=)")
+    ro, rd = rnh.get_rays(H, W, K, c2w)
+    r0, r1 = (0, H) if rows is None else rows
+    h = r1 - r0
+    ro, rd = ro[r0:r1].reshape(-1, 3), rd[r0:r1].reshape(-1, 3)
+    ray_off, _, t, dt, pts = occupancy.march(ro, rd, near, far, march)
+    if t.numel():
+        raw, g = field.density_gradient(pts, return_raw=True)
+        raw, g = L.f32c(raw), L.f32c(g)
+    else:
+        raw, g = torch.empty(0, 4, device=ro.device), torch.empty(0, 3, device=ro.device)
+    _, _, acc, weights, depth = rnh.raw2outputs_packed(raw, t, dt, rd, ray_off)
+    n_i = -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    N = rnh.weighted_sum_packed(weights, n_i.contiguous(), ray_off)
+    normal = N / N.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    z = (normal * L.f32c(c2w[:3, 2]).to(normal.device)).sum(-1).clamp(0, 1)              # (R^T normal)_z = R[:, 2] . normal
+    return {'normal': normal.reshape(h, W, 3), 'z_normal': z.reshape(h, W), 'acc': acc.reshape(h, W), 'depth': depth.reshape(h, W)}
+
+
 def gather_rows(tile, H, group=None):
     """all_gather of the ranks' row tiles [h_r, ...] -> [H, ...] (ragged tiles padded to the largest)."""
     if not (dist.is_initialized() and dist.get_world_size(group) > 1):

@@ -231,7 +231,8 @@ int32_t ctx_uvmlp_bwd(const float *grad_raw /*nullable*/, const float *grad_tex 
    Always the exact-f32 chain; with input_ch = 63 the launches, and so the bits, are those of ctx_uvmlp_fwd_save(emb, dims = 3, L = 10) /
    ctx_uvmlp_bwd.  saved (nullable: plain forward): ctx_uvmlp_saved_bytes(N, D, W, input_ch); ws: ctx_uvmlp_bwd_ws_bytes(N, D, W).
    grad_emb [N, input_ch] (nullable: skipped) = dZ_0 . W_0 + dZ_{skip+1} . W_{skip+1}[:, :input_ch], one kernel after the dZ chain that
-   reads the dZ rows the chain left in ws.  Deterministic. */
+   reads the dZ rows the chain left in ws.  gws and gbs both null with a grad_emb: the input gradient alone, no weight-gradient launch, the
+   same bits in grad_emb.  Deterministic. */
 int32_t ctx_uvmlp_fwd_emb(const float *emb, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
                           int32_t skip, float *raw, void *saved /*nullable*/, ctx_stream_t stream);
 int32_t ctx_uvmlp_bwd_emb(const float *grad_raw, int64_t N, const void *packed, int32_t D, int32_t W, int32_t input_ch, int32_t output_ch,
@@ -427,7 +428,7 @@ int32_t ctx_resample_packed(const float *weights, const float *ts, const float *
    emb[n, l*F + f] = the left-to-right sum over c ascending of w_c * table[l, idx_c, f], starting from 0.  1 <= n < 2^31. */
 int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *table, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
                          const float *lo, const float *hi, float *emb, ctx_stream_t stream);
-/* The gradient to the table, g_table [Lv, T, F], every element written; positions get none.  An integer accumulator, so the result does not
+/* The gradient to the table, g_table [Lv, T, F], every element written (the positions' gradient: ctx_hashgrid_bwd_pts).  An integer accumulator, so the result does not
    depend on the order of the adds: m = max|g_emb|, 2^x the smallest power of two above m, E = 62 - ceil(log2(8n)); every contribution
    w_c * g_emb[n, l*F + f] (one float rounding) is scaled by 2^(E-x) in double (exact), rounded to nearest even into int64 and added to
    acc[l, idx_c, f] with a 64-bit integer atomic; g_table = (float)((double)acc * 2^(x-E)).  m = 0 writes zeros; a non-finite g_emb turns all
@@ -436,6 +437,26 @@ int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *table, int32_
 int64_t ctx_hashgrid_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T);
 int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
                          const float *lo, const float *hi, int32_t stages, void *ws, float *g_table, ctx_stream_t stream);
+/* The gradient to the positions, g_pts [n,3], every element written (definition: tests/hashgrid_grad_rule.py).  Per
+   point, axis a and level, in binary32 in this order: the axis is active iff x_a = (p_a - lo_a)/(hi_a - lo_a), before the clamp, has
+   x_a > 0 && x_a < 1; cell, weights w, corner order and entries t_c are the forward's; s_a = (float)res[l] / (hi_a - lo_a); with o1 < o2 the
+   two other axes, per corner c ascending q_c = s_o1 * s_o2 (s_b = bit_b ? w_b : 1 - w_b), term = q_c * t_c[f], d_a[f] = bit_a ? d_a[f] + term :
+   d_a[f] - term from 0; gl_a = sum_f g_emb[n, l*F + f] * d_a[f] left to right from 0; g_pts[n, a] = sum_l (gl_a * s_a), levels ascending from 0.
+   An inactive axis (NaN, +-inf, on or outside the box faces) gets exactly 0.0f whatever g_emb and the table hold; on an active axis their
+   non-finite values propagate.  The derivative is that of the cell the forward assigns the point to: one-sided on cell faces.  First
+   order only.  No atomics, one writer per element.  ws: ctx_hashgrid_bwd_pts_ws_bytes(n, Lv) bytes (-1 outside 1 <= n < 2^31, 1 <= Lv <= 16):
+   the per-level partials [Lv, n, 3].  The envelope and the refusals are the forward's. */
+int64_t ctx_hashgrid_bwd_pts_ws_bytes(int64_t n, int32_t Lv);
+int32_t ctx_hashgrid_bwd_pts(const float *pts, int64_t n, const float *table, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T,
+                             const int32_t *res, const float *lo, const float *hi, void *ws, float *g_pts /*[n,3]*/, ctx_stream_t stream);
+
+/* ---- per-ray weighted sum on the marched lists ---- */
+/* out[r, c] = sum_i weights[i] * values[i, c] over ray r's samples ray_off[r] .. ray_off[r+1]; weights [n], values [n,C], 1 <= C <= 4,
+   out [R,C], every element written, zeros for a ray without samples.  One wavefront per ray: lane partials over the chunks in ascending
+   order, then one wave sum; no atomics, so two runs give the same bits.  ray_off as ctx_raymarch_packed_fwd; n = 0 zero-fills out (the
+   lists may be null) and launches no kernel. */
+int32_t ctx_weighted_sum_packed(const float *weights, const float *values, const int64_t *ray_off, int64_t R, int64_t n, int32_t C,
+                                float *out, ctx_stream_t stream);
 
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
