@@ -89,6 +89,11 @@ SIGNATURES = {
     "ctx_hashgrid_bwd": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ctx_hashgrid_bwd_pts_ws_bytes": (_i64, [_i64, _i32]),
     "ctx_hashgrid_bwd_pts": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_hashtex_fwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_hashtex_bwd_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "ctx_hashtex_bwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "ctx_texture_head_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "ctx_texture_head_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_weighted_sum_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),

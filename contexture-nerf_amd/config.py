@@ -64,6 +64,13 @@ class GuideConfig:
                                      # UV (ConTEXTure.project_back_scatter, csrc/uvscatter.hip; the outputs of earlier builds, bit for bit);
                                      # 'gather': every chart texel looks its surface point up in the views (project_back_gather,
                                      # csrc/uvgather.hip): no pinholes where the surface is magnified, nothing outside the charts
+    texture_field: str = 'mlp'       # the field behind the atlas.  'mlp': the 8 x 256 MLP on the Fourier embedding of uv (the outputs of earlier
+                                     # builds, bit for bit); 'hashgrid': a multiresolution hash table over the UV square and a 2 x 64 MLP
+                                     # (hashgrid.HashGridTexture, csrc/hashtex.hip; its finest level is texture_resolution)
+    hashgrid_levels: int = 12        # texture_field = 'hashgrid': levels, features per entry, log2 of the entries per level, coarsest resolution
+    hashgrid_features: int = 2
+    hashgrid_log2_table: int = 18
+    hashgrid_base_res: int = 16
 
 
 @dataclass
@@ -87,6 +94,8 @@ class OptimConfig:
     field_texels: str = 'all'        # the texels the SDS loop evaluates and trains the texture field on.  'all': the whole atlas (the outputs
                                      # of earlier builds, bit for bit); 'active': only the texels the loop's cached raster can read
                                      # (kal.active_texels; the rendered images keep their bits, src/models/textured_mesh.py:303-347)
+    hashgrid_lr: float = 1e-2        # guide.texture_field = 'hashgrid': Adam's rate for the hash table and for its MLP in the SDS loop
+    hashgrid_mlp_lr: float = 1e-3    # (instant-ngp's rates, not tuned here)
 
 
 @dataclass
@@ -147,6 +156,7 @@ def _apply(obj, key, value):
 ATLAS_FILL_MODES = ('none', 'nearest')
 PROJECTION_MODES = ('scatter', 'gather')
 FIELD_TEXELS_MODES = ('all', 'active')
+TEXTURE_FIELDS = ('mlp', 'hashgrid')
 
 
 def validate(cfg):
@@ -159,7 +169,11 @@ def validate(cfg):
             raise ValueError(f"guide.atlas_pad={guide.atlas_pad}: expected >= 0")
         if guide.projection not in PROJECTION_MODES:
             raise ValueError(f"guide.projection={guide.projection!r}: expected one of {PROJECTION_MODES}")
+        if guide.texture_field not in TEXTURE_FIELDS:
+            raise ValueError(f"guide.texture_field={guide.texture_field!r}: expected one of {TEXTURE_FIELDS}")
     optim = getattr(cfg, 'optim', None)
+    if optim is not None and not (optim.hashgrid_lr > 0 and optim.hashgrid_mlp_lr > 0):
+        raise ValueError(f"optim.hashgrid_lr={optim.hashgrid_lr}, optim.hashgrid_mlp_lr={optim.hashgrid_mlp_lr}: expected > 0")
     if optim is not None and not optim.consistency_weight >= 0:
         raise ValueError(f"optim.consistency_weight={optim.consistency_weight}: expected >= 0")
     if optim is not None and optim.field_texels not in FIELD_TEXELS_MODES:

@@ -16,11 +16,7 @@
 // thread per point) adds in ascending level order.  From 2^17 points on it runs as one thread per point over the levels instead.
 // The positions' gradient is first order only and opt-in on the host.  No transcendental runs here: the level resolutions are integers
 // computed on the host.
-#include "common.h"
-#include <math.h>
-
-#define HG_MAX_LEVELS 16
-#define HG_BLOCK 256
+#include "hashgrid_common.h"
 
 struct HgGrid {
     float lo[3], hi[3];
@@ -91,11 +87,6 @@ __device__ __forceinline__ HgCell hg_cell(const float *__restrict__ pts, int64_t
     return hg_cell(hg_axes(pts, n, g, l), g, l);
 }
 
-template <int F> struct HgVec;
-template <> struct HgVec<1> { typedef float type; };
-template <> struct HgVec<2> { typedef float2 type; };
-template <> struct HgVec<4> { typedef float4 type; };
-
 template <int F>
 __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_fwd(const float *__restrict__ pts, int64_t n, const float *__restrict__ table, HgGrid g,
                                                            float *__restrict__ emb)
@@ -137,40 +128,7 @@ extern "C" int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *ta
 }
 
 // ---- backward to the table -------------------------------------------------------------------------------------------------------
-// absmax: bits of max|g_emb| (the order of non-negative floats is the order of their bits; inf and NaN sort above every finite value);
-// status: 0 = accumulate, 1 = all zero, 2 = a non-finite gradient poisons the table's gradient;  x: 2^x is the smallest power of two above m
-struct HgCtl { uint32_t absmax; int32_t status; int32_t x; int32_t pad; };
-
-__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_absmax(const float *__restrict__ g, int64_t count, HgCtl *__restrict__ ctl)
-{
-    uint32_t m = 0;
-    const int64_t stride = (int64_t)gridDim.x * HG_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x; i < count; i += stride) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
-    for (int o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    __shared__ uint32_t s_m[HG_BLOCK / 64];
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {                        // one atomic per workgroup
-        for (int k = 1; k < HG_BLOCK / 64; ++k) m = max(m, s_m[k]);
-        if (m) atomicMax(&ctl->absmax, m);
-    }
-}
-
-__global__ void k_hashgrid_scale(HgCtl *ctl)
-{
-    const uint32_t b = ctl->absmax;
-    int status = 0, x = 0;
-    if (b == 0) status = 1;
-    else if (b >= 0x7f800000u) status = 2;
-    else if (b >> 23) x = (int)(b >> 23) - 126;    // m = 1.f * 2^(e - 127) < 2^(e - 126)
-    else x = (31 - __clz((int)b)) - 148;           // subnormal: top bit p is worth 2^(p - 149)
-    ctl->status = status;
-    ctl->x = x;
-}
-
-// the exact power of two 2^e as a double, -1022 <= e <= 1023
-__device__ __forceinline__ double hg_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }
-
+// HgCtl, the absmax / scale / convert kernels and hg_pow2 are in hashgrid_common.h: the 2-D texture field (hashtex.hip) uses them too
 template <int F>
 __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd(const float *__restrict__ pts, int64_t n, const float *__restrict__ g_emb, HgGrid g, int E,
                                                            const HgCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
@@ -194,18 +152,6 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd(const float *__restri
             if (q) atomicAdd(al + (int64_t)c.idx[k] * F + f, (unsigned long long)q);
         }
 }
-
-__global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_convert(const long long *__restrict__ acc, int64_t count, int E, const HgCtl *__restrict__ ctl,
-                                                               float *__restrict__ g_table)
-{
-    const int status = ctl->status;
-    const double inv = hg_pow2(ctl->x - E);
-    const int64_t stride = (int64_t)gridDim.x * HG_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x; i < count; i += stride)
-        g_table[i] = status == 2 ? __uint_as_float(0x7fc00000u) : (status == 1 ? 0.0f : (float)((double)acc[i] * inv));
-}
-
-static inline int64_t hg_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 extern "C" int64_t ctx_hashgrid_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T)
 {

@@ -6,7 +6,10 @@ render_rays_marched, render_image, render_and_refine, train_step, fit_views and 
 The table's gradient is summed in 64-bit integers, so a training run repeats bit for bit.  Positions get a gradient
 (`ctx_hashgrid_bwd_pts`; the rule: tests/hashgrid_grad_rule.py) where it is asked for: through autograd with
 grad_pts=True, and from HashGridField.density_gradient, which volume_render.render_normals turns into rendered normals.  That gradient is
-first order only."""
+first order only.
+HashGridEncoding2D / HashGridTexture are the same idea over the unit UV square for the product's texture field (csrc/hashtex.hip; the rule:
+tests/hashtex_rule.py): bilinear levels, the 2 x 64 MLP and the (tanh + 1) / 2 head behind NeRF2D.texture_map's contract,
+selected by guide.texture_field = 'hashgrid'."""
 import ctypes as C
 import math
 import numpy as np
@@ -196,3 +199,183 @@ class HashGridField(nn.Module):
         raw, g_emb = mlp.features_input_gradient(enc._launch_fwd(x, table), g_raw)
         grad = enc._launch_bwd_pts(x, table, g_emb).reshape(*pts.shape[:-1], 3)
         return (raw.reshape(*pts.shape[:-1], self.output_ch), grad) if return_raw else grad
+
+
+# ---- the texture field: a 2-D hash grid over the unit UV square --------------------------------------------------
+class _HashTexFn(torch.autograd.Function):
+    """emb [n, Lv*F] = encoding(rows; table) with the rows named by uv [n,2], by the grid (whole atlas) or by a texel list; the gradient
+    goes to the table only (`ctx_hashtex_bwd`).  First order only.  With no grad enabled this is not used and nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, enc, uv, idx, n, grid, table):
+        ctx.enc, ctx.uv, ctx.idx, ctx.n, ctx.grid = enc, uv, idx, n, grid
+        return enc._launch_fwd(uv, idx, n, grid, table)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_emb):
+        enc = ctx.enc
+        lib = L.load()
+        table = enc.table
+        g_emb = L.f32c(g_emb)
+        wsb = lib.ctx_hashtex_bwd_ws_bytes(enc.n_levels, enc.n_features, enc.log2_table)
+        if enc._bwd_ws is None or enc._bwd_ws.numel() < wsb or enc._bwd_ws.device != g_emb.device:
+            enc._bwd_ws = None
+            enc._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=g_emb.device)   # the int64 accumulator: scratch, stream-ordered
+        g_table = torch.empty(table.shape, device=g_emb.device)
+        L.check(lib.ctx_hashtex_bwd(L.ptr(ctx.uv), L.ptr(ctx.idx), ctx.n, ctx.grid, L.ptr(g_emb, torch.float32, "g_emb"), *enc._grid_args(), 7,
+                                    L.ptr(enc._bwd_ws), L.ptr(g_table), L.stream()))
+        return None, None, None, None, None, g_table
+
+
+class HashGridEncoding2D(nn.Module):
+    """uv [..., 2] in the unit square -> features [..., n_levels * n_features]: at every level the bilinear interpolation of the 4 table
+    entries at the corners of the point's cell; a level whose (res + 1)^2 nodes fit the table indexes it directly, a finer one by
+    instant-ngp's spatial hash.  Points outside the square take the values on its edge; NaN coordinates read as 0.
+    1 <= n_levels <= 16, n_features in {1, 2, 4}, n_levels * n_features <= 64, 4 <= log2_table <= 22, 1 <= base_res <= max_res <= 2^20.
+    `table` [n_levels, 2^log2_table, n_features] starts uniform in +-1e-4.  There is no gradient to uv: a uv that requires grad is refused."""
+
+    def __init__(self, n_levels=12, n_features=2, log2_table=18, base_res=16, max_res=1024):
+        super().__init__()
+        who = "HashGridEncoding2D"
+        for name, v in (("n_levels", n_levels), ("n_features", n_features), ("log2_table", log2_table), ("base_res", base_res),
+                        ("max_res", max_res)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise L.CtxError(f"{who}: {name}={v!r}: want an int")
+        if not 1 <= n_levels <= MAX_LEVELS:
+            raise L.CtxError(f"{who}: n_levels={n_levels} outside [1, {MAX_LEVELS}]")
+        if n_features not in (1, 2, 4):
+            raise L.CtxError(f"{who}: n_features={n_features}: want 1, 2 or 4 features per entry")
+        if n_levels * n_features > MAX_WIDTH:
+            raise L.CtxError(f"{who}: n_levels * n_features = {n_levels * n_features} is wider than the field's {MAX_WIDTH}-column embedding")
+        if not 4 <= log2_table <= 22:
+            raise L.CtxError(f"{who}: log2_table={log2_table} outside [4, 22]")
+        if not 1 <= base_res <= max_res <= MAX_RES:
+            raise L.CtxError(f"{who}: want 1 <= base_res <= max_res <= 2^20, got base_res={base_res}, max_res={max_res}")
+        self.n_levels, self.n_features, self.log2_table = int(n_levels), int(n_features), int(log2_table)
+        self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
+        self.out_dim = self.n_levels * self.n_features
+        self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
+        self._bwd_ws = None
+
+    def _grid_args(self):
+        """(Lv, F, log2T, res) as the ABI takes them; res is host memory."""
+        return self.n_levels, self.n_features, self.log2_table, self.res.ctypes.data_as(C.c_void_p)
+
+    def _launch_fwd(self, uv, idx, n, grid, table):
+        emb = torch.empty(n, self.out_dim, device=table.device)
+        L.check(L.load().ctx_hashtex_fwd(L.ptr(uv), L.ptr(idx), n, grid, L.ptr(table, torch.float32, "table"), *self._grid_args(), L.ptr(emb),
+                                         L.stream()))
+        return emb
+
+    def _run(self, uv, idx, n, grid):
+        L.ptr(self.table, torch.float32, "table")
+        if torch.is_grad_enabled() and self.table.requires_grad:
+            return _HashTexFn.apply(self, uv, idx, n, grid, self.table)
+        return self._launch_fwd(uv, idx, n, grid, self.table.detach())
+
+    def forward(self, uv):
+        if not isinstance(uv, torch.Tensor) or uv.dim() < 1 or uv.shape[-1] != 2:
+            raise L.CtxError(f"HashGridEncoding2D: want uv [..., 2], got {tuple(getattr(uv, 'shape', ()))}")
+        if torch.is_grad_enabled() and uv.requires_grad:
+            raise L.CtxError("HashGridEncoding2D: the HIP path has no gradient with respect to uv; detach uv")
+        if uv.device != self.table.device or uv.device.type == 'cpu':
+            raise L.CtxError(f"HashGridEncoding2D: uv on {uv.device}, the table on {self.table.device} (the HIP path has no CPU fallback: "
+                             "want a device tensor)")
+        x = L.f32c(uv).reshape(-1, 2)
+        if x.shape[0] == 0:
+            return torch.zeros(*uv.shape[:-1], self.out_dim, device=x.device)
+        return self._run(x, None, x.shape[0], 0).reshape(*uv.shape[:-1], self.out_dim)
+
+    def forward_texels(self, res, texels=None):
+        """The nodes of the res x res atlas (uv = torch.linspace(0, 1, res) on both axes, node y*res + x) -> emb [res*res, out_dim], or with
+        texels (int32 [n] device list of nodes) -> emb [n, out_dim] in list order; an entry outside the atlas gives a zero row."""
+        if isinstance(res, bool) or not isinstance(res, (int, np.integer)) or not 2 <= res <= 46340:
+            raise L.CtxError(f"HashGridEncoding2D.forward_texels: res={res!r}: want an int in [2, 46340]")
+        if self.table.device.type == 'cpu':
+            raise L.CtxError("HashGridEncoding2D: the table is on the cpu (the HIP path has no CPU fallback: want a device tensor)")
+        if texels is None:
+            return self._run(None, None, int(res) * int(res), int(res))
+        L.ptr(texels, torch.int32, "texels")
+        if texels.dim() != 1 or texels.device != self.table.device:
+            raise L.CtxError(f"HashGridEncoding2D.forward_texels: want a 1-D int32 list on {self.table.device}, got shape {tuple(texels.shape)} "
+                             f"on {texels.device}")
+        if texels.numel() == 0:
+            return torch.zeros(0, self.out_dim, device=self.table.device)
+        return self._run(None, texels, texels.numel(), int(res))
+
+
+class _TextureHeadFn(torch.autograd.Function):
+    """tex [C, plane] = (tanh(raw [n,C]) + 1) / 2 on the nodes the rows name (all of them, or a texel list: zero elsewhere); the gradient
+    goes to raw (`ctx_texture_head_bwd`)."""
+
+    @staticmethod
+    def forward(ctx, raw, texels, plane):
+        ctx.texels, ctx.plane = texels, plane
+        ctx.save_for_backward(raw)
+        return _texture_head(raw, texels, plane)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_tex):
+        raw, = ctx.saved_tensors
+        g_raw = torch.empty_like(raw)
+        L.check(L.load().ctx_texture_head_bwd(L.ptr(L.f32c(g_tex), torch.float32, "grad_tex"), None, L.ptr(raw), L.ptr(ctx.texels), raw.shape[0],
+                                              ctx.plane, raw.shape[1], L.ptr(g_raw), L.stream()))
+        return g_raw, None, None
+
+
+def _texture_head(raw, texels, plane):
+    C_ = raw.shape[1]
+    tex = torch.empty(C_, plane, device=raw.device) if texels is None else torch.zeros(C_, plane, device=raw.device)
+    L.check(L.load().ctx_texture_head_fwd(L.ptr(raw, torch.float32, "raw"), L.ptr(texels), raw.shape[0], plane, C_, L.ptr(tex), L.stream()))
+    return tex
+
+
+class HashGridTexture(nn.Module):
+    """The texture field as instant-ngp's image field: HashGridEncoding2D -> NeRF2D(D, W, input_ch = n_levels * n_features, output_ch,
+    skips=[0]) on the `emb` seam -> (tanh + 1) / 2.  It answers texture_map(res, texels=None) with NeRF2D.texture_map's contract, which is
+    all TexturedMeshModel asks of its field, and forward_uv(uv).  The table's gradient is summed in integers: a run repeats bit for bit."""
+
+    def __init__(self, n_levels=12, n_features=2, log2_table=18, base_res=16, max_res=1024, D=2, W=64, output_ch=3):
+        super().__init__()
+        self.encoding = HashGridEncoding2D(n_levels, n_features, log2_table, base_res, max_res)
+        if D < 2:
+            raise L.CtxError(f"HashGridTexture: D={D}: the MLP needs at least two hidden layers (the second one is the skip layer)")
+        if not 1 <= output_ch <= 4:
+            raise L.CtxError(f"HashGridTexture: output_ch={output_ch} outside [1, 4]")
+        self.mlp = NeRF2D(D=D, W=W, input_ch=self.encoding.out_dim, output_ch=output_ch, skips=[0])
+        self.output_ch = output_ch
+
+    def _version(self):
+        return tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
+
+    def forward_uv(self, uv):
+        """uv [..., 2] -> raw [..., output_ch] (before the head)."""
+        return self.mlp.forward_features(self.encoding(uv))
+
+    def _field(self, res, texels):
+        raw = self.mlp.forward_features(self.encoding.forward_texels(res, texels))
+        plane = res * res
+        if torch.is_grad_enabled() and raw.requires_grad:
+            tex = _TextureHeadFn.apply(raw, texels, plane)
+        else:
+            tex = _texture_head(raw, texels, plane)
+        return tex.reshape(1, self.output_ch, res, res), raw
+
+    def texture_map(self, res, texels=None):
+        """-> (texture [1,C,res,res] in [0,1], mlp_output [res*res, C]), the contract of NeRF2D.texture_map: the no-grad whole-atlas result
+        is kept until a parameter's version moves; with texels (int32 [n] device list of distinct nodes y*res + x) the field is evaluated,
+        and trained, on those texels only -> (texture, zero off the list; mlp_output [n, C] in list order), never cached.  Listed texels
+        carry the bits of the whole-atlas call."""
+        if texels is not None:
+            return self._field(res, self.mlp._checked_texels(texels, res))
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+            key = (self._version(), res)
+            hit = getattr(self, '_tex_cache', None)
+            if hit is not None and hit[0] == key:
+                return hit[1], hit[2]
+            out = self._field(res, None)
+            self._tex_cache = (key, out[0], out[1])
+            return out
+        return self._field(res, None)

@@ -29,7 +29,15 @@ class ConTEXTure:
         self.device = device if device is not None else dev
         utils.seed_everything(self.cfg.optim.seed)
         self.uv_embedder, input_ch = get_embedder(10)
-        self.texture_mlp = NeRF2D(D=8, W=256, input_ch=input_ch, output_ch=3, skips=[4]).to(self.device)
+        if self.cfg.guide.texture_field == 'hashgrid':
+            from .hashgrid import HashGridTexture
+            g = self.cfg.guide
+            self.texture_mlp = HashGridTexture(g.hashgrid_levels, g.hashgrid_features, g.hashgrid_log2_table, g.hashgrid_base_res,
+                                               int(g.texture_resolution), D=2, W=64, output_ch=3).to(self.device)
+        elif self.cfg.guide.texture_field == 'mlp':
+            self.texture_mlp = NeRF2D(D=8, W=256, input_ch=input_ch, output_ch=3, skips=[4]).to(self.device)
+        else:
+            raise ValueError(f"guide.texture_field={self.cfg.guide.texture_field!r}: expected 'mlp' or 'hashgrid'")
         # trainer.py:253-255: the UV unwrap of a mesh without texture coordinates is cached under cache/<mesh stem>/
         cache_path = None if mesh_arrays is not None else os.path.join('cache', os.path.splitext(os.path.basename(str(self.cfg.guide.shape_path)))[0])
         self.mesh_model = TexturedMeshModel(self.cfg.guide, render_grid_size=self.cfg.render.train_grid_size, cache_path=cache_path,
@@ -396,7 +404,8 @@ class ConTEXTure:
         score distillation of the UV-MLP against Zero123++ — render the 6 novel views from the cached raster, crop + resize to
         tile^2, 3x2 grid, VAE encode WITH autograd, DreamTime timestep, one Zero123++ evaluation (reference-only attention +
         depth ControlNet, CFG 10) -> v target -> `targets = z0 - grad`, 0.5 * sum-MSE on one random latent tile, backward through
-        the VAE encoder / resize / texture_mapping / texture field, Adam(lr 1e-5, betas (0.9, 0.99), eps 1e-15).
+        the VAE encoder / resize / texture_mapping / texture field, Adam(lr 1e-5, betas (0.9, 0.99), eps 1e-15; with
+        guide.texture_field = 'hashgrid' two parameter groups, the table at optim.hashgrid_lr and its MLP at optim.hashgrid_mlp_lr).
         Host syncs of the reference's loop body that are hoisted out of it: the six crop boxes (the masks do not change) and the
         DreamTime table (rebuilt every iteration there).  -> list of per-iteration dicts (loss, t, fisher, grad_norm).
         optim.consistency_weight > 0 adds the term upstream wrote and switched off (:856-863): the loss that is back-propagated is
@@ -443,7 +452,13 @@ class ConTEXTure:
                 render_cache['active_texels'] = texels
                 self._sds_setup['field_texels'] = 'active'
         params = [p for p in self.texture_mlp.parameters()]
-        optimizer = torch.optim.Adam(params, lr=1e-5, betas=(0.9, 0.99), eps=1e-15)
+        if self.cfg.guide.texture_field == 'hashgrid':
+            # the table and its MLP at their own rates (optim.hashgrid_lr, optim.hashgrid_mlp_lr)
+            groups = [dict(params=list(self.texture_mlp.encoding.parameters()), lr=float(self.cfg.optim.hashgrid_lr)),
+                      dict(params=list(self.texture_mlp.mlp.parameters()), lr=float(self.cfg.optim.hashgrid_mlp_lr))]
+            optimizer = torch.optim.Adam(groups, betas=(0.9, 0.99), eps=1e-15)
+        else:
+            optimizer = torch.optim.Adam(params, lr=1e-5, betas=(0.9, 0.99), eps=1e-15)
         train_sched = DDPMScheduler(prediction_type="v_prediction")
         alphas_cumprod = train_sched.alphas_cumprod.to(self.device)
         dream = utils.DreamTimeScheduler(alphas_cumprod, iterations, m=500, s=125)

@@ -450,6 +450,37 @@ int64_t ctx_hashgrid_bwd_pts_ws_bytes(int64_t n, int32_t Lv);
 int32_t ctx_hashgrid_bwd_pts(const float *pts, int64_t n, const float *table, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T,
                              const int32_t *res, const float *lo, const float *hi, void *ws, float *g_pts /*[n,3]*/, ctx_stream_t stream);
 
+/* ---- the texture field as a 2-D hash grid over the unit UV square (definition: tests/hashtex_rule.py) ---- */
+/* n rows -> emb [n, Lv*F].  Exactly one way of naming the rows: uv [n,2] (idx null, grid 0); the whole atlas (uv, idx null; grid >= 2,
+   n = grid^2, row r is node r); a texel list (uv null; idx int32 [n], row r is node idx[r] of the grid x grid atlas; an entry outside
+   [0, grid^2) gives a zero row).  Any other combination is refused before a launch.  Node i*grid + j has u = j < grid/2 ? (float)j*step :
+   fmaf(-(float)(grid-1-j), step, 1.0f) with step = 1.0f/(float)(grid-1), v likewise from i: torch.linspace(0, 1, grid), as ctx_uvmlp_fwd.
+   table float32 [Lv, T, F], T = 2^log2T, 4 <= log2T <= 22; 1 <= Lv <= 16, F in {1, 2, 4}, Lv*F <= 64; res int32 [Lv] (host), 1 <= res[l] <= 2^20.
+   Per level and axis a (0: u, 1: v), in binary32 in this order: x = fminf(fmaxf(p_a, 0), 1) (NaN -> 0), pos = x*(float)res,
+   i = min((int)floorf(pos), res - 1), w = pos - (float)i.  Corner c = cx + 2 cy at node g = i + bit: idx = gx + (res+1)*gy where
+   (res+1)^2 <= T (dense level), else (gx ^ gy*2654435761u) & (T - 1) in uint32; weight sx*sy with s = bit ? w : 1 - w;
+   emb[r, l*F + f] = the left-to-right sum over c ascending of w_c * table[l, idx_c, f], starting from 0.  1 <= n < 2^31, grid <= 46340. */
+int32_t ctx_hashtex_fwd(const float *uv /*nullable*/, const int32_t *idx /*nullable*/, int64_t n, int32_t grid, const float *table, int32_t Lv,
+                        int32_t F, int32_t log2T, const int32_t *res, float *emb, ctx_stream_t stream);
+/* The gradient to the table, g_table [Lv, T, F], every element written; there is no gradient to uv.  The integer accumulator of
+   ctx_hashgrid_bwd with 4 corners: m = max|g_emb| over the rows that take part (all but the out-of-range entries of a list), 2^x the
+   smallest power of two above m, E = 62 - ceil(log2(4n)); every w_c * g_emb[r, l*F + f] (one float rounding) is scaled by 2^(E-x) in
+   double, rounded to nearest even into int64 and added; g_table = (float)((double)acc * 2^(x-E)).  m = 0 writes zeros; a non-finite
+   g_emb turns all of g_table into NaN.  Adjacent lanes of a wave that address one entry add their integers before one atomic is issued
+   (CTX_HASHTEX_PRESUM=0, read per call: one atomic per term); the bits are the same.  ws: ctx_hashtex_bwd_ws_bytes(Lv, F, log2T)
+   bytes (-1: refused).  stages: bits 1 = zero the accumulator, 2 = reduce m and accumulate, 4 = convert; 7 is the backward. */
+int64_t ctx_hashtex_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T);
+int32_t ctx_hashtex_bwd(const float *uv /*nullable*/, const int32_t *idx /*nullable*/, int64_t n, int32_t grid, const float *g_emb, int32_t Lv,
+                        int32_t F, int32_t log2T, const int32_t *res, int32_t stages, void *ws, float *g_table, ctx_stream_t stream);
+/* The texture field's head.  raw [n, C], 1 <= C <= 4; node of row r = r (idx null; then n = plane) or idx[r] (int32 [n], distinct nodes;
+   an entry outside [0, plane) is skipped).  tex_chw [C, plane]: tex[c, node] = (tanhf(raw[r,c]) + 1.0f) / 2.0f, the listed nodes only are
+   written.  Backward: grad_raw[r,c] = (g_raw_in[r,c], nullable: 0) + grad_tex[c, node] * 0.5f * (1.0f - y*y), y = tanhf(raw[r,c]); every
+   element of grad_raw [n, C] is written, the listed nodes only are read.  One writer per element, no atomics.  1 <= n, plane < 2^31. */
+int32_t ctx_texture_head_fwd(const float *raw, const int32_t *idx /*nullable*/, int64_t n, int64_t plane, int32_t C, float *tex_chw,
+                             ctx_stream_t stream);
+int32_t ctx_texture_head_bwd(const float *grad_tex, const float *g_raw_in /*nullable*/, const float *raw, const int32_t *idx /*nullable*/,
+                             int64_t n, int64_t plane, int32_t C, float *grad_raw, ctx_stream_t stream);
+
 /* ---- per-ray weighted sum on the marched lists ---- */
 /* out[r, c] = sum_i weights[i] * values[i, c] over ray r's samples ray_off[r] .. ray_off[r+1]; weights [n], values [n,C], 1 <= C <= 4,
    out [R,C], every element written, zeros for a ray without samples.  One wavefront per ray: lane partials over the chunks in ascending
