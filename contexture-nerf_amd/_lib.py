@@ -151,6 +151,19 @@ SIGNATURES = {
     "ctx_softmax_bwd_rows_f16": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp]),
     "ctx_quant_bwd_f16": (_i32, [_vp, _vp, _i32, _i32, _i64, _f32, _vp, _vp]),
     "ctx_conv_in_bwd_f16": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "ctx_conv_in_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_conv_out_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_gemv_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_time_embed_f16": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "ctx_transpose_v_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_concat_f16": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "ctx_concat_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "ctx_f32_to_f16": (_i32, [_vp, _i64, _vp, _vp]),
+    "ctx_f16_to_f32": (_i32, [_vp, _i64, _vp, _vp]),
+    "ctx_conv_small_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_add_scaled_f16": (_i32, [_vp, _vp, _f32, _i64, _vp]),
+    "ctx_pointwise_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "ctx_pack_fwd_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "ctx_groupnorm_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_groupnorm2_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "ctx_groupnorm_apply_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),

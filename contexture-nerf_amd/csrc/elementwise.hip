@@ -1,7 +1,7 @@
 // Elementwise and small-convolution kernels of the UNet / VAE engines (NHWC fp16 activations), everything that is not a norm,
 // a GEMM or attention.  HBM-bound ones move a 16-byte (8 x f16) vector per lane.
 //   k_geglu                      GEGLU of a separate projection (the GEMM epilogue form lives in gemm_common.h)
-//   k_concat                     channel concat (skip connections), fp16 or, through ctx_concat_f32, the fp32 residual stream
+//   k_concat                     channel concat (skip connections), fp16 or, through ctx_concat32_core, the fp32 residual stream
 //   k_transpose_v                per-head transpose [B, S, ld] -> [B, heads, 64, Sp] (the VAE's attention and its backward)
 //   k_f32_to_f16, k_f16_to_f32   layout converters
 //   k_time_embed                 sinusoidal timestep embedding
@@ -55,14 +55,14 @@ __global__ __launch_bounds__(256) void k_concat(const f16 *__restrict__ a, const
 }
 
 // same copy with 4-byte elements (the fp32 residual stream): channels counted in f16-equivalents of 2 x the float count
-int ctx_concat_f32(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s)
+int ctx_concat32_core(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s)
 {
-    return ctx_concat_f16((const f16 *)a, (const f16 *)b, M, 2 * Ca, 2 * Cb, (f16 *)y, s);
+    return ctx_concat_core((const f16 *)a, (const f16 *)b, M, 2 * Ca, 2 * Cb, (f16 *)y, s);
 }
 
-int ctx_concat_f16(const f16 *a, const f16 *b, int64_t M, int Ca, int Cb, f16 *y, hipStream_t s)
+int ctx_concat_core(const f16 *a, const f16 *b, int64_t M, int Ca, int Cb, f16 *y, hipStream_t s)
 {
-    CTX_REQUIRE(a && b && y && Ca % 8 == 0 && Cb % 8 == 0, "concat: unsupported Ca=%d Cb=%d", Ca, Cb);
+    CTX_REQUIRE(a && b && y && M > 0 && Ca > 0 && Cb > 0 && Ca % 8 == 0 && Cb % 8 == 0, "concat: unsupported M=%lld Ca=%d Cb=%d", (long long)M, Ca, Cb);
     hipLaunchKernelGGL(k_concat, dim3(capped_blocks(M * ((Ca + Cb) / 8), 256, 4096)), dim3(256), 0, s, a, b, M, Ca, Cb, y);
     CTX_CHECK_LAUNCH("concat");
     return CTX_OK;
@@ -92,9 +92,12 @@ __global__ __launch_bounds__(256) void k_transpose_v(const f16 *__restrict__ v, 
     }
 }
 
-int ctx_transpose_v_f16(const f16 *v, int B, int S, int ld, int heads, int Sp, f16 *vt, hipStream_t s)
+int ctx_transpose_v_core(const f16 *v, int B, int S, int ld, int heads, int Sp, f16 *vt, hipStream_t s)
 {
     CTX_REQUIRE(v && vt, "transpose_v: null pointer");
+    // the kernel moves 16-byte pieces: 8 keys of a Vt row per store (a row must end on one), 8 columns of a V row per load
+    CTX_REQUIRE(B > 0 && S > 0 && heads > 0 && Sp % 8 == 0 && Sp >= S && ld % 8 == 0 && ld >= heads * 64,
+                "transpose_v: need Sp %% 8 == 0, Sp >= S, ld %% 8 == 0, ld >= 64 heads (B=%d S=%d ld=%d heads=%d Sp=%d)", B, S, ld, heads, Sp);
     hipLaunchKernelGGL(k_transpose_v, dim3(cdiv(Sp, 64), heads, B), dim3(256), 0, s, v, S, ld, heads, Sp, vt);
     CTX_CHECK_LAUNCH("transpose_v");
     return CTX_OK;
@@ -114,16 +117,16 @@ __global__ __launch_bounds__(256) void k_f16_to_f32(const f16 *__restrict__ x, i
         *(f32x4 *)(y + i * 8) = a; *(f32x4 *)(y + i * 8 + 4) = b;
     }
 }
-int ctx_f16_to_f32(const f16 *x, int64_t n, float *y, hipStream_t s)
+int ctx_f16_to_f32_core(const f16 *x, int64_t n, float *y, hipStream_t s)
 {
-    CTX_REQUIRE(x && y && n % 8 == 0, "f16_to_f32: n=%lld is not a multiple of 8", (long long)n);
+    CTX_REQUIRE(x && y && n > 0 && n % 8 == 0, "f16_to_f32: n=%lld is not a positive multiple of 8", (long long)n);
     hipLaunchKernelGGL(k_f16_to_f32, dim3(capped_blocks(n / 8, 256, 4096)), dim3(256), 0, s, x, n / 8, y);
     CTX_CHECK_LAUNCH("f16_to_f32");
     return CTX_OK;
 }
-int ctx_f32_to_f16(const float *x, int64_t n, f16 *y, hipStream_t s)
+int ctx_f32_to_f16_core(const float *x, int64_t n, f16 *y, hipStream_t s)
 {
-    CTX_REQUIRE(x && y, "f32_to_f16: null pointer");
+    CTX_REQUIRE(x && y && n > 0, "f32_to_f16: null pointer or n=%lld < 1", (long long)n);
     hipLaunchKernelGGL(k_f32_to_f16, dim3(capped_blocks(n, 256, 2048)), dim3(256), 0, s, x, n, y);
     CTX_CHECK_LAUNCH("f32_to_f16");
     return CTX_OK;
@@ -144,15 +147,15 @@ __global__ void k_time_embed(const float *__restrict__ t, int B, int dim, f16 *_
         out[(size_t)b * dim + half + i] = (f16)sn;
     }
 }
-int ctx_time_embed_f16(const float *t, int B, int dim, f16 *out, hipStream_t s)
+int ctx_time_embed_core(const float *t, int B, int dim, f16 *out, hipStream_t s)
 {
-    CTX_REQUIRE(t && out && dim % 2 == 0, "time_embed: unsupported dim=%d", dim);
+    CTX_REQUIRE(t && out && B > 0 && dim >= 2 && dim % 2 == 0, "time_embed: unsupported B=%d dim=%d", B, dim);
     hipLaunchKernelGGL(k_time_embed, dim3(cdiv(dim / 2, 64)), dim3(64), 0, s, t, B, dim, out);
     CTX_CHECK_LAUNCH("time_embed");
     return CTX_OK;
 }
 
-// conv_in: sample [B,Cin,H,W] f32 NCHW (Cin <= 8) -> y [B,H,W,Cout] f16, 3x3 pad 1.  w packed [Cout][3][3][8] f16.
+// conv_in: sample [B,Cin,H,W] f32 NCHW (Cin <= 16) -> y [B,H,W,Cout] f16, 3x3 pad 1.  w packed [Cout][3][3][8 | 16] f16.
 // One pixel per lane: its 9 x Cin inputs live in registers; the weights of this block's slice of output channels
 // sit in LDS and are read as wave-wide broadcasts; grid.y splits the output channels.
 #define CI_SPLIT 16
@@ -220,11 +223,17 @@ __global__ __launch_bounds__(256) void k_conv_in(const float *__restrict__ x, co
         __syncthreads();
     }
 }
-int ctx_conv_in_f16(const float *x, const f16 *w, const f16 *bias, int B, int Cin, int H, int W, int Cout, f16 *y, hipStream_t s)
+int ctx_conv_in_core(const float *x, const f16 *w, const f16 *bias, int B, int Cin, int H, int W, int Cout, f16 *y, hipStream_t s)
 {
-    CTX_REQUIRE(x && w && bias && y && Cout % 8 == 0, "conv_in: unsupported Cout=%d", Cout);
+    CTX_REQUIRE(x && w && bias && y && Cout > 0 && Cout % 8 == 0, "conv_in: unsupported Cout=%d", Cout);
+    // the widest instantiation multiplies 16 channels of a [Cout][3][3][16] pack: more would be dropped without a word
+    CTX_REQUIRE(Cin >= 1 && Cin <= 16, "conv_in: need 1 <= Cin <= 16 (Cin=%d)", Cin);
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "conv_in: unsupported grid B=%d H=%d W=%d", B, H, W);
     int64_t npix = (int64_t)B * H * W;
     int o8_per = (Cout / 8 + CI_SPLIT - 1) / CI_SPLIT;
+    const int cx = Cin <= 3 ? 3 : Cin <= 5 ? Cin : Cin <= 8 ? 8 : Cin == 9 ? 9 : 16;      // the CX of the instantiation chosen below
+    CTX_REQUIRE((size_t)o8_per * 8 * 9 * cx * sizeof(float) + 256 * 72 * sizeof(f16) <= 64 * 1024,
+                "conv_in: the weight slice of Cout=%d at Cin=%d does not fit the LDS", Cout, Cin);
     const dim3 grid((unsigned)cdiv64(npix, 256), CI_SPLIT);
 #define CI_GO(CP_, CX_) hipLaunchKernelGGL((k_conv_in<CP_, CX_>), grid, dim3(256), (size_t)o8_per * 8 * 9 * CX_ * sizeof(float) + 256 * 72 * sizeof(f16), s, x, w, bias, B, Cin, H, W, Cout, y)
     if (Cin <= 3) CI_GO(8, 3);
@@ -331,12 +340,13 @@ __global__ __launch_bounds__(256) void k_conv_out(const f16 *__restrict__ x, con
         }
     }
 }
-int ctx_conv_out_f16(const f16 *x, const f16 *w, const f16 *bias, int B, int H, int W, int C, int Cout, float *out, hipStream_t s)
+int ctx_conv_out_core(const f16 *x, const f16 *w, const f16 *bias, int B, int H, int W, int C, int Cout, float *out, hipStream_t s)
 {
     const int nitems = 9 * (C / 8);
     const size_t lds16 = (size_t)Cout * 9 * C * sizeof(f16);
     CTX_REQUIRE(x && w && bias && out, "conv_out: null pointer");
-    CTX_REQUIRE(Cout <= 4 && C % 8 == 0 && nitems <= 64 * 12 && lds16 <= 64 * 1024, "conv_out: unsupported C=%d Cout=%d", C, Cout);
+    CTX_REQUIRE(Cout >= 1 && Cout <= 4 && C >= 8 && C % 8 == 0 && nitems <= 64 * 12 && lds16 <= 64 * 1024, "conv_out: unsupported C=%d Cout=%d", C, Cout);
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "conv_out: unsupported grid B=%d H=%d W=%d", B, H, W);
     const unsigned nb = capped_blocks((int64_t)B * H * W, 4, 2048);       // every block stages the weights: keep them few and persistent
     const bool f32w = 2 * lds16 <= 64 * 1024;
     const size_t lds = f32w ? 2 * lds16 : lds16;
@@ -391,4 +401,42 @@ extern "C" int32_t ctx_cfg_plms_step(const float *eps_pair, int64_t n, float gui
                        coef4[0], coef4[1], coef4[2], coef4[3], sample_coeff, eps_coeff, mode, cur_sample_ws, x);
     CTX_CHECK_LAUNCH("cfg_plms_step");
     return CTX_OK;
+}
+
+// ---- test seams: each op above alone, through the host function the engines call (tests/engine_ops_rule.py) -----------------------
+extern "C" int32_t ctx_concat_f16(const void *a, const void *b, int64_t M, int32_t Ca, int32_t Cb, void *y, ctx_stream_t stream)
+{
+    return ctx_concat_core((const f16 *)a, (const f16 *)b, M, Ca, Cb, (f16 *)y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_concat_f32(const float *a, const float *b, int64_t M, int32_t Ca, int32_t Cb, float *y, ctx_stream_t stream)
+{
+    CTX_REQUIRE(Ca > 0 && Cb > 0 && Ca <= (1 << 29) && Cb <= (1 << 29), "concat_f32: unsupported Ca=%d Cb=%d", Ca, Cb);
+    return ctx_concat32_core(a, b, M, Ca, Cb, y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_transpose_v_f16(const void *v, int32_t B, int32_t S, int32_t ld, int32_t heads, int32_t Sp, void *vt, ctx_stream_t stream)
+{
+    CTX_REQUIRE(B <= 65535 && heads <= 65535, "transpose_v: B=%d / heads=%d exceed the grid", B, heads);
+    return ctx_transpose_v_core((const f16 *)v, B, S, ld, heads, Sp, (f16 *)vt, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_f32_to_f16(const float *x, int64_t n, void *y, ctx_stream_t stream)
+{
+    return ctx_f32_to_f16_core(x, n, (f16 *)y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_f16_to_f32(const void *x, int64_t n, float *y, ctx_stream_t stream)
+{
+    return ctx_f16_to_f32_core((const f16 *)x, n, y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_time_embed_f16(const float *t, int32_t B, int32_t dim, void *out, ctx_stream_t stream)
+{
+    return ctx_time_embed_core(t, B, dim, (f16 *)out, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_conv_in_f16(const float *x, const void *w_pack, const void *bias, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                                   void *y, ctx_stream_t stream)
+{
+    return ctx_conv_in_core(x, (const f16 *)w_pack, (const f16 *)bias, B, Cin, H, W, Cout, (f16 *)y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_conv_out_f16(const void *x, const void *w, const void *bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cout,
+                                    float *out, ctx_stream_t stream)
+{
+    return ctx_conv_out_core((const f16 *)x, (const f16 *)w, (const f16 *)bias, B, H, W, C, Cout, out, (hipStream_t)stream);
 }

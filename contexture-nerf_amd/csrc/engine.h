@@ -130,3 +130,5 @@ int32_t engine_param_shape(const Engine *e, int32_t i, int64_t shape4[4]);
 int64_t engine_weight_bytes(const Engine *e);
 int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace_bytes, const char *who);
 int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t stream, const char *who);
+// the forward pack of one parameter alone (kind: PackKind; a, b: its dims in the table; n source elements); no launch check of its own
+int engine_pack_fwd(int kind, const float *src, int64_t n, int a, int b, f16 *d, hipStream_t s, const char *who);

@@ -141,6 +141,32 @@ static unsigned pack_blocks(int64_t n)
     return (unsigned)(nbk > 4096 ? 4096 : nbk);
 }
 
+// The forward pack of one parameter of n source elements: kind and its dims a, b as the parameter table holds them (PK_CONV3 /
+// PK_CONVIN: Cout, Cin; PK_GEGLU_W: C4, K; PK_GEGLU_B: C4).  engine_set_param and the test seam ctx_pack_fwd_f16 launch through here.
+int engine_pack_fwd(int kind, const float *src, int64_t n, int a, int b, f16 *d, hipStream_t s, const char *who)
+{
+    CTX_REQUIRE(src && d && n > 0, "%s: pack: null pointer or empty parameter", who);
+    const unsigned nb = pack_blocks(n);
+    switch (kind) {
+    case PK_COPY: hipLaunchKernelGGL(k_pack_copy, dim3(nb), dim3(256), 0, s, src, n, d); break;
+    case PK_CONV3:
+        CTX_REQUIRE(a > 0 && b > 0 && n == (int64_t)a * b * 9, "%s: conv3 pack of %lld elements is not [%d,%d,3,3]", who, (long long)n, a, b);
+        hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, a, b, b, d); break;
+    case PK_CONVIN:
+        // rows of 8 or 16 channels: a 17th would land in the next row, and conv_in multiplies at most 16
+        CTX_REQUIRE(a > 0 && b >= 1 && b <= 16 && n == (int64_t)a * b * 9, "%s: conv_in pack needs 1 <= Cin <= 16 and [%d,%d,3,3] = %lld elements", who, a, b, (long long)n);
+        hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, a, b, b > 8 ? 16 : 8, d); break;
+    case PK_GEGLU_W:
+        CTX_REQUIRE(a > 0 && a % 32 == 0 && b > 0 && n == (int64_t)2 * a * b, "%s: GEGLU weight pack needs C4 %% 32 == 0 and [2 * %d, %d] = %lld elements", who, a, b, (long long)n);
+        hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, a, b, d); break;
+    case PK_GEGLU_B:
+        CTX_REQUIRE(a > 0 && a % 32 == 0 && n == (int64_t)2 * a, "%s: GEGLU bias pack needs C4 %% 32 == 0 and 2 * %d = %lld elements", who, a, (long long)n);
+        hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, a, 0, d); break;
+    default: ctx_set_error("%s: unknown pack kind %d", who, kind); return CTX_E_ARG;
+    }
+    return CTX_OK;
+}
+
 int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t stream, const char *who)
 {
     CTX_REQUIRE(e && e->W && src && i >= 0 && i < (int)e->params.size(), "%s: bad args / not bound", who);
@@ -150,20 +176,25 @@ int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t st
     for (int k = 0; k < p.ndim; ++k) n *= p.shape[k];
     f16 *d = e->W + p.dst;
     const unsigned nb = pack_blocks(n);
-    switch (p.kind) {
-    case PK_COPY: hipLaunchKernelGGL(k_pack_copy, dim3(nb), dim3(256), 0, s, src, n, d); break;
-    case PK_CONV3: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b, d); break;
-    case PK_CONVIN: hipLaunchKernelGGL(k_pack_conv3, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.b > 8 ? 16 : 8, d); break;
-    case PK_GEGLU_W: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, p.b, d); break;
-    case PK_GEGLU_B: hipLaunchKernelGGL(k_pack_geglu, dim3(nb), dim3(256), 0, s, src, p.a, 0, d); break;
-    }
+    const int rc = engine_pack_fwd(p.kind, src, n, p.a, p.b, d, s, who);
+    if (rc != CTX_OK) return rc;
     if (p.kind2 == 1) hipLaunchKernelGGL(k_pack_conv3_T, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.pad2, e->W + p.dst2);
     else if (p.kind2 == 2) hipLaunchKernelGGL(k_pack_mat_T, dim3(nb), dim3(256), 0, s, src, (int)p.shape[0], (int)p.shape[1], p.ld2, p.col2, e->W + p.dst2);
     CTX_CHECK_LAUNCH(who);
     return CTX_OK;
 }
 
-// ---- test seams: the two backward packs alone, with engine_set_param's launch geometry -----------------------------
+// ---- test seams: the forward packs and the two backward packs alone, with engine_set_param's launch geometry -----------------------------
+extern "C" int32_t ctx_pack_fwd_f16(const float *src, int32_t kind, int32_t a, int32_t b, void *dst, ctx_stream_t stream)
+{
+    CTX_REQUIRE(kind >= PK_COPY && kind <= PK_GEGLU_B && a > 0 && b >= 0, "pack_fwd: kind %d with a=%d b=%d", kind, a, b);
+    const int64_t n = kind == PK_COPY ? (int64_t)a * (b > 0 ? b : 1) : kind == PK_GEGLU_W ? (int64_t)2 * a * b : kind == PK_GEGLU_B ? (int64_t)2 * a
+                                                                                                               : (int64_t)a * b * 9;
+    const int rc = engine_pack_fwd(kind, src, n, a, b, (f16 *)dst, (hipStream_t)stream, "pack_fwd");
+    if (rc != CTX_OK) return rc;
+    CTX_CHECK_LAUNCH("pack_fwd");
+    return CTX_OK;
+}
 extern "C" int32_t ctx_pack_conv3_dgrad_f16(const float *src, int32_t Cout, int32_t Cin, int32_t pad, void *dst, ctx_stream_t stream)
 {
     CTX_REQUIRE(src && dst, "pack_conv3_dgrad: null pointer");

@@ -807,11 +807,11 @@ __global__ __launch_bounds__(256) void k_gemv_f16(const f16 *__restrict__ x, con
     }
 }
 
-int ctx_gemv_f16(const f16 *x, const f16 *w, const f16 *bias, int Bm, int N, int K, int silu_in, int silu_out, f16 *out,
+int ctx_gemv_core(const f16 *x, const f16 *w, const f16 *bias, int Bm, int N, int K, int silu_in, int silu_out, f16 *out,
                  hipStream_t s)
 {
-    if (Bm < 1 || K % 8 != 0 || K < 8) {
-        ctx_set_error("gemv: Bm=%d (>=1) K=%d (%%8)", Bm, K);
+    if (!x || !w || !out || Bm < 1 || N < 1 || K % 8 != 0 || K < 8) {
+        ctx_set_error("gemv: null pointer, or Bm=%d (>=1) N=%d (>=1) K=%d (%%8)", Bm, N, K);
         return CTX_E_ARG;
     }
     for (int b0 = 0; b0 < Bm; b0 += 4) {                       // four rows per pass over the weights
@@ -819,6 +819,15 @@ int ctx_gemv_f16(const f16 *x, const f16 *w, const f16 *bias, int Bm, int N, int
         hipLaunchKernelGGL(k_gemv_f16, dim3(cdiv(N, 8)), dim3(256), 0, s, x + (size_t)b0 * K, w, bias, nb, N, K, silu_in, silu_out,
                            out + (size_t)b0 * N);
     }
+    return CTX_OK;
+}
+// test seam (tests/engine_ops_rule.py): the GEMV alone, through the host function the UNet engine calls
+extern "C" int32_t ctx_gemv_f16(const void *x, const void *w, const void *bias, int32_t Bm, int32_t N, int32_t K, int32_t silu_in, int32_t silu_out,
+                                void *out, ctx_stream_t stream)
+{
+    const int rc = ctx_gemv_core((const f16 *)x, (const f16 *)w, (const f16 *)bias, Bm, N, K, silu_in, silu_out, (f16 *)out, (hipStream_t)stream);
+    if (rc != CTX_OK) return rc;
+    CTX_CHECK_LAUNCH("gemv");
     return CTX_OK;
 }
 

@@ -71,13 +71,15 @@ int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s);
 int ctx_gemm_pick_split(int M, int N, int K, int epi);
 // fills a.splitk / a.tile / a.use8 for a fully described problem: the tuned table (gemm_tuned.h) first, heuristics otherwise
 void ctx_gemm_plan(GemmArgs &a, bool conv);
-int ctx_gemv_f16(const f16 *x, const f16 *w, const f16 *bias, int Bm, int N, int K, int silu_in, int silu_out, f16 *out, hipStream_t s);
-int ctx_concat_f16(const f16 *a, const f16 *b, int64_t M, int Ca, int Cb, f16 *y, hipStream_t s);
-int ctx_transpose_v_f16(const f16 *v, int B, int S, int ld, int heads, int Sp, f16 *vt, hipStream_t s);
-int ctx_f32_to_f16(const float *x, int64_t n, f16 *y, hipStream_t s);
-int ctx_time_embed_f16(const float *t, int B, int dim, f16 *out, hipStream_t s);
-int ctx_conv_in_f16(const float *x, const f16 *w, const f16 *bias, int B, int Cin, int H, int W, int Cout, f16 *y, hipStream_t s);
-int ctx_conv_out_f16(const f16 *x, const f16 *w, const f16 *bias, int B, int H, int W, int C, int Cout, float *out, hipStream_t s);
+// The engines' small ops (elementwise.hip, gemm.hip, unet.hip, vae.hip).  Each validates its arguments (CTX_E_ARG, nothing launched) and
+// launches; include/ctx_nerf.h exports every one as a test seam under the name ctx_<op>_f16 / _f32 with the contract spelled out.
+int ctx_gemv_core(const f16 *x, const f16 *w, const f16 *bias, int Bm, int N, int K, int silu_in, int silu_out, f16 *out, hipStream_t s);
+int ctx_concat_core(const f16 *a, const f16 *b, int64_t M, int Ca, int Cb, f16 *y, hipStream_t s);
+int ctx_transpose_v_core(const f16 *v, int B, int S, int ld, int heads, int Sp, f16 *vt, hipStream_t s);
+int ctx_f32_to_f16_core(const float *x, int64_t n, f16 *y, hipStream_t s);
+int ctx_time_embed_core(const float *t, int B, int dim, f16 *out, hipStream_t s);
+int ctx_conv_in_core(const float *x, const f16 *w, const f16 *bias, int B, int Cin, int H, int W, int Cout, f16 *y, hipStream_t s);
+int ctx_conv_out_core(const f16 *x, const f16 *w, const f16 *bias, int B, int H, int W, int C, int Cout, float *out, hipStream_t s);
 int ctx_attention_core(const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int q_stride,
                        int kv_stride, float scale, f16 *O, int o_stride, hipStream_t s);
 extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
@@ -98,8 +100,14 @@ int ctx_groupnorm_slabs(const GnSlabs &sl, const void *gamma, const void *beta, 
 // GroupNorm(+SiLU) backward, input gradient only, fp16 NHWC: dx = d(loss)/dx (+ add); ws of ctx_groupnorm_bwd_ws_bytes(B, groups)
 // (ctx_groupnorm_bwd_ws_bytes / ctx_groupnorm_bwd_f16: declared in include/ctx_nerf.h, the unit tests call them too)
 int ctx_layernorm_any(const void *x, int x32, const void *gamma, const void *beta, int64_t rows, int C, float eps, void *y, hipStream_t stream);
-int ctx_concat_f32(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s);
-int ctx_f16_to_f32(const f16 *x, int64_t n, float *y, hipStream_t s);
+int ctx_concat32_core(const float *a, const float *b, int64_t M, int Ca, int Cb, float *y, hipStream_t s);
+int ctx_f16_to_f32_core(const f16 *x, int64_t n, float *y, hipStream_t s);
+// ControlNet's few-channel 3x3 convolution (exactly one of x32 f32 NCHW / x16 f16 NHWC) and dst += scale * src over n f16 (n % 8 == 0)
+int ctx_conv_small_core(const float *x32, const f16 *x16, const f16 *w, const f16 *bias, int B, int H, int W, int Cin, int Cout, int stride, int silu,
+                        f16 *y, hipStream_t s);
+int ctx_add_scaled_core(f16 *dst, const f16 *src, float scale, int64_t n, hipStream_t s);
+// the VAE's 1x1 convolutions over a few channels -> f32 NCHW: x f32 NCHW with C <= 8, or (nhwc16) f16 NHWC with C <= 16
+int ctx_pointwise_core(const void *x, const f16 *w, const f16 *b, int B, int C, int64_t HW, bool nhwc16, float *y, hipStream_t s);
 
 // profiling hooks (api.cpp): when on, MFMA kernels are launched with hipExtLaunchKernelGGL start/stop events
 bool ctx_prof_on(void);

@@ -360,6 +360,37 @@ __global__ __launch_bounds__(256) void k_add_scaled_f16(f16 *__restrict__ dst, c
     }
 }
 
+// the two launches above as the ControlNet graph and the test seams below make them
+int ctx_conv_small_core(const float *x32, const f16 *x16, const f16 *w, const f16 *bias, int B, int H, int W, int Cin, int Cout, int stride, int silu,
+                        f16 *y, hipStream_t s)
+{
+    CTX_REQUIRE(w && bias && y, "conv_small: null pointer");
+    CTX_REQUIRE((x32 != nullptr) != (x16 != nullptr), "conv_small: exactly one of the f32 NCHW and the f16 NHWC input must be given");
+    CTX_REQUIRE(Cout > 0 && Cout % 8 == 0 && (stride == 1 || stride == 2), "conv_small: need Cout %% 8 == 0 and stride 1 | 2 (Cout=%d stride=%d)", Cout, stride);
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && (int64_t)B * H * W < (1ll << 31), "conv_small: unsupported B=%d H=%d W=%d Cin=%d", B, H, W, Cin);
+    const int64_t items = (int64_t)B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) * (Cout / 8);
+    hipLaunchKernelGGL(k_conv_small, dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 65535)), dim3(256), 0, s, x32, x16, w, bias, B, H, W, Cin, Cout,
+                       stride, silu, y);
+    CTX_CHECK_LAUNCH("conv_small");
+    return CTX_OK;
+}
+int ctx_add_scaled_core(f16 *dst, const f16 *src, float scale, int64_t n, hipStream_t s)
+{
+    CTX_REQUIRE(dst && src && n > 0 && n % 8 == 0, "add_scaled: null pointer or n=%lld is not a positive multiple of 8", (long long)n);
+    hipLaunchKernelGGL(k_add_scaled_f16, dim3((unsigned)std::min<int64_t>(cdiv64(n / 8, 256), 4096)), dim3(256), 0, s, dst, src, scale, n / 8);
+    CTX_CHECK_LAUNCH("add_scaled");
+    return CTX_OK;
+}
+extern "C" int32_t ctx_conv_small_f16(const float *x32, const void *x16, const void *w, const void *bias, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                                      int32_t Cout, int32_t stride, int32_t silu, void *y, ctx_stream_t stream)
+{
+    return ctx_conv_small_core(x32, (const f16 *)x16, (const f16 *)w, (const f16 *)bias, B, H, W, Cin, Cout, stride, silu, (f16 *)y, (hipStream_t)stream);
+}
+extern "C" int32_t ctx_add_scaled_f16(void *dst, const void *src, float scale, int64_t n, ctx_stream_t stream)
+{
+    return ctx_add_scaled_core((f16 *)dst, (const f16 *)src, scale, n, (hipStream_t)stream);
+}
+
 // ---- op wrappers: the shared op layer (engine.h) on this engine's weight offsets and residual-stream flags ------
 #define RUN(expr) ENGINE_RUN(u, expr)
 
@@ -429,7 +460,7 @@ static const f16 *op_as16(ctx_unet *u, const void *x, size_t n)
     if (!u->res32) return (const f16 *)x;
     f16 *c = u->allocH(n);
     u->note(2, 0);
-    RUN(ctx_f32_to_f16((const float *)x, (int64_t)n, c, u->s));
+    RUN(ctx_f32_to_f16_core((const float *)x, (int64_t)n, c, u->s));
     return c;
 }
 static void op_attn(ctx_unet *u, const f16 *Q, const f16 *K, const f16 *V, int B, int Sq, int Skv, int heads, int qs, int kvs, f16 *O)
@@ -482,8 +513,8 @@ static void *run_resnet(ctx_unet *u, const FwdCtx &f, const ResP &r, const void 
         u->note(2, 0);                             // the concat: a copy, or the in-place reads that stand for it
         if (!gn_pair || !fold) {
             void *cat = u->allocS((size_t)M * r.cin);
-            if (u->res32) RUN(ctx_concat_f32((const float *)x, (const float *)x2, (int64_t)M, Ca, Cb, (float *)cat, u->s));
-            else RUN(ctx_concat_f16((const f16 *)x, (const f16 *)x2, (int64_t)M, Ca, Cb, (f16 *)cat, u->s));
+            if (u->res32) RUN(ctx_concat32_core((const float *)x, (const float *)x2, (int64_t)M, Ca, Cb, (float *)cat, u->s));
+            else RUN(ctx_concat_core((const f16 *)x, (const f16 *)x2, (int64_t)M, Ca, Cb, (f16 *)cat, u->s));
             xin = cat;
         }
     }
@@ -619,16 +650,16 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     f.gn_stats = u->alloc((size_t)ctx_groupnorm_ws_bytes(B, c.groups));
     // time embedding
     f16 *te0 = u->allocH((size_t)B * ch[0]);
-    u->note(2, 0); RUN(ctx_time_embed_f16(timestep, B, ch[0], te0, u->s));
+    u->note(2, 0); RUN(ctx_time_embed_core(timestep, B, ch[0], te0, u->s));
     f16 *te1 = u->allocH((size_t)B * u->temb_dim);
-    u->note(2, 2.0 * B * ch[0] * u->temb_dim); RUN(ctx_gemv_f16(te0, u->W + u->t1w, u->W + u->t1b, B, u->temb_dim, ch[0], 0, 1, te1, u->s));
+    u->note(2, 2.0 * B * ch[0] * u->temb_dim); RUN(ctx_gemv_core(te0, u->W + u->t1w, u->W + u->t1b, B, u->temb_dim, ch[0], 0, 1, te1, u->s));
     f16 *te2 = u->allocH((size_t)B * u->temb_dim);
-    u->note(2, 2.0 * B * u->temb_dim * u->temb_dim); RUN(ctx_gemv_f16(te1, u->W + u->t2w, u->W + u->t2b, B, u->temb_dim, u->temb_dim, 0, 1, te2, u->s));   // + the resnets' SiLU(temb), once
+    u->note(2, 2.0 * B * u->temb_dim * u->temb_dim); RUN(ctx_gemv_core(te1, u->W + u->t2w, u->W + u->t2b, B, u->temb_dim, u->temb_dim, 0, 1, te2, u->s));   // + the resnets' SiLU(temb), once
     f16 *tproj = u->allocH((size_t)B * u->temb_rows);
-    u->note(2, 2.0 * B * u->temb_rows * u->temb_dim); RUN(ctx_gemv_f16(te2, u->W + u->tpw, u->W + u->tpb, B, u->temb_rows, u->temb_dim, 0, 0, tproj, u->s));
+    u->note(2, 2.0 * B * u->temb_rows * u->temb_dim); RUN(ctx_gemv_core(te2, u->W + u->tpw, u->W + u->tpb, B, u->temb_rows, u->temb_dim, 0, 0, tproj, u->s));
     f.tproj = tproj;
     f16 *ctx16 = u->allocH((size_t)B * L * c.cross_attention_dim);
-    u->note(2, 0); RUN(ctx_f32_to_f16(ctx, (int64_t)B * L * c.cross_attention_dim, ctx16, u->s));
+    u->note(2, 0); RUN(ctx_f32_to_f16_core(ctx, (int64_t)B * L * c.cross_attention_dim, ctx16, u->s));
     f.ctx16 = ctx16;
     // cross-attention K/V of every transformer block in one GEMM: they depend only on the context
     f16 *kv_all = u->allocH((size_t)B * L * u->kv_rows_total);
@@ -644,14 +675,13 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     {
         size_t m0 = u->top;
         f16 *x16 = u->res32 ? u->allocH((size_t)B * h * w * ch[0]) : (f16 *)x;
-        u->note(2, 2.0 * B * h * w * ch[0] * c.in_channels * 9); RUN(ctx_conv_in_f16(sample, u->W + u->ciw, u->W + u->cib, B, c.in_channels, h, w, ch[0], x16, u->s));
-        if (u->res32) { u->note(2, 0); RUN(ctx_f16_to_f32(x16, (int64_t)B * h * w * ch[0], (float *)x, u->s)); u->top = m0; }
+        u->note(2, 2.0 * B * h * w * ch[0] * c.in_channels * 9); RUN(ctx_conv_in_core(sample, u->W + u->ciw, u->W + u->cib, B, c.in_channels, h, w, ch[0], x16, u->s));
+        if (u->res32) { u->note(2, 0); RUN(ctx_f16_to_f32_core(x16, (int64_t)B * h * w * ch[0], (float *)x, u->s)); u->top = m0; }
     }
 
     auto add_scaled = [&](f16 *dst, const f16 *src, float scale, size_t n) {
         u->note(2, 0);
-        ENGINE_LAUNCH(u, k_add_scaled_f16, dim3((unsigned)std::min<int64_t>(cdiv64((int64_t)n / 8, 256), 4096)), dim3(256), 0, dst, src, scale,
-                      (int64_t)n / 8);
+        RUN(ctx_add_scaled_core(dst, src, scale, (int64_t)n, u->s));
     };
     if (u->is_controlnet) {
         // sample = conv_in(sample) + controlnet_cond_embedding(cond): the conditioning image is 8x the latent grid
@@ -666,9 +696,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
             f16 *o = (last && u->cn_cache) ? u->cn_cache : u->allocH((size_t)B * oh * ow * cc.cout);
             if (!u->cn_cache_valid) {
                 u->note(2, 2.0 * B * oh * ow * cc.cout * cc.cin * 9);
-                const int64_t items = (int64_t)B * oh * ow * (cc.cout / 8);
-                ENGINE_LAUNCH(u, k_conv_small, dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 65535)), dim3(256), 0,
-                              k == 0 ? u->cn_cond : nullptr, cur16, u->W + cc.w, u->W + cc.b, B, eh, ew, cc.cin, cc.cout, cc.stride, 1, o);
+                RUN(ctx_conv_small_core(k == 0 ? u->cn_cond : nullptr, cur16, u->W + cc.w, u->W + cc.b, B, eh, ew, cc.cin, cc.cout, cc.stride, 1, o, u->s));
             }
             cur16 = o; eh = oh; ew = ow;
         }
@@ -789,7 +817,7 @@ static int unet_run(ctx_unet *u, const float *sample, const float *timestep, con
     f16 *y = u->allocH((size_t)B * h * w * cur);
     op_gn(u, x, u->cng, u->cnb, B, h * w, cur, c.norm_eps, 1, y, f.gn_stats);
     u->note(2, 2.0 * B * h * w * cur * c.out_channels * 9);
-    RUN(ctx_conv_out_f16(y, u->W + u->cow, u->W + u->cob, B, h, w, cur, c.out_channels, out, u->s));
+    RUN(ctx_conv_out_core(y, u->W + u->cow, u->W + u->cob, B, h, w, cur, c.out_channels, out, u->s));
     return engine_finish(u, "unet_forward");
 }
 

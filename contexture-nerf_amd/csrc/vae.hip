@@ -192,6 +192,17 @@ __global__ __launch_bounds__(256) void k_pointwise(const void *__restrict__ xv, 
     }
 }
 
+// the launch of either form, as the decoder / encoder graphs and the test seam ctx_pointwise_f32 make it
+int ctx_pointwise_core(const void *x, const f16 *w, const f16 *b, int B, int C, int64_t HW, bool nhwc16, float *y, hipStream_t s)
+{
+    CTX_REQUIRE(x && w && b && y, "pointwise: null pointer");
+    // the kernel keeps a pixel's channels in a register array of 8 (f32 NCHW input) or 16 (f16 NHWC input) floats
+    CTX_REQUIRE(B > 0 && HW > 0 && C >= 1 && C <= (nhwc16 ? 16 : 8), "pointwise: need 1 <= C <= %d (B=%d C=%d HW=%lld)", nhwc16 ? 16 : 8, B, C, (long long)HW);
+    CTX_BOOL_GO(nhwc16, NH, hipLaunchKernelGGL(k_pointwise<NH>, dim3((unsigned)cdiv64((int64_t)B * HW, 256)), dim3(256), 0, s, x, w, b, B, C, HW, y));
+    CTX_CHECK_LAUNCH("pointwise");
+    return CTX_OK;
+}
+
 // row softmax of f16 scores [rows, n] * scale -> f16 probabilities (fp32 math), one workgroup per row
 __global__ __launch_bounds__(256) void k_softmax_rows(const f16 *__restrict__ s, int n, float scale_log2e, f16 *__restrict__ p)
 {
@@ -299,7 +310,7 @@ static void vattn(ctx_vae *v, const VAttn &at, const f16 *o, f16 *x, int B, int 
         const f16 *base = qkv ? qkv + (size_t)b * S * 3 * top : nullptr;
         vrows(v, base, S, top, qb);
         vrows(v, base ? base + top : nullptr, S, top, kb);
-        VRUN(ctx_transpose_v_f16(base + 2 * top, 1, S, 3 * top, top / 64, S, vt, v->s));     // V^T through the head-transpose kernel
+        VRUN(ctx_transpose_v_core(base + 2 * top, 1, S, 3 * top, top / 64, S, vt, v->s));     // V^T through the head-transpose kernel
         vprobs(v, qb, kb, S, top, softmax_scale_log2e(1.0f / sqrtf((float)top)), sc, pr);
         engine_linear(*v, pr, vt, nullptr, nullptr, S, top, S, att ? att + (size_t)b * S * top : nullptr);
     }
@@ -327,11 +338,10 @@ static int vae_run(ctx_vae *v, const float *z, int B, int H, int W, float *img)
     v->begin();
     void *stats = v->alloc((size_t)ctx_groupnorm_ws_bytes(B, c.groups));
     float *zq = (float *)v->alloc((size_t)B * L * H * W * 4);
-    ENGINE_LAUNCH(v, k_pointwise<false>, dim3((unsigned)cdiv64((int64_t)B * H * W, 256)), dim3(256), 0, z, v->W + v->pqw, v->W + v->pqb, B, L,
-                  (int64_t)H * W, zq);
+    VRUN(ctx_pointwise_core(z, v->W + v->pqw, v->W + v->pqb, B, L, (int64_t)H * W, false, zq, v->s));
     int h = H, w = W;
     f16 *x = v->allocH((size_t)B * h * w * top);
-    VRUN(ctx_conv_in_f16(zq, v->W + v->dec.ciw, v->W + v->dec.cib, B, L, h, w, top, x, v->s));
+    VRUN(ctx_conv_in_core(zq, v->W + v->dec.ciw, v->W + v->dec.cib, B, L, h, w, top, x, v->s));
     f16 *o = v->allocH((size_t)B * h * w * top);
     f16 *cur = vmid(v, v->dec, x, o, x, B, h, w, top, stats);     // the attention's output goes where conv_in's is dead by then
     int cc = top;
@@ -350,7 +360,7 @@ static int vae_run(ctx_vae *v, const float *z, int B, int H, int W, float *img)
     }
     f16 *y = v->allocH((size_t)B * h * w * cc);
     vgn(v, cur, v->dec.cng, v->dec.cnb, B, h * w, cc, 1, y, stats);
-    VRUN(ctx_conv_out_f16(y, v->W + v->dec.cow, v->W + v->dec.cob, B, h, w, cc, c.out_channels, img, v->s));
+    VRUN(ctx_conv_out_core(y, v->W + v->dec.cow, v->W + v->dec.cob, B, h, w, cc, c.out_channels, img, v->s));
     return engine_finish(v, "vae_decode");
 }
 
@@ -381,7 +391,7 @@ static int vae_encode_run(ctx_vae *v, const float *img, int B, int H, int W, flo
     void *stats = v->alloc((size_t)ctx_groupnorm_ws_bytes(B, c.groups));
     int h = H, w = W, cc = c.block_out_channels[0];
     f16 *cur = v->allocH((size_t)B * h * w * cc);
-    VRUN(ctx_conv_in_f16(img, v->W + v->enc.ciw, v->W + v->enc.cib, B, c.out_channels, h, w, cc, cur, v->s));
+    VRUN(ctx_conv_in_core(img, v->W + v->enc.ciw, v->W + v->enc.cib, B, c.out_channels, h, w, cc, cur, v->s));
     v->tape.conv_in_out = cur;
     for (int i = 0; i < n; ++i) {
         for (size_t j = 0; j < v->down[i].size(); ++j) {
@@ -404,8 +414,7 @@ static int vae_encode_run(ctx_vae *v, const float *img, int B, int H, int W, flo
     vgn(v, o, v->enc.cng, v->enc.cnb, B, h * w, top, 1, y, stats);
     f16 *m16 = v->allocH((size_t)B * h * w * L2);
     vconv(v, y, v->enc.cow, v->enc.cob, nullptr, B, h, w, top, L2, m16);
-    ENGINE_LAUNCH(v, k_pointwise<true>, dim3((unsigned)cdiv64((int64_t)B * h * w, 256)), dim3(256), 0, m16, v->W + v->qw, v->W + v->qb, B, L2,
-                  (int64_t)h * w, moments);
+    VRUN(ctx_pointwise_core(m16, v->W + v->qw, v->W + v->qb, B, L2, (int64_t)h * w, true, moments, v->s));
     return engine_finish(v, "vae_encode");
 }
 
@@ -575,16 +584,16 @@ static void vattn_bwd(ctx_vae *v, const VAttn &at, const f16 *o, const f16 *qkv,
         vprobs(v, qb, kb, S, top, softmax_scale_log2e(scale), sc, pr);                               // P (recomputed)
         engine_linear(*v, da, vb, nullptr, nullptr, S, S, top, dp);                                 // dP = dAtt V^T
         // dV = P^T dAtt : X = P^T [S,S], Wt = dAtt^T [top,S]
-        VRUN(ctx_transpose_v_f16(pr, 1, S, S, S / 64, S, tr, v->s));
-        VRUN(ctx_transpose_v_f16(da, 1, S, top, top / 64, S, tb, v->s));
+        VRUN(ctx_transpose_v_core(pr, 1, S, S, S / 64, S, tr, v->s));
+        VRUN(ctx_transpose_v_core(da, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, tr, tb, nullptr, nullptr, S, top, S, dq ? dq + 2 * top : nullptr, 3 * top);
         ENGINE_LAUNCH(v, k_softmax_bwd_rows, dim3(S), dim3(256), 0, pr, dp, S, scale, sc);          // dS -> sc
         // dQ = dS K : Wt = K^T [top,S]
-        VRUN(ctx_transpose_v_f16(kb, 1, S, top, top / 64, S, tb, v->s));
+        VRUN(ctx_transpose_v_core(kb, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, sc, tb, nullptr, nullptr, S, top, S, dq, 3 * top);
         // dK = dS^T Q : X = dS^T, Wt = Q^T
-        VRUN(ctx_transpose_v_f16(sc, 1, S, S, S / 64, S, tr, v->s));
-        VRUN(ctx_transpose_v_f16(qb, 1, S, top, top / 64, S, tb, v->s));
+        VRUN(ctx_transpose_v_core(sc, 1, S, S, S / 64, S, tr, v->s));
+        VRUN(ctx_transpose_v_core(qb, 1, S, top, top / 64, S, tb, v->s));
         engine_linear(*v, tr, tb, nullptr, nullptr, S, top, S, dq ? dq + top : nullptr, 3 * top);
     }
     f16 *dg = datt;                                    // datt is dead
@@ -680,6 +689,12 @@ extern "C" int32_t ctx_softmax_rows_f16(const void *s, int32_t rows, int32_t n, 
     hipLaunchKernelGGL(k_softmax_rows, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16 *)s, n, softmax_scale_log2e(scale), (f16 *)p);
     CTX_CHECK_LAUNCH("softmax_rows");
     return CTX_OK;
+}
+extern "C" int32_t ctx_pointwise_f32(const void *x, const void *w, const void *b, int32_t B, int32_t C, int64_t HW, int32_t nhwc16, float *y,
+                                     ctx_stream_t stream)
+{
+    CTX_REQUIRE((int64_t)B * HW <= 0xffffffffll * 256, "pointwise: B * HW exceeds the grid");
+    return ctx_pointwise_core(x, (const f16 *)w, (const f16 *)b, B, C, HW, nhwc16 != 0, y, (hipStream_t)stream);
 }
 extern "C" int32_t ctx_softmax_bwd_rows_f16(const void *P, const void *dP, int32_t rows, int32_t n, float scale, void *dS, ctx_stream_t stream)
 {

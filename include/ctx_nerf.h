@@ -678,6 +678,56 @@ int32_t ctx_softmax_bwd_rows_f16(const void *P, const void *dP, int32_t rows, in
 int32_t ctx_quant_bwd_f16(const float *g, const void *w, int32_t B, int32_t C, int64_t HW, float gscale, void *d, ctx_stream_t stream);
 int32_t ctx_conv_in_bwd_f16(const void *dy, const void *w_pack, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cimg, float inv_gscale,
                             float *dimg, ctx_stream_t stream);
+/* ---- test-only seams of the engines' small ops: what the UNet / ControlNet / VAE graphs launch besides GEMMs, attention and norms
+   (diffusers' UNet2DConditionModel, ControlNetModel and AutoencoderKL under src/stable_diffusion_depth.py:422-423 and
+   src/training/trainer.py:732).  Each goes through the host function the engine calls: same checks, same grid, same template
+   choice.  A refused call returns CTX_E_ARG and launches nothing.  tests/engine_ops_rule.py holds the float64 references and the
+   error bounds.  Not for product code. ---- */
+/* conv_in: x f32 NCHW [B,Cin,H,W], each value rounded to f16 on load; w_pack f16 [Cout][3][3][8] (Cin <= 8) or [Cout][3][3][16], the
+   channels Cin .. 8 | 16 of a row finite (the pack writes zeros; some are multiplied by a zero input); bias f16 [Cout] -> y f16 NHWC [B,H,W,Cout]; 3x3, padding 1, fp32 sum (bias first).
+   1 <= Cin <= 16, Cout % 8 == 0, and the weight slice of Cout / 16 features must fit the LDS (Cout <= 1152 at Cin <= 8). */
+int32_t ctx_conv_in_f16(const float *x, const void *w_pack, const void *bias, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                        void *y, ctx_stream_t stream);
+/* conv_out: x f16 NHWC [B,H,W,C], w f16 [Cout][3][3][C], bias f16 [Cout] -> out f32 NCHW [B,Cout,H,W]; 3x3, padding 1, fp32 sum over the
+   64 lanes of a wave, bias last.  1 <= Cout <= 4, C % 8 == 0, 8 <= C <= 680, Cout * C <= 3640. */
+int32_t ctx_conv_out_f16(const void *x, const void *w, const void *bias, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Cout,
+                         float *out, ctx_stream_t stream);
+/* GEMV of the time-embedding MLP: out[b][n] = act(sum_k in(x[b][k]) w[n][k] + bias[n]), f16 in and out, fp32 sum; in = SiLU when
+   silu_in, act = SiLU when silu_out; bias nullable.  Bm >= 1 (four rows per pass over w), N >= 1, K % 8 == 0, K >= 8. */
+int32_t ctx_gemv_f16(const void *x, const void *w, const void *bias, int32_t Bm, int32_t N, int32_t K, int32_t silu_in, int32_t silu_out,
+                     void *out, ctx_stream_t stream);
+/* diffusers' get_timestep_embedding(flip_sin_to_cos=True, freq_shift=0) of the ONE timestep t[0] (device f32), written to each of
+   the B rows: out f16 [B][dim] = [cos(t f_i) | sin(t f_i)], f_i = exp(-ln(10000) i / (dim / 2)).  dim even, >= 2. */
+int32_t ctx_time_embed_f16(const float *t, int32_t B, int32_t dim, void *out, ctx_stream_t stream);
+/* Per-head transpose: v f16 [B,S,ld] (head h at columns 64 h .. 64 h + 64; pass v + column offset for a slice of a wider row) ->
+   vt f16 [B,heads,64,Sp], keys contiguous, exactly zero in the keys S .. Sp.  Sp % 8 == 0, Sp >= S, ld % 8 == 0, ld >= 64 heads. */
+int32_t ctx_transpose_v_f16(const void *v, int32_t B, int32_t S, int32_t ld, int32_t heads, int32_t Sp, void *vt, ctx_stream_t stream);
+/* Channel concat of NHWC rows: y[m] = [a[m] (Ca) | b[m] (Cb)] for m < M; f16 with Ca, Cb % 8 == 0; f32 (the fp32 residual stream: the
+   same kernel, a float counted as two halves) with Ca, Cb % 4 == 0. */
+int32_t ctx_concat_f16(const void *a, const void *b, int64_t M, int32_t Ca, int32_t Cb, void *y, ctx_stream_t stream);
+int32_t ctx_concat_f32(const float *a, const float *b, int64_t M, int32_t Ca, int32_t Cb, float *y, ctx_stream_t stream);
+/* The converters: y = (f16)x, round to nearest even, n >= 1; y = (f32)x, n % 8 == 0. */
+int32_t ctx_f32_to_f16(const float *x, int64_t n, void *y, ctx_stream_t stream);
+int32_t ctx_f16_to_f32(const void *x, int64_t n, float *y, ctx_stream_t stream);
+/* ControlNet's conditioning-embedding convolution: 3x3, padding 1, stride 1 | 2 (Ho = (H - 1) / stride + 1); input either x32 f32 NCHW
+   [B,Cin,H,W] (rounded to f16 on load) or x16 f16 NHWC [B,H,W,Cin], exactly one of them non-null; w f16 [Cout][3][3][Cin], bias f16
+   [Cout] -> y f16 NHWC [B,Ho,Wo,Cout] = (f16)act(sum), act = SiLU when silu.  Cout % 8 == 0. */
+int32_t ctx_conv_small_f16(const float *x32, const void *x16, const void *w, const void *bias, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                           int32_t Cout, int32_t stride, int32_t silu, void *y, ctx_stream_t stream);
+/* ControlNet's residual injection: dst = (f16)(dst + scale * src) over n f16, fp32 arithmetic.  n % 8 == 0, n >= 8. */
+int32_t ctx_add_scaled_f16(void *dst, const void *src, float scale, int64_t n, ctx_stream_t stream);
+/* The VAE's 1x1 convolutions over a few channels: y f32 NCHW [B,C,HW] = w[o][c] x + b[o], w f16 [C][C], b f16 [C], fp32 sum (bias
+   first).  nhwc16 0: x f32 NCHW [B,C,HW], C <= 8 (post_quant_conv); 1: x f16 NHWC [B,HW,C], C <= 16 (quant_conv). */
+int32_t ctx_pointwise_f32(const void *x, const void *w, const void *b, int32_t B, int32_t C, int64_t HW, int32_t nhwc16, float *y,
+                          ctx_stream_t stream);
+/* The forward weight packs of ctx_unet_set_param / ctx_vae_set_param, src f32 -> dst f16 (round to nearest even).  kind
+   0 copy: a * max(b, 1) elements in order;
+   1 conv3: [a = Cout, b = Cin, 3, 3] -> [Cout][ky][kx][Cin];
+   2 conv_in: the same with the rows padded to 8 (Cin <= 8) or 16 channels, the padding exactly zero; 1 <= Cin <= 16;
+   3 GEGLU weight [2 a, b] (a = C4 value rows, then C4 gate rows; b = K) and 4 GEGLU bias [2 a]: packed row p takes source row
+     32 (p / 64) + p % 64 when p % 64 < 32 (a value row) and C4 + 32 (p / 64) + p % 64 - 32 otherwise (its gate row): blocks of 32
+     value rows and their 32 gate rows alternate.  C4 % 32 == 0. */
+int32_t ctx_pack_fwd_f16(const float *src, int32_t kind, int32_t a, int32_t b, void *dst, ctx_stream_t stream);
 /* GroupNorm(+SiLU) over NHWC f16; stats_ws: ctx_groupnorm_ws_bytes(B, groups). */
 int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const void *beta, int32_t B, int32_t HW,
