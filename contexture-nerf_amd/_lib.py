@@ -95,6 +95,8 @@ SIGNATURES = {
     "ctx_texture_head_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texture_head_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_weighted_sum_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "ctx_texel_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "ctx_bake_resolve": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),
     "ctx_unet_param_count": (_i32, [_vp]),

@@ -46,6 +46,11 @@ def merge_atlas(contrib, group=None, eps=1e-8, frac_bits=32):
     INTEGERS and converted once, so the result does not depend on how the views were dealt over ranks — the N-rank atlas is
     bit-identical to the 1-rank atlas.  A float32 contrib is summed as floats (order-dependent in the last bit)."""
     all_reduce_sum_(contrib, group)
+    return atlas_from_sums(contrib, eps, frac_bits)
+
+
+def atlas_from_sums(contrib, eps=1e-8, frac_bits=32):
+    """merge_atlas' conversion on its own, for sums every rank already holds in full (ConTEXTure.bake_field): no collective."""
     if contrib.dtype == torch.int64:
         # int64 -> double (round to nearest) -> exact power-of-two scale -> float32: the same three steps as ctx_fixed_to_float
         contrib = (contrib.to(torch.float64) * (2.0 ** -frac_bits)).to(torch.float32)

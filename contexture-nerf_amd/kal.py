@@ -231,6 +231,84 @@ def fixed_to_float(acc, frac_bits=SCATTER_FRAC_BITS, out=None):
     return out
 
 
+def _check_bake_list(who, idx, s):
+    L.ptr(idx, torch.int32, "idx")
+    if idx.dim() != 1:
+        raise L.CtxError(f"{who}: idx must be a 1-D int32 texel list, got shape {tuple(idx.shape)}")
+    if int(s) != s or not 1 <= s <= 4:
+        raise L.CtxError(f"{who}: supersample={s}: want a whole number in [1, 4]")
+    if idx.numel() * int(s) ** 2 >= 2 ** 31:
+        raise L.CtxError(f"{who}: {idx.numel()} entries x {int(s) ** 2} sub-samples: want fewer than 2^31 rows; split the list")
+    return idx.numel(), int(s)
+
+
+def texel_rays(texel_face, texel_bary, face_uv, vertices, faces, idx, supersample, shell):
+    """-> (rays_o [n*s*s,3] f32, rays_d [n*s*s,3] f32, valid [n*s*s] u8): per texel of the list idx int32 [n] and sub-sample k = a + s*b
+    (row j*s*s + k) a ray that starts `shell` outside the surface point of the sub-sample and runs down the face normal (bake.hip; the
+    rule is written out at ctx_texel_rays).  texel_face [T,T] i64 and texel_bary [T,T,3] f32: TexturedMeshModel.texel_map; face_uv
+    [F,3,2] f32 (vt[ft]); vertices [V,3] f32; faces [F,3] i64.  Rows of an entry that names no texel, no face or a face without area are
+    zero with valid = 0.  No host sync."""
+    lib = L.load()
+    p = (L.ptr(texel_face, torch.int64, "texel_face"), L.ptr(texel_bary, torch.float32, "texel_bary"), L.ptr(face_uv, torch.float32, "face_uv"),
+         L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces"))
+    n, s = _check_bake_list("texel_rays", idx, supersample)
+    if texel_face.dim() != 2 or texel_face.shape[0] != texel_face.shape[1] or faces.dim() != 2 or faces.shape[1] != 3 or vertices.dim() != 2 \
+            or vertices.shape[1] != 3:
+        raise L.CtxError(f"texel_rays: want texel_face [T,T], vertices [V,3], faces [F,3]; got {tuple(texel_face.shape)}, "
+                         f"{tuple(vertices.shape)}, {tuple(faces.shape)}")
+    T, F, V = texel_face.shape[0], faces.shape[0], vertices.shape[0]
+    for k, t, shp in (("texel_bary", texel_bary, (T, T, 3)), ("face_uv", face_uv, (F, 3, 2))):
+        if tuple(t.shape) != shp:
+            raise L.CtxError(f"texel_rays: {k} is {tuple(t.shape)}, expected {shp} (texel_face {tuple(texel_face.shape)}, faces {tuple(faces.shape)})")
+    shell = float(shell)
+    if not (shell > 0 and math.isfinite(shell)):
+        raise L.CtxError(f"texel_rays: shell={shell}: want a finite world length > 0")
+    dev = idx.device
+    ro, rd = torch.empty(n * s * s, 3, device=dev), torch.empty(n * s * s, 3, device=dev)
+    valid = torch.empty(n * s * s, dtype=torch.uint8, device=dev)
+    if n == 0:                                        # an empty list: empty outputs (a tensor without elements has no address to hand on)
+        return ro, rd, valid
+    L.check(lib.ctx_texel_rays(*p, L.ptr(idx), n, T, F, V, s, shell, L.ptr(ro), L.ptr(rd), L.ptr(valid), L.stream()))
+    return ro, rd, valid
+
+
+def bake_resolve(rgb, alpha, valid, idx, supersample, acc, min_alpha=0.5, frac_bits=SCATTER_FRAC_BITS):
+    """acc [4,T,T] int64 += per texel of the list idx int32 [n] (DISTINCT texels; not looked at here) the mean over its valid, finite
+    sub-samples of rgb [n*s*s,3] and alpha [n*s*s] in units of 2^-frac_bits, where that mean alpha >= min_alpha (bake.hip; the rule is
+    written out at ctx_bake_resolve).  rgb is premultiplied (sum w_i c_i), so acc[:3]/acc[3] is the colour and acc[3] > 0 the coverage."""
+    lib = L.load()
+    p = (L.ptr(rgb, torch.float32, "rgb"), L.ptr(alpha, torch.float32, "alpha"), L.ptr(valid, torch.uint8, "valid"))
+    p_acc = L.ptr(acc, torch.int64, "acc")
+    n, s = _check_bake_list("bake_resolve", idx, supersample)
+    if acc.dim() != 3 or acc.shape[0] != 4 or acc.shape[1] != acc.shape[2]:
+        raise L.CtxError(f"bake_resolve: acc is {tuple(acc.shape)}, expected [4,T,T]")
+    R = n * s * s
+    for k, t, shp in (("rgb", rgb, (R, 3)), ("alpha", alpha, (R,)), ("valid", valid, (R,))):
+        if tuple(t.shape) != shp:
+            raise L.CtxError(f"bake_resolve: {k} is {tuple(t.shape)}, expected {shp} ({n} entries x {s * s} sub-samples)")
+    if n == 0:
+        return acc
+    L.check(lib.ctx_bake_resolve(*p, L.ptr(idx), n, s, acc.shape[1], float(min_alpha), int(frac_bits), p_acc, L.stream()))
+    return acc
+
+
+def chart_texels(texel_face):
+    """-> idx int32 [n], ascending: the chart texels y*T + x of texel_face [T,T] i64 (texel_face >= 0), by the ordered compaction
+    ctx_texel_compact.  A set-up call: it reads n back, which SYNCS the host."""
+    lib = L.load()
+    L.ptr(texel_face, torch.int64, "texel_face")
+    n_tex = texel_face.numel()
+    n_ws = lib.ctx_texel_compact_ws_bytes(n_tex)
+    if n_ws < 0:
+        raise L.CtxError(f"chart_texels: {n_tex} texels: want 1 <= T*T < 2^31")
+    mask = (texel_face >= 0).to(torch.uint8).contiguous()
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=mask.device)
+    idx = torch.empty(n_tex, dtype=torch.int32, device=mask.device)
+    count = torch.empty(1, dtype=torch.int64, device=mask.device)
+    L.check(lib.ctx_texel_compact(L.ptr(mask), n_tex, L.ptr(idx), L.ptr(count), L.ptr(ws), L.stream()))
+    return idx[:int(count.item())].clone()
+
+
 def _fill_ws(lib, T, device):
     n = lib.ctx_atlas_fill_ws_bytes(T)
     if n < 0:

@@ -16,6 +16,7 @@ class Renderer:
         assert interpolation_mode in ['nearest', 'bilinear', 'bicubic'], f'no interpolation mode {interpolation_mode}'
         self.device = device
         self.interpolation_mode = interpolation_mode
+        self.fovyangle = float(fovyangle)
         self.camera_projection = kal.render.camera.generate_perspective_projection(fovyangle).to(device)
         self.dim = dim
         self.background = torch.ones(dim).to(device).float()

@@ -278,6 +278,43 @@ class ConTEXTure:
                                                                     self.mesh_model.chart_mask(), pad)
         return self.atlas_filled, self.atlas_fill_src
 
+    def train_view_cameras(self, H=None, W=None):
+        """-> (K [3,3], c2ws [V,3,4]): the train views as volume_render.view_camera gives them, for get_rays / fit_views / render_image:
+        the same _offset_phi, radius and dy mesh_model.render uses for them, so ray (j, i) of view v passes through the centre of pixel
+        (j, i) of that view's raster.  H, W default to render.train_grid_size."""
+        from . import volume_render as VR
+        G = int(self.cfg.render.train_grid_size)
+        H, W = int(G if H is None else H), int(G if W is None else W)
+        return VR.view_cameras([float(v['theta']) for v in self.train_views], [self._offset_phi(v['phi']) for v in self.train_views],
+                               [float(v['radius']) for v in self.train_views], self.mesh_model.dy, H, W,
+                               fovyangle=self.mesh_model.renderer.fovyangle)
+
+    def bake_field(self, field, occupancy=None, step=None, shell=None, supersample=2, min_alpha=0.5, G=128, dilate=1):
+        """Bakes a 3-D field trained on views of this mesh (volume_render.fit_views) into the mesh's UV atlas (volume_render.bake_atlas
+        with mesh_model.texel_map()) -> (atlas [3,T,T], coverage [T,T]).  Sets self.atlas_acc, self.atlas and self.atlas_coverage as the
+        merge of a paint does (dist.merge_atlas' conversion, without the collective: every rank bakes the same thing), drops an earlier
+        fill, and runs complete_atlas() when guide.atlas_fill == 'nearest'; eval renders and export() then show the baked colours.
+        occupancy=None: OccupancyGrid.from_mesh(G, dilate) of the mesh over its bounding box padded by 0.1 of its largest extent.
+        step, shell, supersample, min_alpha: bake_atlas.  The limit stated there holds: rays start `shell` outside the surface, and a
+        second wall of the mesh within `shell` of a texel composites first."""
+        from . import volume_render as VR
+        from .config import validate
+        mm = self.mesh_model
+        verts, faces = mm.mesh.vertices.detach().to(torch.float32).contiguous(), mm.mesh.faces.to(torch.int64).contiguous()
+        if occupancy is None:
+            lo, hi = verts.min(0).values.cpu().numpy(), verts.max(0).values.cpu().numpy()
+            pad = 0.1 * float((hi - lo).max())
+            occupancy = VR.OccupancyGrid.from_mesh(verts, faces, G, lo - pad, hi + pad, dilate=dilate)
+        texel_face, texel_bary = mm.texel_map()
+        face_uv = mm.face_attributes[0].detach().to(torch.float32).contiguous()
+        self.atlas_acc = VR.bake_atlas(field, verts, faces, face_uv, texel_face, texel_bary, occupancy, step=step, shell=shell,
+                                       supersample=supersample, min_alpha=min_alpha)
+        self.atlas, self.atlas_coverage = D.atlas_from_sums(self.atlas_acc)
+        self.atlas_filled = self.atlas_fill_src = None
+        if validate(self.cfg).guide.atlas_fill == 'nearest':
+            self.complete_atlas()
+        return self.atlas, self.atlas_coverage
+
     @torch.no_grad()
     def view_consistency(self, images=None, view_ids=None, rows='image'):
         """How well the train views agree where they show the same surface (trainer.py:429-531, kal.view_consistency): the

@@ -28,6 +28,38 @@ def pinhole(H, W, fovy=np.pi / 3):
     return np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], np.float32)
 
 
+def view_cameras(elev, azim, radius, look_at_height, H, W, fovyangle=np.pi / 3):
+    """view_camera for V poses at once: elev, azim, radius are numbers, sequences or tensors of V entries -> (K [3,3], c2ws [V,3,4])."""
+    from . import kal
+    e, a, r = (torch.as_tensor(x, dtype=torch.float32).detach().cpu().reshape(-1) for x in (elev, azim, radius))
+    V = max(e.numel(), a.numel(), r.numel())
+    e, a, r = (x.expand(V) if x.numel() == 1 else x for x in (e, a, r))
+    if not (e.numel() == a.numel() == r.numel() == V and V >= 1):
+        raise L.CtxError(f"view_cameras: elev, azim and radius hold {e.numel()}, {a.numel()} and {r.numel()} poses")
+    pos = torch.stack([r * torch.sin(e) * torch.sin(a), r * torch.cos(e), r * torch.sin(e) * torch.cos(a)], dim=1)   # Renderer.get_camera_from_view
+    look_at = torch.zeros_like(pos)
+    look_at[:, 1] = float(look_at_height)
+    up = torch.tensor([0.0, 1.0, 0.0]).expand(V, 3)
+    M = kal.generate_transformation_matrix(pos, look_at, up)                # [V,4,3] = [rot ; -pos @ rot]: world -> camera, row vectors
+    c2ws = torch.cat([M[:, :3, :], pos[:, :, None]], dim=2).to(torch.float32).contiguous()
+    t = np.tan(fovyangle / 2.0)
+    K = np.array([[W / (2 * t), 0, (W - 1) / 2], [0, H / (2 * t), (H - 1) / 2], [0, 0, 1]], np.float32)
+    return K, c2ws
+
+
+def view_camera(elev, azim, radius, look_at_height, H, W, fovyangle=np.pi / 3):
+    """The camera of a Renderer pose, as get_rays takes it: -> (K float32 [3,3], c2w float32 [3,4]).  elev, azim, radius and look_at_height
+    as Renderer.get_camera_from_view takes them.  kal.generate_transformation_matrix(pos, look_at, up) is [rot ; -pos @ rot], so
+    c2w = [rot | pos]: the camera looks down -z, as get_rays assumes.  fx = W / (2 tan(fov/2)), fy = H / (2 tan(fov/2)) (the renderer's
+    projection has ratio = 1, so x and y both span tan(fov/2)), cx = (W - 1)/2, cy = (H - 1)/2: get_rays' ((i - cx)/fx, -(j - cy)/fy, -1)
+    then passes through the centre of raster pixel (j, i), x = (2i + 1 - W)/W, y = (H - 2j - 1)/H.  `pinhole` has its
+    principal point half a pixel further, at the corner between the four middle pixels."""
+    K, c2ws = view_cameras(elev, azim, radius, look_at_height, H, W, fovyangle)
+    if c2ws.shape[0] != 1:
+        raise L.CtxError(f"view_camera: one pose expected, got {c2ws.shape[0]}; use view_cameras")
+    return K, c2ws[0]
+
+
 def shard_rows(H, rank, world):
     """Row range [r0, r1) of this rank: contiguous tiles, remainder rows to the first ranks."""
     base, rem = divmod(H, world)
@@ -426,3 +458,65 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
                           occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample)
         hist.append(step['loss'])
     return torch.stack(hist).tolist()
+
+
+def _checked_bake_texels(texels, T):
+    """A texel list handed to bake_atlas: int32 [n] device tensor of DISTINCT texels inside the atlas (looking costs a host sync)."""
+    L.ptr(texels, torch.int32, "texels")
+    if texels.dim() != 1:
+        raise L.CtxError(f"bake_atlas: texels must be a 1-D int32 list, got shape {tuple(texels.shape)}")
+    n = texels.numel()
+    if n > T * T:
+        raise L.CtxError(f"bake_atlas: texels holds {n} entries for a {T} x {T} atlas")
+    if n:
+        lo, hi = int(texels.min()), int(texels.max())
+        if lo < 0 or hi >= T * T:
+            raise L.CtxError(f"bake_atlas: texels span [{lo}, {hi}], outside the {T} x {T} atlas [0, {T * T})")
+        if int(torch.unique(texels).numel()) != n:
+            raise L.CtxError("bake_atlas: texels names a texel twice: the resolve adds without atomics, one writer per texel")
+    return texels
+
+
+@torch.no_grad()
+def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupancy, step=None, shell=None, supersample=1, min_alpha=0.5,
+               texels=None, rays_per_chunk=1 << 20, acc=None):
+    """Bakes a 3-D field into the mesh's UV atlas -> acc int64 [4,T,T] in units of 2^-32 (added to when given), what the painting side
+    accumulates: kal.fixed_to_float(acc)[:3] / [3] is the colour, [3] > 0 the coverage, so dist.merge_atlas' conversion, complete_atlas,
+    _painted_texture and export apply unchanged.
+    Every texel of the list marches a short ray down its face normal through the field, as NeRF-to-mesh exporters do: per chunk of at most
+    rays_per_chunk rays (whole texels only) kal.texel_rays places supersample^2 rays per texel `shell` outside the surface,
+    rnh.render_rays_marched composites them over [0, 2 shell] with samples `step` apart inside the occupied cells (no jitter, no white
+    background), and kal.bake_resolve folds the sub-samples whose mean alpha >= min_alpha into the sums.  Invalid rows (a face without
+    area) are marched like any other, find no sample and are dropped by the resolve: no compaction, one host sync per chunk (the march's).
+    field: anything render_rays_marched takes (forward_pts).  vertices [V,3] f32 and faces [F,3] i64 in the world frame of the field,
+    face_uv [F,3,2] f32 (vt[ft]), (texel_face, texel_bary) = TexturedMeshModel.texel_map().  occupancy: an OccupancyGrid, typically
+    OccupancyGrid.from_mesh(dilate=1) of the same mesh.  shell=None: 1.5 x the grid's largest cell edge, what such a grid holds on either
+    side of the surface; step=None: shell / 8, sixteen samples per ray.  texels=None: the chart texels (kal.chart_texels: one more sync);
+    a given list must hold distinct texels (checked: a sync).
+    A known limit: the rays start `shell` outside the surface, so where another wall of the mesh lies within `shell` of a texel (thin
+    fins, tight concavities) that wall composites first.  The answer is a smaller shell with a finer grid; there is no visibility test."""
+    from . import kal
+    if occupancy is None:
+        raise L.CtxError("bake_atlas: needs an occupancy grid (occupancy=): the samples lie in its occupied cells")
+    if not isinstance(texel_face, torch.Tensor) or texel_face.dim() != 2 or texel_face.shape[0] != texel_face.shape[1]:
+        raise L.CtxError(f"bake_atlas: want texel_face [T,T], got {tuple(getattr(texel_face, 'shape', ()))}")
+    T = texel_face.shape[0]
+    s = int(supersample)
+    if s != supersample or not 1 <= s <= 4:
+        raise L.CtxError(f"bake_atlas: supersample={supersample}: want a whole number in [1, 4]")
+    shell = 1.5 * float(np.max(occupancy.h)) if shell is None else float(shell)
+    if not (shell > 0 and np.isfinite(shell)):
+        raise L.CtxError(f"bake_atlas: shell={shell}: want a finite world length > 0")
+    step = shell / 8.0 if step is None else float(step)
+    if acc is None:
+        acc = torch.zeros(4, T, T, dtype=torch.int64, device=texel_face.device)
+    elif tuple(acc.shape) != (4, T, T) or acc.dtype != torch.int64:
+        raise L.CtxError(f"bake_atlas: acc is {acc.dtype} {tuple(acc.shape)}, expected int64 {(4, T, T)}")
+    texels = kal.chart_texels(texel_face) if texels is None else _checked_bake_texels(texels, T)
+    per = max(1, int(rays_per_chunk) // (s * s))
+    for j0 in range(0, texels.numel(), per):
+        part = texels[j0:j0 + per].contiguous()
+        ro, rd, valid = kal.texel_rays(texel_face, texel_bary, face_uv, vertices, faces, part, s, shell)
+        rgb, _, alpha, _, _ = rnh.render_rays_marched(field, ro, rd, 0., 2.0 * shell, occupancy, step)
+        kal.bake_resolve(rgb, alpha, valid, part, s, acc, min_alpha=min_alpha)
+    return acc

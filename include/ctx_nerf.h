@@ -489,6 +489,40 @@ int32_t ctx_texture_head_bwd(const float *grad_tex, const float *g_raw_in /*null
 int32_t ctx_weighted_sum_packed(const float *weights, const float *values, const int64_t *ray_off, int64_t R, int64_t n, int32_t C,
                                 float *out, ctx_stream_t stream);
 
+/* ---- baking the 3-D field into the UV atlas (bake.hip) ---- */
+/* ctx_texel_rays: texels to rays.  texel_face [T,T] i64 and texel_bary [T,T,3] f32 as ctx_uv_gather_fixed takes them, face_uv [F,3,2] f32
+   (vt[ft]), vertices [V,3] f32, faces [F,3] i64, idx int32 [n] a texel list, supersample 1 <= s <= 4, shell h a finite world length > 0.
+   -> rays_o [n*s*s,3], rays_d [n*s*s,3], valid u8 [n*s*s]; EVERY element is written.  Row j*s*s + k with k = a + s*b is list entry j,
+   column offset a, row offset b.  Per entry, in binary32 in the order written, no contraction:
+     p = idx[j] outside [0, T*T), f = texel_face[p] outside [0, F) or a vertex id of faces[f] outside [0, V): the s*s rows get valid = 0
+       and zeros;
+     e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2 (each component two products and one difference: cx = e1y*e2z - e1z*e2y, ...),
+       l2 = (cx*cx + cy*cy) + cz*cz; l2 not finite or not > 0: invalid as above; n = c / sqrtf(l2) (IEEE sqrt and division): the face
+       normal of ctx_prepare_vertices' orientation;
+     s == 1: (b0, b1, b2) = texel_bary[p] as stored;
+     s > 1:  dx = ((float)a + 0.5f)/(float)s - 0.5f, dy likewise from b (texel units along +column and +row);
+       x1 = (u1 - u0)*(float)T, x2 = (u2 - u0)*(float)T, y1 = (v0 - v1)*(float)T, y2 = (v0 - v2)*(float)T   (row = (1 - v)*T - 1/2);
+       D = x1*y2 - x2*y1;  g1x = y2/D, g1y = -x2/D, g2x = -y1/D, g2y = x1/D;
+       b1' = b1 + (dx*g1x + dy*g1y), b2' = b2 + (dx*g2x + dy*g2y), b0' = (1.0f - b1') - b2';
+       D not finite or zero: every sub-sample takes the stored (b0, b1, b2).  A sub-sample outside the triangle keeps its extrapolated
+       barycentrics (the point stays on the face's plane);
+     per axis x = (b0*v0 + b1*v1) + b2*v2, o = x + h*n, d = -n, valid = 1.
+   One thread per row, whole-vector stores through LDS, one writer per element, no atomics.  0 <= n, n*s*s < 2^31, 1 <= T <= 46340;
+   rays_o and rays_d 16-byte, valid 4-byte, face_uv 8-byte aligned.  n = 0 launches nothing.  A refused call leaves the outputs untouched.
+   ctx_bake_resolve: composited sub-samples to atlas sums.  rgb [n*s*s,3] (sum w_i c_i of ctx_raymarch_packed_fwd without white
+   background), alpha [n*s*s] (its acc), valid u8 [n*s*s], idx and s as above, acc int64 [4,T,T] in units of 2^-frac_bits, ADDED to.
+   Per entry with p = idx[j] inside [0, T*T): over k ascending a sub-sample counts when valid != 0 and its alpha and three colours are
+   finite: Sc = Sc + rgb[k,c], Sa = Sa + alpha[k], m += 1 (from 0, left to right).  m == 0: nothing.  Mc = Sc/(float)m, Ma = Sa/(float)m;
+   unless Ma >= min_alpha: nothing.  acc[c,p] += rint(Mc * 2^frac_bits), acc[3,p] += rint(Ma * 2^frac_bits): the conversion of
+   ctx_uv_scatter_fixed (__float2ll_rn(ldexpf(., frac_bits)); |M| * 2^frac_bits < 2^63), so ctx_fixed_to_float gives acc[:3]/acc[3] the
+   un-premultiplied colour and acc[3] > 0 the coverage.  The list must hold DISTINCT texels: one thread per entry does a plain
+   read-modify-write, no atomics.  -64 <= frac_bits <= 62. */
+int32_t ctx_texel_rays(const int64_t *texel_face, const float *texel_bary, const float *face_uv, const float *vertices, const int64_t *faces,
+                       const int32_t *idx, int64_t n, int32_t T, int32_t F, int32_t V, int32_t s, float h, float *rays_o, float *rays_d,
+                       uint8_t *valid, ctx_stream_t stream);
+int32_t ctx_bake_resolve(const float *rgb, const float *alpha, const uint8_t *valid, const int32_t *idx, int64_t n, int32_t s, int32_t T,
+                         float min_alpha, int32_t frac_bits, int64_t *acc, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
