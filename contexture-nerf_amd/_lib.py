@@ -94,6 +94,8 @@ SIGNATURES = {
     "ctx_hashtex_bwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ctx_texture_head_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texture_head_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "ctx_adam_multi": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "ctx_table_adam": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
     "ctx_weighted_sum_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texel_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "ctx_bake_resolve": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),

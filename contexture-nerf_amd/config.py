@@ -96,6 +96,9 @@ class OptimConfig:
                                      # (kal.active_texels; the rendered images keep their bits, src/models/textured_mesh.py:303-347)
     hashgrid_lr: float = 1e-2        # guide.texture_field = 'hashgrid': Adam's rate for the hash table and for its MLP in the SDS loop
     hashgrid_mlp_lr: float = 1e-3    # (instant-ngp's rates, not tuned here)
+    fused_adam: bool = False         # true: the SDS loop steps with optim.FieldAdam (HIP; same groups, betas and eps); a hashgrid texture
+                                     # field's table then takes its step from the backward's integer sums and leaves entries with a zero
+                                     # gradient alone, and the record's grad_norm covers the MLP only.  false: torch.optim.Adam, every bit as before
 
 
 @dataclass

@@ -170,9 +170,7 @@ extern "C" int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_
     const int64_t count = ((int64_t)Lv << log2T) * F;
     unsigned long long *acc = (unsigned long long *)ws;
     HgCtl *ctl = (HgCtl *)((char *)ws + hg_align(count * 8));
-    int c8n = 3;                                   // ceil(log2(8 n)): an entry receives at most 8 n terms, each at most 2^E
-    while (((int64_t)1 << (c8n - 3)) < n) ++c8n;
-    const int E = 62 - c8n;
+    const int E = hg_acc_exponent(n, 8);
     hipStream_t s = (hipStream_t)stream;
     if (stages & 1) {
         (void)hipMemsetAsync(acc, 0, count * 8, s);

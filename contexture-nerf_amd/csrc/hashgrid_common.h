@@ -58,3 +58,13 @@ static __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_convert(const long
 
 static inline int64_t hg_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
+// E = 62 - ceil(log2(corners * n)), corners 8 (3-D) or 4 (2-D): an entry receives at most corners * n terms, each at most 2^E.  The
+// accumulate, the convert and the table optimizer (adam.hip) must agree on it, so all three take it from here.
+static inline int hg_acc_exponent(int64_t n, int corners)
+{
+    const int lc = corners == 8 ? 3 : 2;
+    int c = lc;
+    while (((int64_t)1 << (c - lc)) < n) ++c;
+    return 62 - c;
+}
+

@@ -248,9 +248,7 @@ extern "C" int32_t ctx_hashtex_bwd(const float *uv, const int32_t *idx, int64_t 
     const int64_t count = ((int64_t)Lv << log2T) * F;
     unsigned long long *acc = (unsigned long long *)ws;
     HgCtl *ctl = (HgCtl *)((char *)ws + hg_align(count * 8));
-    int c4n = 2;                                   // ceil(log2(4 n)): an entry receives at most 4 n terms, each at most 2^E
-    while (((int64_t)1 << (c4n - 2)) < n) ++c4n;
-    const int E = 62 - c4n;
+    const int E = hg_acc_exponent(n, 4);
     const int presum = ctx_env_int("CTX_HASHTEX_PRESUM", 1) != 0;   // read per call: a tool times both forms in one process
     hipStream_t s = (hipStream_t)stream;
     if (stages & 1) {

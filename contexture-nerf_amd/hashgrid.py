@@ -9,7 +9,9 @@ grad_pts=True, and from HashGridField.density_gradient, which volume_render.rend
 first order only.
 HashGridEncoding2D / HashGridTexture are the same idea over the unit UV square for the product's texture field (csrc/hashtex.hip; the rule:
 tests/hashtex_rule.py): bilinear levels, the 2 x 64 MLP and the (tanh + 1) / 2 head behind NeRF2D.texture_map's contract,
-selected by guide.texture_field = 'hashgrid'."""
+selected by guide.texture_field = 'hashgrid'.
+Both encodings can leave the table's gradient as those integer sums for optim.FieldAdam to step from (_DeferredTable, DESIGN section 4n);
+nothing changes unless a FieldAdam lists the encoding."""
 import ctypes as C
 import math
 import numpy as np
@@ -30,6 +32,75 @@ def level_resolutions(n_levels, base_res, max_res):
     return np.array([int(math.floor(base_res * math.exp(l * b))) for l in range(n_levels)], np.int32)
 
 
+class _DeferredTable:
+    """What the two encodings share around the table's backward: the workspace of the integer accumulator, and the deferred mode that
+    optim.FieldAdam(encodings=...) switches on.  Deferred: the first backward since the last step / zero_grad only accumulates (stage 2,
+    behind stage 1 unless the workspace is known to be zero), remembers its rows and returns no gradient: FieldAdam.step reads the
+    sums (`ctx_table_adam`, which leaves the workspace zero).  A later backward before the step flushes the sums into a float gradient
+    (stage 4), runs as without deferral (stages 7) and returns the sum of the two; from then on to the step every backward does.
+    Outside deferred mode nothing here changes what the backward computes."""
+    _corners = 8
+
+    def _defer_init(self):
+        self._bwd_ws = None
+        self._defer, self._pending, self._ws_clean, self._float_mode = False, None, False, False
+
+    def _defer_begin(self):
+        self._defer, self._pending, self._ws_clean, self._float_mode = True, None, False, False
+
+    def _defer_end(self):
+        self._defer, self._pending, self._ws_clean, self._float_mode = False, None, False, False
+
+    def _defer_drop(self):
+        """zero_grad: pending sums are cleared."""
+        if self._pending is not None:
+            self._bwd_ws.zero_()
+            self._pending, self._ws_clean = None, True
+        self._float_mode = False
+
+    def _defer_consumed(self):
+        """`ctx_table_adam` has read the sums and left the workspace zero."""
+        self._pending, self._ws_clean, self._float_mode = None, True, False
+
+    def _defer_stepped(self):
+        self._float_mode = False
+
+    def _defer_flush(self):
+        """The pending sums as the float gradient stage 4 makes of them."""
+        g = torch.empty_like(self.table)
+        self._bwd_launch(self._pending, None, 4, g)
+        self._pending, self._ws_clean, self._float_mode = None, False, True
+        return g
+
+    def _workspace(self, device, zeroed):
+        wsb = self._bwd_ws_bytes()
+        if self._bwd_ws is None or self._bwd_ws.numel() < wsb or self._bwd_ws.device != device:
+            self._bwd_ws = None
+            # the int64 accumulator: scratch, stream-ordered
+            self._bwd_ws = (torch.zeros if zeroed else torch.empty)(wsb, dtype=torch.uint8, device=device)
+            self._ws_clean = zeroed
+        return self._bwd_ws
+
+    def _table_backward(self, rows, g_emb):
+        """rows: what names the rows of this backward, its last entry n -> g_table, or None when the sums stay on the device."""
+        device = g_emb.device
+        if not self._defer:
+            self._workspace(device, False)
+            g_table = torch.empty(self.table.shape, device=device)
+            self._bwd_launch(rows, g_emb, 7, g_table)
+            return g_table
+        self._workspace(device, True)
+        if self._pending is None and not self._float_mode:
+            self._bwd_launch(rows, g_emb, 2 if self._ws_clean else 3, None)
+            self._pending, self._ws_clean = rows, False
+            return None
+        g1 = self._defer_flush() if self._pending is not None else None
+        self._float_mode = True
+        g_table = torch.empty(self.table.shape, device=device)
+        self._bwd_launch(rows, g_emb, 7, g_table)
+        return g_table if g1 is None else g_table + g1
+
+
 class _HashGridFn(torch.autograd.Function):
     """emb [n, Lv*F] = encoding(pts [n,3]; table); the gradient goes to the table and, for an encoding with grad_pts=True and a pts that
     requires grad, to pts.  First order only (once_differentiable): the positions' gradient is itself a function of pts and of the table,
@@ -47,22 +118,13 @@ class _HashGridFn(torch.autograd.Function):
     def backward(ctx, g_emb):
         enc = ctx.enc
         pts, table = ctx.saved_tensors
-        lib = L.load()
         g_emb = L.f32c(g_emb)
-        g_table = None
-        if ctx.needs_input_grad[2]:
-            wsb = lib.ctx_hashgrid_bwd_ws_bytes(enc.n_levels, enc.n_features, enc.log2_table)
-            if enc._bwd_ws is None or enc._bwd_ws.numel() < wsb or enc._bwd_ws.device != table.device:
-                enc._bwd_ws = None
-                enc._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=table.device)   # the int64 accumulator: scratch, stream-ordered
-            g_table = torch.empty_like(table)
-            L.check(lib.ctx_hashgrid_bwd(L.ptr(pts), pts.shape[0], L.ptr(g_emb), *enc._grid_args(), 7, L.ptr(enc._bwd_ws), L.ptr(g_table),
-                                         L.stream()))
+        g_table = enc._table_backward((pts, pts.shape[0]), g_emb) if ctx.needs_input_grad[2] else None
         g_pts = enc._launch_bwd_pts(pts, table, g_emb) if ctx.needs_input_grad[1] else None
         return None, g_pts, g_table
 
 
-class HashGridEncoding(nn.Module):
+class HashGridEncoding(_DeferredTable, nn.Module):
     """pts [..., 3] inside the box lo .. hi -> features [..., n_levels * n_features]: at every level the trilinear interpolation of the 8
     table entries at the corners of the point's cell; a level whose (res + 1)^3 nodes fit the table indexes it directly, a finer one by
     instant-ngp's spatial hash.  Points outside the box take the values on its surface; NaN coordinates read as lo.
@@ -98,7 +160,7 @@ class HashGridEncoding(nn.Module):
         self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
         self.out_dim = self.n_levels * self.n_features
         self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
-        self._bwd_ws = None
+        self._defer_init()
         self.grad_pts = bool(grad_pts)
         self._pts_ws = None
 
@@ -112,6 +174,16 @@ class HashGridEncoding(nn.Module):
         L.check(L.load().ctx_hashgrid_fwd(L.ptr(pts, torch.float32, "pts"), pts.shape[0], L.ptr(table, torch.float32, "table"),
                                           *self._grid_args(), L.ptr(emb), L.stream()))
         return emb
+
+    def _bwd_ws_bytes(self):
+        return L.load().ctx_hashgrid_bwd_ws_bytes(self.n_levels, self.n_features, self.log2_table)
+
+    def _bwd_launch(self, rows, g_emb, stages, g_table):
+        """`ctx_hashgrid_bwd` on rows = (pts, n); a stage that is not asked for does not touch its buffer, which only has to be live."""
+        pts, n = rows
+        live = self.table
+        L.check(L.load().ctx_hashgrid_bwd(L.ptr(pts), n, L.ptr(live if g_emb is None else g_emb), *self._grid_args(), stages,
+                                          L.ptr(self._bwd_ws), L.ptr(live if g_table is None else g_table), L.stream()))
 
     def _launch_bwd_pts(self, pts, table, g_emb):
         """g_pts [n,3] of pts [n,3] for g_emb [n, out_dim], all float32 contiguous on the table's device."""
@@ -215,20 +287,11 @@ class _HashTexFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_emb):
         enc = ctx.enc
-        lib = L.load()
-        table = enc.table
-        g_emb = L.f32c(g_emb)
-        wsb = lib.ctx_hashtex_bwd_ws_bytes(enc.n_levels, enc.n_features, enc.log2_table)
-        if enc._bwd_ws is None or enc._bwd_ws.numel() < wsb or enc._bwd_ws.device != g_emb.device:
-            enc._bwd_ws = None
-            enc._bwd_ws = torch.empty(wsb, dtype=torch.uint8, device=g_emb.device)   # the int64 accumulator: scratch, stream-ordered
-        g_table = torch.empty(table.shape, device=g_emb.device)
-        L.check(lib.ctx_hashtex_bwd(L.ptr(ctx.uv), L.ptr(ctx.idx), ctx.n, ctx.grid, L.ptr(g_emb, torch.float32, "g_emb"), *enc._grid_args(), 7,
-                                    L.ptr(enc._bwd_ws), L.ptr(g_table), L.stream()))
+        g_table = enc._table_backward((ctx.uv, ctx.idx, ctx.grid, ctx.n), L.f32c(g_emb))
         return None, None, None, None, None, g_table
 
 
-class HashGridEncoding2D(nn.Module):
+class HashGridEncoding2D(_DeferredTable, nn.Module):
     """uv [..., 2] in the unit square -> features [..., n_levels * n_features]: at every level the bilinear interpolation of the 4 table
     entries at the corners of the point's cell; a level whose (res + 1)^2 nodes fit the table indexes it directly, a finer one by
     instant-ngp's spatial hash.  Points outside the square take the values on its edge; NaN coordinates read as 0.
@@ -256,7 +319,7 @@ class HashGridEncoding2D(nn.Module):
         self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
         self.out_dim = self.n_levels * self.n_features
         self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
-        self._bwd_ws = None
+        self._defer_init()
 
     def _grid_args(self):
         """(Lv, F, log2T, res) as the ABI takes them; res is host memory."""
@@ -267,6 +330,19 @@ class HashGridEncoding2D(nn.Module):
         L.check(L.load().ctx_hashtex_fwd(L.ptr(uv), L.ptr(idx), n, grid, L.ptr(table, torch.float32, "table"), *self._grid_args(), L.ptr(emb),
                                          L.stream()))
         return emb
+
+    _corners = 4
+
+    def _bwd_ws_bytes(self):
+        return L.load().ctx_hashtex_bwd_ws_bytes(self.n_levels, self.n_features, self.log2_table)
+
+    def _bwd_launch(self, rows, g_emb, stages, g_table):
+        """`ctx_hashtex_bwd` on rows = (uv, idx, grid, n); a stage that is not asked for does not touch its buffer, which only has to be live."""
+        uv, idx, grid, n = rows
+        live = self.table
+        L.check(L.load().ctx_hashtex_bwd(L.ptr(uv), L.ptr(idx), n, grid, L.ptr(live if g_emb is None else g_emb, torch.float32, "g_emb"),
+                                         *self._grid_args(), stages, L.ptr(self._bwd_ws), L.ptr(live if g_table is None else g_table),
+                                         L.stream()))
 
     def _run(self, uv, idx, n, grid):
         L.ptr(self.table, torch.float32, "table")

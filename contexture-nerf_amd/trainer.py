@@ -493,7 +493,16 @@ class ConTEXTure:
             # the table and its MLP at their own rates (optim.hashgrid_lr, optim.hashgrid_mlp_lr)
             groups = [dict(params=list(self.texture_mlp.encoding.parameters()), lr=float(self.cfg.optim.hashgrid_lr)),
                       dict(params=list(self.texture_mlp.mlp.parameters()), lr=float(self.cfg.optim.hashgrid_mlp_lr))]
-            optimizer = torch.optim.Adam(groups, betas=(0.9, 0.99), eps=1e-15)
+            if self.cfg.optim.fused_adam:
+                # the HIP step; the table takes it from the backward's integer sums and leaves entries with a zero gradient alone
+                from .optim import FieldAdam
+                groups[0]['sparse'] = True
+                optimizer = FieldAdam(groups, betas=(0.9, 0.99), eps=1e-15, encodings=[self.texture_mlp.encoding])
+            else:
+                optimizer = torch.optim.Adam(groups, betas=(0.9, 0.99), eps=1e-15)
+        elif self.cfg.optim.fused_adam:
+            from .optim import FieldAdam
+            optimizer = FieldAdam(params, lr=1e-5, betas=(0.9, 0.99), eps=1e-15)
         else:
             optimizer = torch.optim.Adam(params, lr=1e-5, betas=(0.9, 0.99), eps=1e-15)
         train_sched = DDPMScheduler(prediction_type="v_prediction")
@@ -505,33 +514,37 @@ class ConTEXTure:
             from . import kal
             faces, n_vertices, vc_seen = self.mesh_model.mesh.faces.contiguous(), int(self.mesh_model.mesh.vertices.shape[0]), None
             vc_idx, vc_fvi = render_cache['face_idx'][1:].contiguous(), render_cache['face_vertices_image'][1:].contiguous()
-        for i in range(iterations):
-            t = dream.get_t(i)
-            optimizer.zero_grad()
-            out = self.mesh_model.render(render_cache=render_cache, background=gray)
-            six = out['image'][1:]
-            tiles = [F.interpolate(six[j:j + 1, :, b[0]:b[2], b[1]:b[3]], (tile, tile), mode='bilinear', align_corners=False)
-                     for j, b in enumerate(boxes)]
-            r = sds.sds_iteration(pipe, torch.cat(tiles, 0), cond_image, depth_grid, self.zero123plus_prompt_embeds, t,
-                                  train_sched.alphas_cumprod, train_sched.add_noise, guidance_scale=10.0, grad_scale=0.2,
-                                  ikl_running_avg=ikl)
-            ikl = r['ikl_running_avg']
-            if cw > 0:
-                # trainer.py:856-863 (`loss = sds_loss - 500 * consistency_reward`, switched off upstream): the seen-vertex map
-                # depends on the cached raster only, so it is built by the first iteration and handed back to the others
-                reward, vc = kal.view_consistency(six.contiguous(), faces, vc_idx, vc_fvi, seen=vc_seen, stats=True, n_vertices=n_vertices)
-                vc_seen = vc['seen']
-                (r['loss'] - cw * reward).backward()
-            else:
-                r['loss'].backward()
-            gn = torch.linalg.norm(torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None]))
-            optimizer.step()
-            rec = dict(i=i, t=int(t), loss=float(r['loss'].detach()), fisher=r['fisher'], ikl_running_avg=ikl, grad_norm=float(gn), index=r['index'])
-            if cw > 0:
-                rec['consistency'] = float(reward.detach())
-            log.append(rec)
-            if on_iteration is not None:
-                on_iteration(rec)
+        try:
+            for i in range(iterations):
+                t = dream.get_t(i)
+                optimizer.zero_grad()
+                out = self.mesh_model.render(render_cache=render_cache, background=gray)
+                six = out['image'][1:]
+                tiles = [F.interpolate(six[j:j + 1, :, b[0]:b[2], b[1]:b[3]], (tile, tile), mode='bilinear', align_corners=False)
+                         for j, b in enumerate(boxes)]
+                r = sds.sds_iteration(pipe, torch.cat(tiles, 0), cond_image, depth_grid, self.zero123plus_prompt_embeds, t,
+                                      train_sched.alphas_cumprod, train_sched.add_noise, guidance_scale=10.0, grad_scale=0.2,
+                                      ikl_running_avg=ikl)
+                ikl = r['ikl_running_avg']
+                if cw > 0:
+                    # trainer.py:856-863 (`loss = sds_loss - 500 * consistency_reward`, switched off upstream): the seen-vertex map
+                    # depends on the cached raster only, so it is built by the first iteration and handed back to the others
+                    reward, vc = kal.view_consistency(six.contiguous(), faces, vc_idx, vc_fvi, seen=vc_seen, stats=True, n_vertices=n_vertices)
+                    vc_seen = vc['seen']
+                    (r['loss'] - cw * reward).backward()
+                else:
+                    r['loss'].backward()
+                gn = torch.linalg.norm(torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None]))
+                optimizer.step()
+                rec = dict(i=i, t=int(t), loss=float(r['loss'].detach()), fisher=r['fisher'], ikl_running_avg=ikl, grad_norm=float(gn), index=r['index'])
+                if cw > 0:
+                    rec['consistency'] = float(reward.detach())
+                log.append(rec)
+                if on_iteration is not None:
+                    on_iteration(rec)
+        finally:
+            if self.cfg.optim.fused_adam:
+                optimizer.release()
         self.mesh_model.eval()
         return log
 

@@ -423,7 +423,7 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0):
+              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0, optimizer='torch', table_lr=None):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -438,7 +438,15 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     samples between its first and last occupied cell (render_rays).  march: a world-space step handed to every train_step: the
     samples are the ragged lists of occupancy.march, N_samples is unused, and the refresh schedule stays as it is (the grid may
     change between iterations and the march follows it).  distortion: the weight of the distortion loss, handed to every train_step.
-    resample: with march, the fine samples per hit ray of the resampled second pass, handed to every train_step."""
+    resample: with march, the fine samples per hit ray of the resampled second pass, handed to every train_step.
+    optimizer: 'torch' (torch.optim.Adam) or 'fused' (optim.FieldAdam: the step is HIP, the tables of the field's hash-grid encodings are
+    in a group of their own with sparse=True and take their step straight from the backward's integer sums; a field without a table
+    simply gets the HIP step).  table_lr: with either optimizer, the rate of that group of tables (None: lr).  The defaults build
+    torch.optim.Adam(field.parameters(), lr) as before."""
+    if optimizer not in ('torch', 'fused'):
+        raise L.CtxError(f"fit_views: optimizer={optimizer!r}: want 'torch' or 'fused'")
+    if table_lr is not None and not table_lr > 0:
+        raise L.CtxError(f"fit_views: table_lr={table_lr!r}: want a rate > 0, or None for lr")
     dev = next(field.parameters()).device
     images = images.to(device=dev, dtype=torch.float32)
     V, H, W, _ = images.shape
@@ -447,17 +455,43 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     rd = torch.stack([r[1] for r in rays]).reshape(-1, 3)
     target = images.reshape(-1, 3)
     gen = torch.Generator(device=dev).manual_seed(seed)
-    opt = torch.optim.Adam(field.parameters(), lr=lr)
+    opt = field_optimizer(field, lr, optimizer, table_lr)
     hist = []
-    for it in range(iters):
-        if occupancy is not None and occupancy_every != 0 and it >= occupancy_warmup and (it - occupancy_warmup) % occupancy_every == 0:
-            occupancy.update(field, occupancy_thresh, generator=gen)
-        idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
-        step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
-                          perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                          occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample)
-        hist.append(step['loss'])
+    try:
+        for it in range(iters):
+            if occupancy is not None and occupancy_every != 0 and it >= occupancy_warmup and (it - occupancy_warmup) % occupancy_every == 0:
+                occupancy.update(field, occupancy_thresh, generator=gen)
+            idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
+            step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
+                              perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
+                              occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample)
+            hist.append(step['loss'])
+    finally:
+        if optimizer == 'fused':
+            opt.release()
     return torch.stack(hist).tolist()
+
+
+def field_optimizer(field, lr, optimizer='torch', table_lr=None, deferred=True):
+    """fit_views' optimizer.  'torch' with table_lr=None: torch.optim.Adam(field.parameters(), lr), one group.  Otherwise the tables of the
+    field's hash-grid encodings form a first group at table_lr (None: lr), everything else a second at lr (a group that would be empty
+    is left out).  'fused': optim.FieldAdam with sparse=True on the group of tables and, with deferred=True, the encodings in deferred
+    mode: call release() on it when training ends."""
+    from .hashgrid import HashGridEncoding, HashGridEncoding2D
+    from .optim import FieldAdam
+    if optimizer == 'torch' and table_lr is None:
+        return torch.optim.Adam(field.parameters(), lr=lr)
+    encodings = [m for m in field.modules() if isinstance(m, (HashGridEncoding, HashGridEncoding2D))]
+    tables = [e.table for e in encodings]
+    rest = [p for p in field.parameters() if not any(p is t for t in tables)]
+    groups = []
+    if tables:
+        groups.append(dict(params=tables, lr=lr if table_lr is None else table_lr, **(dict(sparse=True) if optimizer == 'fused' else {})))
+    if rest:
+        groups.append(dict(params=rest, lr=lr))
+    if optimizer == 'torch':
+        return torch.optim.Adam(groups, lr=lr)
+    return FieldAdam(groups, lr=lr, encodings=encodings if deferred else ())
 
 
 def _checked_bake_texels(texels, T):

@@ -481,6 +481,30 @@ int32_t ctx_texture_head_fwd(const float *raw, const int32_t *idx /*nullable*/, 
 int32_t ctx_texture_head_bwd(const float *grad_tex, const float *g_raw_in /*nullable*/, const float *raw, const int32_t *idx /*nullable*/,
                              int64_t n, int64_t plane, int32_t C, float *grad_raw, ctx_stream_t stream);
 
+/* ---- the field optimizer: Adam in place (adam.hip; definition: tests/adam_rule.py) ---- */
+/* Per element, in binary32, every operation rounding once, in this order (b1, b2, o1 = 1 - b1, o2 = 1 - b2, c1 = lr / (1 - b1^t),
+   c2 = 1 / sqrt(1 - b2^t), eps: computed by the caller in float64 and rounded to float; t = 1, 2, ... counts the steps):
+     if sparse and g == 0.0f (either sign): p, m, v keep their bits
+     else m' = b1*m + o1*g;  v' = b2*v + (o2*g)*g;  d = sqrtf(v')*c2 + eps;  p' = p - (c1*m') / d
+   with the correctly rounded division and square root.  A NaN or infinite g is not zero and propagates.  No weight decay, no amsgrad.
+   ctx_adam_multi: one launch over n_tensors (1 .. 16) tensors that share the seven floats.  p, m, v, g: host arrays of n_tensors device
+   pointers, counts: host int64 [n_tensors], every count >= 1; they travel in the kernel's arguments, nothing is copied to the device.
+   Tensors are contiguous float32 and need 4-byte alignment only: a tensor whose four pointers sit at the same offset from a 16-byte
+   boundary moves in 16-byte accesses behind a scalar head and before a scalar tail, any other in 4-byte accesses.  p, m, v are updated
+   in place, g is read; the tensors must not overlap.  A null pointer, a count < 1 or n_tensors outside [1, 16] is refused before any
+   launch.  One writer per element, no atomics. */
+int32_t ctx_adam_multi(const void *const *p, const void *const *m, const void *const *v, const void *const *g, const int64_t *counts,
+                       int32_t n_tensors, float b1, float b2, float o1, float o2, float c1, float c2, float eps, int32_t sparse,
+                       ctx_stream_t stream);
+/* The step of a hash table straight from the integer accumulator that stage 2 of ctx_hashgrid_bwd (corners = 8) or ctx_hashtex_bwd
+   (corners = 4) left in ws: p, m, v float32 [count], 16-byte aligned, count the table's Lv * T * F elements; ws that call's workspace
+   (count int64 sums, then the control words), n that call's n, from which E is derived as there.  Per element g = NaN for a non-finite
+   g_emb, 0 for an all-zero one, else (float)((double)acc * 2^(x-E)): the bits of g_table from stage 4; then the rule above.  Every
+   accumulator word that was not 0 is set to 0 and the control words are cleared behind the kernel on the stream: the workspace is left
+   as stage 1 leaves it.  One writer per element, no atomics. */
+int32_t ctx_table_adam(float *p, float *m, float *v, int64_t count, void *ws, int64_t n, int32_t corners, float b1, float b2, float o1,
+                       float o2, float c1, float c2, float eps, int32_t sparse, ctx_stream_t stream);
+
 /* ---- per-ray weighted sum on the marched lists ---- */
 /* out[r, c] = sum_i weights[i] * values[i, c] over ray r's samples ray_off[r] .. ray_off[r+1]; weights [n], values [n,C], 1 <= C <= 4,
    out [R,C], every element written, zeros for a ray without samples.  One wavefront per ray: lane partials over the chunks in ascending
