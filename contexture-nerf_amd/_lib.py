@@ -107,6 +107,8 @@ SIGNATURES = {
     "ctx_unet_weight_bytes": (_i64, [_vp]),
     "ctx_unet_workspace_bytes": (_i64, [_vp, _i32, _i32, _i32, _i32]),
     "ctx_unet_bind": (_i32, [_vp, _vp, _vp, _i64]),
+    "ctx_unet_derived_bytes": (_i64, [_vp]),
+    "ctx_unet_bind_derived": (_i32, [_vp, _vp, _i64]),
     "ctx_unet_set_param": (_i32, [_vp, _i32, _vp, _vp]),
     "ctx_unet_forward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ctx_controlnet_create": (_vp, [_vp, _i32]),
@@ -131,6 +133,8 @@ SIGNATURES = {
     "ctx_vae_weight_bytes": (_i64, [_vp]),
     "ctx_vae_workspace_bytes": (_i64, [_vp, _i32, _i32, _i32]),
     "ctx_vae_bind": (_i32, [_vp, _vp, _vp, _i64]),
+    "ctx_vae_derived_bytes": (_i64, [_vp]),
+    "ctx_vae_bind_derived": (_i32, [_vp, _vp, _i64]),
     "ctx_vae_set_param": (_i32, [_vp, _i32, _vp, _vp]),
     "ctx_vae_decode": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ctx_vae_decoder_param_count": (_i32, [_vp]),
@@ -148,6 +152,8 @@ SIGNATURES = {
     "ctx_gemm_last_kernel": (None, [_vp, _vp]),
     "ctx_conv3x3_geom_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "ctx_pack_conv3_dgrad_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_pack_conv3_phase_f16": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "ctx_conv3x3_phase_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "ctx_pack_mat_dgrad_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ctx_groupnorm_bwd_ws_bytes": (_i64, [_i32, _i32]),
     "ctx_groupnorm_bwd_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),

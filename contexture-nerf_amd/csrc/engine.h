@@ -25,12 +25,19 @@ struct Param {
     // second pack for the VAE encoder's backward (input gradients): kind2 1 = conv3 [Cout,Cin,3,3] -> [Cin][2-ky][2-kx][pad2 >= Cout]
     // (the data-gradient of a 3x3 convolution is a 3x3 convolution with this matrix), 2 = [out,in] -> [in][ld2] at column col2
     int kind2 = 0; size_t dst2 = 0; int pad2 = 0, ld2 = 0, col2 = 0;
+    // pack derived from the parameter, in the derived blob (Engine::D): kind3 1 = the phase pack of an upsampler's conv3
+    // [Cout,Cin,3,3] -> [4][Cout][2][2][Cin] (GemmArgs::phase), 16 Cout Cin elements at dst3
+    int kind3 = 0; size_t dst3 = 0;
 };
 
 struct Engine {
     const char *tag = "";      // engine name in error messages
     std::vector<Param> params;
     size_t wtop = 0;           // elements
+    // The derived blob: packs that are functions of parameters but have no place in the weight blob, whose size is part of the ABI.
+    // Optional: an engine with none bound (D null) runs every layer from the weight blob alone.  dtop: elements.
+    size_t dtop = 0;
+    f16 *D = nullptr;
     // bound memory
     f16 *W = nullptr;
     char *ws = nullptr;
@@ -58,6 +65,21 @@ struct Engine {
         for (int i = 0; i < 4; ++i) p.shape[i] = i < p.ndim ? shp[i] : 1;
         params.push_back(p);
         return dst;
+    }
+    // the parameter added last is an upsampler's conv3 [Cout,Cin,3,3]: reserve its phase pack in the derived blob (where the form exists)
+    void derive_phase()
+    {
+        Param &p = params.back();
+        if (!ctx_conv3_phase_ok(p.b, p.a, 1, 1, 0, 0)) return;
+        p.kind3 = 1; p.dst3 = dtop; dtop += ((size_t)16 * p.a * p.b + 127) / 128 * 128;
+    }
+    // the phase pack of the conv3 weights at Wt, or null: none bound, or the layer has none
+    const f16 *phase_pack(const f16 *Wt) const
+    {
+        if (!D || !W) return nullptr;
+        for (const Param &p : params)
+            if (p.kind3 == 1 && W + p.dst == Wt) return D + p.dst3;
+        return nullptr;
     }
     size_t vec(const std::string &name, int n) { return add(name, {n}, PK_COPY, walloc(n)); }
     size_t lin(const std::string &name, int out, int in) { return add(name, {out, in}, PK_COPY, walloc((size_t)out * in)); }
@@ -130,5 +152,9 @@ int32_t engine_param_shape(const Engine *e, int32_t i, int64_t shape4[4]);
 int64_t engine_weight_bytes(const Engine *e);
 int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace_bytes, const char *who);
 int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t stream, const char *who);
+// bodies of ctx_<engine>_derived_bytes / _bind_derived: the derived blob's size (0: the engine derives nothing) and its binding (null unbinds).
+// Parameters set while it is bound fill it; bind it before loading weights, or share a filled one between engines over the same weights.
+int64_t engine_derived_bytes(const Engine *e);
+int32_t engine_bind_derived(Engine *e, void *derived, int64_t bytes, const char *who);
 // the forward pack of one parameter alone (kind: PackKind; a, b: its dims in the table; n source elements); no launch check of its own
 int engine_pack_fwd(int kind, const float *src, int64_t n, int a, int b, f16 *d, hipStream_t s, const char *who);

@@ -23,11 +23,26 @@ int32_t engine_bind(Engine *e, void *weights, void *workspace, int64_t workspace
     return CTX_OK;
 }
 
+int64_t engine_derived_bytes(const Engine *e) { return e && e->dtop ? (int64_t)e->dtop * 2 + 256 : 0; }
+int32_t engine_bind_derived(Engine *e, void *derived, int64_t bytes, const char *who)
+{
+    CTX_REQUIRE(e, "%s: bad args", who);
+    if (!derived) { e->D = nullptr; return CTX_OK; }
+    CTX_REQUIRE(e->dtop > 0, "%s: this engine derives nothing", who);
+    CTX_REQUIRE(bytes >= engine_derived_bytes(e) && ((uintptr_t)derived & 255) == 0, "%s: the derived blob needs %lld bytes, 256-byte aligned", who,
+                (long long)engine_derived_bytes(e));
+    e->D = (f16 *)derived;
+    return CTX_OK;
+}
+
 // one GEMM / implicit-GEMM conv of a fully described problem: plan, split-K scratch above the arena mark, dispatch, release
-static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs = nullptr, const GnReq *gn = nullptr, GnSlabs *slabs = nullptr)
+// phase: the phase pack of an upsampling convolution; the op is counted as the nine-tap convolution it stands for and runs the phase form
+static void engine_gemm(Engine &e, GemmArgs &a, bool conv, const ConvSegs *segs = nullptr, const GnReq *gn = nullptr, GnSlabs *slabs = nullptr,
+                        const f16 *phase = nullptr)
 {
     e.note(0, 2.0 * a.M * a.N * a.K);
     size_t mark = e.top;
+    if (phase) ctx_conv3_phase(a, phase);
     ctx_gemm_plan(a, conv);                               // a segmented convolution runs the plan of its 3x3 part's shape
     if (segs && segs->n) {
         int kseg = 0;
@@ -77,7 +92,13 @@ void engine_conv3(Engine &e, const f16 *x, const f16 *Wt, const f16 *bias, const
     a.X = x; a.Wt = Wt; a.bias = bias; a.rowbias = rowbias; a.residual = (const f16 *)res; a.out = (f16 *)out;
     a.ldrb = ldrb;
     a.res32 = res32; a.out32 = out32;
-    engine_gemm(e, a, true, segs, gn, slabs);
+    // An upsampler whose phase pack is bound runs the phase form (4 / 9 of the multiplies); it takes a bias only.  Which form runs is
+    // a function of the problem and of what is bound, never of a measurement.
+    const f16 *phase = nullptr;
+    if (g.ups && ctx_conv3_phase_ok(Cin, Cout, g.stride, g.ups, g.poff, g.zins) && !res && !rowbias && !segs && !gn && !slabs && !res32 && !out32 &&
+        !ctx_conv3_phase_loses(a.M, Cout, Cin))
+        phase = e.phase_pack(Wt);
+    engine_gemm(e, a, true, segs, gn, slabs, phase);
 }
 
 int engine_finish(Engine *e, const char *who)
@@ -100,6 +121,29 @@ __global__ void k_pack_conv3(const float *__restrict__ s, int Cout, int Cin, int
         int tap = (int)((i / Cinp) % 9);
         int o = (int)(i / ((int64_t)Cinp * 9));
         d[i] = c < Cin ? (f16)s[((int64_t)o * Cin + c) * 9 + tap] : (f16)0.f;
+    }
+}
+// the phase pack of an upsampler's conv3 (GemmArgs::phase): [Cout,Cin,3,3] -> [4 phases (a, b)][Cout][2 u][2 v][Cin], where tap (u, v)
+// of phase (a, b) is the sum of the source taps ky in R(a, u), kx in R(b, v), R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}:
+// fp32, added left to right with ky ascending, then kx ascending, rounded once
+__global__ void k_pack_conv3_phase(const float *__restrict__ s, int Cout, int Cin, f16 *__restrict__ d)
+{
+    const int64_t per = (int64_t)Cout * 4 * Cin, n = 4 * per;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % Cin), t = (int)((i / Cin) % 4), o = (int)((i / ((int64_t)Cin * 4)) % Cout), ph = (int)(i / per);
+        const int pa = ph >> 1, pb = ph & 1, u = t >> 1, v = t & 1;
+        const int ky0 = pa == 0 ? (u ? 1 : 0) : (u ? 2 : 0), ky1 = pa == 0 ? (u ? 2 : 0) : (u ? 2 : 1);
+        const int kx0 = pb == 0 ? (v ? 1 : 0) : (v ? 2 : 0), kx1 = pb == 0 ? (v ? 2 : 0) : (v ? 2 : 1);
+        const float *w = s + ((int64_t)o * Cin + c) * 9;
+        float acc = 0.f;
+        bool first = true;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                const float x = w[ky * 3 + kx];
+                acc = first ? x : acc + x;
+                first = false;
+            }
+        d[i] = (f16)acc;
     }
 }
 // GEGLU rows: packed row p (of 2*C4) <- source row  (w<32 ? blk*32+w : C4 + blk*32 + w-32), blk=p/64, w=p%64
@@ -180,6 +224,7 @@ int32_t engine_set_param(Engine *e, int32_t i, const float *src, ctx_stream_t st
     if (rc != CTX_OK) return rc;
     if (p.kind2 == 1) hipLaunchKernelGGL(k_pack_conv3_T, dim3(nb), dim3(256), 0, s, src, p.a, p.b, p.pad2, e->W + p.dst2);
     else if (p.kind2 == 2) hipLaunchKernelGGL(k_pack_mat_T, dim3(nb), dim3(256), 0, s, src, (int)p.shape[0], (int)p.shape[1], p.ld2, p.col2, e->W + p.dst2);
+    if (p.kind3 == 1 && e->D) hipLaunchKernelGGL(k_pack_conv3_phase, dim3(pack_blocks(16 * n / 9)), dim3(256), 0, s, src, p.a, p.b, e->D + p.dst3);
     CTX_CHECK_LAUNCH(who);
     return CTX_OK;
 }
@@ -193,6 +238,15 @@ extern "C" int32_t ctx_pack_fwd_f16(const float *src, int32_t kind, int32_t a, i
     const int rc = engine_pack_fwd(kind, src, n, a, b, (f16 *)dst, (hipStream_t)stream, "pack_fwd");
     if (rc != CTX_OK) return rc;
     CTX_CHECK_LAUNCH("pack_fwd");
+    return CTX_OK;
+}
+// the phase pack alone (k_pack_conv3_phase), with engine_set_param's launch geometry; dst holds 16 Cout Cin f16
+extern "C" int32_t ctx_pack_conv3_phase_f16(const float *src, int32_t Cout, int32_t Cin, void *dst, ctx_stream_t stream)
+{
+    CTX_REQUIRE(src && dst, "pack_conv3_phase: null pointer");
+    CTX_REQUIRE(Cout > 0 && Cin > 0 && (int64_t)16 * Cout * Cin < (1ll << 31), "pack_conv3_phase: need Cout, Cin > 0 and 16 Cout Cin < 2^31 (Cout=%d Cin=%d)", Cout, Cin);
+    hipLaunchKernelGGL(k_pack_conv3_phase, dim3(pack_blocks((int64_t)16 * Cout * Cin)), dim3(256), 0, (hipStream_t)stream, src, Cout, Cin, (f16 *)dst);
+    CTX_CHECK_LAUNCH("pack_conv3_phase");
     return CTX_OK;
 }
 extern "C" int32_t ctx_pack_conv3_dgrad_f16(const float *src, int32_t Cout, int32_t Cin, int32_t pad, void *dst, ctx_stream_t stream)

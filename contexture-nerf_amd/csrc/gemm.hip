@@ -17,13 +17,15 @@
 #include "gemm_common.h"
 
 // Direct epilogue (GEGLU, or when strides are not 16-byte friendly): lane owns row m, registers walk n.
-template <int MI, int NI>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[MI][NI], int mw, int nw, int r, int h)
+// PH (both epilogues): the phase form; rows are masked against the phase's row count and stored through conv_phase_row
+template <int MI, int NI, bool PH = false>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[MI][NI], int mw, int nw, int r, int h, const ConvPhase &ph)
 {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
         int m = mw + mi * 32 + r;
-        if (m >= a.M) continue;
+        if (m >= ph.M) continue;
+        const int mo = PH ? conv_phase_row(a, ph, m) : m;
         int bidx = a.rowbias ? m / a.rows_per_batch : 0;
         if (a.epi == 1) {
             if constexpr (NI == 2) {
@@ -51,7 +53,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[M
                     int nn = nw + ni * 32 + 8 * g + 4 * h;
                     if (nn >= a.N) continue;
                     f32x4 v = acc4(acc[mi][ni], g);
-                    store4<true>(a, bias4(a, v, nn), m, bidx, nn);
+                    store4<true>(a, bias4(a, v, nn), mo, bidx, nn);
                 }
         }
     }
@@ -62,9 +64,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x16 (&acc)[M
 // instead parks 32 rows x (32 NI) features of fp32 in its own LDS patch (row stride 32 NI + 4 floats: conflict-free
 // ds_write_b128) and walks it back in whole rows: bias / row bias / residual / output all move as 64- or 128-byte
 // row segments, 16 bytes per lane, and the sum is still rounded to fp16 exactly once.
-template <int MI, int NI>
+template <int MI, int NI, bool PH = false>
 __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (&acc)[MI][NI], int mw, int nw, int r, int h,
-                                                     float *stage, int lane)
+                                                     float *stage, int lane, const ConvPhase &ph)
 {
     constexpr int RS = 32 * NI + 4;                    // patch row stride (floats)
     constexpr int LPR = 4 * NI;                        // lanes per row (8 features each)
@@ -85,11 +87,11 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (
             const int row = RPP * p + prow;
             const int m = mw + mi * 32 + row;
             f32x4 v0 = *(const f32x4 *)(stage + row * RS + c8), v1 = *(const f32x4 *)(stage + row * RS + c8 + 4);
-            if (m < a.M && n < a.N) {
+            if (m < ph.M && n < a.N) {
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 add8(v, bs);
                 if (a.bias2) add8(v, *(const f16x8 *)(a.bias2 + n));
-                store8<true>(a, v, m, n);
+                store8<true>(a, v, PH ? conv_phase_row(a, ph, m) : m, n);
             }
         }
     }
@@ -104,7 +106,9 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs &a, f32x16 (
 //                  8 x MFMA on stage kt
 // 64-byte LDS rows ([rows][32 f16]), chunk swizzle c ^ ((row>>2)&3) applied on the DMA source address and on the
 // fragment read (conflict-free ds_read_b128 under the 64-bank / 16-lane-group rule).
-template <int WM, int WN, int MI, int NI, bool CONV, int NS, int PKT>
+// PH: the upsample's phase form (GemmArgs::phase): 4 taps with the shifts of the tile's phase, that phase's weight matrix, and the row
+// remap in the epilogues; the other instantiations compile to what they were
+template <int WM, int WN, int MI, int NI, bool CONV, int NS, int PKT, bool PH = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
 {
     constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN, NW = WM * WN;
@@ -123,7 +127,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     // an XCD then streams ~1/8 of the K range of both operands.  Inside a slice the tile order walks the operand that is
     // re-read most (mfast: consecutive blocks share the weight panel; else the activation panel).
     const GemmTile t = gemm_tile(a, blockIdx.x, PKT, BM, BN);
-    const int slice = t.slice, tile_m = t.tile_m, tile_n = t.tile_n, m0 = t.m0, n0 = t.n0, kbeg = t.kbeg, nk = t.nk;
+    static_assert(!PH || CONV, "the phase form is a convolution");
+    const ConvPhase ph = PH ? conv_phase_tile(a, t.tile_m, BM) : ConvPhase{0, 0, 0, t.m0, a.M};
+    const int slice = t.slice, tile_m = t.tile_m, tile_n = t.tile_n, m0 = ph.m0, n0 = t.n0, kbeg = t.kbeg, nk = t.nk;
+    const int ldw = CONV ? (PH ? 4 : 9) * a.Cin : a.K;             // weight row stride
+    const f16 *const Wt = PH ? a.Wt + (size_t)ph.ph * a.N * ldw : a.Wt;
     const int lr = lane / LPR, pc = lane % LPR;        // row within the piece's 16 rows, physical 16-B chunk
 
     // ---- issue-side state: one running source pointer per DMA piece (advanced by a fixed step per stage; rows that
@@ -137,7 +145,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
         int row = RP * (wave + NW * i) + lr;
         int m = m0 + row;
         const int lc = (pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8;
-        xok[i] = m < a.M;
+        xok[i] = m < ph.M;
         if (CONV) {
             conv_pixel(a, m, lc, xoy[i], xox[i], xoff[i]);
             xp[i] = ctx_zero_page; xst[i] = 0;
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
     for (int i = 0; i < WI; ++i) {
         int row = RP * (wave + NW * i) + lr;
         bool ok = (n0 + row) < a.N;
-        wp[i] = ok ? a.Wt + (size_t)(n0 + row) * (CONV ? 9 * a.Cin : a.K) + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : ctx_zero_page;
+        wp[i] = ok ? Wt + (size_t)(n0 + row) * ldw + kbeg * PKT + ((pc ^ (PKT == 32 ? ((row >> 2) & 3) : ((row >> 1) & 7))) * 8) : ctx_zero_page;
         wst[i] = ok ? PKT : 0;
     }
     // K rotation: workgroups that stream the same weight rows (same tile_n) or the same activation rows (same tile_m)
@@ -172,7 +180,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
         const bool seg = a.nseg && k_issue >= 9 * a.Cin;
         const ConvSrc cs = conv_stage_src(a, k_issue);
         const int sg = cs.src - 9;
-        const ConvTap tap = conv_tap(a, seg ? 4 * a.Cin : k_issue);
+        const ConvTap tap = PH ? conv_phase_tap(a, ph, k_issue) : conv_tap(a, seg ? 4 * a.Cin : k_issue);
         unsigned lox = 0;
         if (seg) {
             // a piece's rows start at a multiple of RP and the wave count is even wherever a stage is 64 deep, so the lane's
@@ -305,22 +313,23 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_pipe(GemmArgs a)
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             int m = m0 + wm * 32 * MI + mi * 32 + r;
-            if (m >= a.M) continue;
+            if (m >= ph.M) continue;
+            const int mo = PH ? conv_phase_row(a, ph, m) : m;
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    store_part4(a, pb + (size_t)m * a.N, n0 + wn * 32 * NI + ni * 32 + 8 * g + 4 * h, acc4(acc[mi][ni], g));
+                    store_part4(a, pb + (size_t)mo * a.N, n0 + wn * 32 * NI + ni * 32 + 8 * g + 4 * h, acc4(acc[mi][ni], g));
         }
         return;
     }
     if (a.epi == 0 && a.stage_epi) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         ctx_barrier();                 // every wave is done reading the ring
-        gemm_epilogue_staged<MI, NI>(a, acc, m0 + wm * 32 * MI, n0 + wn * 32 * NI, r, h, (float *)smem + wave * (32 * (32 * NI + 4)), lane);
+        gemm_epilogue_staged<MI, NI, PH>(a, acc, m0 + wm * 32 * MI, n0 + wn * 32 * NI, r, h, (float *)smem + wave * (32 * (32 * NI + 4)), lane, ph);
         return;
     }
-    gemm_epilogue<MI, NI>(a, acc, m0 + wm * 32 * MI, n0 + wn * 32 * NI, r, h);
+    gemm_epilogue<MI, NI, PH>(a, acc, m0 + wm * 32 * MI, n0 + wn * 32 * NI, r, h, ph);
 }
 
 // Split-K second pass: out = sum_s part[s] (+bias)(+rowbias)(+residual) -> f16.  Fixed summation order.
@@ -403,11 +412,11 @@ extern "C" void ctx_gemm_tune(int32_t tile, int32_t gemm8)
     g_force_gemm8 = gemm8;          // -1: heuristic, 0: never, 1: always when applicable
 }
 
-template <int WM, int WN, int MI, int NI, bool CONV, int NS = 4, int PKT = 32>
+template <int WM, int WN, int MI, int NI, bool CONV, int NS = 4, int PKT = 32, bool PH = false>
 static void launch_gemm(GemmArgs &a, hipStream_t s)
 {
     constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
-    a.ntm = cdiv(a.M, BM);
+    a.ntm = PH ? 4 * cdiv(a.M / 4, BM) : cdiv(a.M, BM);              // phase form: whole tiles per phase
     a.ntn = cdiv(a.N, BN);
     if (a.splitk < 1 || !a.part) a.splitk = 1;
     static const int mfast = ctx_env_int("CTX_GEMM_MFAST", -1);
@@ -421,7 +430,7 @@ static void launch_gemm(GemmArgs &a, hipStream_t s)
     constexpr size_t ring = (size_t)NS * (BM + BN) * PKT * sizeof(f16);
     constexpr size_t patch = (size_t)WM * WN * 32 * (32 * NI + 4) * sizeof(float);
     constexpr size_t lds = (ring > patch || patch > 160 * 1024) ? ring : patch;
-    ctx_launch<k_gemm_pipe<WM, WN, MI, NI, CONV, NS, PKT>>(0, dim3(a.ntm * a.ntn * a.splitk), dim3(NT), lds, s, a);
+    ctx_launch<k_gemm_pipe<WM, WN, MI, NI, CONV, NS, PKT, PH>>(0, dim3(a.ntm * a.ntn * a.splitk), dim3(NT), lds, s, a);
 }
 
 static void launch_reduce(GemmArgs &a, hipStream_t s)
@@ -470,14 +479,21 @@ int ctx_gemm_pick_split(int M, int N, int K, int epi)
 }
 
 #include "gemm_tuned.h"
+#include "gemm_tuned_phase.h"
 void ctx_gemm_plan(GemmArgs &a, bool conv)
 {
     a.tile = -1; a.use8 = -1;
     static const int use_table = ctx_env_int("CTX_GEMM_TUNED", 1);
     if (use_table) {
-        const int flags = conv ? ((a.stride == 2 ? 1 : 0) | (a.ups ? 2 : 0)) : 0;
+        const int flags = conv ? ((a.stride == 2 ? 1 : 0) | (a.ups ? 2 : 0) | (a.phase ? 4 : 0)) : 0;
+        auto match = [&](const TunedGemm &t) { return t.conv == (conv ? 1 : 0) && t.M == a.M && t.N == a.N && t.K == a.K && t.flags == flags && t.epi == a.epi; };
         for (const TunedGemm &t : g_tuned)
-            if (t.conv == (conv ? 1 : 0) && t.M == a.M && t.N == a.N && t.K == a.K && t.flags == flags && t.epi == a.epi) {
+            if (match(t)) {
+                a.tile = t.tile; a.use8 = t.use8; a.splitk = t.splitk;
+                return;
+            }
+        for (const TunedGemm &t : g_tuned_phase)                    // the phase form's rows (flag bit 2) have a table of their own
+            if (match(t)) {
                 a.tile = t.tile; a.use8 = t.use8; a.splitk = t.splitk;
                 return;
             }
@@ -539,7 +555,24 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
     }
     const bool only_pipe = a.zins || a.res32 || a.out32;                     // features of this file's kernel only
     if (only_pipe) a.use8 = 0;
-    const int want8 = only_pipe ? 0 : (g_force_gemm8 >= 0 ? g_force_gemm8 : a.use8);          // -1: gemm8's own heuristic
+    int want8 = only_pipe ? 0 : (g_force_gemm8 >= 0 ? g_force_gemm8 : a.use8);                // -1: gemm8's own heuristic
+    if (a.phase) {
+        // The phase form of an upsampling convolution (GemmArgs::phase): bias only, and only the kernels that implement it (gemm144.hip
+        // and this file's tiles).  Any other kernel would read the four 2x2 matrices as one nine-tap matrix: a request for one is an error.
+        const bool ok = conv && a.Wt && a.ups == 1 && a.stride == 1 && !a.poff && !a.zins && a.epi == 0 && !a.res32 && !a.out32 && !a.rowbias &&
+                        !a.residual && !a.nseg && !a.bias2 && !a.gn_part && !a.keep_slabs && a.Cin % 64 == 0 && a.K == 4 * a.Cin && a.M % 4 == 0;
+        if (!ok) {
+            ctx_set_error("gemm: the phase form takes an upsampling convolution (stride 1, Cin %% 64 == 0) over its phase pack with a bias only");
+            return CTX_E_ARG;
+        }
+        const bool tile_first = g_force_tile >= 0 || (g_force_gemm8 < 0 && a.tile >= 0);      // (want_tile >= 0 below)
+        if (!tile_first && want8 >= 1 && want8 <= 3) {
+            ctx_set_error("gemm: kernel %d (gemm8.hip / conv_halo.hip) does not implement the phase form", want8);
+            return CTX_E_ARG;
+        }
+        if (want8 < 0) want8 = 0;                                            // gemm8.hip's own heuristic never sees the form
+        a.Ho = a.H; a.Wo = a.W; a.ups = 0; a.rows_per_batch = a.H * a.W;    // what the kernels walk: the source grid, stride 1
+    }
     const int want_tile = g_force_tile >= 0 ? g_force_tile : (g_force_gemm8 >= 0 ? -1 : a.tile);
     // the kernels of the other files first (each *_try launches and returns 1 when the problem suits it), else this file's tiles
     const bool launched = want_tile < 0 && ((want8 >= 4 && want8 <= 8 && ctx_gemm144_try(a, conv, want8 - 4, s)) ||
@@ -564,7 +597,7 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
         if (want_tile >= 0) pick = want_tile;
         if (a.epi == 1 && (pick == 5 || pick == 6 || pick == 9 || pick == 11 || pick == 13 || pick == 15 || pick == 17 || pick == 19 || pick == 21 || pick == 23 || pick == 26 || pick == 27)) pick = 1;   // GEGLU needs 64-wide wave tiles
         if (pick >= 10 && (a.K % 64 != 0 || (conv && a.Cin % 64 != 0) || !seg64)) pick = 1;   // 64-deep stages
-#define CTX_LAUNCH(WM_, WN_, MI_, NI_) do { if (conv) launch_gemm<WM_, WN_, MI_, NI_, true>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false>(a, s); } while (0)
+#define CTX_LAUNCH(WM_, WN_, MI_, NI_) do { if (a.phase) launch_gemm<WM_, WN_, MI_, NI_, true, 4, 32, true>(a, s); else if (conv) launch_gemm<WM_, WN_, MI_, NI_, true>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false>(a, s); } while (0)
         g_last_tile = pick;
         switch (pick) {
         case 0: CTX_LAUNCH(4, 2, 2, 2); break;
@@ -577,7 +610,7 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
         case 7: CTX_LAUNCH(4, 2, 1, 2); break;
         case 8: CTX_LAUNCH(2, 2, 1, 2); break;
         case 9: CTX_LAUNCH(2, 2, 2, 1); break;
-#define CTX_LAUNCH64(WM_, WN_, MI_, NI_) do { if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, 3, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, 3, 64>(a, s); } while (0)
+#define CTX_LAUNCH64(WM_, WN_, MI_, NI_) do { if (a.phase) launch_gemm<WM_, WN_, MI_, NI_, true, 3, 64, true>(a, s); else if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, 3, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, 3, 64>(a, s); } while (0)
         case 10: CTX_LAUNCH64(8, 2, 1, 2); break;     // 256x128, 16 waves (32x64), 64-deep stages
         case 11: CTX_LAUNCH64(4, 4, 2, 1); break;     // 256x128, 16 waves (64x32)
         case 12: CTX_LAUNCH64(4, 2, 2, 2); break;     // 256x128, 8 waves
@@ -587,14 +620,14 @@ int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s)
         case 16: CTX_LAUNCH64(2, 2, 1, 2); break;     // 64x128, 4 waves (32x64)
         case 17: CTX_LAUNCH64(2, 2, 2, 1); break;     // 128x64, 4 waves (64x32)
         case 18: CTX_LAUNCH64(2, 2, 2, 2); break;     // 128x128, 4 waves
-#define CTX_LAUNCH64N2(WM_, WN_, MI_, NI_) do { if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, 2, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, 2, 64>(a, s); } while (0)
+#define CTX_LAUNCH64N2(WM_, WN_, MI_, NI_) do { if (a.phase) launch_gemm<WM_, WN_, MI_, NI_, true, 2, 64, true>(a, s); else if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, 2, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, 2, 64>(a, s); } while (0)
         case 19: CTX_LAUNCH64N2(2, 2, 1, 1); break;   // ring of 2 (half the LDS, more workgroups per CU): 64x64, 4 waves
         case 20: CTX_LAUNCH64N2(4, 2, 1, 2); break;   // 128x128, 8 waves
         case 21: CTX_LAUNCH64N2(4, 4, 1, 1); break;   // 128x128, 16 waves
         case 22: CTX_LAUNCH64N2(2, 2, 2, 2); break;   // 128x128, 4 waves
         // deep rings (one workgroup per CU, 4-5 stages in flight) for the weight-streaming layers of the two deepest levels,
         // whose few workgroups wait on HBM latency rather than on staging bandwidth
-#define CTX_LAUNCH64NS(NS_, WM_, WN_, MI_, NI_) do { if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, NS_, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, NS_, 64>(a, s); } while (0)
+#define CTX_LAUNCH64NS(NS_, WM_, WN_, MI_, NI_) do { if (a.phase) launch_gemm<WM_, WN_, MI_, NI_, true, NS_, 64, true>(a, s); else if (conv) launch_gemm<WM_, WN_, MI_, NI_, true, NS_, 64>(a, s); else launch_gemm<WM_, WN_, MI_, NI_, false, NS_, 64>(a, s); } while (0)
         case 23: CTX_LAUNCH64NS(6, 2, 2, 1, 1); break;   // 64x64, 4 waves, ring of 6
         case 24: CTX_LAUNCH64NS(5, 2, 2, 1, 2); break;   // 64x128, 4 waves, ring of 5
         case 25: CTX_LAUNCH64NS(4, 4, 2, 1, 2); break;   // 128x128, 8 waves, ring of 4
@@ -715,6 +748,32 @@ extern "C" int32_t ctx_conv3x3_geom_f16(const void *x, const void *w, const void
     a.tile = -1; a.use8 = -1;
     CTX_REQUIRE((int64_t)B * H * W * Cin < (1ll << 31) && (int64_t)Cout * a.K < (1ll << 31) && (int64_t)B * a.Ho * a.Wo * Cout < (1ll << 31),
                 "conv3x3_geom: tensor too large for 32-bit offsets");
+    if (splitk < 0 && part) ctx_gemm_plan(a, true); else a.splitk = part && splitk > 1 ? splitk : 1;
+    a.part = (float *)part;
+    return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
+}
+
+// The upsampling convolution in its phase form (test seam; GemmArgs::phase): nearest x2 upsample of x [B,H,W,Cin] and a pad-1 3x3
+// convolution, computed as four 2x2 convolutions over x with the pack wp [4][Cout][2][2][Cin] of ctx_pack_conv3_phase_f16 -> y
+// [B,2H,2W,Cout].  The form takes a bias only: rowbias / residual are here to be refused (CTX_E_ARG, nothing launched), as is a null
+// pack.  splitk / part as ctx_conv3x3_geom_f16 (splitk <= min(32, 4 Cin / 64)).  Honours ctx_gemm_tune; a forced kernel without the form fails.
+extern "C" int32_t ctx_conv3x3_phase_f16(const void *x, const void *wp, const void *bias, const void *rowbias, const void *residual, int32_t B,
+                                         int32_t H, int32_t W, int32_t Cin, int32_t Cout, void *part, int32_t splitk, void *y, ctx_stream_t stream)
+{
+    CTX_REQUIRE(x && y, "conv3x3_phase: null pointer");
+    CTX_REQUIRE(wp, "conv3x3_phase: no phase pack (ctx_pack_conv3_phase_f16 writes it)");
+    CTX_REQUIRE(!rowbias && !residual, "conv3x3_phase: the phase form takes a bias only, no row bias or residual");
+    CTX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 8 == 0,
+                "conv3x3_phase: need Cin%%64==0, Cout%%8==0 (B=%d H=%d W=%d Cin=%d Cout=%d)", B, H, W, Cin, Cout);
+    CTX_REQUIRE(splitk != 0 && splitk <= 32 && (splitk <= 1 || splitk <= 4 * Cin / 64), "conv3x3_phase: splitk %d (1 .. min(32, K / 64), or < 0 for the plan)", splitk);
+    GemmArgs a = {};
+    ctx_conv3_problem(a, B, H, W, Cin, Cout, 1, 1, 0, 0);
+    ctx_conv3_phase(a, (const f16 *)wp);
+    a.X = (const f16 *)x; a.bias = (const f16 *)bias; a.out = (f16 *)y;
+    a.ldrb = Cout;
+    a.tile = -1; a.use8 = -1;
+    CTX_REQUIRE((int64_t)B * H * W * Cin < (1ll << 31) && (int64_t)4 * Cout * a.K < (1ll << 31) && (int64_t)a.M * Cout < (1ll << 31),
+                "conv3x3_phase: tensor too large for 32-bit offsets");
     if (splitk < 0 && part) ctx_gemm_plan(a, true); else a.splitk = part && splitk > 1 ? splitk : 1;
     a.part = (float *)part;
     return ctx_gemm_dispatch(a, true, (hipStream_t)stream);
@@ -847,6 +906,7 @@ extern "C" float ctx_bench_gemm(const void *A, const void *Wt, const void *bias,
         int Hv = conv_H << a.ups, Wv = conv_W << a.ups;
         a.H = conv_H; a.W = conv_W; a.Cin = conv_Cin; a.Ho = (Hv - 1) / a.stride + 1; a.Wo = (Wv - 1) / a.stride + 1;
         a.M = conv_B * a.Ho * a.Wo; a.N = N; a.K = 9 * conv_Cin; a.rows_per_batch = a.Ho * a.Wo;
+        if (conv_flags & 4) ctx_conv3_phase(a, a.Wt);      // bit 2 (with bit 1): the phase form; Wt is then the phase pack (no residual)
     } else {
         a.M = M; a.N = N; a.K = K; a.rows_per_batch = 1;
     }

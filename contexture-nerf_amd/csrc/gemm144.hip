@@ -23,13 +23,14 @@
 #define G144_BN 160
 #define G144_STAGE ((G144_BM + G144_BN) * 64)      // f16 per stage
 
-// UPS: the convolution has the fused nearest x2 upsample (generic per-tap address arithmetic); without it a tap is one scalar
-// offset from the lane's centre-tap pointer and a bit of a 9-bit in-bounds mask
+// UPS 1: the convolution has the fused nearest x2 upsample over nine taps (generic per-tap address arithmetic); 0: a tap is one scalar
+// offset from the lane's centre-tap pointer and a bit of a 9-bit in-bounds mask; 2: the upsample's phase form (GemmArgs::phase), which
+// is the fast path again with 4 taps, the shifts of the tile's phase and a row remap in the epilogues
 // BMB: token rows of the tile in 16-row blocks: 9 (144 x 160) or 18 (288 x 160: 103 instead of 76 FLOP per staged byte, for problems
 // with >= ~512 such tiles, i.e. the lockstep batch; its 56 KB stages leave room for a ring of 2 only, so it runs the lockstep schedule)
 // GNP: the GroupNorm partials request (GemmArgs::gn_part) is honoured in the LDS-staged epilogue; instantiated for the 15-wave forms
 // only, and the kernels without it compile to what they were
-template <int WM, int WN, bool CONV, int NS, int VAR, bool UPS = false, int BMB = 9, bool GNP = false>
+template <int WM, int WN, bool CONV, int NS, int VAR, int UPS = 0, int BMB = 9, bool GNP = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
 {
     constexpr int NW = WM * WN, MI = BMB / WM, NI = 10 / WN;        // waves; 16x16 blocks per wave along tokens / features
@@ -46,11 +47,17 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
     const int r16 = lane & 15, kg = lane >> 4;
 
     const GemmTile tl = gemm_tile(a, blockIdx.x, 64, BM, G144_BN);
-    const int slice = tl.slice, m0 = tl.m0, n0 = tl.n0, kbeg = tl.kbeg, nk = tl.nk;
+    constexpr bool PH = UPS == 2;
+    static_assert(!PH || (CONV && !GNP), "the phase form is a convolution without GroupNorm partials");
+    const ConvPhase ph = PH ? conv_phase_tile(a, tl.tile_m, BM) : ConvPhase{0, 0, 0, tl.m0, a.M};
+    const int slice = tl.slice, m0 = ph.m0, n0 = tl.n0, kbeg = tl.kbeg, nk = tl.nk;
+    const int ldw = CONV ? (PH ? 4 : 9) * a.Cin : a.K;             // weight row stride
+    const f16 *const Wt = PH ? a.Wt + (size_t)ph.ph * a.N * ldw : a.Wt;
 
     // ---- DMA state: piece p = wave + NW i of the stage image; p < 18 activation rows 8p.., else weight rows 8(p-18).. -----
     const int prow = lane >> 3, pc = lane & 7;
-    constexpr bool FAST = CONV && !UPS;
+    constexpr bool FAST = CONV && UPS != 1;
+    constexpr int NTAP = PH ? 4 : 9;
     const f16 *pp[SL], *xcen[SL];
     int pst[SL], xoff[SL], xoy[SL], xox[SL], xlc[SL], xval[SL];
     bool xok[SL];
@@ -65,7 +72,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         xoff[i] = 0; xoy[i] = 0; xox[i] = 0;
         if (isx) {
             const int m = m0 + s;
-            xok[i] = m < a.M;
+            xok[i] = m < ph.M;
             if (CONV) {
                 conv_pixel(a, xok[i] ? m : 0, xlc[i], xoy[i], xox[i], xoff[i]);
                 pp[i] = zp; pst[i] = 0;
@@ -73,8 +80,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
                     xcen[i] = a.X + (size_t)xoff[i] + (size_t)(xoy[i] * a.W + xox[i]) * a.Cin;
                     int v = 0;
 #pragma unroll
-                    for (int t = 0; t < 9; ++t) {
-                        const int iy = xoy[i] + t / 3 - 1 + a.poff, ix = xox[i] + t % 3 - 1 + a.poff;
+                    for (int t = 0; t < NTAP; ++t) {
+                        const int iy = xoy[i] + (PH ? conv_phase_dy(ph, t) : t / 3 - 1 + a.poff), ix = xox[i] + (PH ? conv_phase_dx(ph, t) : t % 3 - 1 + a.poff);
                         if (xok[i] && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v |= 1 << t;
                     }
                     xval[i] = v;
@@ -86,7 +93,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
         } else {
             const bool ok = live && (n0 + s) < a.N;
             xok[i] = ok;
-            pp[i] = ok ? a.Wt + (size_t)(n0 + s) * (CONV ? 9 * a.Cin : a.K) + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
+            pp[i] = ok ? Wt + (size_t)(n0 + s) * ldw + (size_t)kbeg * 64 + xlc[i] : ctx_zero_page;
             pst[i] = ok ? 64 : 0;
         }
     }
@@ -107,7 +114,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
             const bool seg = cur_tap >= 9;
             const int sg = cur_tap - 9, tap = seg ? 4 : cur_tap;    // bit 4 of xval: the row exists
             if (seg) cur_C = sg ? a.segC[1] : a.segC[0];
-            const int dy = tap / 3 - 1 + a.poff, dx = tap - (tap / 3) * 3 - 1 + a.poff;
+            const int dy = PH ? conv_phase_dy(ph, tap) : tap / 3 - 1 + a.poff, dx = PH ? conv_phase_dx(ph, tap) : tap - (tap / 3) * 3 - 1 + a.poff;
             const int soff = seg ? cur_c0 : (dy * a.W + dx) * a.Cin + cur_c0;     // scalar: the same for every lane
             // the weight pointers walk on from where they stand, in place
             ConvWJump wj = {0, 0};
@@ -407,9 +414,10 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int m = mb + 16 * i + r16;
-            if (m >= a.M) continue;
+            if (m >= ph.M) continue;
+            const int mo = PH ? conv_phase_row(a, ph, m) : m;
 #pragma unroll
-            for (int j = 0; j < NI; ++j) store_part4(a, pb + (size_t)m * a.N, nb + 16 * j + 4 * kg, acc[i][j]);
+            for (int j = 0; j < NI; ++j) store_part4(a, pb + (size_t)mo * a.N, nb + 16 * j + 4 * kg, acc[i][j]);
         }
         return;
     }
@@ -446,11 +454,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
             for (int ch = tid; ch < 144 * CPR; ch += NT) {
                 const int row = ch / CPR, c8 = (ch - row * CPR) * 8;
                 const int m = m0 + 144 * half + row, n = n0 + c8;
-                if (m >= a.M || n >= a.N) continue;
+                if (m >= ph.M || n >= a.N) continue;
                 const f32x4 v0 = *(const f32x4 *)(tile + row * RS + c8), v1 = *(const f32x4 *)(tile + row * RS + c8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 bias8(a, v, n);
-                const f16x8 o = store8(a, v, m, n);
+                const f16x8 o = store8(a, v, PH ? conv_phase_row(a, ph, m) : m, n);
                 if constexpr (GNP) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { const float f = (float)o[j]; gs[j] += f; gq[j] += f * f; }
@@ -506,15 +514,16 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm144(GemmArgs a)
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int m = mb + 16 * i + r16;
-        if (m >= a.M) continue;
+        if (m >= ph.M) continue;
         const int bidx = a.rowbias ? m / a.rows_per_batch : 0;
+        const int mo = PH ? conv_phase_row(a, ph, m) : m;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int nn = nb + 16 * j + 4 * kg;
             if (nn >= a.N) continue;
             f32x4 v = add4(acc[i][j], bs[j]);
             if (a.bias2) v = add4(v, *(const f16x4 *)(a.bias2 + nn));
-            store4(a, v, m, bidx, nn);
+            store4(a, v, mo, bidx, nn);
         }
     }
 }
@@ -529,7 +538,7 @@ int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
         if (a.segC[i] % 64 != 0 || a.segLdw[i] % 64 != 0) return 0;  // K segments in whole stages, weight rows in whole swizzle periods
     if (a.ldc % 4 != 0 || (a.residual && a.ldr % 4 != 0) || (a.rowbias && a.ldrb % 4 != 0)) return 0;
     const int bm = form == 4 ? 288 : G144_BM;
-    a.ntm = cdiv(a.M, bm);
+    a.ntm = a.phase ? 4 * cdiv(a.M / 4, bm) : cdiv(a.M, bm);       // phase form: whole tiles per phase
     a.ntn = cdiv(a.N, G144_BN);
     int S = (a.splitk > 1 && a.part) ? a.splitk : 1;
     if (S > a.K / 64) S = a.K / 64;
@@ -549,36 +558,41 @@ int ctx_gemm144_try(GemmArgs &a, bool conv, int form, hipStream_t s)
     }
     // threads, ring depth, then the kernel's template arguments
 #define G144_GO(NT_, NS_, ...) ctx_launch<k_gemm144<__VA_ARGS__>>(0, grid, dim3(NT_), (size_t)NS_ * (bm + G144_BN) * 64 * sizeof(f16), s, a)
-    const bool ups = conv && a.ups;
+    const int ups = !conv ? 0 : a.phase ? 2 : a.ups ? 1 : 0;        // the kernels' UPS
     if (gnp) {                                                       // the same forms with the partials in the epilogue
         switch (form) {
-        case 4: if (conv) G144_GO(960, 2, 3, 5, true, 2, 0, false, 18, true); else G144_GO(960, 2, 3, 5, false, 2, 0, false, 18, true); break;
-        case 1: if (conv) G144_GO(960, 3, 3, 5, true, 3, 0, false, 9, true); else G144_GO(960, 3, 3, 5, false, 3, 0, false, 9, true); break;
-        case 2: if (conv) G144_GO(960, 4, 3, 5, true, 4, 1, false, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 1, false, 9, true); break;
-        default: if (conv) G144_GO(960, 4, 3, 5, true, 4, 2, false, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 2, false, 9, true); break;
+        case 4: if (conv) G144_GO(960, 2, 3, 5, true, 2, 0, 0, 18, true); else G144_GO(960, 2, 3, 5, false, 2, 0, 0, 18, true); break;
+        case 1: if (conv) G144_GO(960, 3, 3, 5, true, 3, 0, 0, 9, true); else G144_GO(960, 3, 3, 5, false, 3, 0, 0, 9, true); break;
+        case 2: if (conv) G144_GO(960, 4, 3, 5, true, 4, 1, 0, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 1, 0, 9, true); break;
+        default: if (conv) G144_GO(960, 4, 3, 5, true, 4, 2, 0, 9, true); else G144_GO(960, 4, 3, 5, false, 4, 2, 0, 9, true); break;
         }
         return 1;
     }
     switch (form) {
     case 4:                                                          // 288 x 160, 15 waves, lockstep, ring of 2
-        if (!conv) G144_GO(960, 2, 3, 5, false, 2, 0, false, 18);
-        else if (ups) G144_GO(960, 2, 3, 5, true, 2, 0, true, 18); else G144_GO(960, 2, 3, 5, true, 2, 0, false, 18);
+        if (!conv) G144_GO(960, 2, 3, 5, false, 2, 0, 0, 18);
+        else if (ups == 2) G144_GO(960, 2, 3, 5, true, 2, 0, 2, 18);
+        else if (ups) G144_GO(960, 2, 3, 5, true, 2, 0, 1, 18); else G144_GO(960, 2, 3, 5, true, 2, 0, 0, 18);
         break;
     case 1:
         if (!conv) G144_GO(960, 3, 3, 5, false, 3, 0);
-        else if (ups) G144_GO(960, 3, 3, 5, true, 3, 0, true); else G144_GO(960, 3, 3, 5, true, 3, 0);
+        else if (ups == 2) G144_GO(960, 3, 3, 5, true, 3, 0, 2);
+        else if (ups) G144_GO(960, 3, 3, 5, true, 3, 0, 1); else G144_GO(960, 3, 3, 5, true, 3, 0);
         break;
     case 2:
         if (!conv) G144_GO(960, 4, 3, 5, false, 4, 1);
-        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 1, true); else G144_GO(960, 4, 3, 5, true, 4, 1);
+        else if (ups == 2) G144_GO(960, 4, 3, 5, true, 4, 1, 2);
+        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 1, 1); else G144_GO(960, 4, 3, 5, true, 4, 1);
         break;
     case 3:
         if (!conv) G144_GO(960, 4, 3, 5, false, 4, 2);
-        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 2, true); else G144_GO(960, 4, 3, 5, true, 4, 2);
+        else if (ups == 2) G144_GO(960, 4, 3, 5, true, 4, 2, 2);
+        else if (ups) G144_GO(960, 4, 3, 5, true, 4, 2, 1); else G144_GO(960, 4, 3, 5, true, 4, 2);
         break;
     default:
         if (!conv) G144_GO(384, 3, 3, 2, false, 3, 0);
-        else if (ups) G144_GO(384, 3, 3, 2, true, 3, 0, true); else G144_GO(384, 3, 3, 2, true, 3, 0);
+        else if (ups == 2) G144_GO(384, 3, 3, 2, true, 3, 0, 2);
+        else if (ups) G144_GO(384, 3, 3, 2, true, 3, 0, 1); else G144_GO(384, 3, 3, 2, true, 3, 0);
         break;
     }
 #undef G144_GO

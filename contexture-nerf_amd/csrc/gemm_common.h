@@ -75,6 +75,33 @@ __device__ __forceinline__ const f16 *conv_tap_src(const GemmArgs &a, const Conv
     return ok ? src : ctx_zero_page;
 }
 
+// ---- phase form (GemmArgs::phase) ----------------------------------------------------------------------------------
+// The kernels see a stride-1 convolution over the source grid (Ho = H, Wo = W, ups = 0) with 4 taps per pixel, and the M dimension is
+// phase-major: ntm = 4 x the tiles of one phase's B H W rows, so a tile lies in one phase, which selects its weight matrix.
+// ph: phase 2a + b; m0: the tile's first row inside the phase; M: rows per phase (the last tile of each phase is masked against it)
+struct ConvPhase { int ph, pa, pb, m0, M; };
+__device__ __forceinline__ ConvPhase conv_phase_tile(const GemmArgs &a, int tile_m, int bm)
+{
+    const int ntmp = a.ntm >> 2, ph = tile_m / ntmp;
+    return {ph, ph >> 1, ph & 1, (tile_m - ph * ntmp) * bm, a.M >> 2};
+}
+// shift of tap t = 2u + v of phase parity p along one axis: p - 1 + (u | v)
+__device__ __forceinline__ int conv_phase_dy(const ConvPhase &p, int t) { return p.pa - 1 + (t >> 1); }
+__device__ __forceinline__ int conv_phase_dx(const ConvPhase &p, int t) { return p.pb - 1 + (t & 1); }
+// conv_tap of the phase form: K index k0 falls in tap k0 / Cin of the 4
+__device__ __forceinline__ ConvTap conv_phase_tap(const GemmArgs &a, const ConvPhase &p, int k0)
+{
+    const int tap = k0 / a.Cin;
+    return {conv_phase_dy(p, tap), conv_phase_dx(p, tap), k0 - tap * a.Cin, a.H, a.W};
+}
+// row m of the phase (pixel (n, i, j) of the source grid) -> the row of output pixel (n, 2i + a, 2j + b); every epilogue and the split-K
+// partials store through it, so the fp32 slabs are already in the output's order and the reduce kernel does not know the form
+__device__ __forceinline__ int conv_phase_row(const GemmArgs &a, const ConvPhase &p, int m)
+{
+    const int hw = a.H * a.W, n = m / hw, r = m - n * hw, i = r / a.W, j = r - i * a.W;
+    return ((n * 2 * a.H + 2 * i + p.pa) * 2 * a.W) + 2 * j + p.pb;
+}
+
 // K segments (GemmArgs::nseg): the source that the K stage starting at k0 reads.  src 0 .. 8: that tap of the 3x3 part; 9 / 10:
 // segment 0 / 1.  c0: first channel inside the source, C: the source's channel count (C - c0 is what is left of it), so a split-K
 // slice may start anywhere.  Weight rows of the 3x3 part are 9 Cin long whatever K is.
@@ -220,7 +247,8 @@ __device__ __forceinline__ f16 geglu(float xv, float gv) { return (f16)(xv * gel
 // 1: the weights are the larger operand (unique bytes: weights N*K, activations M*K; conv: M*Cin, the 9 taps re-read the same pixels)
 static inline int ctx_gemm_mfast(const GemmArgs &a, bool conv)
 {
-    const double wbytes = (double)a.N * a.K, xbytes = (double)a.M * (conv ? a.Cin : a.K);
+    // (the phase form: four weight matrices of N x K, and the B H W source pixels that its M / 4 rows per phase share)
+    const double wbytes = (double)a.N * a.K * (a.phase ? 4 : 1), xbytes = (double)(a.phase ? a.M / 4 : a.M) * (conv ? a.Cin : a.K);
     return wbytes > xbytes ? 1 : 0;
 }
 // Launch KERN; under profiling with the start / stop events of ctx_prof_events(klass, ...).  lds > 0: dynamic LDS, whose limit is

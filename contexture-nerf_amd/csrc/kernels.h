@@ -21,8 +21,13 @@ struct GemmArgs {
     int res32, out32;      // 1: `residual` / `out` point at fp32 tensors (the fp32 residual-stream experiment; gemm.hip epilogues only)
     int zins;              // conv: 1 = with ups, the 2x grid is ZERO-INSERTED (odd rows / columns read the zero page) instead of
                            // nearest-upsampled: the input gradient of a stride-2 convolution (poff = -1 there); gemm.hip kernel only
+    int phase;             // conv: 1 = the nearest x2 upsample + 3x3 convolution as four 2x2 convolutions over the SOURCE grid, one per output
+                           // parity (a, b): Wt is the phase pack [4][N][2][2][Cin] (ctx_pack_conv3_phase_f16), K = 4 Cin, M = 4 B H W rows,
+                           // phase-major; tap (u, v) of phase (a, b) reads source pixel (i + a - 1 + u, j + b - 1 + v) and row (n, i, j) of
+                           // the phase goes to output pixel (n, 2i + a, 2j + b).  Bias only: no row bias, residual, K segments or GroupNorm
+                           // partials.  The dispatcher turns the geometry into the kernels' (Ho = H, Wo = W, ups = 0) and checks the form.
     int ntm, ntn;
-    int splitk;            // >1: grid.y = splitk, fp32 partials [splitk][M][N] go to `part`
+    int splitk;           // >1: grid.y = splitk, fp32 partials [splitk][M][N] go to `part`
     float *part;
     int pk;                // K-stage depth chosen by the launcher (32 or 64)
     int krot;              // 1: per-workgroup K rotation (spreads concurrent accesses to shared operand rows); 2: no rotation and no
@@ -59,6 +64,20 @@ static inline void ctx_conv3_problem(GemmArgs &a, int B, int H, int W, int Cin, 
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = 9 * Cin; a.ldc = Cout; a.ldr = Cout; a.rows_per_batch = a.Ho * a.Wo;
     a.H = H; a.W = W; a.Cin = Cin; a.stride = stride; a.ups = ups; a.poff = poff; a.zins = zins;
 }
+
+// the same upsampling problem (ups 1, stride 1, poff 0, no zins) in the phase form over the pack `wp`: M and the output stay what they were
+static inline void ctx_conv3_phase(GemmArgs &a, const f16 *wp)
+{
+    a.phase = 1; a.Wt = wp; a.K = 4 * a.Cin;
+}
+// 1: this upsampling convolution has a phase form (the kernels that implement it stage 64 channels at a time)
+static inline int ctx_conv3_phase_ok(int Cin, int Cout, int stride, int ups, int poff, int zins)
+{
+    return ups == 1 && stride == 1 && poff == 0 && !zins && Cin % 64 == 0 && Cout % 8 == 0;
+}
+// 1: at this shape (M output pixels) the per-shape table (tools/bench_upsample_phase.py) has the phase form slower than nine taps, and the
+// engines keep the nine-tap form
+static inline int ctx_conv3_phase_loses(int M, int Cout, int Cin) { return 0; }
 
 int ctx_gemm_dispatch(GemmArgs &a, bool conv, hipStream_t s);
 // 256x256 8-wave kernel (gemm8.hip): launches and returns 1 when the problem suits it, else 0

@@ -224,6 +224,7 @@ static ctx_unet_t *unet_create_impl(const ctx_unet_config_t *cfg, bool controlne
             if (i != n - 1) {
                 L.has_sampler = true; L.sc = out;
                 L.sw = u->add(p + ".upsamplers.0.conv.weight", {out, out, 3, 3}, PK_CONV3, u->walloc((size_t)out * out * 9), out, out);
+                u->derive_phase();
                 L.sb = u->vec(p + ".upsamplers.0.conv.bias", out);
             }
         }
@@ -289,6 +290,8 @@ extern "C" int32_t ctx_unet_bind(ctx_unet_t *u, void *weights, void *workspace, 
 {
     return engine_bind(u, weights, workspace, workspace_bytes, "unet_bind");
 }
+extern "C" int64_t ctx_unet_derived_bytes(const ctx_unet_t *u) { return engine_derived_bytes(u); }
+extern "C" int32_t ctx_unet_bind_derived(ctx_unet_t *u, void *derived, int64_t bytes) { return engine_bind_derived(u, derived, bytes, "unet_bind_derived"); }
 extern "C" int32_t ctx_unet_set_param(ctx_unet_t *u, int32_t i, const float *src, ctx_stream_t stream)
 {
     return engine_set_param(u, i, src, stream, "unet_set_param");

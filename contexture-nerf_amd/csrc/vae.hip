@@ -129,6 +129,7 @@ extern "C" ctx_vae_t *ctx_vae_create(const ctx_vae_config_t *cfg)
         if (i != n - 1) {
             v->upc[i] = out;
             v->upw[i] = v->add(p + ".upsamplers.0.conv.weight", {out, out, 3, 3}, 1, v->walloc((size_t)out * out * 9), out, out);
+            v->derive_phase();
             v->upb[i] = v->vec(p + ".upsamplers.0.conv.bias", out);
         }
     }
@@ -169,6 +170,8 @@ extern "C" int32_t ctx_vae_bind(ctx_vae_t *v, void *weights, void *workspace, in
 {
     return engine_bind(v, weights, workspace, workspace_bytes, "vae_bind");
 }
+extern "C" int64_t ctx_vae_derived_bytes(const ctx_vae_t *v) { return engine_derived_bytes(v); }
+extern "C" int32_t ctx_vae_bind_derived(ctx_vae_t *v, void *derived, int64_t bytes) { return engine_bind_derived(v, derived, bytes, "vae_bind_derived"); }
 extern "C" int32_t ctx_vae_set_param(ctx_vae_t *v, int32_t i, const float *src, ctx_stream_t stream)
 {
     return engine_set_param(v, i, src, stream, "vae_set_param");

@@ -23,6 +23,8 @@ class HipEngine:
             self._shapes.append(tuple(int(shp[k]) for k in range(nd)))
         self._index = {n: i for i, n in enumerate(self._names)}
         self._weights = None
+        self._derived = None
+        self._derived_on = True
         self._ws = None
         self._ws_key = None
         self._t = None
@@ -30,6 +32,9 @@ class HipEngine:
         if self.device.type == 'cuda':
             self._weights = torch.empty(self._c('weight_bytes')(self._h), dtype=torch.uint8, device=self.device)
             self._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
+            nd = self._c('derived_bytes')(self._h)
+            if nd > 0:                                   # packs derived from parameters (the upsamplers' phase packs): filled by _set
+                self._derived = torch.empty(nd, dtype=torch.uint8, device=self.device)
             self._bind()
             if init:
                 self.init_random(seed)
@@ -53,6 +58,7 @@ class HipEngine:
         o._names, o._shapes, o._index = self._names, self._shapes, self._index
         o._h = self._create_handle()                    # same config, same C constructor
         o._weights = self._weights                      # shared, read-only during forward
+        o._derived, o._derived_on = self._derived, self._derived_on     # derived from those weights: shared with them
         o._ws = torch.empty(256, dtype=torch.uint8, device=self.device)
         o._ws_key, o._t = None, None
         o._bind()
@@ -76,6 +82,18 @@ class HipEngine:
 
     def _bind(self):
         L.check(self._c('bind')(self._h, L.ptr(self._weights), L.ptr(self._ws), self._ws.numel()))
+        if self._derived is not None:
+            on = self._derived_on
+            L.check(self._c('bind_derived')(self._h, L.ptr(self._derived) if on else None, self._derived.numel() if on else 0))
+
+    def use_derived(self, on=True):
+        """Bind (default) or unbind the derived blob.  Unbound, every layer runs from the weight blob alone (the upsamplers as
+        nine-tap convolutions over the x2 grid); the blob keeps its contents, so binding it again needs no reload as long as no
+        parameter was set in between."""
+        self._derived_on = bool(on)
+        self._ws_key = None                # the two forms split K differently: re-query the workspace
+        self._bind()
+        return self
 
     def _set(self, i, t):
         t = L.f32c(t, self.device)

@@ -571,6 +571,13 @@ int64_t ctx_unet_weight_bytes(const ctx_unet_t *u);
 int64_t ctx_unet_workspace_bytes(const ctx_unet_t *u, int32_t B, int32_t H, int32_t W, int32_t ctx_len);
 /* Bind caller-allocated blobs (256-B aligned). */
 int32_t ctx_unet_bind(ctx_unet_t *u, void *weights, void *workspace, int64_t workspace_bytes);
+/* The derived blob: packs that are functions of parameters and live outside the weight blob (the phase packs of the upsamplers'
+   convolutions, ctx_conv3x3_phase_f16).  ctx_unet_derived_bytes: its size (0: this engine derives nothing, e.g. a ControlNet);
+   ctx_unet_bind_derived: bind it (256-B aligned, >= that size; NULL unbinds).  Optional: with none bound the upsamplers run as
+   nine-tap convolutions over the x2 grid.  ctx_unet_set_param fills it for the parameters set while it is bound, so bind it
+   before loading; engines over the same weight blob may share one. */
+int64_t ctx_unet_derived_bytes(const ctx_unet_t *u);
+int32_t ctx_unet_bind_derived(ctx_unet_t *u, void *derived, int64_t bytes);
 /* Convert + repack parameter i from fp32 [diffusers layout] into the fp16 weight blob. */
 int32_t ctx_unet_set_param(ctx_unet_t *u, int32_t i, const float *src, ctx_stream_t stream);
 /* sample[B,Cin,H,W] f32 NCHW, timestep: device float[1] (graph-replay friendly), ctx[B,L,D] f32
@@ -642,6 +649,9 @@ int32_t ctx_vae_param_shape(const ctx_vae_t *v, int32_t i, int64_t shape4[4]);
 int64_t ctx_vae_weight_bytes(const ctx_vae_t *v);
 int64_t ctx_vae_workspace_bytes(const ctx_vae_t *v, int32_t B, int32_t H, int32_t W);
 int32_t ctx_vae_bind(ctx_vae_t *v, void *weights, void *workspace, int64_t workspace_bytes);
+/* the derived blob of the decoder's upsamplers, as ctx_unet_derived_bytes / ctx_unet_bind_derived */
+int64_t ctx_vae_derived_bytes(const ctx_vae_t *v);
+int32_t ctx_vae_bind_derived(ctx_vae_t *v, void *derived, int64_t bytes);
 int32_t ctx_vae_set_param(ctx_vae_t *v, int32_t i, const float *src, ctx_stream_t stream);
 /* latents [B,L,H,W] f32 (already divided by the 0.18215 scaling factor) -> image [B,3,8H,8W] f32 */
 int32_t ctx_vae_decode(ctx_vae_t *v, const float *latents, int32_t B, int32_t H, int32_t W, float *image, ctx_stream_t stream);
@@ -714,6 +724,18 @@ void ctx_gemm_last_kernel(int32_t *tile, int32_t *use8);
 int32_t ctx_conv3x3_geom_f16(const void *x, const void *w, const void *bias, const void *residual, int32_t B, int32_t H, int32_t W,
                              int32_t Cin, int32_t Cout, int32_t stride, int32_t upsample, int32_t poff, int32_t zins, void *part,
                              int32_t splitk, void *y, ctx_stream_t stream);
+/* The phase form of the upsampling convolution: nearest x2 upsample of x [B,H,W,Cin] followed by a pad-1 3x3 convolution, computed
+   as four 2x2 convolutions over x, one per output parity (a, b): y[n, 2i+a, 2j+b, o] = bias[o] + sum_{u,v,c} x[n, i+a-1+u, j+b-1+v, c]
+   wp[a,b][o][u][v][c] (x reads 0 outside the grid); 4 / 9 of the nine-tap form's multiplies.
+   ctx_pack_conv3_phase_f16: w f32 [Cout,Cin,3,3] -> wp f16 [4 phases (0,0),(0,1),(1,0),(1,1)][Cout][2][2][Cin]; tap (u, v) of phase
+     (a, b) is the sum over ky in R(a,u), kx in R(b,v), R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}, in fp32, added
+     left to right with ky ascending, then kx ascending, rounded once.
+   ctx_conv3x3_phase_f16: y f16 [B,2H,2W,Cout]; Cin % 64 == 0, Cout % 8 == 0.  Bias only: a rowbias, a residual or a NULL pack is
+     CTX_E_ARG with nothing launched.  splitk / part as ctx_conv3x3_geom_f16 (splitk <= min(32, 4 Cin / 64)).  Honours ctx_gemm_tune;
+     a forced kernel that does not implement the form (gemm8.hip, conv_halo.hip) fails with CTX_E_ARG. */
+int32_t ctx_pack_conv3_phase_f16(const float *src, int32_t Cout, int32_t Cin, void *dst, ctx_stream_t stream);
+int32_t ctx_conv3x3_phase_f16(const void *x, const void *wp, const void *bias, const void *rowbias, const void *residual, int32_t B,
+                              int32_t H, int32_t W, int32_t Cin, int32_t Cout, void *part, int32_t splitk, void *y, ctx_stream_t stream);
 /* The weight packs of the data gradients, as ctx_vae_set_param writes them next to the forward packs.
    conv: src f32 [Cout,Cin,3,3] -> dst f16 [Cin][t' = 3 (2 - ky) + (2 - kx)][pad], zero in the columns Cout .. pad (pad >= Cout): the
    weights [N = Cin][3][3][K-channels = pad] of the convolution that maps a cotangent of pad channels to the input gradient.
@@ -837,7 +859,7 @@ int32_t ctx_profile_end(int32_t klass, double *total_ms /*host*/, int64_t *count
 
 /* Benchmark support (tools/bench_gemm.py): `iters` back-to-back launches timed on the device; conv_B > 0 selects the
    implicit-GEMM conv (N = Cout, input [conv_B, conv_H, conv_W, conv_Cin]; conv_flags bit 0: stride 2, bit 1: fused nearest
-   x2 upsample).  epi 1: GEGLU epilogue.  splitk < 0: the UNet executor's own choice (needs `part`).  Returns average ms
+   x2 upsample, bit 2 (with bit 1): the upsample's phase form, Wt then being the phase pack and residual NULL).  epi 1: GEGLU epilogue.  splitk < 0: the UNet executor's own choice (needs `part`).  Returns average ms
    per launch (< 0: error). */
 float ctx_bench_gemm(const void *A, const void *Wt, const void *bias, const void *residual, int32_t M, int32_t N, int32_t K,
                      void *C, int32_t conv_B, int32_t conv_H, int32_t conv_W, int32_t conv_Cin, int32_t conv_flags, int32_t epi,

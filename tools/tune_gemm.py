@@ -3,7 +3,10 @@
 (tools/bench_gemm.py's list, built for one or more latent sizes) time every tile of gemm.hip, the 256x256 kernel of
 gemm8.hip and a ladder of split-K factors; write the winners as contexture-nerf_amd/csrc/gemm_tuned.h (stdout with
 --emit).  Device-timed back-to-back launches, bias + residual epilogues on, random operands.
+--phase 1 searches only the upsampling convolutions, in their phase form (flags bit 2: four 2x2 convolutions over the source grid,
+K = 4 Cin, bias only); --vae adds the VAE decoder's three upsamplers at that image size (batch 1).  tools/merge_tuned.py merges the rows.
 
+  python tools/tune_gemm.py --phase 1 --latents 96,120x80 --vae 768 --emit phase_rows.h     (and again with --batch 12)
   python tools/tune_gemm.py --latents 96,64 --emit gpurun_out/gemm_tuned.h"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +21,8 @@ ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--batch", type=int, default=2, help="UNet batch (2 = CFG pair; 1 = one CFG half per stream)")
 ap.add_argument("--forms", default="", help="comma list of use8 values: time ONLY these kernels (A/B of kernel variants), print all")
 ap.add_argument("--convs", type=int, default=0, help="1: convolution shapes only")
+ap.add_argument("--phase", type=int, default=0, help="1: only the upsampling convolutions, in the phase form (flags 6)")
+ap.add_argument("--vae", default="", help="with --phase: comma list of image sizes whose VAE decoder upsamplers are added (batch 1)")
 args = ap.parse_args()
 lib = L.load(); dev = torch.device('cuda:0')
 
@@ -53,6 +58,11 @@ shapes = []
 for Lt in [(tuple(int(v) for v in x.split("x")) if "x" in x else int(x)) for x in args.latents.split(",")]:
     for s_ in layer_list(Lt, args.batch):
         if s_ not in shapes: shapes.append(s_)
+if args.phase:
+    shapes = [(1, b, n, c, 6, 0) for (cv, b, n, c, fl, e) in shapes if cv == 1 and fl == 2]
+    for img in [int(v) for v in args.vae.split(",") if v]:
+        lt = img // 8
+        shapes += [(1, (1, lt, lt), 512, 512, 6, 0), (1, (1, 2 * lt, 2 * lt), 512, 512, 6, 0), (1, (1, 4 * lt, 4 * lt), 256, 256, 6, 0)]
 g = torch.Generator(device=dev).manual_seed(0)
 part = torch.empty(384 << 20, dtype=torch.uint8, device=dev)
 rows = []
@@ -61,15 +71,16 @@ for s_ in shapes:
         _, (B, H, W), N, Cin, flags, epi = s_
         st, up = (2 if flags & 1 else 1), (1 if flags & 2 else 0)
         Ho, Wo = ((H << up) - 1) // st + 1, ((W << up) - 1) // st + 1
-        M, K = B * Ho * Wo, 9 * Cin
+        M, K = B * Ho * Wo, (4 if flags & 4 else 9) * Cin
         x = torch.randn(B, H, W, Cin, generator=g, device=dev).half(); cb = (B, H, W, Cin, flags)
     else:
         _, M, N, K, flags, epi = s_
         x = torch.randn(M, K, generator=g, device=dev).half(); cb = (0, 0, 0, 0, 0)
-    w = (torch.randn(N, K, generator=g, device=dev) / K ** 0.5).half()
+    phase = s_[0] == 1 and bool(flags & 4)                      # the pack: four [N][K] matrices; the form takes no residual
+    w = (torch.randn((4 if phase else 1) * N, K, generator=g, device=dev) / K ** 0.5).half()
     No = N // 2 if epi else N
     y = torch.empty(M, No, dtype=torch.float16, device=dev)
-    res_ = torch.randn(M, No, generator=g, device=dev).half() if not epi else None
+    res_ = torch.randn(M, No, generator=g, device=dev).half() if not epi and not phase else None
     bias = torch.randn(N, generator=g, device=dev).half()
 
     def run(tile, use8, S):
@@ -103,7 +114,7 @@ for s_ in shapes:
             if tile >= 10 and (K % 64 or (s_[0] == 1 and Cin % 64)): continue
             t = run(tile, 0, S)
             if t: cands.append((t, tile, 0, S))
-        if K % 64 == 0 and (s_[0] == 0 or Cin % 64 == 0) and (K // 64 // S) >= 1:
+        if K % 64 == 0 and (s_[0] == 0 or Cin % 64 == 0) and (K // 64 // S) >= 1 and not phase:
             t = run(-1, 1, S)
             if t: cands.append((t, -1, 1, S))
         if epi == 0 and K % 64 == 0 and (s_[0] == 0 or Cin % 64 == 0) and (K // 64 // S) >= 1:
@@ -129,10 +140,16 @@ if args.forms:
 print(f"sum best {sum(r[9] for r in rows) * 1e3:.0f} us vs current {sum(r[10] for r in rows) * 1e3:.0f} us (one launch per distinct shape)")
 if args.emit:
     with open(args.emit, "w") as f:
-        f.write("// Tuned GEMM / conv plans (tools/tune_gemm.py on MI355X): exact-shape matches override the heuristics of gemm.hip.\n"
-                "// flags: bit 0 stride 2, bit 1 fused x2 upsample; tile: id of gemm.hip's list (-1 heuristic); use8: gemm8.hip's 256x256 kernel.\n"
-                f"// generated for latents {args.latents} (CFG batch 2)\n#pragma once\n"
-                "struct TunedGemm { int conv, M, N, K, flags, epi, tile, use8, splitk; };\nstatic const TunedGemm g_tuned[] = {\n")
+        if args.phase:
+            f.write("// Tuned plans of the upsampling convolutions in their phase form (tools/tune_gemm.py --phase 1 on MI355X): the rows of\n"
+                    "// contexture-nerf_amd/csrc/gemm_tuned_phase.h (flags 6, K = 4 Cin); tools/merge_tuned.py merges them into that file.\n"
+                    f"// generated for latents {args.latents}, batch {args.batch}, VAE image sizes '{args.vae}'\n#pragma once\n"
+                    "static const TunedGemm g_tuned_phase[] = {\n")
+        else:
+            f.write("// Tuned GEMM / conv plans (tools/tune_gemm.py on MI355X): exact-shape matches override the heuristics of gemm.hip.\n"
+                    "// flags: bit 0 stride 2, bit 1 fused x2 upsample; tile: id of gemm.hip's list (-1 heuristic); use8: gemm8.hip's 256x256 kernel.\n"
+                    f"// generated for latents {args.latents} (CFG batch 2)\n#pragma once\n"
+                    "struct TunedGemm { int conv, M, N, K, flags, epi, tile, use8, splitk; };\nstatic const TunedGemm g_tuned[] = {\n")
         for r in rows:
             f.write(f"    {{{r[0]}, {r[1]}, {r[2]}, {r[3]}, {r[4]}, {r[5]}, {r[6]}, {r[7]}, {r[8]}}},   // {r[9] * 1e3:.1f} us (was {r[10] * 1e3:.1f})\n")
         f.write("};\n")
