@@ -213,10 +213,11 @@ struct UvmPlan {
     int64_t wt16_off[UVM_MAX_LAYERS]; // layer i >= 1: wt_off's operand as two fp16 planes (backward chain of k_uvmlp_dgrad16), or -1
 };
 
-// the shapes every entry point accepts
+// the shapes every entry point accepts: the widths are the ones uvm_dispatch has kernels for (one wave per 64 hidden columns as 1, 2 or
+// 4 waves; there is no 3-wave form, so W = 192 is refused like any other width)
 static inline bool uvm_envelope(int D, int W, int input_ch = 1 /* where the answer does not depend on it */)
 {
-    return D >= 1 && D <= UVM_MAX_LAYERS && W >= 64 && W % 64 == 0 && W <= 256 && input_ch >= 1 && input_ch <= UVM_EPAD3;
+    return D >= 1 && D <= UVM_MAX_LAYERS && (W == 64 || W == 128 || W == 256) && input_ch >= 1 && input_ch <= UVM_EPAD3;
 }
 static inline int uvm_epad(int input_ch) { return input_ch <= UVM_EPAD ? UVM_EPAD : UVM_EPAD3; }
 
@@ -263,11 +264,19 @@ static bool uvm_use_split16(const UvmPlan &p, int dims, bool backward)
 
 // (W, EP) of a plan as compile-time constants: f(integral_constant<W>, integral_constant<EP>)
 template <int V> using uvm_c = std::integral_constant<int, V>;
-template <class F> static void uvm_dispatch(int W, int EP, F f)
+// The widths are uvm_envelope's, one branch each.  Any other width is unreachable here (every caller has built its plan, and
+// uvm_build_plan starts with uvm_envelope); should the gate ever be widened without a kernel, nothing is launched and the caller
+// reports the false return as an error instead of running another width's kernel on the blob.
+template <class F> static bool uvm_dispatch(int W, int EP, F f)
 {
     auto with_w = [&](auto w) { if (EP == UVM_EPAD) f(w, uvm_c<UVM_EPAD>{}); else f(w, uvm_c<UVM_EPAD3>{}); };
-    if (W == 256) with_w(uvm_c<256>{}); else if (W == 128) with_w(uvm_c<128>{}); else with_w(uvm_c<64>{});
+    if (W == 256) with_w(uvm_c<256>{});
+    else if (W == 128) with_w(uvm_c<128>{});
+    else if (W == 64) with_w(uvm_c<64>{});
+    else return false;
+    return true;
 }
+#define UVM_DISPATCHED(ok, who) CTX_REQUIRE(ok, "%s: no kernel for W=%d (unreachable behind uvm_envelope)", who, W)
 
 extern "C" int64_t ctx_uvmlp_packed_bytes(int32_t D, int32_t W, int32_t input_ch, int32_t output_ch, int32_t skip)
 {
@@ -694,12 +703,13 @@ static int32_t uvm_fwd(const float *uv, const float *emb, const int32_t *idx, in
         CTX_CHECK_LAUNCH("uvmlp_fwd16");
         return CTX_OK;
     }
-    uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
+    const bool known = uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
         constexpr int WW = decltype(w)::value, EE = decltype(ep)::value;
         const size_t lds = (size_t)UVM_TM * ((EE == UVM_EPAD ? UVM_EPAD : 0) + WW + 4) * 4;   // the 3-D layout overlays the embedding
         (void)hipFuncSetAttribute((const void *)k_uvmlp_fwd<WW, EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_uvmlp_fwd<WW, EE>), dim3((unsigned)cdiv64(N, UVM_TM)), dim3(WW), lds, s, uv, emb, list, N, res, L, pk, p, raw, tex_chw, saved);
     });
+    UVM_DISPATCHED(known, "uvmlp_fwd");
     CTX_CHECK_LAUNCH("uvmlp_fwd");
     return CTX_OK;
 }
@@ -1335,12 +1345,13 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
         (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
         hipLaunchKernelGGL(k_uvmlp_dgrad16, dim3(dg), dim3(256), lds16, s, grad_raw, grad_tex, raw, list, N, pk, p, saved, dz, part_w, part_b, ctl);
     } else {
-        uvm_dispatch(W, p.epad, [&](auto w, auto) {
+        const bool known = uvm_dispatch(W, p.epad, [&](auto w, auto) {
             constexpr int WW = decltype(w)::value;
             const size_t lds = (size_t)(UVM_TM * (WW + 4) + UVM_TM * 4) * 4;
             (void)hipFuncSetAttribute((const void *)k_uvmlp_dgrad<WW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(k_uvmlp_dgrad<WW>, dim3(dg), dim3(WW), lds, s, grad_raw, grad_tex, raw, list, N, pk, p, saved, dz, part_w, part_b);
         });
+        UVM_DISPATCHED(known, "uvmlp_dgrad");
     }
     CTX_CHECK_LAUNCH("uvmlp_dgrad");
     if (want_w) {
@@ -1359,7 +1370,8 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
     int Ge = (int)cdiv64(N, chunk_e);
     const float *emb = saved;
     const float *acts = saved + N * p.epad;
-    static const int wg8 = [] { const char *e = getenv("CTX_UVM_WG8"); return e ? atoi(e) : 0; }();
+    const char *wg8_env = getenv("CTX_UVM_WG8");   // read on every call, like CTX_UVMLP_EXACT_F32: the switch may be flipped inside one process
+    const int wg8 = wg8_env ? atoi(wg8_env) : 0;
     for (int li = D - 1; want_w && li >= 0; --li) {
         const float *dzl = dz + (int64_t)li * N * W;
         const int kin = li == 0 ? input_ch : (li == skip + 1 ? input_ch + W : W);
@@ -1367,11 +1379,12 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
         const bool has_hid = li != 0;
         if (has_hid) {
             const float *in = acts + (int64_t)(li - 1) * N * W;
-            uvm_dispatch(W, p.epad, [&](auto w, auto) {
+            const bool known = uvm_dispatch(W, p.epad, [&](auto w, auto) {
                 constexpr int WW = decltype(w)::value;
                 if (WW == 256 && wg8) uvm_launch_wgrad<2, 4, 4, 2, 256, 256, 256>(G, dzl, in, N, chunk, slab, bslab, s);
                 else uvm_launch_wgrad<2, 2, WW / 64, WW / 64, WW, WW, WW>(G, dzl, in, N, chunk, slab, bslab, s);
             });
+            UVM_DISPATCHED(known, "uvmlp_wgrad");
             CTX_CHECK_LAUNCH("uvmlp_wgrad");
             hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(W * W / 4, 64)), dim3(256), 0, s, slab, G, (int64_t)W * W, W, W, W, gws[li], kin,
                                has_emb ? input_ch : 0);
@@ -1379,10 +1392,11 @@ static int32_t uvm_bwd(const float *grad_raw, const float *grad_tex, const int32
         }
         if (has_emb) {
             float *bsl = has_hid ? nullptr : bslab;
-            uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
+            const bool known = uvm_dispatch(W, p.epad, [&](auto w, auto ep) {
                 constexpr int WW = decltype(w)::value, EE = decltype(ep)::value;
                 uvm_launch_wgrad<WW / 64, 1, 2, 2, WW, EE, EE>(Ge, dzl, emb, N, chunk_e, slab, bsl, s);
             });
+            UVM_DISPATCHED(known, "uvmlp_wgrad_emb");
             CTX_CHECK_LAUNCH("uvmlp_wgrad_emb");
             hipLaunchKernelGGL(k_uvm_reduce, dim3(cdiv(W * 64 / 4, 64)), dim3(256), 0, s, slab, Ge, (int64_t)W * 64, W, 64, input_ch, gws[li], kin, 0);
             if (!has_hid)

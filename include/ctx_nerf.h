@@ -191,7 +191,16 @@ int32_t ctx_face_view_map(const int64_t *face_idx, int32_t B, int32_t H, int32_t
 /* ---- texture field: get_embedder / NeRF2D (src/run_nerf_helpers.py:15-135) ---------------- */
 /* embed(x[N,d]) -> [N, d*(1+2L)], order [x, sin(2^0 x), cos(2^0 x), sin(2^1 x), ...]. */
 int32_t ctx_embed_fwd(const float *x, int64_t N, int32_t d, int32_t L, float *out, ctx_stream_t stream);
-/* Bytes of the packed-weight blob for NeRF2D(D,W,input_ch,output_ch,skip). */
+/* The envelope of every ctx_uvmlp_* entry point: 1 <= D <= 16 hidden layers, W in {64, 128, 256} (no other width: W = 192 is refused),
+   1 <= input_ch <= 64 (dims * (1 + 2L) with dims in {2, 3} where an entry takes dims / L; the embedding is padded to EP = 48 for
+   input_ch <= 48, else to 64), 1 <= output_ch <= 4, N >= 1.  Outside it the three size queries return -1 and every other entry
+   returns CTX_E_ARG before it launches anything.
+   skip: the hidden layer after which the embedding is concatenated again, i.e. layer skip + 1 reads [embedding, hidden].  A skip
+   outside [0, D-2] means NO skip layer to ctx_uvmlp_packed_bytes, ctx_uvmlp_pack and the forward entries (every hidden layer after the
+   first reads the hidden vector alone; ws[i] is then [W, W] for every 1 <= i < D), and is refused (CTX_E_ARG, nothing launched) by the
+   three backward entries ctx_uvmlp_bwd, ctx_uvmlp_bwd_idx and ctx_uvmlp_bwd_emb; so D = 1 is forward only. */
+/* Bytes of the packed-weight blob for NeRF2D(D,W,input_ch,output_ch,skip); never less than the parameters' 4 bytes each, and
+   non-decreasing in D. */
 int64_t ctx_uvmlp_packed_bytes(int32_t D, int32_t W, int32_t input_ch, int32_t output_ch, int32_t skip);
 /* Pack nn.Linear weights: ws[i] -> device float [out_i,in_i], bs[i] -> device float [out_i];
    index D is output_linear. */
@@ -210,7 +219,8 @@ int32_t ctx_uvmlp_fwd(const float *uv /*nullable*/, const float *emb /*nullable*
 /* General / training forward.  dims = 2 (uv, as ctx_uvmlp_fwd) or 3 (xyz sample points of the ray path: the reference's
    NeRF2D defaults, input_ch = 3*(1+2L) <= 64, output_ch = 4 = rgb + sigma); `uv` is then the [N,dims] point list.
    saved (nullable: plain forward) keeps what the backward needs (ctx_uvmlp_saved_bytes(N,D,W,input_ch) bytes: the padded
-   embedding [N,48|64], the post-ReLU activations [D,N,W] fp32 and the ReLU pattern as bit masks). */
+   embedding [N,EP], the post-ReLU activations [D,N,W] fp32 and the ReLU pattern as bit masks [D, ceil(N/64), W] u64:
+   N*(EP + D*W)*4 + D*ceil(N/64)*W*8). */
 int64_t ctx_uvmlp_saved_bytes(int64_t N, int32_t D, int32_t W, int32_t input_ch);
 int32_t ctx_uvmlp_fwd_save(const float *uv /*nullable*/, const float *emb /*nullable*/, int64_t N, int32_t res, const void *packed,
                            int32_t D, int32_t W, int32_t dims, int32_t L, int32_t output_ch, int32_t skip,

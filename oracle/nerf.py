@@ -34,12 +34,13 @@ def nerf2d_forward(e, weights, biases, out_w, out_b, skips=(4,), dtype=np.float3
 
 
 def nerf2d_backward(e, weights, biases, out_w, out_b, grad_raw=None, grad_tex=None, skips=(4,), dtype=np.float64, masks=None,
-                    return_pre=False):
+                    return_pre=False, return_emb=False):
     """Parameter gradients of NeRF2D.  grad_raw: d loss / d raw [N,C]; grad_tex: d loss / d ((tanh(raw)+1)/2) [N,C].
     Returns (gws, gbs) with index D = output_linear, nn.Linear layouts.
     masks (optional, list of bool [N,W]): the ReLU derivative pattern to use instead of (pre-activation > 0) — a comparison
     against an fp32 implementation must share the pattern, since a unit whose pre-activation is ~1e-7 may round to either
-    side and one flipped unit moves a gradient entry by a whole term.  return_pre: also return the pre-activations."""
+    side and one flipped unit moves a gradient entry by a whole term.  return_pre: also return the pre-activations.
+    return_emb: also return (last) d loss / d e [N, input_ch] = dZ_0 . W_0 + sum over s in skips of dZ_{s+1} . W_{s+1}[:, :input_ch]."""
     e = np.asarray(e, dtype)
     ins, acts, pre = [], [], []
     h = e
@@ -62,14 +63,18 @@ def nerf2d_backward(e, weights, biases, out_w, out_b, grad_raw=None, grad_tex=No
     gws[D] = g.T @ h
     gbs[D] = g.sum(0)
     dh = g @ np.asarray(out_w, dtype)                   # wrt the input of output_linear (no skip-cat after the last layer)
+    ge = np.zeros_like(e)
     for i in range(D - 1, -1, -1):
         if i in skips:
-            dh = dh[:, e.shape[1]:]                     # the cat put the (non-trainable) embedding first
+            ge = ge + dh[:, :e.shape[1]]                # the cat put the embedding first: layer i+1's gradient to it
+            dh = dh[:, e.shape[1]:]
         dz = dh * ((acts[i] > 0) if masks is None else masks[i])
         gws[i] = dz.T @ ins[i]
         gbs[i] = dz.sum(0)
         dh = dz @ np.asarray(weights[i], dtype)
-    return (gws, gbs, pre) if return_pre else (gws, gbs)
+    ge = ge + dh
+    out = (gws, gbs, pre) if return_pre else (gws, gbs)
+    return out + (ge,) if return_emb else out
 
 
 def texture_from_mlp(mlp_out, res):
