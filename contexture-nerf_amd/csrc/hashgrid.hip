@@ -18,73 +18,30 @@
 // computed on the host.
 #include "hashgrid_common.h"
 
-struct HgGrid {
+// the table, and the box that maps a position to unit coordinates
+struct HgGrid : HgTable {
     float lo[3], hi[3];
-    int res[HG_MAX_LEVELS];
-    int Lv, log2T;
 };
 
 // what every entry point accepts
 static int32_t hg_check(const char *who, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res, const float *lo, const float *hi, HgGrid &g)
 {
     CTX_REQUIRE(res && lo && hi, "%s: null res / lo / hi", who);
-    CTX_REQUIRE(Lv >= 1 && Lv <= HG_MAX_LEVELS, "%s: Lv=%d outside [1, %d]", who, Lv, HG_MAX_LEVELS);
-    CTX_REQUIRE(F == 1 || F == 2 || F == 4, "%s: F=%d (1, 2 or 4 features per entry)", who, F);
-    CTX_REQUIRE(Lv * F <= 64, "%s: Lv*F=%d above 64, the width of the field's embedding", who, Lv * F);
-    CTX_REQUIRE(log2T >= 4 && log2T <= 22, "%s: log2T=%d outside [4, 22]", who, log2T);
+    if (int32_t rc = hg_check_table(who, Lv, F, log2T, res, g)) return rc;
     for (int a = 0; a < 3; ++a) {
         CTX_REQUIRE(isfinite(lo[a]) && isfinite(hi[a]) && lo[a] < hi[a], "%s: box axis %d: want finite lo < hi (lo=%g hi=%g)", who, a, lo[a], hi[a]);
         g.lo[a] = lo[a]; g.hi[a] = hi[a];
     }
-    for (int l = 0; l < Lv; ++l) {
-        CTX_REQUIRE(res[l] >= 1 && res[l] <= (1 << 20), "%s: res[%d]=%d outside [1, 2^20]", who, l, res[l]);
-        g.res[l] = res[l];
-    }
-    g.Lv = Lv; g.log2T = log2T;
     return CTX_OK;
 }
 
-// A point on one level, axis by axis: cell i, weight w inside it, and whether the axis is active, i.e. strictly inside the box before the
-// clamp (x > 0 && x < 1: false for NaN, +-inf and the faces).  NaN clamps to 0, so every index is in range.
-struct HgAxes { int i[3]; float w[3]; bool active[3]; };
-__device__ __forceinline__ HgAxes hg_axes(const float *__restrict__ pts, int64_t n, const HgGrid &g, int l)
+// point n on level l: its unit coordinates in the box, axis by axis; every row is live
+__device__ __forceinline__ HgAxes<3> hg_axes(const float *__restrict__ pts, int64_t n, const HgGrid &g, int l)
 {
-    const int res = g.res[l];
-    HgAxes ax;
+    float x[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float x = (pts[n * 3 + a] - g.lo[a]) / (g.hi[a] - g.lo[a]);
-        ax.active[a] = x > 0.0f && x < 1.0f;
-        x = fminf(fmaxf(x, 0.0f), 1.0f);
-        const float pos = x * (float)res;
-        ax.i[a] = min((int)floorf(pos), res - 1);
-        ax.w[a] = pos - (float)ax.i[a];
-    }
-    return ax;
-}
-
-// A point's cell at one level: entry index and weight of the 8 corners, c = cx + 2 cy + 4 cz.
-struct HgCell { uint32_t idx[8]; float w[8]; };
-__device__ __forceinline__ HgCell hg_cell(const HgAxes &ax, const HgGrid &g, int l)
-{
-    const int res = g.res[l];
-    const uint32_t T = 1u << g.log2T;
-    const int64_t side = (int64_t)res + 1;
-    const bool dense = side * side * side <= (int64_t)T;
-    HgCell c;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
-        const uint32_t gx = (uint32_t)(ax.i[0] + bx), gy = (uint32_t)(ax.i[1] + by), gz = (uint32_t)(ax.i[2] + bz);
-        c.idx[k] = dense ? gx + (uint32_t)side * (gy + (uint32_t)side * gz) : ((gx ^ (gy * 2654435761u) ^ (gz * 805459861u)) & (T - 1));
-        const float sx = bx ? ax.w[0] : 1.0f - ax.w[0], sy = by ? ax.w[1] : 1.0f - ax.w[1], sz = bz ? ax.w[2] : 1.0f - ax.w[2];
-        c.w[k] = (sx * sy) * sz;
-    }
-    return c;
-}
-__device__ __forceinline__ HgCell hg_cell(const float *__restrict__ pts, int64_t n, const HgGrid &g, int l)
-{
-    return hg_cell(hg_axes(pts, n, g, l), g, l);
+    for (int a = 0; a < 3; ++a) x[a] = (pts[n * 3 + a] - g.lo[a]) / (g.hi[a] - g.lo[a]);
+    return hg_axes<3>(x, g.res[l]);
 }
 
 template <int F>
@@ -95,20 +52,9 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_fwd(const float *__restri
     const int l = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const HgCell c = hg_cell(pts, p, g, l);
-    const float *tl = table + ((int64_t)l << g.log2T) * F;
-    float t[8][F];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) *(V *)t[k] = *(const V *)(tl + (int64_t)c.idx[k] * F);   // the 8 gathers in flight together
     float o[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        float s = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s = s + c.w[k] * t[k][f];
-        o[f] = s;
-    }
-    *(V *)(emb + p * ((int64_t)g.Lv * F) + l * F) = *(const V *)o;
+    hg_interpolate<3, F>(hg_axes(pts, p, g, l), g, l, table, o);
+    *(V *)(emb + hg_row<F>(p, g, l)) = *(const V *)o;
 }
 
 extern "C" int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *table, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
@@ -118,17 +64,13 @@ extern "C" int32_t ctx_hashgrid_fwd(const float *pts, int64_t n, const float *ta
     if (int32_t rc = hg_check("hashgrid_fwd", Lv, F, log2T, res, lo, hi, g)) return rc;
     CTX_REQUIRE(pts && table && emb, "hashgrid_fwd: null pointer");
     CTX_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "hashgrid_fwd: n=%lld outside [1, 2^31)", (long long)n);
-    const dim3 grid((unsigned)cdiv64(n, HG_BLOCK), Lv);
-    hipStream_t s = (hipStream_t)stream;
-    if (F == 1) hipLaunchKernelGGL(k_hashgrid_fwd<1>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
-    else if (F == 2) hipLaunchKernelGGL(k_hashgrid_fwd<2>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
-    else hipLaunchKernelGGL(k_hashgrid_fwd<4>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g, emb);
+    HG_LAUNCH_F(k_hashgrid_fwd, F, dim3((unsigned)cdiv64(n, HG_BLOCK), Lv), dim3(HG_BLOCK), 0, (hipStream_t)stream, pts, n, table, g, emb);
     CTX_CHECK_LAUNCH("hashgrid_fwd");
     return CTX_OK;
 }
 
 // ---- backward to the table -------------------------------------------------------------------------------------------------------
-// HgCtl, the absmax / scale / convert kernels and hg_pow2 are in hashgrid_common.h: the 2-D texture field (hashtex.hip) uses them too
+// the accumulator, its helper kernels and the host driver are in hashgrid_common.h.  Points arrive unordered: every lane adds its own terms
 template <int F>
 __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd(const float *__restrict__ pts, int64_t n, const float *__restrict__ g_emb, HgGrid g, int E,
                                                            const HgCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
@@ -138,25 +80,15 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd(const float *__restri
     const int l = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const double scale = hg_pow2(E - ctl->x);
     float ge[F];
-    *(V *)ge = *(const V *)(g_emb + p * ((int64_t)g.Lv * F) + l * F);
-    const HgCell c = hg_cell(pts, p, g, l);
-    unsigned long long *al = acc + ((int64_t)l << g.log2T) * F;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const float prod = c.w[k] * ge[f];                                  // one rounding
-            const long long q = __double2ll_rn((double)prod * scale);           // |prod| < 2^x: |q| <= 2^E, exact scaling, nearest even
-            if (q) atomicAdd(al + (int64_t)c.idx[k] * F + f, (unsigned long long)q);
-        }
+    *(V *)ge = *(const V *)(g_emb + hg_row<F>(p, g, l));
+    hg_accumulate<3, F>(hg_cell(hg_axes(pts, p, g, l), g.res[l], g.log2T), ge, hg_pow2(E - ctl->x), acc + ((int64_t)l << g.log2T) * F,
+                        [](uint32_t, const long long (&)[F]) { return true; });
 }
 
 extern "C" int64_t ctx_hashgrid_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T)
 {
-    if (Lv < 1 || Lv > HG_MAX_LEVELS || !(F == 1 || F == 2 || F == 4) || Lv * F > 64 || log2T < 4 || log2T > 22) return -1;
-    return hg_align(((int64_t)Lv << log2T) * F * 8) + 256;      // the int64 accumulator [Lv, T, F], then the control words
+    return hg_table_bwd_ws_bytes("hashgrid_bwd_ws_bytes", Lv, F, log2T);
 }
 
 extern "C" int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_emb, int32_t Lv, int32_t F, int32_t log2T, const int32_t *res,
@@ -166,29 +98,13 @@ extern "C" int32_t ctx_hashgrid_bwd(const float *pts, int64_t n, const float *g_
     if (int32_t rc = hg_check("hashgrid_bwd", Lv, F, log2T, res, lo, hi, g)) return rc;
     CTX_REQUIRE(pts && g_emb && ws && g_table, "hashgrid_bwd: null pointer");
     CTX_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "hashgrid_bwd: n=%lld outside [1, 2^31)", (long long)n);
-    CTX_REQUIRE(stages >= 1 && stages <= 7, "hashgrid_bwd: stages=%d (bits: 1 zero, 2 accumulate, 4 convert; 7 is the backward)", stages);
-    const int64_t count = ((int64_t)Lv << log2T) * F;
-    unsigned long long *acc = (unsigned long long *)ws;
-    HgCtl *ctl = (HgCtl *)((char *)ws + hg_align(count * 8));
-    const int E = hg_acc_exponent(n, 8);
     hipStream_t s = (hipStream_t)stream;
-    if (stages & 1) {
-        (void)hipMemsetAsync(acc, 0, count * 8, s);
-        (void)hipMemsetAsync(ctl, 0, sizeof(HgCtl), s);
-    }
-    if (stages & 2) {
-        hipLaunchKernelGGL(k_hashgrid_absmax, dim3(capped_blocks(n * Lv * F, HG_BLOCK * 4, 1024)), dim3(HG_BLOCK), 0, s, g_emb, n * Lv * F, ctl);
-        hipLaunchKernelGGL(k_hashgrid_scale, dim3(1), dim3(1), 0, s, ctl);
-        const dim3 grid((unsigned)cdiv64(n, HG_BLOCK), Lv);
-        if (F == 1) hipLaunchKernelGGL(k_hashgrid_bwd<1>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
-        else if (F == 2) hipLaunchKernelGGL(k_hashgrid_bwd<2>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
-        else hipLaunchKernelGGL(k_hashgrid_bwd<4>, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
-    }
-    if (stages & 4)
-        hipLaunchKernelGGL(k_hashgrid_convert, dim3(capped_blocks(count, HG_BLOCK * 4, 4096)), dim3(HG_BLOCK), 0, s, (const long long *)acc, count, E,
-                           ctl, g_table);
-    CTX_CHECK_LAUNCH("hashgrid_bwd");
-    return CTX_OK;
+    return hg_table_bwd<3>(
+        "hashgrid_bwd", n, g, F, stages, ws, g_table, s,
+        [&](dim3 blocks, HgCtl *ctl) { hipLaunchKernelGGL(k_hashgrid_absmax, blocks, dim3(HG_BLOCK), 0, s, g_emb, n * Lv * F, ctl); },
+        [&](dim3 grid, int E, const HgCtl *ctl, unsigned long long *acc) {
+            HG_LAUNCH_F(k_hashgrid_bwd, F, grid, dim3(HG_BLOCK), 0, s, pts, n, g_emb, g, E, ctl, acc);
+        });
 }
 
 // ---- backward to the positions ---------------------------------------------------------------------------------------------------
@@ -199,14 +115,14 @@ __device__ __forceinline__ void hg_level_grad(const float *__restrict__ pts, int
                                               const float *__restrict__ g_emb, const HgGrid &g, int l, float out[3])
 {
     typedef typename HgVec<F>::type V;
-    const HgAxes ax = hg_axes(pts, p, g, l);
-    const HgCell c = hg_cell(ax, g, l);
+    const HgAxes<3> ax = hg_axes(pts, p, g, l);
+    const HgCell<3> c = hg_cell(ax, g.res[l], g.log2T);
     const float *tl = table + ((int64_t)l << g.log2T) * F;
     float t[8][F];
 #pragma unroll
     for (int k = 0; k < 8; ++k) *(V *)t[k] = *(const V *)(tl + (int64_t)c.idx[k] * F);   // the 8 gathers in flight together
     float ge[F];
-    *(V *)ge = *(const V *)(g_emb + p * ((int64_t)g.Lv * F) + l * F);
+    *(V *)ge = *(const V *)(g_emb + hg_row<F>(p, g, l));
     float d[3][F];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -255,7 +171,7 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd_pts_sum(const float *
 {
     const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const HgAxes ax = hg_axes(pts, p, g, 0);                                              // the active flags do not depend on the level
+    const HgAxes<3> ax = hg_axes(pts, p, g, 0);                                              // the active flags do not depend on the level
     float s[3] = {0.0f, 0.0f, 0.0f};
     for (int l = 0; l < g.Lv; ++l) {
         const float *src = part + ((int64_t)l * n + p) * 3;
@@ -276,7 +192,7 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_bwd_pts_loop(const float 
 {
     const int64_t p = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const HgAxes ax = hg_axes(pts, p, g, 0);
+    const HgAxes<3> ax = hg_axes(pts, p, g, 0);
     float s[3] = {0.0f, 0.0f, 0.0f};
     for (int l = 0; l < g.Lv; ++l) {
         float o[3];
@@ -305,17 +221,11 @@ extern "C" int32_t ctx_hashgrid_bwd_pts(const float *pts, int64_t n, const float
     hipStream_t s = (hipStream_t)stream;
     const int forced = ctx_env_int("CTX_HASHGRID_PTS_LOOP", -1);  // read per call: a tool measures both mappings in one process
     if (forced < 0 ? n >= HG_PTS_LOOP_MIN_N : forced != 0) {
-        const dim3 grid1((unsigned)cdiv64(n, HG_BLOCK));
-        if (F == 1) hipLaunchKernelGGL(k_hashgrid_bwd_pts_loop<1>, grid1, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, g_pts);
-        else if (F == 2) hipLaunchKernelGGL(k_hashgrid_bwd_pts_loop<2>, grid1, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, g_pts);
-        else hipLaunchKernelGGL(k_hashgrid_bwd_pts_loop<4>, grid1, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, g_pts);
+        HG_LAUNCH_F(k_hashgrid_bwd_pts_loop, F, dim3((unsigned)cdiv64(n, HG_BLOCK)), dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, g_pts);
         CTX_CHECK_LAUNCH("hashgrid_bwd_pts");
         return CTX_OK;
     }
-    const dim3 grid((unsigned)cdiv64(n, HG_BLOCK), Lv);
-    if (F == 1) hipLaunchKernelGGL(k_hashgrid_bwd_pts<1>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, part);
-    else if (F == 2) hipLaunchKernelGGL(k_hashgrid_bwd_pts<2>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, part);
-    else hipLaunchKernelGGL(k_hashgrid_bwd_pts<4>, grid, dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, part);
+    HG_LAUNCH_F(k_hashgrid_bwd_pts, F, dim3((unsigned)cdiv64(n, HG_BLOCK), Lv), dim3(HG_BLOCK), 0, s, pts, n, table, g_emb, g, part);
     hipLaunchKernelGGL(k_hashgrid_bwd_pts_sum, dim3((unsigned)cdiv64(n, HG_BLOCK)), dim3(HG_BLOCK), 0, s, pts, n, g, (const float *)part, g_pts);
     CTX_CHECK_LAUNCH("hashgrid_bwd_pts");
     return CTX_OK;

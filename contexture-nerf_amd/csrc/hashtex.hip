@@ -14,10 +14,6 @@
 // its order) and only the run's first lane issues the atomic.  CTX_HASHTEX_PRESUM=0 turns that off.
 #include "hashgrid_common.h"
 
-struct HtGrid {
-    int res[HG_MAX_LEVELS];
-    int Lv, log2T;
-};
 // how the rows are named: uv [n,2], or nodes of the grid x grid atlas (idx null: node = row)
 struct HtRows {
     const float *uv;
@@ -26,18 +22,10 @@ struct HtRows {
 };
 
 static int32_t ht_check(const char *who, const float *uv, const int32_t *idx, int64_t n, int32_t grid, int32_t Lv, int32_t F, int32_t log2T,
-                        const int32_t *res, HtGrid &g, HtRows &rows)
+                        const int32_t *res, HgTable &g, HtRows &rows)
 {
     CTX_REQUIRE(res, "%s: null res", who);
-    CTX_REQUIRE(Lv >= 1 && Lv <= HG_MAX_LEVELS, "%s: Lv=%d outside [1, %d]", who, Lv, HG_MAX_LEVELS);
-    CTX_REQUIRE(F == 1 || F == 2 || F == 4, "%s: F=%d (1, 2 or 4 features per entry)", who, F);
-    CTX_REQUIRE(Lv * F <= 64, "%s: Lv*F=%d above 64, the width of the field's embedding", who, Lv * F);
-    CTX_REQUIRE(log2T >= 4 && log2T <= 22, "%s: log2T=%d outside [4, 22]", who, log2T);
-    for (int l = 0; l < Lv; ++l) {
-        CTX_REQUIRE(res[l] >= 1 && res[l] <= (1 << 20), "%s: res[%d]=%d outside [1, 2^20]", who, l, res[l]);
-        g.res[l] = res[l];
-    }
-    g.Lv = Lv; g.log2T = log2T;
+    if (int32_t rc = hg_check_table(who, Lv, F, log2T, res, g)) return rc;
     CTX_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "%s: n=%lld outside [1, 2^31)", who, (long long)n);
     if (uv) {
         CTX_REQUIRE(!idx && grid == 0, "%s: points (uv) exclude a texel list and a grid (idx=%p, grid=%d)", who, (const void *)idx, grid);
@@ -49,12 +37,12 @@ static int32_t ht_check(const char *who, const float *uv, const int32_t *idx, in
     return CTX_OK;
 }
 
-// The row's point.  false: a list entry outside the atlas (a zero row that takes no part in the backward).
-__device__ __forceinline__ bool ht_point(const HtRows &rows, int64_t r, float &u, float &v)
+// The row's point x = (u, v), already unit coordinates.  false: a list entry outside the atlas (a zero row that takes no part in the backward).
+__device__ __forceinline__ bool ht_point(const HtRows &rows, int64_t r, float (&x)[2])
 {
     if (rows.uv) {
-        u = rows.uv[r * 2 + 0];
-        v = rows.uv[r * 2 + 1];
+        x[0] = rows.uv[r * 2 + 0];
+        x[1] = rows.uv[r * 2 + 1];
         return true;
     }
     const int grid = rows.grid;
@@ -67,43 +55,13 @@ __device__ __forceinline__ bool ht_point(const HtRows &rows, int64_t r, float &u
     // built with contraction and fuses its `1.0f - (float)(res-1-j) * step`; this file is not, so the fused operation is written out
     const int i = (int)(node / grid), j = (int)(node % grid);
     const float step = 1.0f / (float)(grid - 1);
-    u = (j < grid / 2) ? (float)j * step : fmaf(-(float)(grid - 1 - j), step, 1.0f);
-    v = (i < grid / 2) ? (float)i * step : fmaf(-(float)(grid - 1 - i), step, 1.0f);
+    x[0] = (j < grid / 2) ? (float)j * step : fmaf(-(float)(grid - 1 - j), step, 1.0f);
+    x[1] = (i < grid / 2) ? (float)i * step : fmaf(-(float)(grid - 1 - i), step, 1.0f);
     return true;
 }
 
-// A point's cell at one level: entry index and weight of the 4 corners, c = cx + 2 cy.  NaN clamps to 0, so every index is in range.
-struct HtCell { uint32_t idx[4]; float w[4]; };
-__device__ __forceinline__ HtCell ht_cell(float u, float v, const HtGrid &g, int l)
-{
-    const int res = g.res[l];
-    const uint32_t T = 1u << g.log2T;
-    const int64_t side = (int64_t)res + 1;
-    const bool dense = side * side <= (int64_t)T;
-    const float p[2] = {u, v};
-    int i[2];
-    float w[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const float x = fminf(fmaxf(p[a], 0.0f), 1.0f);
-        const float pos = x * (float)res;
-        i[a] = min((int)floorf(pos), res - 1);
-        w[a] = pos - (float)i[a];
-    }
-    HtCell c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int bx = k & 1, by = (k >> 1) & 1;
-        const uint32_t gx = (uint32_t)(i[0] + bx), gy = (uint32_t)(i[1] + by);
-        c.idx[k] = dense ? gx + (uint32_t)side * gy : ((gx ^ (gy * 2654435761u)) & (T - 1));
-        const float sx = bx ? w[0] : 1.0f - w[0], sy = by ? w[1] : 1.0f - w[1];
-        c.w[k] = sx * sy;
-    }
-    return c;
-}
-
 template <int F>
-__global__ __launch_bounds__(HG_BLOCK) void k_hashtex_fwd(HtRows rows, int64_t n, const float *__restrict__ table, HtGrid g, float *__restrict__ emb)
+__global__ __launch_bounds__(HG_BLOCK) void k_hashtex_fwd(HtRows rows, int64_t n, const float *__restrict__ table, HgTable g, float *__restrict__ emb)
 {
     typedef typename HgVec<F>::type V;
     const int l = blockIdx.y;
@@ -112,41 +70,19 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashtex_fwd(HtRows rows, int64_t n
     float o[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) o[f] = 0.0f;
-    float u, v;
-    if (ht_point(rows, r, u, v)) {
-        const HtCell c = ht_cell(u, v, g, l);
-        const float *tl = table + ((int64_t)l << g.log2T) * F;
-        float t[4][F];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) *(V *)t[k] = *(const V *)(tl + (int64_t)c.idx[k] * F);   // the 4 gathers in flight together
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            float s = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s = s + c.w[k] * t[k][f];
-            o[f] = s;
-        }
-    }
-    *(V *)(emb + r * ((int64_t)g.Lv * F) + l * F) = *(const V *)o;
+    float x[2];
+    if (ht_point(rows, r, x)) hg_interpolate<2, F>(hg_axes<2>(x, g.res[l]), g, l, table, o);
+    *(V *)(emb + hg_row<F>(r, g, l)) = *(const V *)o;
 }
-
-#define HT_LAUNCH_F(kernel, F, ...)                                                          \
-    do {                                                                                     \
-        if (F == 1) hipLaunchKernelGGL(kernel<1>, __VA_ARGS__);                              \
-        else if (F == 2) hipLaunchKernelGGL(kernel<2>, __VA_ARGS__);                         \
-        else hipLaunchKernelGGL(kernel<4>, __VA_ARGS__);                                     \
-    } while (0)
 
 extern "C" int32_t ctx_hashtex_fwd(const float *uv, const int32_t *idx, int64_t n, int32_t grid, const float *table, int32_t Lv, int32_t F,
                                    int32_t log2T, const int32_t *res, float *emb, ctx_stream_t stream)
 {
-    HtGrid g;
+    HgTable g;
     HtRows rows;
     if (int32_t rc = ht_check("hashtex_fwd", uv, idx, n, grid, Lv, F, log2T, res, g, rows)) return rc;
     CTX_REQUIRE(table && emb, "hashtex_fwd: null pointer");
-    const dim3 blocks((unsigned)cdiv64(n, HG_BLOCK), Lv);
-    hipStream_t s = (hipStream_t)stream;
-    HT_LAUNCH_F(k_hashtex_fwd, F, blocks, dim3(HG_BLOCK), 0, s, rows, n, table, g, emb);
+    HG_LAUNCH_F(k_hashtex_fwd, F, dim3((unsigned)cdiv64(n, HG_BLOCK), Lv), dim3(HG_BLOCK), 0, (hipStream_t)stream, rows, n, table, g, emb);
     CTX_CHECK_LAUNCH("hashtex_fwd");
     return CTX_OK;
 }
@@ -162,14 +98,7 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashtex_absmax_list(const float *_
         const int64_t node = idx[i / width];
         if (node >= 0 && node < plane) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
     }
-    for (int o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    __shared__ uint32_t s_m[HG_BLOCK / 64];
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {                        // one atomic per workgroup
-        for (int k = 1; k < HG_BLOCK / 64; ++k) m = max(m, s_m[k]);
-        if (m) atomicMax(&ctl->absmax, m);
-    }
+    hg_absmax_commit(m, ctl);
 }
 
 // Every lane of the wave calls this.  Lanes lane .. end-1 form the run this lane belongs to (adjacent lanes with one key); returns the sum
@@ -185,90 +114,60 @@ __device__ __forceinline__ long long ht_run_sum(long long q, int lane, int end)
 }
 
 template <int F>
-__global__ __launch_bounds__(HG_BLOCK) void k_hashtex_bwd(HtRows rows, int64_t n, const float *__restrict__ g_emb, HtGrid g, int E, int presum,
+__global__ __launch_bounds__(HG_BLOCK) void k_hashtex_bwd(HtRows rows, int64_t n, const float *__restrict__ g_emb, HgTable g, int E, int presum,
                                                           const HgCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
 {
     typedef typename HgVec<F>::type V;
     if (ctl->status != 0) return;                  // uniform over the grid
     const int l = blockIdx.y;
     const int64_t r = (int64_t)blockIdx.x * HG_BLOCK + threadIdx.x;
-    float u = 0.0f, v = 0.0f;
-    const bool live = r < n && ht_point(rows, r, u, v);     // a lane that is not live stays for the shuffles, with terms of 0 and a key of its own
-    const double scale = hg_pow2(E - ctl->x);
+    float x[2] = {0.0f, 0.0f};
+    const bool live = r < n && ht_point(rows, r, x);        // a lane that is not live stays for the shuffles, with terms of 0 and a key of its own
     float ge[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) ge[f] = 0.0f;
-    if (live) *(V *)ge = *(const V *)(g_emb + r * ((int64_t)g.Lv * F) + l * F);
-    const HtCell c = ht_cell(u, v, g, l);
-    unsigned long long *al = acc + ((int64_t)l << g.log2T) * F;
+    for (int f = 0; f < F; ++f) ge[f] = 0.0f;               // times the finite weights of the point (0, 0): every term of such a lane is 0
+    if (live) *(V *)ge = *(const V *)(g_emb + hg_row<F>(r, g, l));
     const int lane = threadIdx.x & 63;
+    hg_accumulate<2, F>(hg_cell(hg_axes<2>(x, g.res[l]), g.res[l], g.log2T), ge, hg_pow2(E - ctl->x), acc + ((int64_t)l << g.log2T) * F,
+                        [&](uint32_t entry, long long (&q)[F]) {
+        if (!presum) return live;
+        const uint32_t key = live ? entry : 0xffffffffu;                        // no entry has this index: T <= 2^22
+        const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
+        const bool first = lane == 0 || prev != key || !live;
+        const unsigned long long heads = __ballot(first);
+        if (heads != ~0ull) {                                                   // uniform: some run is longer than one lane
+            const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+            const int end = after ? lane + 1 + __ffsll((long long)after) - 1 : 64;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        long long q[F];
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const float prod = c.w[k] * ge[f];                                  // one rounding
-            q[f] = live ? __double2ll_rn((double)prod * scale) : 0;             // |prod| < 2^x: |q| <= 2^E, exact scaling, nearest even
+            for (int f = 0; f < F; ++f) q[f] = ht_run_sum(q[f], lane, end);
         }
-        bool first = true;
-        if (presum) {
-            const uint32_t key = live ? c.idx[k] : 0xffffffffu;                 // no entry has this index: T <= 2^22
-            const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
-            first = lane == 0 || prev != key || !live;
-            const unsigned long long heads = __ballot(first);
-            if (heads != ~0ull) {                                               // uniform: some run is longer than one lane
-                const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-                const int end = after ? lane + 1 + __ffsll((long long)after) - 1 : 64;
-#pragma unroll
-                for (int f = 0; f < F; ++f) q[f] = ht_run_sum(q[f], lane, end);
-            }
-        }
-        if (live && first) {
-#pragma unroll
-            for (int f = 0; f < F; ++f)
-                if (q[f]) atomicAdd(al + (int64_t)c.idx[k] * F + f, (unsigned long long)q[f]);
-        }
-    }
+        return live && first;
+    });
 }
 
 extern "C" int64_t ctx_hashtex_bwd_ws_bytes(int32_t Lv, int32_t F, int32_t log2T)
 {
-    if (Lv < 1 || Lv > HG_MAX_LEVELS || !(F == 1 || F == 2 || F == 4) || Lv * F > 64 || log2T < 4 || log2T > 22) return -1;
-    return hg_align(((int64_t)Lv << log2T) * F * 8) + 256;      // the int64 accumulator [Lv, T, F], then the control words
+    return hg_table_bwd_ws_bytes("hashtex_bwd_ws_bytes", Lv, F, log2T);
 }
 
 extern "C" int32_t ctx_hashtex_bwd(const float *uv, const int32_t *idx, int64_t n, int32_t grid, const float *g_emb, int32_t Lv, int32_t F,
                                    int32_t log2T, const int32_t *res, int32_t stages, void *ws, float *g_table, ctx_stream_t stream)
 {
-    HtGrid g;
+    HgTable g;
     HtRows rows;
     if (int32_t rc = ht_check("hashtex_bwd", uv, idx, n, grid, Lv, F, log2T, res, g, rows)) return rc;
     CTX_REQUIRE(g_emb && ws && g_table, "hashtex_bwd: null pointer");
-    CTX_REQUIRE(stages >= 1 && stages <= 7, "hashtex_bwd: stages=%d (bits: 1 zero, 2 accumulate, 4 convert; 7 is the backward)", stages);
-    const int64_t count = ((int64_t)Lv << log2T) * F;
-    unsigned long long *acc = (unsigned long long *)ws;
-    HgCtl *ctl = (HgCtl *)((char *)ws + hg_align(count * 8));
-    const int E = hg_acc_exponent(n, 4);
     const int presum = ctx_env_int("CTX_HASHTEX_PRESUM", 1) != 0;   // read per call: a tool times both forms in one process
     hipStream_t s = (hipStream_t)stream;
-    if (stages & 1) {
-        (void)hipMemsetAsync(acc, 0, count * 8, s);
-        (void)hipMemsetAsync(ctl, 0, sizeof(HgCtl), s);
-    }
-    if (stages & 2) {
-        const int64_t total = n * Lv * F;
-        const dim3 rb(capped_blocks(total, HG_BLOCK * 4, 1024));
-        if (idx) hipLaunchKernelGGL(k_hashtex_absmax_list, rb, dim3(HG_BLOCK), 0, s, g_emb, total, Lv * F, idx, (int64_t)grid * grid, ctl);
-        else hipLaunchKernelGGL(k_hashgrid_absmax, rb, dim3(HG_BLOCK), 0, s, g_emb, total, ctl);
-        hipLaunchKernelGGL(k_hashgrid_scale, dim3(1), dim3(1), 0, s, ctl);
-        const dim3 blocks((unsigned)cdiv64(n, HG_BLOCK), Lv);
-        HT_LAUNCH_F(k_hashtex_bwd, F, blocks, dim3(HG_BLOCK), 0, s, rows, n, g_emb, g, E, presum, ctl, acc);
-    }
-    if (stages & 4)
-        hipLaunchKernelGGL(k_hashgrid_convert, dim3(capped_blocks(count, HG_BLOCK * 4, 4096)), dim3(HG_BLOCK), 0, s, (const long long *)acc, count, E,
-                           ctl, g_table);
-    CTX_CHECK_LAUNCH("hashtex_bwd");
-    return CTX_OK;
+    return hg_table_bwd<2>(
+        "hashtex_bwd", n, g, F, stages, ws, g_table, s,
+        [&](dim3 blocks, HgCtl *ctl) {
+            if (idx) hipLaunchKernelGGL(k_hashtex_absmax_list, blocks, dim3(HG_BLOCK), 0, s, g_emb, n * Lv * F, Lv * F, idx, (int64_t)grid * grid, ctl);
+            else hipLaunchKernelGGL(k_hashgrid_absmax, blocks, dim3(HG_BLOCK), 0, s, g_emb, n * Lv * F, ctl);
+        },
+        [&](dim3 blocks, int E, const HgCtl *ctl, unsigned long long *acc) {
+            HG_LAUNCH_F(k_hashtex_bwd, F, blocks, dim3(HG_BLOCK), 0, s, rows, n, g_emb, g, E, presum, ctl, acc);
+        });
 }
 
 // ---- the head: raw -> atlas ----------------------------------------------------------------------------------------------------------

@@ -32,14 +32,36 @@ def level_resolutions(n_levels, base_res, max_res):
     return np.array([int(math.floor(base_res * math.exp(l * b))) for l in range(n_levels)], np.int32)
 
 
-class _DeferredTable:
-    """What the two encodings share around the table's backward: the workspace of the integer accumulator, and the deferred mode that
-    optim.FieldAdam(encodings=...) switches on.  Deferred: the first backward since the last step / zero_grad only accumulates (stage 2,
-    behind stage 1 unless the workspace is known to be zero), remembers its rows and returns no gradient: FieldAdam.step reads the
-    sums (`ctx_table_adam`, which leaves the workspace zero).  A later backward before the step flushes the sums into a float gradient
-    (stage 4), runs as without deferral (stages 7) and returns the sum of the two; from then on to the step every backward does.
-    Outside deferred mode nothing here changes what the backward computes."""
+class _DeferredTable(nn.Module):
+    """What the two encodings share: the table with the checks of its parameters, and around its backward the workspace of the integer
+    accumulator and the deferred mode that optim.FieldAdam(encodings=...) switches on.  Deferred: the first backward since the last step /
+    zero_grad only accumulates (stage 2, behind stage 1 unless the workspace is known to be zero), remembers its rows and returns no
+    gradient: FieldAdam.step reads the sums (`ctx_table_adam`, which leaves the workspace zero).  A later backward before the step
+    flushes the sums into a float gradient (stage 4), runs as without deferral (stages 7) and returns the sum of the two; from then on to
+    the step every backward does.  Outside deferred mode nothing here changes what the backward computes."""
     _corners = 8
+
+    def __init__(self, who, n_levels, n_features, log2_table, base_res, max_res):
+        super().__init__()
+        for name, v in (("n_levels", n_levels), ("n_features", n_features), ("log2_table", log2_table), ("base_res", base_res),
+                        ("max_res", max_res)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise L.CtxError(f"{who}: {name}={v!r}: want an int")
+        if not 1 <= n_levels <= MAX_LEVELS:
+            raise L.CtxError(f"{who}: n_levels={n_levels} outside [1, {MAX_LEVELS}]")
+        if n_features not in (1, 2, 4):
+            raise L.CtxError(f"{who}: n_features={n_features}: want 1, 2 or 4 features per entry")
+        if n_levels * n_features > MAX_WIDTH:
+            raise L.CtxError(f"{who}: n_levels * n_features = {n_levels * n_features} is wider than the field's {MAX_WIDTH}-column embedding")
+        if not 4 <= log2_table <= 22:
+            raise L.CtxError(f"{who}: log2_table={log2_table} outside [4, 22]")
+        if not 1 <= base_res <= max_res <= MAX_RES:
+            raise L.CtxError(f"{who}: want 1 <= base_res <= max_res <= 2^20, got base_res={base_res}, max_res={max_res}")
+        self.n_levels, self.n_features, self.log2_table = int(n_levels), int(n_features), int(log2_table)
+        self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
+        self.out_dim = self.n_levels * self.n_features
+        self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
+        self._defer_init()
 
     def _defer_init(self):
         self._bwd_ws = None
@@ -71,6 +93,10 @@ class _DeferredTable:
         self._bwd_launch(self._pending, None, 4, g)
         self._pending, self._ws_clean, self._float_mode = None, False, True
         return g
+
+    def _bwd_ws_bytes(self):
+        """The accumulator and its control words: one size for both encodings, whichever query is asked."""
+        return L.load().ctx_hashgrid_bwd_ws_bytes(self.n_levels, self.n_features, self.log2_table)
 
     def _workspace(self, device, zeroed):
         wsb = self._bwd_ws_bytes()
@@ -124,7 +150,7 @@ class _HashGridFn(torch.autograd.Function):
         return None, g_pts, g_table
 
 
-class HashGridEncoding(_DeferredTable, nn.Module):
+class HashGridEncoding(_DeferredTable):
     """pts [..., 3] inside the box lo .. hi -> features [..., n_levels * n_features]: at every level the trilinear interpolation of the 8
     table entries at the corners of the point's cell; a level whose (res + 1)^3 nodes fit the table indexes it directly, a finer one by
     instant-ngp's spatial hash.  Points outside the box take the values on its surface; NaN coordinates read as lo.
@@ -135,32 +161,13 @@ class HashGridEncoding(_DeferredTable, nn.Module):
     a loss on that gradient (on normals, an eikonal term) cannot be trained through."""
 
     def __init__(self, lo, hi, n_levels=16, n_features=2, log2_table=19, base_res=16, max_res=2048, grad_pts=False):
-        super().__init__()
         who = "HashGridEncoding"
-        for name, v in (("n_levels", n_levels), ("n_features", n_features), ("log2_table", log2_table), ("base_res", base_res),
-                        ("max_res", max_res)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise L.CtxError(f"{who}: {name}={v!r}: want an int")
-        if not 1 <= n_levels <= MAX_LEVELS:
-            raise L.CtxError(f"{who}: n_levels={n_levels} outside [1, {MAX_LEVELS}]")
-        if n_features not in (1, 2, 4):
-            raise L.CtxError(f"{who}: n_features={n_features}: want 1, 2 or 4 features per entry")
-        if n_levels * n_features > MAX_WIDTH:
-            raise L.CtxError(f"{who}: n_levels * n_features = {n_levels * n_features} is wider than the field's {MAX_WIDTH}-column embedding")
-        if not 4 <= log2_table <= 22:
-            raise L.CtxError(f"{who}: log2_table={log2_table} outside [4, 22]")
-        if not 1 <= base_res <= max_res <= MAX_RES:
-            raise L.CtxError(f"{who}: want 1 <= base_res <= max_res <= 2^20, got base_res={base_res}, max_res={max_res}")
+        super().__init__(who, n_levels, n_features, log2_table, base_res, max_res)
         lo = np.broadcast_to(np.asarray(lo, np.float32), (3,)).copy()
         hi = np.broadcast_to(np.asarray(hi, np.float32), (3,)).copy()
         if not bool(np.all(np.isfinite(lo))) or not bool(np.all(lo < hi)) or not bool(np.all(np.isfinite(hi - lo))):
             raise L.CtxError(f"{who}: the box needs finite lo < hi on every axis, got lo={lo.tolist()}, hi={hi.tolist()}")
         self.lo, self.hi = lo, hi
-        self.n_levels, self.n_features, self.log2_table = int(n_levels), int(n_features), int(log2_table)
-        self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
-        self.out_dim = self.n_levels * self.n_features
-        self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
-        self._defer_init()
         self.grad_pts = bool(grad_pts)
         self._pts_ws = None
 
@@ -174,9 +181,6 @@ class HashGridEncoding(_DeferredTable, nn.Module):
         L.check(L.load().ctx_hashgrid_fwd(L.ptr(pts, torch.float32, "pts"), pts.shape[0], L.ptr(table, torch.float32, "table"),
                                           *self._grid_args(), L.ptr(emb), L.stream()))
         return emb
-
-    def _bwd_ws_bytes(self):
-        return L.load().ctx_hashgrid_bwd_ws_bytes(self.n_levels, self.n_features, self.log2_table)
 
     def _bwd_launch(self, rows, g_emb, stages, g_table):
         """`ctx_hashgrid_bwd` on rows = (pts, n); a stage that is not asked for does not touch its buffer, which only has to be live."""
@@ -291,7 +295,7 @@ class _HashTexFn(torch.autograd.Function):
         return None, None, None, None, None, g_table
 
 
-class HashGridEncoding2D(_DeferredTable, nn.Module):
+class HashGridEncoding2D(_DeferredTable):
     """uv [..., 2] in the unit square -> features [..., n_levels * n_features]: at every level the bilinear interpolation of the 4 table
     entries at the corners of the point's cell; a level whose (res + 1)^2 nodes fit the table indexes it directly, a finer one by
     instant-ngp's spatial hash.  Points outside the square take the values on its edge; NaN coordinates read as 0.
@@ -299,27 +303,7 @@ class HashGridEncoding2D(_DeferredTable, nn.Module):
     `table` [n_levels, 2^log2_table, n_features] starts uniform in +-1e-4.  There is no gradient to uv: a uv that requires grad is refused."""
 
     def __init__(self, n_levels=12, n_features=2, log2_table=18, base_res=16, max_res=1024):
-        super().__init__()
-        who = "HashGridEncoding2D"
-        for name, v in (("n_levels", n_levels), ("n_features", n_features), ("log2_table", log2_table), ("base_res", base_res),
-                        ("max_res", max_res)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise L.CtxError(f"{who}: {name}={v!r}: want an int")
-        if not 1 <= n_levels <= MAX_LEVELS:
-            raise L.CtxError(f"{who}: n_levels={n_levels} outside [1, {MAX_LEVELS}]")
-        if n_features not in (1, 2, 4):
-            raise L.CtxError(f"{who}: n_features={n_features}: want 1, 2 or 4 features per entry")
-        if n_levels * n_features > MAX_WIDTH:
-            raise L.CtxError(f"{who}: n_levels * n_features = {n_levels * n_features} is wider than the field's {MAX_WIDTH}-column embedding")
-        if not 4 <= log2_table <= 22:
-            raise L.CtxError(f"{who}: log2_table={log2_table} outside [4, 22]")
-        if not 1 <= base_res <= max_res <= MAX_RES:
-            raise L.CtxError(f"{who}: want 1 <= base_res <= max_res <= 2^20, got base_res={base_res}, max_res={max_res}")
-        self.n_levels, self.n_features, self.log2_table = int(n_levels), int(n_features), int(log2_table)
-        self.res = level_resolutions(self.n_levels, int(base_res), int(max_res))
-        self.out_dim = self.n_levels * self.n_features
-        self.table = nn.Parameter((torch.rand(self.n_levels, 1 << self.log2_table, self.n_features) * 2 - 1) * 1e-4)
-        self._defer_init()
+        super().__init__("HashGridEncoding2D", n_levels, n_features, log2_table, base_res, max_res)
 
     def _grid_args(self):
         """(Lv, F, log2T, res) as the ABI takes them; res is host memory."""
@@ -332,9 +316,6 @@ class HashGridEncoding2D(_DeferredTable, nn.Module):
         return emb
 
     _corners = 4
-
-    def _bwd_ws_bytes(self):
-        return L.load().ctx_hashtex_bwd_ws_bytes(self.n_levels, self.n_features, self.log2_table)
 
     def _bwd_launch(self, rows, g_emb, stages, g_table):
         """`ctx_hashtex_bwd` on rows = (uv, idx, grid, n); a stage that is not asked for does not touch its buffer, which only has to be live."""

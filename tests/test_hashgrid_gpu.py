@@ -67,6 +67,19 @@ def test_kernels_equal_the_rule(dev, Lv, F, log2T, max_res):
         assert np.array_equal(gt, HG.backward_np(pts, g_emb, LO, HI, res, log2T, F)), ("backward", n)
 
 
+def test_node_count_beyond_32_bits(dev):
+    """res = 2047: the level has 2048^3 = 2^33 nodes, a count that is 0 in 32 bits.  The level is hashed; a kernel that took the wrapped
+    count for a dense level would index the table unmasked.  Forward and table backward, array_equal."""
+    Lv, F, log2T, n, res = 1, 2, 12, 300, [2047]
+    assert not HG.is_dense(res[0], log2T)
+    table = HG.case_table(Lv, F, log2T, seed=5)
+    pts = HG.case_points(n, LO, HI, res, seed=n)
+    assert np.array_equal(_abi_fwd(dev, pts, table, res, log2T), HG.forward_np(pts, table, LO, HI, res, log2T))
+    g_emb = np.random.default_rng(n).standard_normal((n, Lv * F)).astype(f32) * f32(3e-3)
+    gt = _abi_bwd(dev, pts, g_emb, res, log2T, F).cpu().numpy()
+    assert np.array_equal(gt, HG.backward_np(pts, g_emb, LO, HI, res, log2T, F))
+
+
 def test_backward_contention_zero_nan_and_repeat(dev):
     Lv, F, log2T = 4, 2, 6
     res = HG.resolutions(Lv, 2, 64)

@@ -91,6 +91,19 @@ def test_kernels_equal_the_rule(dev, Lv, F, log2T, max_res):
         assert np.array_equal(gt, HT.backward_np(g_emb, res, log2T, F, **rows)), ("backward", mode, size)
 
 
+def test_node_count_beyond_32_bits(dev):
+    """res = 65535: the level has 65536^2 = 2^32 nodes, a count that is 0 in 32 bits.  The level is hashed; a kernel that took the
+    wrapped count for a dense level would index the table unmasked.  Forward and table backward on uv rows, array_equal."""
+    Lv, F, log2T, n, res = 1, 2, 12, 300, [65535]
+    assert not HT.is_dense(res[0], log2T)
+    table = HT.case_table(Lv, F, log2T, seed=5)
+    uv = HT.case_points(n, res, seed=n)
+    assert np.array_equal(_abi_fwd(dev, table, res, log2T, uv=uv), HT.forward_np(table, res, log2T, uv=uv))
+    g_emb = np.random.default_rng(n).standard_normal((n, Lv * F)).astype(f32) * f32(3e-3)
+    gt = _abi_bwd(dev, g_emb, res, log2T, F, uv=uv).cpu().numpy()
+    assert np.array_equal(gt, HT.backward_np(g_emb, res, log2T, F, uv=uv))
+
+
 def test_row_modes_are_exclusive(dev):
     """An inconsistent combination is refused before any launch: the output keeps its prefill."""
     from contexture_nerf_amd import _lib as L
