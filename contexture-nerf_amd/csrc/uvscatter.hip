@@ -2,7 +2,7 @@
 // align_corners=False, padding 'border'; reference call site src/models/render.py:135 under autograd, src/training/trainer.py:866)
 // and the direct UV scatter of north_star's "torch-scatter UV back-projection".
 //
-// The atomics form (geometry.hip: k_texmap_bwd) is bound by the chip's float-atomic rate (~1.3 TB/s of added bytes: 749 us for
+// The atomics form (texmap.hip: k_texmap_bwd) is bound by the chip's float-atomic rate (~1.3 TB/s of added bytes: 749 us for
 // 7 views @1200^2).  Here pixels are first BINNED by atlas tile (32 x 32 texels); a workgroup then owns one tile, accumulates
 // the bilinear contributions of its pixel list in an LDS-resident tile and writes every texel once with a plain store.
 //
@@ -33,6 +33,7 @@
 #include <algorithm>
 #include "common.h"
 #include "kernels.h"
+#include "texel_taps.h"
 
 #define SB_TS 32                  // tile side (texels)
 #define SB_CH 8192                // entries per chunk (measured at 7 x 1200^2 onto 1024^2: 4096 -> 74.9 us, 8192 -> 70, 16384 -> 78.1)
@@ -76,18 +77,11 @@ static SbPlan sb_map(void *plan, int ntiles, int64_t cap)
     return p;
 }
 
-__device__ __forceinline__ float sb_src_index(float g, int size)
-{
-    float c = ((g + 1.0f) * (float)size - 1.0f) / 2.0f;
-    return fminf((float)(size - 1), fmaxf(c, 0.0f));
-}
 // the (up to 4) distinct tiles touched by the pixel's valid taps; returns their count
 __device__ __forceinline__ int sb_tiles(float u, float v, int T, int ntx, int (&tiles)[4])
 {
-    const float ix = sb_src_index(u * 2.0f - 1.0f, T), iy = sb_src_index((1.0f - v) * 2.0f - 1.0f, T);
-    const int x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;
-    const bool bx1 = x1 < T, by1 = y1 < T;                          // x0, y0 are in range after the border clamp
-    const int tx0 = x0 / SB_TS, ty0 = y0 / SB_TS, tx1 = bx1 ? x1 / SB_TS : tx0, ty1 = by1 ? y1 / SB_TS : ty0;
+    const TexelTaps t = texel_taps(u, v, T);
+    const int tx0 = t.x0 / SB_TS, ty0 = t.y0 / SB_TS, tx1 = t.in[1] ? t.x1 / SB_TS : tx0, ty1 = t.in[2] ? t.y1 / SB_TS : ty0;
     int n = 0;
     tiles[n++] = ty0 * ntx + tx0;
     if (tx1 != tx0) tiles[n++] = ty0 * ntx + tx1;
@@ -264,19 +258,15 @@ __global__ __launch_bounds__(256) void k_sb_accum(const SbHeader *__restrict__ h
     for (int i = threadIdx.x; i < n; i += 256) {
         const size_t pix = entries[beg + i];
         const float2 q = *(const float2 *)(uv + pix * 2);
-        const float ix = sb_src_index(q.x * 2.0f - 1.0f, T), iy = sb_src_index((1.0f - q.y) * 2.0f - 1.0f, T);
-        const int x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;
-        const float w[4] = {((float)x1 - ix) * ((float)y1 - iy), (ix - (float)x0) * ((float)y1 - iy),
-                            ((float)x1 - ix) * (iy - (float)y0), (ix - (float)x0) * (iy - (float)y0)};
-        const int xs[4] = {x0, x1, x0, x1}, ys[4] = {y0, y0, y1, y1};
+        const TexelTaps t = texel_taps(q.x, q.y, T);
         float g[SB_MAXC];
         for (int c = 0; c < C; ++c) g[c] = go[pix * C + c];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int lx = xs[k] - X0, ly = ys[k] - Y0;
-            if (xs[k] >= T || ys[k] >= T || lx < 0 || lx >= SB_TS || ly < 0 || ly >= SB_TS) continue;
+            const int lx = t.x(k) - X0, ly = t.y(k) - Y0;
+            if (!t.in[k] || lx < 0 || lx >= SB_TS || ly < 0 || ly >= SB_TS) continue;
             for (int c = 0; c < C; ++c) {
-                const long long v = __float2ll_rn(ldexpf(g[c] * w[k], e));      // one float rounding of the tap, exact scaling
+                const long long v = __float2ll_rn(ldexpf(g[c] * t.w[k], e));    // one float rounding of the tap, exact scaling
                 if (v) atomicAdd(&s_t[(c * SB_TS + ly) * SB_TS + lx], (unsigned long long)v);
             }
         }
@@ -323,16 +313,12 @@ __global__ __launch_bounds__(256) void k_sb_direct(const float *__restrict__ go,
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (pix >= N || (mask_idx && mask_idx[pix] < 0)) return;
     const float2 q = *(const float2 *)(uv + pix * 2);
-    const float ix = sb_src_index(q.x * 2.0f - 1.0f, T), iy = sb_src_index((1.0f - q.y) * 2.0f - 1.0f, T);
-    const int x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;
-    const float w[4] = {((float)x1 - ix) * ((float)y1 - iy), (ix - (float)x0) * ((float)y1 - iy),
-                        ((float)x1 - ix) * (iy - (float)y0), (ix - (float)x0) * (iy - (float)y0)};
-    const int xs[4] = {x0, x1, x0, x1}, ys[4] = {y0, y0, y1, y1};
+    const TexelTaps t = texel_taps(q.x, q.y, T);
     for (int k = 0; k < 4; ++k) {
-        if (xs[k] >= T || ys[k] >= T) continue;
+        if (!t.in[k]) continue;
         for (int c = 0; c < C; ++c) {
-            const long long v = __float2ll_rn(ldexpf(go[pix * C + c] * w[k], frac));
-            if (v) atomicAdd((unsigned long long *)&acc[((size_t)c * T + ys[k]) * T + xs[k]], (unsigned long long)v);
+            const long long v = __float2ll_rn(ldexpf(go[pix * C + c] * t.w[k], frac));
+            if (v) atomicAdd((unsigned long long *)&acc[((size_t)c * T + t.y(k)) * T + t.x(k)], (unsigned long long)v);
         }
     }
 }

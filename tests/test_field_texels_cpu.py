@@ -1,7 +1,7 @@
 """CPU: the texture field on the texels the views sample (optim.field_texels = 'active') — the definition of the active set, the
 config surface and the host control flow.
 
-`active_texels_np` below IS the rule csrc/geometry.hip (ctx_texel_active_mark + ctx_texel_compact) is held to;
+`active_texels_np` below IS the rule csrc/texmap.hip (ctx_texel_active_mark) and csrc/compact.hip (ctx_texel_compact) are held to;
 tests/test_field_texels_gpu.py imports it from here and compares with array_equal.  All float arithmetic is binary32 in the order of
 k_texmap_fwd (numpy array operations round every product and sum on their own: no contraction).
 
@@ -112,6 +112,22 @@ def test_clamped_uv_marks_inside_the_atlas_only():
     # (u, v) = (0, 0): ix = 0, iy = T-1 -> (T-1, 0), (T-1, 1);  (1, 1): ix = T-1, iy = 0 -> (0, T-1), (1, T-1);
     # (0, 1): ix = 0, iy = 0 -> (0..1, 0..1);  (1, 0): ix = iy = T-1 -> (T-1, T-1)
     assert np.array_equal(mask, want) and np.array_equal(idx, np.flatnonzero(want))
+
+
+def test_compaction_workspaces_share_one_layout():
+    """ctx_texel_compact_ws_bytes(n) and ctx_face_view_map_ws_bytes(B, H, W): one int64 base and one int32 count per block of 1024
+    items and 64 spare bytes, at the block edges and up to the largest n; n = 0 and n = 2^31 are refused (the indices are int32)."""
+    from contexture_nerf_amd import _lib as L
+    lib = L.load()
+    edges = [1, 2, 63, 64, 1023, 1024, 1025, 2047, 2048, 2049, 4096, 4097, 2 ** 20 - 1, 2 ** 20, 2 ** 20 + 1, 3 * 2 ** 20 + 517, 2 ** 31 - 1]
+    for n in edges:
+        want = -(-n // 1024) * 12 + 64
+        assert lib.ctx_texel_compact_ws_bytes(n) == want, n
+        assert lib.ctx_face_view_map_ws_bytes(1, 1, n) == want, n
+    assert lib.ctx_face_view_map_ws_bytes(7, 1200, 1200) == -(-7 * 1200 * 1200 // 1024) * 12 + 64
+    assert lib.ctx_face_view_map_ws_bytes(3, 11, 31) == 12 + 64 and lib.ctx_face_view_map_ws_bytes(1, 25, 41) == 24 + 64
+    for n in (0, -1, 2 ** 31, 2 ** 40):
+        assert lib.ctx_texel_compact_ws_bytes(n) == -1, n
 
 
 # ---- 2. config ------------------------------------------------------------------------------------------------------------------
