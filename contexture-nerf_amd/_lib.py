@@ -179,6 +179,10 @@ SIGNATURES = {
     "ctx_groupnorm_apply_f16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "ctx_groupnorm_slabs_f16": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "ctx_layernorm_f16": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
+    "ctx_groupnorm_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ctx_layernorm_plan": (_i32, [_i64, _i32, _i32, _vp]),
+    "ctx_groupnorm_f32in_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "ctx_layernorm_f32in_f16": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp]),
     "ctx_attention_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "ctx_attention_f16": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp]),
     "ctx_groupnorm_ws_bytes": (_i64, [_i32, _i32]),

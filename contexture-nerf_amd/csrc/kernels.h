@@ -106,7 +106,7 @@ extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups);
 // [x ; x2] read in place (x: channels 0 .. Ca with pixel stride Ca; x2: channels Ca .. C with pixel stride C - Ca; Ca % 8 == 0)
 int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps, int silu,
                       void *y, void *stats_ws, hipStream_t stream, const void *x2 = nullptr, int Ca = 0);
-// 1: a one-source GroupNorm of this shape takes the two-pass form (k_gn_stats + k_gn_apply), 0: the one-kernel form
+// 1: a GroupNorm of this shape, of one source or two, takes the two-pass form (k_gn_stats + k_gn_apply), 0: the one-kernel form
 int ctx_groupnorm_two_pass(int HW, int C, int groups);
 // the apply half of the two-pass form on partials part[B][NS][groups][2] that a producer wrote (GemmArgs::gn_part), fp16 input
 int ctx_groupnorm_apply(const void *x, const float *part, int NS, const void *gamma, const void *beta, int B, int HW, int C, int groups, float eps,

@@ -68,6 +68,41 @@ __device__ __forceinline__ GnSrc gn_src(const void *x, const void *x2, int Ca, i
     return ch < Ca ? GnSrc{x, Ca, ch} : GnSrc{x2, C - Ca, ch - Ca};
 }
 
+// Statistics are accumulated about a per-(sample, group) pivot, the group's first channel at pixel 0 (from whichever source holds
+// it): sum (x - pivot) and sum (x - pivot)^2.  var = sumsq/n - mean^2 of the raw values cancels to nothing once a group's mean is a few
+// hundred of its sigmas away from zero; about a member of the group the two terms are of the variance's own size.  x - pivot is exact
+// (fp16 input) or rounded once at the size of the difference, not of x.
+template <bool X32>
+__device__ __forceinline__ float gn_pivot(const void *x, const void *x2, int Ca, int C, int HW, int b, int ch)
+{
+    const GnSrc s = gn_src(x, x2, Ca, C, ch);
+    const size_t e = (size_t)b * HW * s.cs + s.col;
+    if constexpr (X32) return ((const float *)s.p)[e];
+    else return (float)((const f16 *)s.p)[e];
+}
+// a thread's 8 channels ch0 .. ch0 + 8 (ch0 % 8 == 0): they lie in one group when a group is whole chunks, in at most two when it
+// is wider than a chunk (the UNet's 10 .. 80 channels: two loads and a select, no branch per channel), else one load per group
+template <bool X32>
+__device__ __forceinline__ void gn_pivots(const void *x, const void *x2, int Ca, int C, int HW, int b, int ch0, int cg, float (&pv)[8])
+{
+    int first = ch0 / cg * cg, next = first + cg;          // the first channel of channel ch0's group, and of the group behind it
+    float t = gn_pivot<X32>(x, x2, Ca, C, HW, b, first);
+    if (cg % 8 == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pv[j] = t;
+    } else if (cg > 8) {
+        const float t1 = gn_pivot<X32>(x, x2, Ca, C, HW, b, min(next, C - cg));     // next == C: no channel of this thread is behind it
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pv[j] = ch0 + j >= next ? t1 : t;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (ch0 + j >= next) { first = next; next += cg; t = gn_pivot<X32>(x, x2, Ca, C, HW, b, first); }
+            pv[j] = t;
+        }
+    }
+}
+
 #define GN_MAX_GROUPS 64
 #define GN_MAX_SPLITS CTX_GN_MAX_SLOTS
 #define GN_MAX_C 4096
@@ -83,14 +118,16 @@ __global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, c
     const int c8n = C / 8;
     const int b = blockIdx.y, sp = blockIdx.x;
     const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
+    const bool act = pl < PL;                  // blockDim.x is rounded up to whole waves: the lanes behind c8n * PL only help folding
     const int per = (HW + NS - 1) / NS;
     const int p0 = sp * per, p1 = min(HW, p0 + per);
-    float s[8], q[8];
+    float s[8], q[8], pv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
+    gn_pivots<X32>(x, x2, Ca, C, HW, b, c8 * 8, C / G, pv);
     const GnSrc src = gn_src(x, x2, Ca, C, c8 * 8);
     const size_t base = ((size_t)b * HW) * src.cs + src.col;
-    for (int p = p0 + pl; p < p1; p += PL * GN_U) {
+    for (int p = p0 + pl; act && p < p1; p += PL * GN_U) {
         Wide8 v[GN_U];
 #pragma unroll
         for (int u = 0; u < GN_U; ++u) v[u] = ldraw<X32>(src.p, base + (size_t)min(p + u * PL, p1 - 1) * src.cs).widen();   // unconditional
@@ -98,13 +135,15 @@ __global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, c
         for (int u = 0; u < GN_U; ++u) {
             const bool live = p + u * PL < p1;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { float f = live ? v[u].get(j) : 0.f; s[j] += f; q[j] += f * f; }
+            for (int j = 0; j < 8; ++j) { float f = live ? v[u].get(j) - pv[j] : 0.f; s[j] += f; q[j] += f * f; }
         }
     }
+    if (act) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        s_part[((size_t)pl * C + c8 * 8 + j) * 2 + 0] = s[j];
-        s_part[((size_t)pl * C + c8 * 8 + j) * 2 + 1] = q[j];
+        for (int j = 0; j < 8; ++j) {
+            s_part[((size_t)pl * C + c8 * 8 + j) * 2 + 0] = s[j];
+            s_part[((size_t)pl * C + c8 * 8 + j) * 2 + 1] = q[j];
+        }
     }
     __syncthreads();
     // fixed-order fold, two short steps.  A: (channel, slice a of the pixel lanes) -> s_ch[a][C]; B: 8 lanes per group
@@ -124,7 +163,7 @@ __global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, c
     }
     __syncthreads();
     const int cg = C / G, cells = na * cg;
-    const int octs = (int)blockDim.x >> 3;               // whole 8-lane groups only
+    const int octs = (int)blockDim.x >> 3;               // whole 8-lane groups (blockDim.x is whole waves: octs >= 8)
     for (int g0 = 0; g0 < G; g0 += octs) {
         const int oc = (int)threadIdx.x >> 3, l = threadIdx.x & 7;
         const int g = oc < octs ? g0 + oc : G;
@@ -144,11 +183,12 @@ __global__ __launch_bounds__(1024) void k_gn_stats(const void *__restrict__ x, c
     }
 }
 
-// The tail that the two-pass and the one-kernel form share.  (mean, rstd) of n values from their sum and sum of squares:
-__device__ __forceinline__ float2 gn_mean_rstd(float sum, float sumsq, float n, float eps)
+// (mean, rstd) of n values from the sum and the sum of squares of their distances to `pivot` (0: of the values themselves, which is
+// what a producer's epilogue can write)
+__device__ __forceinline__ float2 gn_mean_rstd(float sum, float sumsq, float n, float eps, float pivot)
 {
-    const float mean = sum / n;
-    return make_float2(mean, rsqrtf(fmaxf(sumsq / n - mean * mean, 0.f) + eps));
+    const float m = sum / n;
+    return make_float2(pivot + m, rsqrtf(fmaxf(sumsq / n - m * m, 0.f) + eps));
 }
 // y = x * sa + sh for a thread's 8 channels; mr(j) gives channel j's (mean, rstd)
 template <class MR>
@@ -187,8 +227,9 @@ __device__ __forceinline__ void gn_store(const V8 &v, const float (&sa)[8], cons
 template <bool X32>
 __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, const void *__restrict__ x2, int Ca, const float *__restrict__ part,
                                                   const f16 *__restrict__ gamma, const f16 *__restrict__ beta, int HW, int C,
-                                                  int G, int NS, int PL, float eps, int silu, f16 *__restrict__ y)
+                                                  int G, int NS, int PL, int piv, float eps, int silu, f16 *__restrict__ y)
 {
+    // piv: the partials are k_gn_stats' (about the group's pivot, added back here); 0: a producer's (plain sums)
     constexpr int AU = GN_AU;
     __shared__ float s_mean[GN_MAX_GROUPS], s_rstd[GN_MAX_GROUPS];
     const int b = blockIdx.y;
@@ -206,6 +247,7 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
         const int lpg = min(256 / G, 64);                                   // lanes per group: a power of two inside one wave (G < 4: idle lanes)
         const int gi = threadIdx.x / lpg, l = threadIdx.x % lpg;
         const int g = min(gi, G - 1);
+        const float pivot = piv ? gn_pivot<X32>(x, x2, Ca, C, HW, b, g * (C / G)) : 0.f;
         float s = 0.f, q = 0.f;
         for (int k0 = 0; k0 < NS; k0 += GN_FOLD * lpg) {                    // GN_FOLD independent loads per trip, fixed order
             float2 pv[GN_FOLD];
@@ -218,7 +260,7 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
         }
         for (int o = lpg >> 1; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
         if (l == 0 && gi < G) {
-            const float2 m = gn_mean_rstd(s, q, (float)HW * (float)(C / G), eps);
+            const float2 m = gn_mean_rstd(s, q, (float)HW * (float)(C / G), eps, pivot);
             s_mean[g] = m.x;
             s_rstd[g] = m.y;
         }
@@ -236,7 +278,8 @@ __global__ __launch_bounds__(512) void k_gn_apply(const void *__restrict__ x, co
 
 // Small-tensor GroupNorm in ONE kernel: when a group's channels are whole 16-byte chunks (C/G % 8 == 0) and one
 // (batch, group) slab fits a workgroup's registers (<= GN_FT x GN_FU chunks), a workgroup loads its slab once, reduces
-// it (fixed order: lane partials -> DPP wave sums -> 8 wave partials), and writes the normalised slab from registers.
+// it twice (the mean, then sum (x - mean)^2 over the same registers; fixed order: lane partials -> DPP wave sums -> 8 wave
+// partials), and writes the normalised slab from registers.
 // At the UNet's two deepest levels this replaces two latency-bound launches and one re-read of the tensor.
 // SLAB: the input is a split-K convolution's fp32 slabs (GnSlabs) that no reduce launch has summed: a thread forms the fp16 value the
 // reduce would have stored, in its operand order (slabs ascending, bias, bias2, row bias, one rounding: store4 of gemm_common.h), and
@@ -276,7 +319,7 @@ __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, 
     const int cg = C / G, cpg = cg / 8;                // chunks per pixel in this group
     const int c = threadIdx.x % cpg, pl = threadIdx.x / cpg;
     const bool act = pl < PLF;                         // blockDim.x is rounded up to whole waves
-    const GnSrc src = gn_src(x, x2, Ca, C, g * cg + c * 8);    // two sources: the launcher takes this form only when no group straddles Ca
+    const GnSrc src = gn_src(x, x2, Ca, C, g * cg + c * 8);    // two sources: per column, so a group may straddle Ca
     const size_t xb = (size_t)b * HW * src.cs + src.col;
     f16 *yb = y + (size_t)b * HW * C + g * cg + c * 8;
     const f16x8 ga = *(const f16x8 *)(gamma + g * cg + c * 8), be = *(const f16x8 *)(beta + g * cg + c * 8);
@@ -286,21 +329,34 @@ __global__ __launch_bounds__(GN_FT) void k_gn_fused(const void *__restrict__ x, 
         if constexpr (SLAB) v[u] = gn_slab_chunk(sl, (size_t)b * HW + min(pl + PLF * u, HW - 1), b, C, g * cg + c * 8);
         else v[u] = ldraw<X32>(src.p, xb + (size_t)min(pl + PLF * u, HW - 1) * src.cs).widen();
     }
-    float s = 0.f, q = 0.f;
+    const int wave = threadIdx.x >> 6, nw = ((int)blockDim.x + 63) >> 6;
+    const float n = (float)HW * (float)cg;
+    float s = 0.f;
 #pragma unroll
     for (int u = 0; u < GN_FU; ++u)
         if (act && pl + PLF * u < HW) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { float f = v[u].get(j); s += f; q += f * f; }
+            for (int j = 0; j < 8; ++j) s += v[u].get(j);
         }
-    s = wave_sum_dpp(s); q = wave_sum_dpp(q);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_red[0][wave] = s; s_red[1][wave] = q; }
+    s = wave_sum_dpp(s);
+    if ((threadIdx.x & 63) == 0) s_red[0][wave] = s;
     __syncthreads();
-    float ss = 0.f, qq = 0.f;
-    const int nw = ((int)blockDim.x + 63) >> 6;
-    for (int w = 0; w < nw; ++w) { ss += s_red[0][w]; qq += s_red[1][w]; }
-    const float2 m = gn_mean_rstd(ss, qq, (float)HW * (float)cg, eps);
+    float ss = 0.f;
+    for (int w = 0; w < nw; ++w) ss += s_red[0][w];
+    const float mean = ss / n;
+    float q = 0.f;
+#pragma unroll
+    for (int u = 0; u < GN_FU; ++u)
+        if (act && pl + PLF * u < HW) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float d = v[u].get(j) - mean; q += d * d; }
+        }
+    q = wave_sum_dpp(q);
+    if ((threadIdx.x & 63) == 0) s_red[1][wave] = q;
+    __syncthreads();
+    float qq = 0.f;
+    for (int w = 0; w < nw; ++w) qq += s_red[1][w];
+    const float2 m = make_float2(mean, rsqrtf(qq / n + eps));
     float sa[8], sh[8];
     gn_scale_shift([&](int) { return m; }, ga, be, sa, sh);
 #pragma unroll
@@ -325,16 +381,73 @@ static int gn_one_kernel_lanes(int HW, int C, int groups)
     const int plf = cg % 8 == 0 ? GN_FT / cpg : 0;
     return (fuse && plf > 0 && cpg <= GN_FT && (HW + plf - 1) / plf <= GN_FU) ? plf : 0;
 }
-// pass 2 on NS partials per (sample, group): fat blocks (the per-block fold of the split partials is amortised), at least one batch each
-static void gn_launch_apply(const void *x, int x32, const void *x2, int Ca, const float *part, int NS, const void *gamma, const void *beta, int B, int HW,
-                            int C, int groups, float eps, int silu, void *y, hipStream_t stream)
+// The launch plan: every number the GroupNorm launchers derive from a shape, in one place.  ctx_groupnorm_any launches exactly what
+// gn_plan returns, and ctx_groupnorm_plan hands the same struct to the tests (tests/test_norm_cpu.py sweeps the accepted envelope).
+//   one      1: the one-kernel form, grid (groups, B), `thr` threads = cpg chunk columns x `plf` pixel lanes rounded up to whole waves
+//            0: the two-pass form.  Pass 1: grid (NS, B), `threads` = C/8 chunk columns x `PL` pixel lanes rounded up to whole waves
+//               (a block of fewer than 8 threads would leave the fold without one whole 8-lane group), `lds` dynamic bytes
+//               = (PL + na) * C * 2 floats, at most GN_LDS_OPTIN, which the launcher opts into.
+//   apl, athreads, nb: pass 2 (also ctx_groupnorm_apply's): grid (nb, B), athreads = C/8 columns x apl pixel lanes in 256 .. 512 (the
+//            fold of the partials uses the first 256), GN_AU pixels per lane.
+struct GnPlan { int one, plf, thr, PL, threads, NS, na, lds, apl, athreads, nb; };
+#define GN_LDS_OPTIN (96 * 1024)
+static void gn_plan_apply(int HW, int C, GnPlan &p)
 {
     const int c8n = C / 8;
-    const int apl = (256 + c8n - 1) / c8n;                      // pixel lanes: >= 256 threads (the fold uses 256), <= 512
-    const int athreads = c8n * apl;
-    const int nb = (HW + apl * GN_AU - 1) / (apl * GN_AU);
-    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(nb, B), dim3(athreads), 0, stream, x, x2, Ca, part, (const f16 *)gamma, (const f16 *)beta, HW, C,
-                                           groups, NS, apl, eps, silu, (f16 *)y));
+    p.apl = (256 + c8n - 1) / c8n;
+    p.athreads = c8n * p.apl;
+    p.nb = (HW + p.apl * GN_AU - 1) / (p.apl * GN_AU);
+}
+// two != 0: two sources, the first Ca channels wide
+static int gn_plan(int B, int HW, int C, int groups, int x32, int two, int Ca, GnPlan &p)
+{
+    p = GnPlan{};
+    CTX_REQUIRE(gn_shape_ok(B, HW, C, groups), "groupnorm: unsupported B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
+    CTX_REQUIRE(!two || (Ca > 0 && Ca < C && Ca % 8 == 0), "groupnorm: two sources need 0 < Ca < C in whole 8-channel columns (Ca=%d C=%d)", Ca, C);
+    gn_plan_apply(HW, C, p);
+    if (const int plf = gn_one_kernel_lanes(HW, C, groups); plf) {      // either source count: the bits must not depend on it
+        p.one = 1;
+        p.plf = plf;
+        p.thr = (C / groups / 8 * plf + 63) / 64 * 64;
+        return CTX_OK;
+    }
+    const int c8n = C / 8;
+    p.PL = min(max(1024 / c8n, 1), HW);                       // pixel lanes: ~1000 threads per block
+    p.threads = (c8n * p.PL + 63) / 64 * 64;
+    p.NS = min(GN_MAX_SPLITS, max(1, HW / p.PL));             // >= one pixel per lane per split
+    {
+        // Fat splits: a block's fold (two barriers, LDS walks, a shuffle tree) costs the same whatever it summed, and every apply block
+        // re-reads all NS partials of its sample — but a 150 MB VAE tensor at batch 1 still needs all 128 of them to fill the chip.
+        // ~384 KB of the sample per split, at least 64 stats blocks in all (measured, GroupNorm per evaluation: UNet batch 12 3.30 ms at
+        // 128 splits / 2.13 at 16; batch 2 1.01 / 0.94 at 32; the VAE decoder's at 768^2 1.36 ms at 128 / 1.71 at 48).  CTX_GN_NS overrides.
+        static const int ns_env = ctx_env_int("CTX_GN_NS", 0);
+        const int64_t sample_bytes = (int64_t)HW * C * (x32 ? 4 : 2);
+        const int by_size = (int)min((int64_t)GN_MAX_SPLITS, sample_bytes / (384 * 1024));
+        const int want = ns_env > 0 ? ns_env : max(16, max(by_size, (64 + B - 1) / B));
+        p.NS = min(p.NS, want);
+    }
+    p.na = max(1, p.threads / C);                             // k_gn_stats derives the same from blockDim.x
+    p.lds = (p.PL + p.na) * C * 2 * (int)sizeof(float);
+    CTX_REQUIRE(p.lds <= GN_LDS_OPTIN, "groupnorm: C=%d needs %d bytes of LDS", C, p.lds);
+    return CTX_OK;
+}
+
+extern "C" int32_t ctx_groupnorm_plan(int32_t B, int32_t HW, int32_t C, int32_t groups, int32_t x32, int32_t Ca, int32_t *out)
+{
+    CTX_REQUIRE(out, "groupnorm plan: null pointer");
+    GnPlan p;
+    if (const int rc = gn_plan(B, HW, C, groups, x32, Ca != 0, Ca, p); rc != CTX_OK) return rc;
+    const int v[12] = {p.one, p.plf, p.thr, p.PL, p.threads, p.NS, p.na, p.lds, p.apl, p.athreads, p.nb, GN_LDS_OPTIN};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return CTX_OK;
+}
+
+// pass 2 on NS partials per (sample, group): fat blocks (the per-block fold of the split partials is amortised), at least one batch each
+static void gn_launch_apply(const GnPlan &p, const void *x, int x32, const void *x2, int Ca, const float *part, int NS, int piv, const void *gamma,
+                            const void *beta, int B, int HW, int C, int groups, float eps, int silu, void *y, hipStream_t stream)
+{
+    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_apply<X>, dim3(p.nb, B), dim3(p.athreads), 0, stream, x, x2, Ca, part, (const f16 *)gamma, (const f16 *)beta,
+                                           HW, C, groups, NS, p.apl, piv, eps, silu, (f16 *)y));
 }
 
 extern "C" int64_t ctx_groupnorm_ws_bytes(int32_t B, int32_t groups)
@@ -346,6 +459,13 @@ extern "C" int32_t ctx_groupnorm_f16(const void *x, const void *gamma, const voi
                                      int32_t groups, float eps, int32_t silu, void *y, void *stats_ws, ctx_stream_t stream)
 {
     return ctx_groupnorm_any(x, 0, gamma, beta, B, HW, C, groups, eps, silu, y, stats_ws, (hipStream_t)stream);
+}
+
+// test seam of the fp32-input kernels (the engines reach them through the fp32 residual stream): x [B, HW, C] fp32
+extern "C" int32_t ctx_groupnorm_f32in_f16(const float *x, const void *gamma, const void *beta, int32_t B, int32_t HW, int32_t C,
+                                           int32_t groups, float eps, int32_t silu, void *y, void *stats_ws, ctx_stream_t stream)
+{
+    return ctx_groupnorm_any(x, 1, gamma, beta, B, HW, C, groups, eps, silu, y, stats_ws, (hipStream_t)stream);
 }
 
 // GroupNorm(+SiLU) of the channel concatenation [xa ; xb] read in place: xa [B, HW, Ca], xb [B, HW, C - Ca]; y [B, HW, C].
@@ -376,43 +496,27 @@ int ctx_groupnorm_any(const void *x, int x32, const void *gamma, const void *bet
                       void *y, void *stats_ws, hipStream_t stream, const void *x2, int Ca)
 {
     CTX_REQUIRE(x && gamma && beta && y && stats_ws, "groupnorm: null pointer");
-    CTX_REQUIRE(!x2 || (Ca > 0 && Ca < C && Ca % 8 == 0), "groupnorm: two sources need 0 < Ca < C in whole 8-channel columns (Ca=%d C=%d)", Ca, C);
-    CTX_REQUIRE(gn_shape_ok(B, HW, C, groups), "groupnorm: unsupported B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
-    if (const int plf = gn_one_kernel_lanes(HW, C, groups); plf && (!x2 || Ca % (C / groups) == 0)) {
-        const int thr = (C / groups / 8 * plf + 63) / 64 * 64;
-        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(thr), 0, stream, x, x2, Ca, (const f16 *)gamma, (const f16 *)beta, HW, C,
-                                               groups, plf, eps, silu, (f16 *)y, GnSlabs{}));
+    GnPlan p;
+    if (const int rc = gn_plan(B, HW, C, groups, x32, x2 != nullptr, Ca, p); rc != CTX_OK) return rc;
+    if (p.one) {
+        CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_fused<X>, dim3(groups, B), dim3(p.thr), 0, stream, x, x2, Ca, (const f16 *)gamma, (const f16 *)beta, HW, C,
+                                               groups, p.plf, eps, silu, (f16 *)y, GnSlabs{}));
         CTX_CHECK_LAUNCH("groupnorm");
         return CTX_OK;
     }
-    int c8n = C / 8;
-    int PL = 1024 / c8n;                                      // pixel lanes: ~1000 threads per block
-    if (PL < 1) PL = 1;
-    if (PL > HW) PL = HW;
-    int threads = c8n * PL;
-    int NS = min(GN_MAX_SPLITS, max(1, HW / PL));             // >= one pixel per lane per split
-    {
-        // Fat splits: a block's fold (two barriers, LDS walks, a shuffle tree) costs the same whatever it summed, and every apply block
-        // re-reads all NS partials of its sample — but a 150 MB VAE tensor at batch 1 still needs all 128 of them to fill the chip.
-        // ~384 KB of the sample per split, at least 64 stats blocks in all (measured, GroupNorm per evaluation: UNet batch 12 3.30 ms at
-        // 128 splits / 2.13 at 16; batch 2 1.01 / 0.94 at 32; the VAE decoder's at 768^2 1.36 ms at 128 / 1.71 at 48).  CTX_GN_NS overrides.
-        static const int ns_env = ctx_env_int("CTX_GN_NS", 0);
-        const int64_t sample_bytes = (int64_t)HW * C * (x32 ? 4 : 2);
-        const int by_size = (int)min((int64_t)GN_MAX_SPLITS, sample_bytes / (384 * 1024));
-        const int want = ns_env > 0 ? ns_env : max(16, max(by_size, (64 + B - 1) / B));
-        NS = min(NS, want);
-    }
     float *part = (float *)stats_ws;
-    const int na = threads / C > 1 ? threads / C : 1;
-    size_t lds = (size_t)(PL + na) * C * 2 * sizeof(float);   // <= 72 KiB (threads <= 1024, 8 channels each)
-    static bool attr = false;
+    static bool attr = false;                                 // more than 64 KiB of dynamic LDS (C > 2048) needs the opt-in
     if (!attr) {
-        (void)hipFuncSetAttribute((const void *)k_gn_stats<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_gn_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void *)k_gn_stats<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_LDS_OPTIN);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_gn_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_LDS_OPTIN);
+        if (e != hipSuccess) {
+            ctx_set_error("groupnorm: the LDS opt-in failed: %s", hipGetErrorString(e));
+            return CTX_E_LAUNCH;
+        }
         attr = true;
     }
-    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_stats<X>, dim3(NS, B), dim3(threads), lds, stream, x, x2, Ca, HW, C, groups, NS, PL, part));
-    gn_launch_apply(x, x32, x2, Ca, part, NS, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
+    CTX_BOOL_GO(x32, X, hipLaunchKernelGGL(k_gn_stats<X>, dim3(p.NS, B), dim3(p.threads), (size_t)p.lds, stream, x, x2, Ca, HW, C, groups, p.NS, p.PL, part));
+    gn_launch_apply(p, x, x32, x2, Ca, part, p.NS, 1, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
     CTX_CHECK_LAUNCH("groupnorm");
     return CTX_OK;
 }
@@ -426,7 +530,9 @@ int ctx_groupnorm_apply(const void *x, const float *part, int NS, const void *ga
 {
     CTX_REQUIRE(x && part && gamma && beta && y, "groupnorm apply: null pointer");
     CTX_REQUIRE(gn_shape_ok(B, HW, C, groups) && NS >= 1 && NS <= GN_MAX_SPLITS, "groupnorm apply: unsupported B=%d HW=%d C=%d groups=%d NS=%d", B, HW, C, groups, NS);
-    gn_launch_apply(x, 0, nullptr, 0, part, NS, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
+    GnPlan p{};
+    gn_plan_apply(HW, C, p);
+    gn_launch_apply(p, x, 0, nullptr, 0, part, NS, 0, gamma, beta, B, HW, C, groups, eps, silu, y, stream);
     CTX_CHECK_LAUNCH("groupnorm apply");
     return CTX_OK;
 }
@@ -449,7 +555,7 @@ int ctx_groupnorm_slabs(const GnSlabs &sl, const void *gamma, const void *beta, 
 // x, then sum(du) and sum(du x^)) and one apply pass, all deterministic (fixed-order partial sums).
 #define GNB_MAX_SPLITS 128
 
-// MODE 0: per-group partial (sum x, sum x^2); MODE 1: partial (sum du, sum du x^) with du = dy silu'(u) gamma, u = gamma x^ + beta
+// MODE 0: per-group partial (sum (x - pivot), sum (x - pivot)^2) about the group's pivot (gn_pivot); MODE 1: partial (sum du, sum du x^) with du = dy silu'(u) gamma, u = gamma x^ + beta
 // du = dy silu'(u) gamma for one element (u: the GroupNorm output before the SiLU)
 __device__ __forceinline__ float gnb_du(float dy, float u, float gamma, int silu)
 {
@@ -466,7 +572,8 @@ __global__ __launch_bounds__(256) void k_gnb_reduce(const f16 *__restrict__ x, c
     const int b = blockIdx.y, sp = blockIdx.x;
     const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
     const int per = (HW + NS - 1) / NS, p0 = sp * per, p1 = min(HW, p0 + per), cg = C / G;
-    float s[8], q[8], a[8], b0[8], ga[8], mu[8], rs[8];
+    float s[8], q[8], a[8], b0[8], ga[8], mu[8], rs[8], pv[8];
+    if (MODE == 0) gn_pivots<false>(x, nullptr, 0, C, HW, b, c8 * 8, cg, pv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         s[j] = 0.f; q[j] = 0.f;
@@ -482,7 +589,7 @@ __global__ __launch_bounds__(256) void k_gnb_reduce(const f16 *__restrict__ x, c
             const f16x8 xv = *(const f16x8 *)(x + off);
             if (MODE == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { float f = (float)xv[j]; s[j] += f; q[j] += f * f; }
+                for (int j = 0; j < 8; ++j) { float f = (float)xv[j] - pv[j]; s[j] += f; q[j] += f * f; }
             } else {
                 const f16x8 dv = *(const f16x8 *)(dy + off);
 #pragma unroll
@@ -510,16 +617,17 @@ __global__ __launch_bounds__(256) void k_gnb_reduce(const f16 *__restrict__ x, c
         part[(((size_t)b * NS + sp) * G + g) * 2] = ss; part[(((size_t)b * NS + sp) * G + g) * 2 + 1] = qq;
     }
 }
-// MODE 0 -> (mean, rstd); MODE 1 -> (sum du / n, sum du x^ / n)
+// MODE 0 -> (mean, rstd), the pivot of x's group added back; MODE 1 -> (sum du / n, sum du x^ / n)
 template <int MODE>
-__global__ void k_gnb_finalize(const float *__restrict__ part, int G, int NS, float n, float eps, float *__restrict__ out)
+__global__ void k_gnb_finalize(const float *__restrict__ part, const f16 *__restrict__ x, int HW, int C, int G, int NS, float n, float eps,
+                               float *__restrict__ out)
 {
     const int b = blockIdx.x;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         float ss = 0.f, qq = 0.f;
         for (int k = 0; k < NS; ++k) { ss += part[(((size_t)b * NS + k) * G + g) * 2]; qq += part[(((size_t)b * NS + k) * G + g) * 2 + 1]; }
         if (MODE == 0) {
-            const float2 m = gn_mean_rstd(ss, qq, n, eps);
+            const float2 m = gn_mean_rstd(ss, qq, n, eps, gn_pivot<false>(x, nullptr, 0, C, HW, b, g * (C / G)));
             out[((size_t)b * G + g) * 2] = m.x; out[((size_t)b * G + g) * 2 + 1] = m.y;
         } else { out[((size_t)b * G + g) * 2] = ss / n; out[((size_t)b * G + g) * 2 + 1] = qq / n; }
     }
@@ -572,9 +680,9 @@ extern "C" int32_t ctx_groupnorm_bwd_f16(const void *xv, const void *dyv, const 
     const size_t lds = ((size_t)PL * C * 2 + (size_t)C * 2) * sizeof(float);
     const float n = (float)HW * (float)(C / G);
     hipLaunchKernelGGL(k_gnb_reduce<0>, dim3(NS, B), dim3(256), lds, s, x, (const f16 *)nullptr, gamma, beta, (const float *)nullptr, HW, C, G, NS, silu, part);
-    hipLaunchKernelGGL(k_gnb_finalize<0>, dim3(B), dim3(64), 0, s, part, G, NS, n, eps, mr);
+    hipLaunchKernelGGL(k_gnb_finalize<0>, dim3(B), dim3(64), 0, s, part, x, HW, C, G, NS, n, eps, mr);
     hipLaunchKernelGGL(k_gnb_reduce<1>, dim3(NS, B), dim3(256), lds, s, x, dy, gamma, beta, mr, HW, C, G, NS, silu, part);
-    hipLaunchKernelGGL(k_gnb_finalize<1>, dim3(B), dim3(64), 0, s, part, G, NS, n, 0.f, cc);
+    hipLaunchKernelGGL(k_gnb_finalize<1>, dim3(B), dim3(64), 0, s, part, x, HW, C, G, NS, n, 0.f, cc);
     hipLaunchKernelGGL(k_gnb_apply, dim3(capped_blocks((int64_t)HW * c8n, 256, 2048), B), dim3(256), 0, s, x, dy, gamma, beta, mr, cc, add, HW, C, G, silu, dx);
     CTX_CHECK_LAUNCH("groupnorm backward");
     return CTX_OK;
@@ -697,35 +805,69 @@ extern "C" int32_t ctx_layernorm_f16(const void *x, const void *gamma, const voi
     return ctx_layernorm_any(x, 0, gamma, beta, rows, C, eps, y, (hipStream_t)stream);
 }
 
+// test seam of the fp32-input kernels: x [rows, C] fp32
+extern "C" int32_t ctx_layernorm_f32in_f16(const float *x, const void *gamma, const void *beta, int64_t rows, int32_t C, float eps,
+                                           void *y, ctx_stream_t stream)
+{
+    return ctx_layernorm_any(x, 1, gamma, beta, rows, C, eps, y, (hipStream_t)stream);
+}
+
+// The launch plan.  g8 1: k_layernorm_g8<KC>, 8 lanes per row, 32 rows per block; 0: k_layernorm<KC, R>, a wave per R rows, 4 waves per block
+struct LnPlan { int g8, KC, R; int64_t blocks; };
+static int ln_plan(int64_t rows, int C, int x32, LnPlan &p)
+{
+    p = LnPlan{};
+    CTX_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 2048, "layernorm: unsupported rows=%lld C=%d", (long long)rows, C);
+    // fp16 input, C a multiple of 64 up to 640 (beyond that the one-wave-per-row form fills >= 83 % of its lanes and gamma / beta for 20
+    // chunks per lane would not fit the registers): 8 lanes per row (CTX_LN_G8=0: the one-wave-per-row kernels)
+    static const int g8 = ctx_env_int("CTX_LN_G8", 1);
+    if (g8 && !x32 && C % 64 == 0 && C <= 640 && rows >= 64) {
+        p.g8 = 1; p.KC = C / 64; p.R = 8;
+        p.blocks = cdiv64(cdiv64(rows, 8), 4);
+        return CTX_OK;
+    }
+    p.KC = (C / 8 + 63) / 64;                                 // 16-byte chunks per lane per row
+    // rows per wave: ~4 loads in flight per lane, but keep >= ~2 waves per SIMD of work on the chip
+    p.R = rows >= 8192 ? (p.KC == 1 ? 4 : p.KC == 2 ? 2 : 1) : 1;
+    p.blocks = cdiv64(cdiv64(rows, p.R), 4);
+    return CTX_OK;
+}
+
+extern "C" int32_t ctx_layernorm_plan(int64_t rows, int32_t C, int32_t x32, int64_t *out)
+{
+    CTX_REQUIRE(out, "layernorm plan: null pointer");
+    LnPlan p;
+    if (const int rc = ln_plan(rows, C, x32, p); rc != CTX_OK) return rc;
+    out[0] = p.g8; out[1] = p.KC; out[2] = p.R; out[3] = p.blocks;
+    return CTX_OK;
+}
+
 int ctx_layernorm_any(const void *x, int x32, const void *gamma, const void *beta, int64_t rows, int C, float eps, void *y, hipStream_t stream)
 {
-    CTX_REQUIRE(x && gamma && beta && y && rows > 0 && C % 8 == 0 && C <= 2048, "layernorm: unsupported rows=%lld C=%d", (long long)rows, C);
-    {
-        // fp16 input, C a multiple of 64 up to 640 (beyond that the one-wave-per-row form fills >= 83 % of its lanes and gamma / beta for 20
-        // chunks per lane would not fit the registers): 8 lanes per row (CTX_LN_G8=0: the one-wave-per-row kernels)
-        static const int g8 = ctx_env_int("CTX_LN_G8", 1);
-        if (g8 && !x32 && C % 64 == 0 && C <= 640 && rows >= 64) {
-            const unsigned nb = (unsigned)cdiv64(cdiv64(rows, 8), 4);
+    CTX_REQUIRE(x && gamma && beta && y, "layernorm: null pointer");
+    LnPlan p;
+    if (const int rc = ln_plan(rows, C, x32, p); rc != CTX_OK) return rc;
+    const unsigned nb = (unsigned)p.blocks;
+    if (p.g8) {
 #define LN_G8(KC_) case KC_: hipLaunchKernelGGL(k_layernorm_g8<KC_>, dim3(nb), dim3(256), 0, stream, (const f16 *)x, (const f16 *)gamma, (const f16 *)beta, rows, eps, (f16 *)y); break
-            switch (C / 64) {
-                LN_G8(1); LN_G8(2); LN_G8(3); LN_G8(4); LN_G8(5); LN_G8(6); LN_G8(7); LN_G8(8); LN_G8(9); LN_G8(10);
-            }
-#undef LN_G8
-            CTX_CHECK_LAUNCH("layernorm");
-            return CTX_OK;
+        switch (p.KC) {
+            LN_G8(1); LN_G8(2); LN_G8(3); LN_G8(4); LN_G8(5); LN_G8(6); LN_G8(7); LN_G8(8); LN_G8(9); LN_G8(10);
         }
+#undef LN_G8
+        CTX_CHECK_LAUNCH("layernorm");
+        return CTX_OK;
     }
-    const int kc = (C / 8 + 63) / 64;                          // 16-byte chunks per lane per row
-#define LN_GO(KC_, R_) CTX_BOOL_GO(x32, X, hipLaunchKernelGGL((k_layernorm<KC_, R_, X>), dim3((unsigned)cdiv64(cdiv64(rows, R_), 4)), dim3(256), 0, stream, x, \
+#define LN_GO(KC_, R_) CTX_BOOL_GO(x32, X, hipLaunchKernelGGL((k_layernorm<KC_, R_, X>), dim3(nb), dim3(256), 0, stream, x, \
                                                           (const f16 *)gamma, (const f16 *)beta, rows, C, eps, (f16 *)y))
-    // rows per wave: ~4 loads in flight per lane, but keep >= ~2 waves per SIMD of work on the chip
-    const bool many = rows >= 8192;
-    if (kc == 1) { if (many) LN_GO(1, 4); else LN_GO(1, 1); }
-    else if (kc == 2) { if (many) LN_GO(2, 2); else LN_GO(2, 1); }
-    else if (kc == 3) LN_GO(3, 1);
-    else LN_GO(4, 1);
+    switch (p.KC * 8 + p.R) {
+        case 1 * 8 + 4: LN_GO(1, 4); break;
+        case 1 * 8 + 1: LN_GO(1, 1); break;
+        case 2 * 8 + 2: LN_GO(2, 2); break;
+        case 2 * 8 + 1: LN_GO(2, 1); break;
+        case 3 * 8 + 1: LN_GO(3, 1); break;
+        default: LN_GO(4, 1); break;
+    }
 #undef LN_GO
     CTX_CHECK_LAUNCH("layernorm");
     return CTX_OK;
 }
-

@@ -842,6 +842,21 @@ int32_t ctx_groupnorm_slabs_f16(const void *part, int32_t splitk, const void *bi
                                 int32_t groups, float eps, int32_t silu, void *y, ctx_stream_t stream);
 int32_t ctx_layernorm_f16(const void *x, const void *gamma, const void *beta, int64_t rows, int32_t C,
                           float eps, void *y, ctx_stream_t stream);
+/* ---- test-only seams of the norm kernels (GroupNorm / LayerNorm of diffusers' UNet2DConditionModel and AutoencoderKL under
+   src/stable_diffusion_depth.py:422-423).  tests/norm_rule.py holds the float64 references and the error bound.  Not for product code. ----
+   The launch plans, host only: what ctx_groupnorm_f16 / ctx_groupnorm2_f16 (Ca != 0: two sources, the first Ca channels wide) /
+   ctx_groupnorm_f32in_f16 (x32) would launch for a shape, from the function the launcher itself calls; CTX_E_ARG where it refuses.
+   groupnorm out[12]: one (1 the one-kernel form, 0 the two-pass form), plf, thr (one-kernel: pixel lanes, block), PL, threads, NS,
+     na, lds (pass 1: pixel lanes, block, splits, fold slices, dynamic LDS bytes), apl, athreads, nb (pass 2, also
+     ctx_groupnorm_apply_f16's: pixel lanes, block, blocks per sample at 6 pixels per lane), the LDS bytes pass 1 opts into.
+   layernorm out[4]: g8 (1: 8 lanes per row, else a wave per R rows), KC (16-byte chunks per lane per row), R, blocks of 256 threads. */
+int32_t ctx_groupnorm_plan(int32_t B, int32_t HW, int32_t C, int32_t groups, int32_t x32, int32_t Ca, int32_t *out);
+int32_t ctx_layernorm_plan(int64_t rows, int32_t C, int32_t x32, int64_t *out);
+/* ctx_groupnorm_f16 and ctx_layernorm_f16 with x in fp32 (the kernels behind ctx_unet_set_residual_fp32); y stays f16. */
+int32_t ctx_groupnorm_f32in_f16(const float *x, const void *gamma, const void *beta, int32_t B, int32_t HW, int32_t C,
+                                int32_t groups, float eps, int32_t silu, void *y, void *stats_ws, ctx_stream_t stream);
+int32_t ctx_layernorm_f32in_f16(const float *x, const void *gamma, const void *beta, int64_t rows, int32_t C, float eps,
+                                void *y, ctx_stream_t stream);
 /* softmax(Q K^T * scale) V; Q[B,Sq,heads*64], K[B,Skv,heads*64], V likewise (f16) -> O[B,Sq,heads*64];
    row strides in elements.  vt_ws: unused since V is consumed untransposed (ds_read_b64_tr_b16); may be null, ctx_attention_ws_bytes() returns a token size. */
 int64_t ctx_attention_ws_bytes(int32_t B, int32_t Skv, int32_t heads);

@@ -73,7 +73,8 @@ def emu_pack_mat_T(dst, w, col):
 
 
 def emu_gn_bwd(x, dy, gamma, beta, add, G, silu, mut=None):
-    """k_gnb_reduce<0/1>, k_gnb_finalize and k_gnb_apply in fp32: statistics from (sum x, sum x^2), du = dy silu'(u) gamma, c1 = sum du / n,
+    """k_gnb_reduce<0/1>, k_gnb_finalize and k_gnb_apply in fp32: statistics from (sum x, sum x^2) (the kernel sums about a pivot of the
+    group, the same quantities in exact arithmetic: tests/norm_rule.py), du = dy silu'(u) gamma, c1 = sum du / n,
     c2 = sum du x^ / n, dx = (f16)(rstd (du - c1 - x^ c2) + add).  mut: 'no_c1' | 'c2_from_x' | 'skip_last' (every split of the two
     reductions stops one pixel early)."""
     B, HW, Cc = x.shape
