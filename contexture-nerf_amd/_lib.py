@@ -39,7 +39,10 @@ SIGNATURES = {
     "ctx_atlas_fill_ws_bytes": (_i64, [_i32]),
     "ctx_nearest_seed": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "ctx_atlas_fill": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "ctx_view_consistency_ws_bytes": (_i64, [_i32, _i32]),
+    "ctx_mask_morph": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_sep_filter": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _vp, _vp]),
+    "ctx_atlas_blend": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "ctx_view_consistency_ws_bytes":(_i64, [_i32, _i32]),
     "ctx_view_consistency_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctx_view_consistency_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ctx_texture_pack4": (_i32, [_vp, _i32, _i32, _vp, _vp]),

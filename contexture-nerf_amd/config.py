@@ -48,8 +48,10 @@ class GuideConfig:
     initial_texture: Optional[Path] = None
     use_background_color: bool = False
     background_img: str = 'textures/brick_wall.png'
-    z_update_thr: float = 0.2
-    strict_projection: bool = True
+    z_update_thr: float = 0.2        # read under paint_mode = 'progressive' only: a painted texel is refined when a view sees it this much more
+                                     # frontally than the view that painted it (ConTEXTure.calculate_trimap)
+    strict_projection: bool = True   # read under paint_mode = 'progressive' only: the projection weight drops below 0.5 and where an
+                                     # earlier view was more frontal (ConTEXTure.projection_weight)
     # --- additions of this build (not in the reference): BASELINE.json configs vary the SD image size ---
     sd_image_size: int = 512
     num_inference_steps: int = 50
@@ -64,6 +66,11 @@ class GuideConfig:
                                      # UV (ConTEXTure.project_back_scatter, csrc/uvscatter.hip; the outputs of earlier builds, bit for bit);
                                      # 'gather': every chart texel looks its surface point up in the views (project_back_gather,
                                      # csrc/uvgather.hip): no pinholes where the surface is magnified, nothing outside the charts
+    paint_mode: str = 'independent'  # 'independent': every view is denoised from pure noise and the views are merged by the view-weight masks
+                                     # (the outputs of earlier builds, bit for bit); 'progressive': TEXTure's loop (ConTEXTure.paint_progressive):
+                                     # the views are painted one after another, each conditioned on what the earlier ones painted, through a
+                                     # generate / refine / keep trimap, masked latent blending and a meta-texture of the z-normal every texel
+                                     # was painted at (csrc/maskops.hip).  One rank; optim.views_per_eval and optim.views_in_flight are not read
     texture_field: str = 'mlp'       # the field behind the atlas.  'mlp': the 8 x 256 MLP on the Fourier embedding of uv (the outputs of earlier
                                      # builds, bit for bit); 'hashgrid': a multiresolution hash table over the UV square and a 2 x 64 MLP
                                      # (hashgrid.HashGridTexture, csrc/hashtex.hip; its finest level is texture_resolution)
@@ -160,6 +167,7 @@ ATLAS_FILL_MODES = ('none', 'nearest')
 PROJECTION_MODES = ('scatter', 'gather')
 FIELD_TEXELS_MODES = ('all', 'active')
 TEXTURE_FIELDS = ('mlp', 'hashgrid')
+PAINT_MODES = ('independent', 'progressive')
 
 
 def validate(cfg):
@@ -174,6 +182,8 @@ def validate(cfg):
             raise ValueError(f"guide.projection={guide.projection!r}: expected one of {PROJECTION_MODES}")
         if guide.texture_field not in TEXTURE_FIELDS:
             raise ValueError(f"guide.texture_field={guide.texture_field!r}: expected one of {TEXTURE_FIELDS}")
+        if guide.paint_mode not in PAINT_MODES:
+            raise ValueError(f"guide.paint_mode={guide.paint_mode!r}: expected one of {PAINT_MODES}")
     optim = getattr(cfg, 'optim', None)
     if optim is not None and not (optim.hashgrid_lr > 0 and optim.hashgrid_mlp_lr > 0):
         raise ValueError(f"optim.hashgrid_lr={optim.hashgrid_lr}, optim.hashgrid_mlp_lr={optim.hashgrid_mlp_lr}: expected > 0")

@@ -347,6 +347,85 @@ def atlas_fill(atlas, coverage, chart, pad):
     return filled, src
 
 
+# ---- mask operators of the progressive paint loop (csrc/maskops.hip) ---------------------------------------
+MORPH_OPS = {'dilate': 0, 'erode': 1}
+MASK_MAX_K = 63
+
+
+def _mask_image(who, src):
+    """src float32 [..., H, W] (device, contiguous) -> (pointer, N, H, W)."""
+    p = L.ptr(src, torch.float32, "src")
+    if src.dim() < 2 or src.numel() == 0:
+        raise L.CtxError(f"{who}: want a non-empty float32 image [..., H, W], got {tuple(src.shape)}")
+    H, W = int(src.shape[-2]), int(src.shape[-1])
+    return p, src.numel() // (H * W), H, W
+
+
+def mask_morph(src, k, op):
+    """k x k dilation (op 'dilate': max) or erosion ('erode': min) of float32 images [..., H, W], the window clipped to the image (pixels
+    outside take no part: OpenCV's default border of both).  k odd in [1, 63]; it may exceed H or W.  Any finite values: soft masks too.
+    -> a new tensor of src's shape; src is not modified.  No host sync."""
+    if op not in MORPH_OPS:
+        raise L.CtxError(f"mask_morph: op={op!r}: expected one of {tuple(MORPH_OPS)}")
+    p, N, H, W = _mask_image("mask_morph", src)
+    dst, ws = torch.empty_like(src), torch.empty_like(src)
+    L.check(L.load().ctx_mask_morph(p, N, H, W, int(k), MORPH_OPS[op], L.ptr(dst), L.ptr(ws), L.stream()))
+    return dst
+
+
+def dilate(src, k):
+    return mask_morph(src, k, 'dilate')
+
+
+def erode(src, k):
+    return mask_morph(src, k, 'erode')
+
+
+def gaussian_taps(k, sigma):
+    """The k taps of torchvision's gaussian_blur kernel: exp(-0.5 (x / sigma)^2) at the integer offsets x = -(k//2) .. k//2, normalised to
+    sum 1 in float64, then rounded to float32.  -> list of k Python floats (each exactly a float32)."""
+    k, sigma = int(k), float(sigma)
+    if k < 1 or k % 2 == 0 or not (sigma > 0 and math.isfinite(sigma)):
+        raise L.CtxError(f"gaussian_taps: k={k}, sigma={sigma}: want an odd k >= 1 and a finite sigma > 0")
+    x = torch.arange(-(k // 2), k // 2 + 1, dtype=torch.float64)
+    pdf = torch.exp(-0.5 * (x / sigma) ** 2)
+    return (pdf / pdf.sum()).to(torch.float32).tolist()
+
+
+def sep_filter(src, taps):
+    """Separable k-tap filter of float32 images [..., H, W]: the taps along the rows, then along the columns, reflect padding that does
+    not repeat the edge (index -1 reads 1), every output the taps summed left to right in binary32.  taps: k host floats, k odd in
+    [1, 63], k // 2 <= min(H, W) - 1.  -> a new tensor; no host sync (the taps travel with the launch)."""
+    p, N, H, W = _mask_image("sep_filter", src)
+    taps = [float(t) for t in taps]
+    k = len(taps)
+    if k < 1 or k > MASK_MAX_K or k % 2 == 0:
+        raise L.CtxError(f"sep_filter: {k} taps: want an odd count in [1, {MASK_MAX_K}]")
+    dst, ws = torch.empty_like(src), torch.empty_like(src)
+    L.check(L.load().ctx_sep_filter(p, N, H, W, (L.C.c_float * k)(*taps), k, L.ptr(dst), L.ptr(ws), L.stream()))
+    return dst
+
+
+def gaussian_blur(src, k, sigma):
+    return sep_filter(src, gaussian_taps(k, sigma))
+
+
+def atlas_blend(contrib, zsum, acc, meta):
+    """The progressive atlas update (ctx_atlas_blend; the rule is written out there): acc [4,T,T] int64 and meta [T,T] float32 take one
+    view's contribution contrib [4,T,T] int64 / zsum [T,T] int64 (sums in units of 2^-32, as scatter_fixed / gather_fixed leave them),
+    IN PLACE.  A texel the view gave no weight keeps its bits; a painted one ends with acc[3] = 2^32.  -> (acc, meta)."""
+    p = (L.ptr(contrib, torch.int64, "contrib"), L.ptr(zsum, torch.int64, "zsum"))
+    p_acc, p_meta = L.ptr(acc, torch.int64, "acc"), L.ptr(meta, torch.float32, "meta")
+    if acc.dim() != 3 or acc.shape[0] != 4 or acc.shape[1] != acc.shape[2]:
+        raise L.CtxError(f"atlas_blend: acc is {tuple(acc.shape)}, expected [4,T,T]")
+    T = int(acc.shape[1])
+    for name, t, shp in (("contrib", contrib, (4, T, T)), ("zsum", zsum, (T, T)), ("meta", meta, (T, T))):
+        if tuple(t.shape) != shp:
+            raise L.CtxError(f"atlas_blend: {name} is {tuple(t.shape)}, expected {shp}")
+    L.check(L.load().ctx_atlas_blend(*p, T, p_acc, p_meta, L.stream()))
+    return acc, meta
+
+
 # ---- multi-view consistency (src/training/trainer.py:429-531) ------------------------------------------
 VIEW_ROWS = {'reference': 0, 'image': 1}      # 'reference': upstream's rows (row 0 at Y = -1); 'image': the raster's (row 0 at Y = +1)
 

@@ -152,8 +152,14 @@ class StableDiffusion:
         update out); the evaluation itself is the lane runner's (`_run_wave`)."""
 
         def __init__(self, sd, scheduler, text_embeddings, latents, depth_mask, strength, num_inference_steps, update_mask,
-                     fixed_seed, guidance_scale):
+                     fixed_seed, guidance_scale, check_mask=None, blend=False):
             self.scheduler = scheduler
+            # blend (progressive painting, TEXTure section 3.3): the encoded render is kept as gt_latents and, before every evaluation,
+            # put back at its noise level wherever the current mask is 0 (model_input).  The random draws are those of blend=False
+            if blend and (latents is None or update_mask is None):
+                raise L.CtxError("img2img_step: blend=True needs `inputs` (the render whose latents are kept) and an `update_mask`")
+            self.blend, self.gt_latents = bool(blend), (latents if blend else None)
+            self.update_mask, self.check_mask = (update_mask, check_mask) if blend else (None, None)
             self.text_embeddings, self.guidance_scale = text_embeddings, guidance_scale
             scheduler.set_timesteps(num_inference_steps)
             shape = (text_embeddings.shape[0] // 2, sd.unet.in_channels - 1, depth_mask.shape[2], depth_mask.shape[3])
@@ -183,6 +189,11 @@ class StableDiffusion:
         def model_input(self):
             """-> (x [2,C+1,h,w] = the CFG pair of this view's latents with its depth, t)."""
             t = self.timesteps[self.i]
+            if self.blend:
+                # the checkerboard holds for the first half of the evaluations, the plain update mask after it; the latents the UNet
+                # sees (and the step then updates) are the blended ones
+                curr = self.check_mask if self.check_mask is not None and self.i < len(self.timesteps) // 2 else self.update_mask
+                self.latents = self.latents * curr + self.scheduler.add_noise(self.gt_latents, self.noise, t.reshape(1)) * (1 - curr)
             latent_model_input = torch.cat([self.latents] * 2)
             latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
             return torch.cat([latent_model_input, self.depth2], dim=1), t
@@ -194,7 +205,9 @@ class StableDiffusion:
             self.latents = self.scheduler.step_cfg(noise_pred, self.guidance_scale, int(t), self.latents)['prev_sample']
             self.i += 1
 
-    def _prepare(self, inputs, original_depth_mask, update_mask, latent_mode, image_size):
+    def _prepare(self, inputs, original_depth_mask, update_mask, latent_mode, image_size, blend=False):
+        if blend and inputs is not None and not latent_mode and not hasattr(self.vae, 'encode'):
+            raise L.CtxError(f"img2img_step: blend=True keeps the encoded render, and the VAE {type(self.vae).__name__} has no encode()")
         depth_mask = F.interpolate(original_depth_mask, size=(image_size // 8, image_size // 8), mode='bicubic', align_corners=False)
         if inputs is None:
             latents = None
@@ -216,23 +229,41 @@ class StableDiffusion:
         """img2img_step's keyword arguments -> its _Denoise job (everything the reference does before the loop), with its own
         scheduler; `vis` collects the intermediate images when the call asks for them."""
         latent_mode, image_size = kw.get('latent_mode', False), kw.get('image_size', 512)
-        latents, depth_mask, update_mask = self._prepare(kw['inputs'], kw['original_depth_mask'], kw.get('update_mask'), latent_mode, image_size)
+        blend = bool(kw.get('blend', False))
+        latents, depth_mask, update_mask = self._prepare(kw['inputs'], kw['original_depth_mask'], kw.get('update_mask'), latent_mode, image_size, blend)
+        check_mask = kw.get('check_mask') if blend else None
+        if check_mask is not None:
+            check_mask = F.interpolate(check_mask, (image_size // 8, image_size // 8), mode='nearest')
         job = StableDiffusion._Denoise(self, self._new_scheduler(), kw['text_embeddings'], latents, depth_mask, kw.get('strength', 0.5),
-                                       kw.get('num_inference_steps', 50), update_mask, kw.get('fixed_seed'), kw.get('guidance_scale', 100))
+                                       kw.get('num_inference_steps', 50), update_mask, kw.get('fixed_seed'), kw.get('guidance_scale', 100),
+                                       check_mask=check_mask, blend=blend)
         job.latent_mode, job.vis = latent_mode, []
         if kw.get('intermediate_vis'):
             job.on_step = lambda t, lat, noise: job.vis.append(self._vis_step(t, lat, noise))
+        elif kw.get('on_step') is not None:
+            job.on_step = kw['on_step']
         return job
 
     def img2img_step(self, text_embeddings, inputs, original_depth_mask, guidance_scale=100, strength=0.5,
                      num_inference_steps=50, update_mask=None, latent_mode=False, fixed_seed=None, intermediate_vis=False,
-                     view_dir=None, front_image=None, phi=None, theta=None, condition_guidance_scales=None, image_size=512):
+                     view_dir=None, front_image=None, phi=None, theta=None, condition_guidance_scales=None, image_size=512,
+                     check_mask=None, blend=False, on_step=None):
         """One view: (rgb, latents) with latent_mode, else (rgb, intermediate images).  view_dir ... condition_guidance_scales
-        are the reference's call contract and are not read."""
-        return self.img2img_steps([dict(text_embeddings=text_embeddings, inputs=inputs, original_depth_mask=original_depth_mask,
-                                        guidance_scale=guidance_scale, strength=strength, num_inference_steps=num_inference_steps,
-                                        update_mask=update_mask, latent_mode=latent_mode, fixed_seed=fixed_seed,
-                                        intermediate_vis=intermediate_vis, image_size=image_size)])[0]
+        are the reference's call contract and are not read.
+        blend=True (single views only; progressive painting): the latents of `inputs` are kept and, before every UNet evaluation i,
+        `latents = latents * curr + add_noise(gt_latents, noise, t) * (1 - curr)` with curr = check_mask while i < len(timesteps) // 2
+        (when one is given), update_mask after that, both resized to the latent grid by nearest: the blend the reference carries
+        commented out (stable_diffusion_depth.py:382).  blend=False is the loop as it was, bit for bit, and reads no check_mask.
+        on_step(t, latents, noise): called with the latents that entered each evaluation, before its step."""
+        call = dict(text_embeddings=text_embeddings, inputs=inputs, original_depth_mask=original_depth_mask,
+                    guidance_scale=guidance_scale, strength=strength, num_inference_steps=num_inference_steps,
+                    update_mask=update_mask, latent_mode=latent_mode, fixed_seed=fixed_seed,
+                    intermediate_vis=intermediate_vis, image_size=image_size)
+        if blend:
+            call.update(blend=True, check_mask=check_mask)
+        if on_step is not None:
+            call['on_step'] = on_step
+        return self.img2img_steps([call])[0]
 
     def _vis_step(self, t, latents, noise):
         """`intermediate_vis` of img2img_step (stable_diffusion_depth.py:500-511, LogConfig.vis_diffusion_steps): the x0 estimate
@@ -254,6 +285,8 @@ class StableDiffusion:
         independent, so a view's bits depend on the size of its group, not on its mates, its position or what runs beside it.
         Calls that differ in image size, step count, strength or latent mode are not batched; a call with intermediate_vis runs
         as its own one-lane wave on the current stream."""
+        if len(calls) > 1 and any(kw.get('blend') for kw in calls):
+            raise L.CtxError(f"img2img_steps: blend=True is for single views (the progressive loop is sequential), got {len(calls)} calls")
         key = lambda kw: (kw.get('image_size', 512), kw.get('num_inference_steps', 50), kw.get('strength', 0.5), kw.get('latent_mode', False))
         vis = [bool(kw.get('intermediate_vis')) for kw in calls]
         batchable = not any(vis) and all(key(kw) == key(calls[0]) for kw in calls)

@@ -20,6 +20,19 @@ from .textured_mesh import TexturedMeshModel
 from .views_dataset import Zero123PlusDataset, MultiviewDataset
 
 
+# TEXTure's mask constants are window sizes for 1200^2 renders; their radii scale with render.train_grid_size G in integers:
+# r(G) = (2 r0 G + 1200) // 2400 (r0 G / 1200 rounded half up), k = 2 r + 1, which is k0 itself at G = 1200
+TRIMAP_K0 = dict(generate=19, rim=7, open=5, project=25, blur=21)
+
+
+def scaled_radius(r0, G):
+    return (2 * int(r0) * int(G) + 1200) // 2400
+
+
+def scaled_k(k0, G):
+    return 2 * scaled_radius(int(k0) // 2, G) + 1
+
+
 class ConTEXTure:
     def __init__(self, cfg, device=None, diffusion=None, mesh_arrays=None, group=None):
         self.cfg = cfg
@@ -548,9 +561,155 @@ class ConTEXTure:
         self.mesh_model.eval()
         return log
 
+    # ---- progressive painting (guide.paint_mode = 'progressive'): TEXTure, Richardson et al. 2023, sections 3.2-3.3 ----------------
+    # The reference is forked from TEXTure and carries the remains of this loop (GuideConfig.z_update_thr / strict_projection,
+    # train_config.py:79,81; the use_meta_texture render flag; project_back(update_mask=, z_normals_cache=) at trainer.py:1076-1090 with
+    # undefined names; the commented-out latent blend, stable_diffusion_depth.py:382).  TEXTure's source is not available to this
+    # project: the rules below are its own definition, written from the paper.  PARITY UNPINNED, as project_back is.
+    def _k(self, name):
+        return scaled_k(TRIMAP_K0[name], int(self.cfg.render.train_grid_size))
+
+    @torch.no_grad()
+    def calculate_trimap(self, object_mask, z_normals, painted, z_cache):
+        """-> (update, generate, refine), each float {0,1} [1,1,G,G].  painted / z_cache: the nearest-mode renders of `atlas_acc[3] > 0`
+        and of the meta-texture.  generate: the object where nothing is painted yet, grown by k(19); refine: painted pixels this view
+        sees more than guide.z_update_thr more frontally than the view that painted them, opened by k(5) (specks go, blocks stay);
+        update = generate | refine, without the object's rim of k(7) where it is not generate.  The rest of the object is kept."""
+        from . import kal
+        obj, ptd = object_mask > 0, painted > 0
+        generate = kal.dilate((obj & ~ptd).float().contiguous(), self._k('generate'))
+        better = ((z_normals > z_cache + float(self.cfg.guide.z_update_thr)) & ptd & obj).float().contiguous()
+        refine = kal.dilate(kal.erode(better, self._k('open')), self._k('open'))
+        update = torch.maximum(generate, refine)
+        rim = kal.erode(obj.float().contiguous(), self._k('rim'))
+        update[(rim == 0) & (generate == 0)] = 0
+        return update, generate, refine
+
+    @torch.no_grad()
+    def checker_mask(self, update, refine, generate, S):
+        """The mask of the first half of a blended denoise loop, [1,1,S,S]: `update` resized by nearest, with a checkerboard of
+        S // 32 pixel cells (two latent pixels at S = 512) where the view only refines: there every other cell keeps the earlier
+        paint, so the refinement stays anchored to it."""
+        rs = lambda m: F.interpolate(m, (S, S), mode='nearest')
+        out = rs(update)
+        c = max(1, S // 32)
+        i = torch.arange(S, device=out.device) // c
+        board = ((i[:, None] + i[None, :]) % 2).to(out.dtype)[None, None]
+        only = (rs(refine) > 0) & ~(rs(generate) > 0)
+        return torch.where(only, board, out)
+
+    @torch.no_grad()
+    def projection_weight(self, object_mask, update, z_normals, painted, z_cache):
+        """-> the soft weight [1,1,G,G] a painted view is projected back with: the updated part of the object eroded by k(5), grown by
+        k(25) and blurred (k(21) taps, sigma 16 G / 1200), zero outside the eroded object; under guide.strict_projection also zero
+        below 0.5 and where an earlier, more frontal view painted (z_cache > z_normals): that view keeps its texels."""
+        from . import kal
+        G = int(self.cfg.render.train_grid_size)
+        oe = kal.erode((object_mask > 0).float().contiguous(), self._k('open'))
+        core = ((oe > 0) & (update > 0)).float()
+        soft = kal.gaussian_blur(kal.dilate(core, self._k('project')), self._k('blur'), 16.0 * G / 1200.0)
+        soft[oe == 0] = 0
+        if self.cfg.guide.strict_projection:
+            soft[soft < 0.5] = 0
+            soft[(painted > 0) & (z_cache > z_normals)] = 0
+        return soft
+
+    @torch.no_grad()
+    def begin_progressive(self):
+        """Empties the running atlas (atlas_acc [4,T,T] int64 sums, atlas_meta [T,T]: the z-normal every texel was painted at), the
+        trimap log and paint_step."""
+        from .config import validate
+        validate(self.cfg)
+        if self.world > 1:
+            raise RuntimeError(f"guide.paint_mode='progressive' paints the views one after another on one rank; this run has {self.world} ranks")
+        T = int(self.cfg.guide.texture_resolution)
+        self.atlas_acc = torch.zeros(4, T, T, dtype=torch.int64, device=self.device)
+        self.atlas_meta = torch.zeros(T, T, dtype=torch.float32, device=self.device)
+        self.trimaps, self.paint_step = [], 0
+
+    @torch.no_grad()
+    def render_progress(self, render_cache, object_mask):
+        """The running atlas seen through a raster -> (rgb [1,3,G,G] (valid where painted), painted [1,1,G,G] {0,1}, z_cache [1,1,G,G]).
+        Colour is the bilinear mean over the PAINTED taps only; painted and z_cache are nearest-mode renders."""
+        from . import kal
+        uv, face_idx = render_cache['uv_features'], render_cache['face_idx']
+        colour, wsum = D.atlas_from_sums(self.atlas_acc)
+        cov = (wsum > 0).float()
+        tm = lambda tex, mode: kal.render.mesh.texture_mapping(uv, tex[None].contiguous(), mode=mode, mask_idx=face_idx).permute(0, 3, 1, 2)
+        pre = tm(torch.cat([colour * cov, cov[None]]), 'bilinear')
+        near = tm(torch.stack([cov, self.atlas_meta]), 'nearest')
+        painted = (near[:, :1] > 0).float() * (object_mask > 0).float()
+        return (pre[:, :3] / pre[:, 3:].clamp_min(1e-8)).clamp(0, 1), painted, near[:, 1:] * painted
+
+    @torch.no_grad()
+    def paint_view_progressive(self, data, image_size=None, num_inference_steps=None):
+        """One view of the progressive loop: raster; colour, painted and z_cache from the running atlas (unpainted pixels show the
+        field's colour, as in the independent loop); trimap; crop; img2img_step on the current render (blended with it from the
+        second view on); projection of the colour and of the z-normal with projection_weight into temporaries; ctx_atlas_blend.
+        -> dict(rgb_output, object_mask, update, generate, refine, weight, contrib [4,T,T] i64, zsum [T,T] i64)."""
+        from . import kal
+        kw, ctx = self._paint_prepare(data, image_size, num_inference_steps)
+        rc, obj, z = ctx['render_cache'], ctx['object_mask'], ctx['z_normals']
+        rgb_atlas, painted, z_cache = self.render_progress(rc, obj)
+        ctx['rgb_render'] = ctx['rgb_render'] * (1 - painted) + rgb_atlas * painted
+        update, generate, refine = self.calculate_trimap(obj, z, painted, z_cache)
+        min_h, min_w, max_h, max_w = ctx['box']
+        crop = lambda x: x[:, :, min_h:max_h, min_w:max_w]
+        S = int(kw['image_size'])
+        te = kw.pop('text_embeddings'); kw.pop('inputs'); dm = kw.pop('original_depth_mask')
+        kw.update(update_mask=crop(update).contiguous(), check_mask=self.checker_mask(crop(update), crop(refine), crop(generate), S),
+                  blend=self.paint_step > 0)
+        cropped_rgb_output, _ = self.diffusion.img2img_step(te, crop(ctx['rgb_render']).detach(), dm, **kw)
+        rgb_output, _ = self._paint_finish(ctx, cropped_rgb_output)
+        weight = self.projection_weight(obj, update, z, painted, z_cache)
+        project = self.projector()
+        contrib = project(rc, rgb_output, weight)
+        zsum = project(rc, z.expand(-1, 3, -1, -1), weight)[0]
+        kal.atlas_blend(contrib, zsum, self.atlas_acc, self.atlas_meta)
+        self.trimaps.append(dict(object=obj, update=update, generate=generate, refine=refine))
+        self.paint_step += 1
+        return dict(rgb_output=rgb_output, object_mask=obj, update=update, generate=generate, refine=refine, weight=weight, contrib=contrib,
+                    zsum=zsum)
+
+    @torch.no_grad()
+    def finish_progressive(self):
+        """atlas, atlas_coverage and guide.atlas_fill from the running atlas, exactly as MeshBatchPainter.paint_all leaves them."""
+        from .config import validate
+        self.atlas, self.atlas_coverage = D.atlas_from_sums(self.atlas_acc)
+        self.atlas_filled = self.atlas_fill_src = None
+        if validate(self.cfg).guide.atlas_fill == 'nearest':
+            self.complete_atlas()
+        return self.atlas, self.atlas_coverage
+
+    def paint_progressive(self, image_size=None, num_inference_steps=None, view_ids=None):
+        """guide.paint_mode = 'progressive': the train views in dataset order, one at a time, each painted over what the earlier ones
+        left (paint_view_progressive) -> (atlas [3,T,T], coverage [T,T]).  The per-view trimaps stay in self.trimaps (save_trimaps
+        writes them).  One rank only; optim.views_per_eval and optim.views_in_flight are not read: a view needs the atlas its
+        predecessor wrote.  Both guide.projection modes work: the blend divides by the summed weight."""
+        self.begin_progressive()
+        for k in (range(len(self.train_views)) if view_ids is None else view_ids):
+            self.paint_view_progressive(self.train_views[k], image_size, num_inference_steps)
+        return self.finish_progressive()
+
+    def save_trimaps(self, path):
+        """One PNG per painted view under `path` (the train images of log.log_images): generate red, refine green, keep blue."""
+        import numpy as np
+        from PIL import Image
+        os.makedirs(str(path), exist_ok=True)
+        for i, t in enumerate(getattr(self, 'trimaps', None) or []):
+            keep = (t['object'] > 0).float() * (1 - t['update'])
+            img = torch.cat([t['generate'], t['refine'] * (1 - t['generate']), keep], dim=1)[0].permute(1, 2, 0)
+            Image.fromarray((img.cpu().numpy() * 255).astype(np.uint8)).save(os.path.join(str(path), f"{i:04d}_trimap.png"))
+        return len(getattr(self, 'trimaps', None) or [])
+
     def paint(self, image_size=None, num_inference_steps=None):
         """Per-view paint loop: views sharded over the ranks (view k -> rank k mod world, as D.shard_views), one all-reduce(MAX)
-        of the view-weight maxima and one atlas all-reduce(SUM); an idle rank joins both.  It is the one-mesh MeshBatchPainter."""
+        of the view-weight maxima and one atlas all-reduce(SUM); an idle rank joins both.  It is the one-mesh MeshBatchPainter.
+        guide.paint_mode = 'progressive' takes paint_progressive instead."""
+        if self.cfg.guide.paint_mode != 'independent':
+            from .config import validate
+            validate(self.cfg)
+            return self.paint_progressive(image_size, num_inference_steps)
         painter = MeshBatchPainter([self], view_ids=list(range(len(self.train_views))), group=self.group)
         return painter.paint_all(image_size, num_inference_steps)[0]
 

@@ -142,6 +142,31 @@ int32_t ctx_nearest_seed(const uint8_t *seed, int32_t T, int32_t *src, int32_t *
 int32_t ctx_atlas_fill(const float *atlas, const float *coverage, const uint8_t *chart, int32_t C, int32_t T, int32_t pad, float *filled, int32_t *src,
                        void *ws, int64_t ws_bytes, ctx_stream_t stream);
 
+/* ---- mask operators and the atlas update of the progressive paint loop (maskops.hip; guide.paint_mode = 'progressive') ----
+   TEXTure (Richardson et al. 2023, sections 3.2-3.3) builds its generate / refine / keep trimap and its projection weight from mask
+   morphology and a Gaussian blur done on the host; these are the same operators on the device.  Images are f32 [N,H,W], N*H*W < 2^31.
+   Every entry refuses bad arguments BEFORE any launch and leaves its outputs untouched then; one writer per element, no atomics,
+   no host sync.  src, dst and ws (N*H*W floats) are pairwise distinct.
+   ctx_mask_morph: dst[n,y,x] = max (op 0, dilate) or min (op 1, erode) of src[n,y',x'] over |y'-y| <= k/2, |x'-x| <= k/2 INSIDE the
+     image: pixels outside take no part (OpenCV's default border of both operators).  k odd in [1, 63], and it may exceed H or W;
+     values are any finite floats (soft masks too).  Separable: the row pass writes ws, the column pass dst.
+   ctx_sep_filter: taps = HOST array of k floats, k odd in [1, 63], k/2 <= min(H, W) - 1.  r = k/2, R(i, n) = -i for i < 0,
+     2(n-1) - i for i >= n, i otherwise (reflection that does not repeat the edge: index -1 reads 1):
+       ws[n,y,x]  = sum_j taps[j] * src[n, y, R(x - r + j, W)],   dst[n,y,x] = sum_j taps[j] * ws[n, R(y - r + j, H), x],
+     each sum in binary32 from j = 0 upwards: s = taps[0]*v_0, then s = s + taps[j]*v_j (product and sum round on their own). */
+int32_t ctx_mask_morph(const float *src, int32_t N, int32_t H, int32_t W, int32_t k, int32_t op, float *dst, float *ws, ctx_stream_t stream);
+int32_t ctx_sep_filter(const float *src, int32_t N, int32_t H, int32_t W, const float *taps, int32_t k, float *dst, float *ws, ctx_stream_t stream);
+/* ctx_atlas_blend: the progressive replacement for plain summation of view contributions, in the atlas's own 2^-32 currency.
+   contrib [4,T,T] i64 (one view's colour * weight sums and its weight sum, as ctx_uv_scatter_fixed / ctx_uv_gather_fixed leave them),
+   zsum [T,T] i64 (the same view's z-normal * weight sum), acc [4,T,T] i64 (the running atlas), meta [T,T] f32 (the z-normal each
+   texel was painted at).  F(v) = (float)ldexp((double)v, -32) (ctx_fixed_to_float's conversion).  Per texel, in binary32 in the order written:
+     w = contrib[3];  w <= 0: nothing changes.  wf = F(w), m = min(1, wf), new_c = F(contrib[c]) / wf, z = F(zsum) / wf;
+     acc[3] <= 0 (never painted): out_c = new_c, meta = z;
+     else old_c = F(acc[c]) / F(acc[3]):  out_c = old_c*(1 - m) + new_c*m,  meta = meta*(1 - m) + z*m;
+     acc[c] = rint(out_c * 2^32) (the conversion of the scatter), acc[3] = 2^32.
+   acc stays a sum image, so ctx_fixed_to_float and everything after the atlas merge apply unchanged.  1 <= T <= 16384. */
+int32_t ctx_atlas_blend(const int64_t *contrib, const int64_t *zsum, int32_t T, int64_t *acc, float *meta, ctx_stream_t stream);
+
 /* ---- multi-view consistency (src/training/trainer.py:429-531; the reward of :856-863, switched off upstream) ------- */
 /* views [V,C,h,w] f32, faces [F,3] i64, face_idx [V,h,w] i64 (-1 = background), face_vertices_image [V,F,3,2] f32 in [-1, 1].
    Vertex k is seen in view j when it is a corner of a face owning a pixel of face_idx[j].  For target view i, pixel (y, x) with

@@ -40,6 +40,8 @@ def main(cfg: cfgmod.TrainConfig):
                      f"{float(((trainer.atlas_fill_src >= 0) & chart).sum()) / n:.3f} after fill (pad {cfg.guide.atlas_pad})")
         torch.save(saved, os.path.join(exp, 'atlas.pt'))
         print(line)
+        if cfg.log.log_images and getattr(trainer, 'trimaps', None):        # guide.paint_mode = 'progressive'
+            print(f"{trainer.save_trimaps(os.path.join(exp, 'vis', 'train'))} trimaps -> {exp}/vis/train")
     if cfg.log.save_mesh:                               # src/training/trainer.py:962-968: mesh.obj / mesh.mtl / albedo.png
         out = trainer.export()
         if out:
