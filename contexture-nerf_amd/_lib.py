@@ -102,6 +102,10 @@ SIGNATURES = {
     "ctx_weighted_sum_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texel_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "ctx_bake_resolve": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "ctx_viewdep_input_fwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "ctx_viewdep_input_bwd": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "ctx_viewdep_raw_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "ctx_viewdep_raw_bwd": (_i32, [_vp, _i64, _vp, _vp]),
     "ctx_unet_create": (_vp, [_vp]),
     "ctx_unet_destroy": (None, [_vp]),
     "ctx_unet_param_count": (_i32, [_vp]),

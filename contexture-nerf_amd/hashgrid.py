@@ -7,6 +7,8 @@ The table's gradient is summed in 64-bit integers, so a training run repeats bit
 (`ctx_hashgrid_bwd_pts`; the rule: tests/hashgrid_grad_rule.py) where it is asked for: through autograd with
 grad_pts=True, and from HashGridField.density_gradient, which volume_render.render_normals turns into rendered normals.  That gradient is
 first order only.
+ViewDependentField adds a colour residual from a second small MLP on the same features and the spherical harmonics of the ray's direction
+(csrc/viewdep.hip; the rule: tests/sh_rule.py); its forward_pts stays the position-only base term.
 HashGridEncoding2D / HashGridTexture are the same idea over the unit UV square for the product's texture field (csrc/hashtex.hip; the rule:
 tests/hashtex_rule.py): bilinear levels, the 2 x 64 MLP and the (tanh + 1) / 2 head behind NeRF2D.texture_map's contract,
 selected by guide.texture_field = 'hashgrid'.
@@ -275,6 +277,131 @@ class HashGridField(nn.Module):
         raw, g_emb = mlp.features_input_gradient(enc._launch_fwd(x, table), g_raw)
         grad = enc._launch_bwd_pts(x, table, g_emb).reshape(*pts.shape[:-1], 3)
         return (raw.reshape(*pts.shape[:-1], self.output_ch), grad) if return_raw else grad
+
+
+# ---- view-dependent colour: a residual net on the features and the ray's spherical harmonics ----------------------
+SH_MAX_DEGREE = 4
+
+
+def _view_input(emb, rays_d, ray_id, deg):
+    n, E = emb.shape
+    inp = torch.empty(n, E + deg * deg, device=emb.device)
+    L.check(L.load().ctx_viewdep_input_fwd(L.ptr(emb, torch.float32, "emb"), L.ptr(rays_d, torch.float32, "rays_d"),
+                                           L.ptr(ray_id, torch.int32, "ray_id"), n, rays_d.shape[0], E, deg, L.ptr(inp), L.stream()))
+    return inp
+
+
+class _ViewInputFn(torch.autograd.Function):
+    """inp [n, E + deg^2] = [ emb | SH(rays_d[ray_id]) ] (`ctx_viewdep_input_fwd`); the gradient goes to emb alone, the first E columns of
+    g_inp (`ctx_viewdep_input_bwd`).  The directions have none.  With no grad enabled this is not used; nothing is saved either way."""
+
+    @staticmethod
+    def forward(ctx, emb, rays_d, ray_id, deg):
+        ctx.deg = deg
+        return _view_input(emb, rays_d, ray_id, deg)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_inp):
+        g_inp = L.f32c(g_inp)
+        n, E = g_inp.shape[0], g_inp.shape[1] - ctx.deg * ctx.deg
+        g_emb = torch.empty(n, E, device=g_inp.device)
+        L.check(L.load().ctx_viewdep_input_bwd(L.ptr(g_inp, torch.float32, "g_inp"), n, E, ctx.deg, L.ptr(g_emb), L.stream()))
+        return g_emb, None, None, None
+
+
+def _view_raw(base, res):
+    raw = torch.empty_like(base)
+    L.check(L.load().ctx_viewdep_raw_fwd(L.ptr(base, torch.float32, "base"), L.ptr(res, torch.float32, "res"), base.shape[0], L.ptr(raw),
+                                         L.stream()))
+    return raw
+
+
+class _ViewRawFn(torch.autograd.Function):
+    """raw [n,4] = base [n,4] with res [n,3] added to its colour channels (`ctx_viewdep_raw_fwd`).  The gradient to base is g_raw itself, the
+    one to res its first three columns (`ctx_viewdep_raw_bwd`).  Nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, base, res):
+        return _view_raw(base, res)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_raw):
+        g_raw = L.f32c(g_raw)
+        g_res = None
+        if ctx.needs_input_grad[1]:
+            g_res = torch.empty(g_raw.shape[0], 3, device=g_raw.device)
+            L.check(L.load().ctx_viewdep_raw_bwd(L.ptr(g_raw, torch.float32, "g_raw"), g_raw.shape[0], L.ptr(g_res), L.stream()))
+        return (g_raw if ctx.needs_input_grad[0] else None), g_res
+
+
+class ViewDependentField(HashGridField):
+    """HashGridField with a view-dependent colour residual, as NeRF and instant-ngp condition colour on the viewing direction:
+    raw[:, :3] = base[:, :3] + res, raw[:, 3] = base[:, 3].  The base term is the parent's field (`encoding` -> `mlp`), a function of position
+    alone; res [n,3] = dir_mlp([ emb | SH(direction) ]) with dir_mlp = NeRF2D(dir_D, dir_W, input_ch = E + sh_degree^2, output_ch = 3,
+    skips=[0]) on the same features emb and the sh_degree^2 real spherical harmonics of the ray's unit direction (csrc/viewdep.hip; the
+    rule: tests/sh_rule.py).  The density never sees the direction.  dir_mlp.output_linear starts at zero, so a new field is its base term.
+    forward_pts (inherited) is the base term alone: OccupancyGrid.update, density_gradient and render_normals read it and never run the
+    direction net.  forward_dirs adds the residual; render_rays_marched calls it for a field with view_dependent = True.
+    1 <= sh_degree <= 4 and E + sh_degree^2 <= 64 with E = n_levels * n_features, the MLP kernel's input width."""
+    view_dependent = True
+
+    def __init__(self, lo, hi, n_levels=16, n_features=2, log2_table=19, base_res=16, max_res=2048, D=2, W=64, sh_degree=4, dir_D=2,
+                 dir_W=64, grad_pts=False):
+        super().__init__(lo, hi, n_levels, n_features, log2_table, base_res, max_res, D=D, W=W, output_ch=4, grad_pts=grad_pts)
+        if isinstance(sh_degree, bool) or not isinstance(sh_degree, (int, np.integer)) or not 1 <= sh_degree <= SH_MAX_DEGREE:
+            raise L.CtxError(f"ViewDependentField: sh_degree={sh_degree!r}: want an int in [1, {SH_MAX_DEGREE}]")
+        E, K = self.encoding.out_dim, int(sh_degree) ** 2
+        if E + K > MAX_WIDTH:
+            raise L.CtxError(f"ViewDependentField: n_levels * n_features + sh_degree^2 = {E} + {K} = {E + K} is wider than the direction "
+                             f"net's {MAX_WIDTH}-column input")
+        if dir_D < 2:
+            raise L.CtxError(f"ViewDependentField: dir_D={dir_D}: the MLP needs at least two hidden layers (the second one is the skip layer)")
+        self.sh_degree = int(sh_degree)
+        self.dir_mlp = NeRF2D(D=dir_D, W=dir_W, input_ch=E + K, output_ch=3, skips=[0])
+        with torch.no_grad():
+            self.dir_mlp.output_linear.weight.zero_()
+            self.dir_mlp.output_linear.bias.zero_()
+
+    def forward_dirs(self, pts, rays_d, ray_id, return_residual=False):
+        """pts [n,3], rays_d [R,3] float32, ray_id int32 [n] (the ray of every point, as the marched lists carry it; an entry outside [0, R)
+        takes the direction (0,0,0)) -> raw [n,4], and with return_residual=True (raw, res [n,3]).  The encoding runs once; the base MLP
+        and the input kernel both read its features, and the table's gradient arrives through both nets.  There is no gradient to the
+        directions.  n = 0 returns empties without a launch."""
+        who = "ViewDependentField.forward_dirs"
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+            raise L.CtxError(f"{who}: want pts [n,3], got {tuple(getattr(pts, 'shape', ()))}")
+        if not isinstance(rays_d, torch.Tensor) or rays_d.dim() != 2 or rays_d.shape[1] != 3 or rays_d.shape[0] < 1:
+            raise L.CtxError(f"{who}: want rays_d [R,3] with R >= 1, got {tuple(getattr(rays_d, 'shape', ()))}")
+        if not isinstance(ray_id, torch.Tensor) or tuple(ray_id.shape) != (pts.shape[0],):
+            raise L.CtxError(f"{who}: want ray_id [n] with n = {pts.shape[0]}, one ray per point, got {tuple(getattr(ray_id, 'shape', ()))}")
+        if rays_d.requires_grad or ray_id.requires_grad:
+            raise L.CtxError(f"{who}: the HIP path has no gradient with respect to rays_d / ray_id; detach them")
+        device = self.encoding.table.device
+        for name, t, dtype in (("rays_d", rays_d, torch.float32), ("ray_id", ray_id, torch.int32)):
+            if t.dtype != dtype:
+                raise L.CtxError(f"{who}: {name}: expected dtype {dtype}, got {t.dtype}")
+            if t.device != device or device.type == 'cpu':
+                raise L.CtxError(f"{who}: {name} on {t.device}, the table on {device} (the HIP path has no CPU fallback: want a device tensor)")
+        emb = self.encoding(pts)                                             # checks pts: device, grad_pts
+        n = pts.shape[0]
+        if n == 0:
+            raw, res = torch.zeros(0, 4, device=device), torch.zeros(0, 3, device=device)
+            return (raw, res) if return_residual else raw
+        rays_d, ray_id = rays_d.contiguous(), ray_id.contiguous()
+        grad_mode = torch.is_grad_enabled()
+        base = self.mlp.forward_features(emb)
+        if grad_mode and emb.requires_grad:
+            inp = _ViewInputFn.apply(emb, rays_d, ray_id, self.sh_degree)
+        else:
+            inp = _view_input(emb, rays_d, ray_id, self.sh_degree)
+        res = self.dir_mlp.forward_features(inp)
+        if grad_mode and (base.requires_grad or res.requires_grad):
+            raw = _ViewRawFn.apply(base, res)
+        else:
+            raw = _view_raw(base, res)
+        return (raw, res) if return_residual else raw
 
 
 # ---- the texture field: a 2-D hash grid over the unit UV square (DESIGN section 4l) --------------------------------------------------

@@ -658,8 +658,24 @@ def resample_packed(weights, ts, dt, ray_off, rays_o, rays_d, K, perturb=False, 
     return fine_off, ray_id, t1, dt1, pts
 
 
+def _field_on_list(field, pts, rd, ray_id, view_dirs):
+    """-> (raw [n,4], res [n,3] or None): a view-dependent field (field.view_dependent) asked with view_dirs answers forward_dirs with its
+    colour residual, any other field, and any field without view_dirs, forward_pts as before."""
+    if view_dirs and getattr(field, 'view_dependent', False):
+        raw, res = field.forward_dirs(pts, rd, ray_id, return_residual=True)
+        return L.f32c(raw), res
+    return L.f32c(field.forward_pts(pts)), None
+
+
+def _refuse_view_dependent(field, who):
+    """The dense [R,S] passes have no ray index per sample to hand a view-dependent field: it renders on the marched lists only."""
+    if getattr(field, 'view_dependent', False):
+        raise L.CtxError(f"{who}: a view-dependent field ({type(field).__name__}) renders on the marched lists only: it needs march= (with "
+                         "occupancy=); the dense [R,S] passes do not carry the directions")
+
+
 def render_rays_marched(field, rays_o, rays_d, near, far, occupancy, step, white_bkgd=False, perturb=0., raw_noise_std=0., generator=None,
-                        return_extras=False, resample=0):
+                        return_extras=False, resample=0, view_dirs=True):
     """The ray path on ragged per-ray sample lists, as instant-ngp and nerfacc march: occupancy.march places samples `step` apart (a
     world length) inside each ray's runs of occupied cells and nowhere else, field.forward_pts runs on exactly those n points, and
     raw2outputs_packed composites the lists directly: no expansion, no fill, no [R,S] tensor; one host sync (n).
@@ -671,23 +687,34 @@ def render_rays_marched(field, rays_o, rays_d, near, far, occupancy, step, white
     raw2outputs_packed on (t', dt', ray_off').  The returned tuple is the fine one (weights [n']); the extras' ray_off / ray_id / t / dt /
     pts are the fine lists, the coarse pass is kept as rgb0 / disp0 / acc0 / weights0 / depth0 (part of the autograd graph) and
     ray_off0 / ray_id0 / t0 / dt0 / pts0.  The generator is drawn from in a fixed order: the march's u, the coarse noise, xi, the fine
-    noise.  Two host syncs (n, n').  n = 0: no field call and no fine pass; the coarse keys hold the same empty-ray outputs."""
+    noise.  Two host syncs (n, n').  n = 0: no field call and no fine pass; the coarse keys hold the same empty-ray outputs.
+    view_dirs: a field with view_dependent = True (hashgrid.ViewDependentField) is asked forward_dirs(pts, rays_d, ray_id) in both passes,
+    each with its own ray_id, and the extras gain `residual` [n,3], its colour residual on the returned lists (`residual0` [n0,3]: on the
+    coarse ones, with resample); view_dirs=False asks it forward_pts, its base term.  Any other field never sees the argument."""
     K = _check_resample(resample, "render_rays_marched")
+    vd = bool(view_dirs) and getattr(field, 'view_dependent', False)
     if occupancy is None:
         raise L.CtxError("render_rays_marched: march needs an occupancy grid (occupancy=): the samples lie in its occupied cells")
     ro, rd = L.f32c(rays_o).reshape(-1, 3), L.f32c(rays_d).reshape(-1, 3)
     ray_off, ray_id, t, dt, pts, *ts = occupancy.march(ro, rd, near, far, step, perturb=perturb > 0., generator=generator, starts=K > 0)
-    raw = L.f32c(field.forward_pts(pts)) if t.numel() else torch.empty(0, 4, device=ro.device)
+    raw, res = _field_on_list(field, pts, rd, ray_id, vd) if t.numel() else (torch.empty(0, 4, device=ro.device), None)
+    if vd and res is None:
+        res = torch.zeros(0, 3, device=ro.device)
     out = raw2outputs_packed(raw, t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
     extras = {}
     if K > 0:
         extras = {'rgb0': out[0], 'disp0': out[1], 'acc0': out[2], 'weights0': out[3], 'depth0': out[4], 'ray_off0': ray_off,
                   'ray_id0': ray_id, 't0': t, 'dt0': dt, 'pts0': pts}
+        if vd:
+            extras['residual0'] = res
         if t.numel():
             ray_off, ray_id, t, dt, pts = resample_packed(out[3].detach(), ts[0], dt, ray_off, ro, rd, K, perturb=perturb > 0.,
                                                           generator=generator)
-            out = raw2outputs_packed(L.f32c(field.forward_pts(pts)), t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
+            raw, res = _field_on_list(field, pts, rd, ray_id, vd)
+            out = raw2outputs_packed(raw, t, dt, rd, ray_off, raw_noise_std, white_bkgd, generator)
     extras.update({'ray_off': ray_off, 'ray_id': ray_id, 't': t, 'dt': dt, 'pts': pts})
+    if vd:
+        extras['residual'] = res
     return (out, extras) if return_extras else out
 
 
@@ -759,7 +786,8 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
     march=step (needs occupancy; refuses clip=True, N_importance > 0, given z_vals and pytest=True, because it places and draws the samples itself): the
     pass is render_rays_marched with that world-space step, N_samples is unused and weights is the flat list [n].
     resample=K (an int in [1, 4096]; needs march): the march becomes the coarse pass and every hit ray gets K fine samples drawn from its
-    coarse weights, the hierarchical pass of the lists (render_rays_marched); the returned tuple is the fine one.  0: off."""
+    coarse weights, the hierarchical pass of the lists (render_rays_marched); the returned tuple is the fine one.  0: off.
+    A view-dependent field (hashgrid.ViewDependentField) needs march=: without it it is refused."""
     if _check_resample(resample, "render_rays") and march is None:
         raise L.CtxError("render_rays: resample= resamples the marched lists; it needs march=")
     if march is not None:
@@ -773,6 +801,7 @@ def render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=False, z
             raise L.CtxError("render_rays: march= draws its jitter and noise from torch (generator=); it cannot be combined with pytest=True")
         return render_rays_marched(field, rays_o, rays_d, near, far, occupancy, march, white_bkgd=white_bkgd, perturb=perturb,
                                    raw_noise_std=raw_noise_std, generator=generator, return_extras=return_extras, resample=resample)
+    _refuse_view_dependent(field, "render_rays")
     if clip and occupancy is None:
         raise L.CtxError("render_rays: clip=True needs an occupancy grid (occupancy=): the spans are those of its occupied cells")
     if clip and z_vals is not None:

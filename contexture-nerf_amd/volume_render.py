@@ -378,7 +378,7 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0., resample=0):
+               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0., resample=0, view_residual=0.):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
@@ -393,9 +393,20 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
     z_vals.  The dict then gains 'distortion', the unweighted mean, detached.  distortion = 0 (the default) runs nothing new.
     resample=K > 0 (needs march): the march is the coarse pass and every hit ray gets K fine samples drawn from its detached coarse
     weights (render_rays_marched); the loss is img2mse(fine) + img2mse(coarse), the distortion loss acts on the fine weights and lists,
-    and the step costs a second host sync."""
+    and the step costs a second host sync.
+    A view-dependent field (hashgrid.ViewDependentField) trains on the marched lists only: without march= it is refused.
+    view_residual > 0 (such a field only) adds view_residual * mean(res^2) over the samples of every pass, res being the field's colour
+    residual: the term pulls colour into the base term, which is what the grid refresh, the normals and a 'diffuse' bake read.  The dict
+    then gains 'view_residual', the unweighted mean, detached.  0 (the default) runs nothing new."""
     if not distortion >= 0.:
         raise L.CtxError(f"train_step: distortion={distortion}: want a weight >= 0")
+    if not view_residual >= 0.:
+        raise L.CtxError(f"train_step: view_residual={view_residual}: want a weight >= 0")
+    if view_residual > 0. and not getattr(field, 'view_dependent', False):
+        raise L.CtxError(f"train_step: view_residual={view_residual} weighs the colour residual of a view-dependent field; "
+                         f"{type(field).__name__} has none")
+    if march is None:
+        rnh._refuse_view_dependent(field, "train_step")
     optimizer.zero_grad(set_to_none=True)
     out, extras = rnh.render_rays(field, rays_o, rays_d, near, far, N_samples, white_bkgd=white_bkgd, perturb=perturb,
                                   raw_noise_std=raw_noise_std, N_importance=N_importance, generator=generator,
@@ -412,18 +423,26 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
         else:
             dloss = rnh.distortion_loss(out[3], extras['z_vals'], None, rays_d).mean()
         loss = loss + distortion * dloss
+    vloss = None
+    if view_residual > 0.:
+        parts = [extras[k] for k in ('residual0', 'residual') if k in extras]
+        count = sum(p.numel() for p in parts)
+        vloss = sum((p * p).sum() for p in parts) / count if count else torch.zeros((), device=loss.device)
+        loss = loss + view_residual * vloss
     if occupancy is None or loss.requires_grad:
         loss.backward()
         optimizer.step()
     res = {'loss': loss.detach(), 'psnr': rnh.mse2psnr(img_loss.detach()).reshape(())}
     if dloss is not None:
         res['distortion'] = dloss.detach()
+    if vloss is not None:
+        res['view_residual'] = vloss.detach()
     return res
 
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0, optimizer='torch', table_lr=None):
+              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0, optimizer='torch', table_lr=None, view_residual=0.):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -439,6 +458,7 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     samples are the ragged lists of occupancy.march, N_samples is unused, and the refresh schedule stays as it is (the grid may
     change between iterations and the march follows it).  distortion: the weight of the distortion loss, handed to every train_step.
     resample: with march, the fine samples per hit ray of the resampled second pass, handed to every train_step.
+    view_residual: the weight of a view-dependent field's residual penalty, handed to every train_step (such a field needs march=).
     optimizer: 'torch' (torch.optim.Adam) or 'fused' (optim.FieldAdam: the step is HIP, the tables of the field's hash-grid encodings are
     in a group of their own with sparse=True and take their step straight from the backward's integer sums; a field without a table
     simply gets the HIP step).  table_lr: with either optimizer, the rate of that group of tables (None: lr).  The defaults build
@@ -464,7 +484,8 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
             idx = torch.randint(0, ro.shape[0], (rays_per_iter,), device=dev, generator=gen)
             step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                               perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
-                              occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample)
+                              occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample,
+                              view_residual=view_residual)
             hist.append(step['loss'])
     finally:
         if optimizer == 'fused':
@@ -513,7 +534,7 @@ def _checked_bake_texels(texels, T):
 
 @torch.no_grad()
 def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupancy, step=None, shell=None, supersample=1, min_alpha=0.5,
-               texels=None, rays_per_chunk=1 << 20, acc=None):
+               texels=None, rays_per_chunk=1 << 20, acc=None, colour='view'):
     """Bakes a 3-D field into the mesh's UV atlas -> acc int64 [4,T,T] in units of 2^-32 (added to when given), what the painting side
     accumulates: kal.fixed_to_float(acc)[:3] / [3] is the colour, [3] > 0 the coverage, so dist.merge_atlas' conversion, complete_atlas,
     _painted_texture and export apply unchanged.
@@ -528,8 +549,13 @@ def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupanc
     side of the surface; step=None: shell / 8, sixteen samples per ray.  texels=None: the chart texels (kal.chart_texels: one more sync);
     a given list must hold distinct texels (checked: a sync).
     A known limit: the rays start `shell` outside the surface, so where another wall of the mesh lies within `shell` of a texel (thin
-    fins, tight concavities) that wall composites first.  The answer is a smaller shell with a finer grid; there is no visibility test."""
+    fins, tight concavities) that wall composites first.  The answer is a smaller shell with a finer grid; there is no visibility test.
+    colour: what a view-dependent field (hashgrid.ViewDependentField) bakes.  'view': what it shows along each texel's ray, whose
+    direction is minus the face normal; 'diffuse': its base term alone (render_rays_marched(view_dirs=False)).  For any other field the
+    two are the same bake."""
     from . import kal
+    if colour not in ('view', 'diffuse'):
+        raise L.CtxError(f"bake_atlas: colour={colour!r}: want 'view' or 'diffuse'")
     if occupancy is None:
         raise L.CtxError("bake_atlas: needs an occupancy grid (occupancy=): the samples lie in its occupied cells")
     if not isinstance(texel_face, torch.Tensor) or texel_face.dim() != 2 or texel_face.shape[0] != texel_face.shape[1]:
@@ -547,10 +573,11 @@ def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupanc
     elif tuple(acc.shape) != (4, T, T) or acc.dtype != torch.int64:
         raise L.CtxError(f"bake_atlas: acc is {acc.dtype} {tuple(acc.shape)}, expected int64 {(4, T, T)}")
     texels = kal.chart_texels(texel_face) if texels is None else _checked_bake_texels(texels, T)
+    base_only = dict(view_dirs=False) if colour == 'diffuse' and getattr(field, 'view_dependent', False) else {}
     per = max(1, int(rays_per_chunk) // (s * s))
     for j0 in range(0, texels.numel(), per):
         part = texels[j0:j0 + per].contiguous()
         ro, rd, valid = kal.texel_rays(texel_face, texel_bary, face_uv, vertices, faces, part, s, shell)
-        rgb, _, alpha, _, _ = rnh.render_rays_marched(field, ro, rd, 0., 2.0 * shell, occupancy, step)
+        rgb, _, alpha, _, _ = rnh.render_rays_marched(field, ro, rd, 0., 2.0 * shell, occupancy, step, **base_only)
         kal.bake_resolve(rgb, alpha, valid, part, s, acc, min_alpha=min_alpha)
     return acc

@@ -582,6 +582,34 @@ int32_t ctx_texel_rays(const int64_t *texel_face, const float *texel_bary, const
 int32_t ctx_bake_resolve(const float *rgb, const float *alpha, const uint8_t *valid, const int32_t *idx, int64_t n, int32_t s, int32_t T,
                          float min_alpha, int32_t frac_bits, int64_t *acc, ctx_stream_t stream);
 
+/* ---- the view-dependent field's glue (viewdep.hip; definition: tests/sh_rule.py) ---- */
+/* The direction net's input row and the sum of the base and the residual term.  K = deg^2, 1 <= deg <= 4.
+   SH(d), d = rays_d[r]: n = sqrtf((d0*d0 + d1*d1) + d2*d2); (x,y,z) = d / n where n > 0 and (0,0,0) where it is not; then, every operation
+   rounding on its own in binary32 in the order written (no contraction), the constants being the float64 values rounded once:
+      0:  0.28209479177387814
+      1: -0.48860251190291987*y      2: 0.48860251190291987*z      3: -0.48860251190291987*x
+      4:  1.0925484305920792*(x*y)   5: -1.0925484305920792*(y*z)  6: 0.94617469575755997*(z*z) - 0.31539156525251999
+      7: -1.0925484305920792*(x*z)   8: 0.54627421529603959*(x*x - y*y)
+      9:  0.59004358992664352*y*(y*y - 3*(x*x))      10: 2.8906114426405538*(x*y)*z
+     11:  0.45704579946446572*y*(1 - 5*(z*z))        12: 0.3731763325901154*z*(5*(z*z) - 3)
+     13:  0.45704579946446572*x*(1 - 5*(z*z))        14: 1.4453057213202769*z*(x*x - y*y)
+     15:  0.59004358992664352*x*(3*(y*y) - x*x)
+   of which degree deg is the first K.
+   ctx_viewdep_input_fwd: inp[i] = [ emb[i, 0:E] | SH(rays_d[ray_id[i]]) ], inp [n, E+K]; emb [n,E], rays_d [R,3], ray_id int32 [n]; an
+     entry of ray_id outside [0, R) reads nothing and takes the direction (0,0,0).
+   ctx_viewdep_input_bwd: g_emb[i] = g_inp[i, 0:E]; g_inp [n, E+K], g_emb [n,E].  The directions have no gradient.
+   ctx_viewdep_raw_fwd:   raw[i,c] = base[i,c] + res[i,c] for c < 3 (one binary32 add), raw[i,3] = base[i,3]; base, raw [n,4], res [n,3].
+   ctx_viewdep_raw_bwd:   g_res[i] = g_raw[i, 0:3]; g_raw [n,4], g_res [n,3].  The gradient to base is g_raw itself.
+   Every output element is written; one writer per element, no atomics, no LDS, no host sync.  Tensors are contiguous and need 4-byte
+   alignment only: rows move in 16-byte accesses where the widths (E % 4 == 0 and K % 4 == 0; (E+K) % 4 == 0 for the backward) and the
+   base pointers (16-byte aligned) allow, in 4-byte accesses otherwise.  1 <= n < 2^31, R >= 1, 1 <= E, E + K <= 64.  Outside that, or with
+   a null pointer, a call returns CTX_E_ARG before any launch and leaves the outputs untouched. */
+int32_t ctx_viewdep_input_fwd(const float *emb, const float *rays_d, const int32_t *ray_id, int64_t n, int64_t R, int32_t E, int32_t deg,
+                              float *inp, ctx_stream_t stream);
+int32_t ctx_viewdep_input_bwd(const float *g_inp, int64_t n, int32_t E, int32_t deg, float *g_emb, ctx_stream_t stream);
+int32_t ctx_viewdep_raw_fwd(const float *base, const float *res, int64_t n, float *raw, ctx_stream_t stream);
+int32_t ctx_viewdep_raw_bwd(const float *g_raw, int64_t n, float *g_res, ctx_stream_t stream);
+
 /* ---- UNet denoise engine (src/stable_diffusion_depth.py:422-430,514) ----------------------- */
 typedef struct ctx_unet ctx_unet_t;
 typedef struct {
