@@ -948,9 +948,14 @@ float ctx_bench_gemm(const void *A, const void *Wt, const void *bias, const void
 void ctx_gemm_tune(int32_t tile, int32_t gemm8);
 
 /* Tuning / test support (tests/test_attention_gpu.py, tools/bench_attn.py): select the attention kernel for every following
-   launch of this process instead of CTX_ATTN_NS (2 | 3 | 4), CTX_ATTN_NW8 (0 | 1), CTX_ATTN_SPREAD (0 | 1) and CTX_ATTN_LAZY
-   (0 .. 12).  -1 (a negative lazy) = what the environment or the default says. */
+   launch of this process instead of CTX_ATTN_NS (2 | 3 | 4), CTX_ATTN_NW8 (0: always 4-wave workgroups, 1: always 8-wave ones,
+   2: always the 12-wave K/V-split ones), CTX_ATTN_SPREAD (0 | 1) and CTX_ATTN_LAZY (0 .. 12).  -1 (a negative lazy) = what the
+   environment or the default says; for nw8 the default is the balance model ctx_attention_plan reports. */
 void ctx_attention_tune(int32_t ns, int32_t nw8, int32_t spread, float lazy);
+/* Test-only seam, host only: what ctx_attention_f16 launches for a shape on a device of n_cu compute units under the switches in
+   force.  out[4]: waves per workgroup (4 | 8 | 12), key ranges per workgroup (1 | 2), workgroups, and the model's wave-tiles
+   (32 queries x 64 keys, the split form's merge counted as one) on the busiest SIMD. */
+int32_t ctx_attention_plan(int32_t B, int32_t Sq, int32_t Skv, int32_t heads, int32_t n_cu, int32_t *out);
 
 /* Unit-test support: one 32x32 tile through the MFMA fragment maps the kernels assume.
    which 0: f16 32x32x16 (A[32][16], Bt[32][16]); 1: f32 32x32x2 (A[32][2], Bt[32][2]); C[32][32] f32.
