@@ -80,6 +80,12 @@ SIGNATURES = {
     "ctx_occ_dilate": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "ctx_occ_ray_spans": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
                                  _vp, _vp, _vp]),
+    "ctx_mesh_cells_count": (_i32, [_vp, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
+    "ctx_mesh_cells_scan": (_i32, [_vp, _i64, _vp, _vp, _vp]),
+    "ctx_mesh_cells_fill": (_i32, [_vp, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ctx_mesh_tri_setup": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "ctx_mesh_ray_hit": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 12 + [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp,
+                                _vp]),
     "ctx_occ_march_count": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 13 + [_vp, _vp]),
     "ctx_occ_march_write": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 13 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctx_raymarch_packed_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

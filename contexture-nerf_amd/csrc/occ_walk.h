@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include <math.h>
+#include <type_traits>
 
 struct ocm3 { float x, y, z; };
 
@@ -12,6 +13,23 @@ __device__ __forceinline__ bool ocm_finite(float x) { return fabsf(x) < INFINITY
 // index (no running sum, no drift); te = the smallest, ties x, y, z; t_out = min(max(te, t_in), t_b) is the next cell's t_in.  Ends when
 // te >= t_b, when the step leaves the grid, or after 3G + 3 cells.  visit(occupied, t_in, t_out) is called once per cell, in walk order;
 // a ray that is non-finite or misses the box visits nothing.
+// A visitor may also take the cell: visit(occupied, t_in, t_out, cell) with cell = (cz*G + cy)*G + cx, and such a visitor may return bool:
+// true ends the walk after this cell (meshhit.hip stops at the cell that holds its nearest hit).  The three-argument visitors of the span
+// and march kernels take the first branch below at compile time: their code is what it was.
+template <class Visit>
+__device__ __forceinline__ bool occ_walk_visit(Visit &visit, bool occ, float tin, float tout, int cell)
+{
+    if constexpr (std::is_invocable_v<Visit &, bool, float, float>) {
+        visit(occ, tin, tout);
+        return false;
+    } else if constexpr (std::is_same_v<std::invoke_result_t<Visit &, bool, float, float, int>, bool>) {
+        return visit(occ, tin, tout, cell);
+    } else {
+        visit(occ, tin, tout, cell);
+        return false;
+    }
+}
+
 template <class Visit>
 __device__ __forceinline__ void occ_walk(float ox, float oy, float oz, float dx, float dy, float dz, float near, float far,
                                          const uint8_t *__restrict__ cells, int G, ocm3 lo, ocm3 hi, ocm3 inv, ocm3 h, Visit &&visit)
@@ -43,7 +61,8 @@ __device__ __forceinline__ void occ_walk(float ox, float oy, float oz, float dx,
         if (ey < te) { ax = 1; te = ey; }
         if (ez < te) { ax = 2; te = ez; }
         const float tout = fminf(fmaxf(te, tin), tb);
-        visit(cells[((int64_t)cz * G + cy) * G + cx] != 0, tin, tout);     // 0 <= c < G: clamped at the start, checked at every step
+        const int cell = (cz * G + cy) * G + cx;                           // 0 <= c < G: clamped at the start, checked at every step; < 2^24
+        if (occ_walk_visit(visit, cells[cell] != 0, tin, tout, cell)) break;
         if (te >= tb) break;
         if (ax == 0) { cx += dx > 0.f ? 1 : -1; if (cx < 0 || cx > G - 1) break; }
         else if (ax == 1) { cy += dy > 0.f ? 1 : -1; if (cy < 0 || cy > G - 1) break; }

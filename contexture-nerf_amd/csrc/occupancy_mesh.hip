@@ -4,99 +4,28 @@
 // restatements (tests/test_occupancy_mesh_cpu.py) give the same bits; they are the definition, this file follows them line by line.
 // No atomics.  The voxeliser only ever stores the byte 1 (as k_texel_mark / k_vc_seen do): racing stores write the same value, the
 // caller zeroes the grid, several calls accumulate a union.  Every other output element has one writer.
-#include "occ_walk.h"
+#include "occ_tri.h"
 
 #define OCM_BLK 256
 #define OCM_CAP 2048          // blocks of a grid-stride launch: 8 per CU
 
-#define OCM_E 0.0078125f      // 2^-7 of a cell: the inflation of the cell's box on every side
-#define OCM_DELTA 1.015625f   // 1 + 2e, the side of the inflated box
-
 // ---- voxeliser: one wave per triangle, the lanes stride over the candidate cells of its bounding box, x fastest --------------------
 // The triangle index is wave-uniform, so the vertex loads are scalar loads and the set-up (normal, plane terms, nine edge terms) is done
-// once per wave, outside the cell loop (gfx950 has no scalar float arithmetic: the values are uniform, in vector registers);
-// per cell a lane evaluates the plane pair and nine edge functions of Schwarz and Seidel's conservative test on the inflated box.
+// once per wave, outside the cell loop; per cell a lane evaluates the plane pair and nine edge functions of Schwarz and Seidel's
+// conservative test on the inflated box.  Set-up and test are occ_tri.h's, shared with the cell triangle lists of meshhit.hip.
 __global__ __launch_bounds__(OCM_BLK) void k_occ_voxelize(const float *__restrict__ vtx, const int64_t *__restrict__ faces, int64_t V, int64_t F, int G,
                                                           ocm3 lo, ocm3 inv, uint8_t *__restrict__ cells)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * OCM_BLK + threadIdx.x) >> 6));
     const int64_t nwaves = ((int64_t)gridDim.x * OCM_BLK) >> 6;
-    const float Gm1 = (float)(G - 1);
     for (int64_t f = wave0; f < F; f += nwaves) {
-        const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-        if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) continue;
-        float g[3][3];                                                // g[vertex][axis], grid coordinates: the expression of ctx_occ_mark
-        const int64_t iv[3] = {i0, i1, i2};
-        bool fin = true;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            g[k][0] = (vtx[iv[k] * 3 + 0] - lo.x) * inv.x;
-            g[k][1] = (vtx[iv[k] * 3 + 1] - lo.y) * inv.y;
-            g[k][2] = (vtx[iv[k] * 3 + 2] - lo.z) * inv.z;
-            fin = fin && ocm_finite(g[k][0]) && ocm_finite(g[k][1]) && ocm_finite(g[k][2]);
-        }
-        if (!fin) continue;
-        int c0[3], cn[3];                                             // first candidate and count per axis
-        bool empty = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float mn = fminf(fminf(g[0][a], g[1][a]), g[2][a]), mx = fmaxf(fmaxf(g[0][a], g[1][a]), g[2][a]);
-            const float fa = floorf(mn - OCM_E), fb = floorf(mx + OCM_E);
-            empty = empty || fb < 0.f || fa > Gm1;
-            c0[a] = (int)fmaxf(fa, 0.f);                              // in [0, G - 1] unless empty (then unused)
-            cn[a] = (int)fminf(fb, Gm1) - c0[a] + 1;
-        }
-        if (empty) continue;
-        const int total = cn[0] * cn[1] * cn[2];                      // <= 256^3
-
-        float ea[3], eb[3], e1[3], e2[3], n[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            ea[a] = g[1][a] - g[0][a]; eb[a] = g[2][a] - g[0][a];
-            e1[a] = g[2][a] - g[1][a]; e2[a] = g[0][a] - g[2][a];
-        }
-        n[0] = ea[1] * eb[2] - ea[2] * eb[1];
-        n[1] = ea[2] * eb[0] - ea[0] * eb[2];
-        n[2] = ea[0] * eb[1] - ea[1] * eb[0];
-        const bool degenerate = n[0] == 0.f && n[1] == 0.f && n[2] == 0.f;
-        float crit[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) crit[a] = n[a] > 0.f ? OCM_DELTA : 0.f;
-        const float d1 = (n[0] * (crit[0] - g[0][0]) + n[1] * (crit[1] - g[0][1])) + n[2] * (crit[2] - g[0][2]);
-        const float d2 = (n[0] * ((OCM_DELTA - crit[0]) - g[0][0]) + n[1] * ((OCM_DELTA - crit[1]) - g[0][1])) + n[2] * ((OCM_DELTA - crit[2]) - g[0][2]);
-        float neu[9], nev[9], de[9];                                  // [plane * 3 + edge]; planes xy, yz, zx
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            const int u = pl, v = (pl + 1) % 3, w = (pl + 2) % 3;
-#pragma unroll
-            for (int ed = 0; ed < 3; ++ed) {
-                const float eu = ed == 0 ? ea[u] : ed == 1 ? e1[u] : e2[u];
-                const float ev = ed == 0 ? ea[v] : ed == 1 ? e1[v] : e2[v];
-                const float a_u = n[w] >= 0.f ? -ev : ev, a_v = n[w] >= 0.f ? eu : -eu;
-                neu[pl * 3 + ed] = a_u; nev[pl * 3 + ed] = a_v;
-                de[pl * 3 + ed] = (-(a_u * g[ed][u] + a_v * g[ed][v]) + fmaxf(0.f, OCM_DELTA * a_u)) + fmaxf(0.f, OCM_DELTA * a_v);
-            }
-        }
-
-        for (int i = lane; i < total; i += 64) {
-            const int ix = i % cn[0], t = i / cn[0];
-            const int cx = c0[0] + ix, cy = c0[1] + t % cn[1], cz = c0[2] + t / cn[1];
-            bool ok = true;
-            if (!degenerate) {
-                const float p[3] = {(float)cx - OCM_E, (float)cy - OCM_E, (float)cz - OCM_E};
-                const float npd = (n[0] * p[0] + n[1] * p[1]) + n[2] * p[2];
-                const float s1 = npd + d1, s2 = npd + d2;
-                ok = (s1 <= 0.f && s2 >= 0.f) || (s1 >= 0.f && s2 <= 0.f);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const int u = pl, v = (pl + 1) % 3;
-#pragma unroll
-                    for (int ed = 0; ed < 3; ++ed)
-                        ok = ok && ((neu[pl * 3 + ed] * p[u] + nev[pl * 3 + ed] * p[v]) + de[pl * 3 + ed]) >= 0.f;
-                }
-            }
-            if (ok) cells[((int64_t)cz * G + cy) * G + cx] = 1;       // 0 <= c < G on the three axes by the clamps above
+        OccTri T;
+        if (!occ_tri_setup(vtx, faces, V, f, G, lo, inv, T)) continue;
+        for (int i = lane; i < T.total; i += 64) {
+            int cx, cy, cz;
+            occ_tri_candidate(T, i, cx, cy, cz);
+            if (occ_tri_cell(T, cx, cy, cz)) cells[((int64_t)cz * G + cy) * G + cx] = 1;       // 0 <= c < G on the three axes by the set-up's clamps
         }
     }
 }

@@ -309,6 +309,64 @@ def chart_texels(texel_face):
     return idx[:int(count.item())].clone()
 
 
+# ---- ray / mesh hits on the occupancy grid (csrc/meshhit.hip; the rule is written out at ctx_mesh_ray_hit) --------
+def mesh_cell_lists(vertices, faces, G, lo, inv):
+    """-> (count int32 [G^3], cell_off int32 [G^3 + 1], cell_tri int32 [n]): per cell of the grid the faces the voxeliser marks it for,
+    ascending by face id (ctx_mesh_cells_count, the exclusive scan, ctx_mesh_cells_fill).  vertices float32 [V,3] and faces int64 [F,3]
+    are device tensors; lo, inv: three floats each, the grid's.  A set-up call: it reads n back, which SYNCS the host, once."""
+    lib = L.load()
+    p_v, p_f = L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces")
+    V, F, G = vertices.shape[0], faces.shape[0], int(G)
+    if not 1 <= G <= 256:
+        raise L.CtxError(f"mesh_cell_lists: G={G} outside [1, 256]")
+    dev, ncell = vertices.device, G ** 3
+    box = (*map(float, lo), *map(float, inv))
+    count = torch.empty(ncell, dtype=torch.int32, device=dev)
+    L.check(lib.ctx_mesh_cells_count(p_v, p_f, V, F, G, *box, L.ptr(count), L.stream()))
+    cell_off = torch.empty(ncell + 1, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.ctx_mesh_cells_scan(L.ptr(count), ncell, L.ptr(cell_off), L.ptr(total), L.stream()))
+    n = int(total.item())                                                                  # the one host sync
+    if n >= 2 ** 31:
+        raise L.CtxError(f"mesh_cell_lists: {n} (cell, face) entries for {F} faces at G={G}: want fewer than 2^31; use a coarser grid")
+    cell_tri = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        cursor, slots = torch.empty(ncell, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        L.check(lib.ctx_mesh_cells_fill(p_v, p_f, V, F, G, *box, L.ptr(cell_off), n, L.ptr(cursor), L.ptr(slots), L.ptr(cell_tri), L.stream()))
+    return count, cell_off, cell_tri
+
+
+def mesh_tri_records(vertices, faces):
+    """-> tri float32 [F,12]: per face v0, e1 = v1 - v0, e2 = v2 - v0, each padded to four floats (ctx_mesh_tri_setup); NaN for a face
+    with an index outside [0, V) or a non-finite vertex.  No host sync."""
+    p_v, p_f = L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces")
+    tri = torch.empty(faces.shape[0], 12, dtype=torch.float32, device=vertices.device)
+    L.check(L.load().ctx_mesh_tri_setup(p_v, p_f, vertices.shape[0], faces.shape[0], L.ptr(tri), L.stream()))
+    return tri
+
+
+def mesh_ray_hit(rays_o, rays_d, near, far, cells, G, lo, hi, inv, h, cell_off, cell_tri, tri, faces, own_face=None, any_hit=False):
+    """ctx_mesh_ray_hit -> (hit u8 [R], t f32 [R], face i32 [R], uv f32 [R,2]), or hit alone with any_hit=True (mode 1).  rays_o, rays_d
+    float32 [R,3]; own_face int64 [R] or None.  R = 0 gives empty tensors.  No host sync."""
+    p_o, p_d = L.ptr(rays_o, torch.float32, "rays_o"), L.ptr(rays_d, torch.float32, "rays_d")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+        raise L.CtxError(f"mesh_ray_hit: want rays_o, rays_d [R,3]; got {tuple(rays_o.shape)}, {tuple(rays_d.shape)}")
+    R, dev = rays_o.shape[0], rays_o.device
+    p_own = L.ptr(own_face, torch.int64, "own_face")
+    if own_face is not None and tuple(own_face.shape) != (R,):
+        raise L.CtxError(f"mesh_ray_hit: own_face is {tuple(own_face.shape)}, expected {(R,)}")
+    hit = torch.empty(R, dtype=torch.uint8, device=dev)
+    out = () if any_hit else (torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+                              torch.empty(R, 2, dtype=torch.float32, device=dev))
+    if R:
+        L.check(L.load().ctx_mesh_ray_hit(p_o, p_d, R, float(near), float(far), L.ptr(cells, torch.uint8, "cells"), int(G), *map(float, lo),
+                                          *map(float, hi), *map(float, inv), *map(float, h), L.ptr(cell_off, torch.int32, "cell_off"),
+                                          L.ptr(cell_tri, torch.int32, "cell_tri") if cell_tri.numel() else None, cell_tri.numel(),
+                                          L.ptr(tri, torch.float32, "tri"), L.ptr(faces, torch.int64, "faces"), faces.shape[0], p_own,
+                                          1 if any_hit else 0, L.ptr(hit), *(L.ptr(x) for x in out), *([None] * (3 - len(out))), L.stream()))
+    return hit if any_hit else (hit, *out)
+
+
 def _fill_ws(lib, T, device):
     n = lib.ctx_atlas_fill_ws_bytes(T)
     if n < 0:

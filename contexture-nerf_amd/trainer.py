@@ -302,15 +302,18 @@ class ConTEXTure:
                                [float(v['radius']) for v in self.train_views], self.mesh_model.dy, H, W,
                                fovyangle=self.mesh_model.renderer.fovyangle)
 
-    def bake_field(self, field, occupancy=None, step=None, shell=None, supersample=2, min_alpha=0.5, G=128, dilate=1, colour='view'):
+    def bake_field(self, field, occupancy=None, step=None, shell=None, supersample=2, min_alpha=0.5, G=128, dilate=1, colour='view',
+                   visibility=False):
         """Bakes a 3-D field trained on views of this mesh (volume_render.fit_views) into the mesh's UV atlas (volume_render.bake_atlas
         with mesh_model.texel_map()) -> (atlas [3,T,T], coverage [T,T]).  Sets self.atlas_acc, self.atlas and self.atlas_coverage as the
         merge of a paint does (dist.merge_atlas' conversion, without the collective: every rank bakes the same thing), drops an earlier
         fill, and runs complete_atlas() when guide.atlas_fill == 'nearest'; eval renders and export() then show the baked colours.
         occupancy=None: OccupancyGrid.from_mesh(G, dilate) of the mesh over its bounding box padded by 0.1 of its largest extent.
         step, shell, supersample, min_alpha, colour ('view' | 'diffuse': what a view-dependent field bakes): bake_atlas.
-        The limit stated there holds: rays start `shell` outside the surface, and a
-        second wall of the mesh within `shell` of a texel composites first."""
+        visibility=True builds a volume_render.MeshTracer of the mesh on the occupancy grid's box and resolution and hands it to bake_atlas:
+        a sub-sample whose ray meets another wall of the mesh before its own surface point is dropped.  False (the default): the limit
+        stated there holds, rays start `shell` outside the surface, and a second wall of the mesh within `shell` of a texel composites
+        first."""
         from . import volume_render as VR
         from .config import validate
         mm = self.mesh_model
@@ -321,8 +324,9 @@ class ConTEXTure:
             occupancy = VR.OccupancyGrid.from_mesh(verts, faces, G, lo - pad, hi + pad, dilate=dilate)
         texel_face, texel_bary = mm.texel_map()
         face_uv = mm.face_attributes[0].detach().to(torch.float32).contiguous()
+        tracer = VR.MeshTracer(verts, faces, occupancy.G, occupancy.lo, occupancy.hi) if visibility else None
         self.atlas_acc = VR.bake_atlas(field, verts, faces, face_uv, texel_face, texel_bary, occupancy, step=step, shell=shell,
-                                       supersample=supersample, min_alpha=min_alpha, colour=colour)
+                                       supersample=supersample, min_alpha=min_alpha, colour=colour, visibility=tracer)
         self.atlas, self.atlas_coverage = D.atlas_from_sums(self.atlas_acc)
         self.atlas_filled = self.atlas_fill_src = None
         if validate(self.cfg).guide.atlas_fill == 'nearest':

@@ -83,6 +83,19 @@ def _check_mesh(vertices, faces, dilate, who):
         raise L.CtxError(f"{who}: dilate={dilate}: want a whole number of cells >= 0")
 
 
+def _grid_box(G, lo, hi, who):
+    """-> (G, lo [3], hi [3], inv [3], h [3]) of a G^3 grid over the box lo .. hi (a number or three per axis), float32."""
+    G = int(G)
+    if not 1 <= G <= 256:
+        raise L.CtxError(f"{who}: G={G} outside [1, 256]")
+    lo = np.broadcast_to(np.asarray(lo, np.float32), (3,)).copy()
+    hi = np.broadcast_to(np.asarray(hi, np.float32), (3,)).copy()
+    if not bool(np.all(lo < hi)) or not bool(np.all(np.isfinite(hi - lo))):
+        raise L.CtxError(f"{who}: the box needs finite lo < hi on every axis, got lo={lo.tolist()}, hi={hi.tolist()}")
+    ext = hi - lo                                           # binary32, once: the kernels and the restatement take these by value
+    return G, lo, hi, np.float32(G) / ext, ext / np.float32(G)
+
+
 class OccupancyGrid:
     """Which cells of a G^3 grid over the box lo .. hi hold density: the ray path evaluates the field only on the samples inside
     occupied cells (render_rays(occupancy=)), the ray-path counterpart of optim.field_texels = 'active'.
@@ -91,17 +104,8 @@ class OccupancyGrid:
     so until the first `update` it only clips the samples to the box."""
 
     def __init__(self, G, lo, hi, device):
-        G = int(G)
-        if not 1 <= G <= 256:
-            raise L.CtxError(f"OccupancyGrid: G={G} outside [1, 256]")
-        lo = np.broadcast_to(np.asarray(lo, np.float32), (3,)).copy()
-        hi = np.broadcast_to(np.asarray(hi, np.float32), (3,)).copy()
-        if not bool(np.all(lo < hi)) or not bool(np.all(np.isfinite(hi - lo))):
-            raise L.CtxError(f"OccupancyGrid: the box needs finite lo < hi on every axis, got lo={lo.tolist()}, hi={hi.tolist()}")
-        self.G, self.lo, self.hi = G, lo, hi
-        ext = hi - lo                                       # binary32, once: the kernels and the restatement take these by value
-        self.inv = np.float32(G) / ext
-        self.h = ext / np.float32(G)
+        self.G, self.lo, self.hi, self.inv, self.h = _grid_box(G, lo, hi, "OccupancyGrid")
+        G = self.G
         self.device = torch.device(device)
         self.cells = torch.ones(G, G, G, dtype=torch.uint8, device=self.device)
         self.dens = torch.zeros(G, G, G, dtype=torch.float32, device=self.device)
@@ -275,6 +279,86 @@ class OccupancyGrid:
         return float(self.cells.count_nonzero().item()) / self.G ** 3
 
 
+class MeshTracer:
+    """Where a ray meets the mesh: per cell of a G^3 grid over the box lo .. hi the list of the triangles that touch it, and the hit kernel
+    that walks a ray through the grid and tests the listed triangles (`ctx_mesh_ray_hit`; the rule is written out there, its numpy
+    definition is tests/meshhit_rule.py).  vertices float32 [V,3] and faces int64 [F,3] are device tensors in the world frame of the rays,
+    as OccupancyGrid.from_mesh takes them; the tracer keeps them as given (it does not follow later changes).  The lists use the
+    voxeliser's predicate, so `occupancy` gives from_mesh's grid without a second pass over the mesh.
+    Building the lists reads their total length back: one host sync, here; nothing after construction syncs."""
+
+    def __init__(self, vertices, faces, G=64, lo=-1., hi=1.):
+        from . import kal
+        _check_mesh(vertices, faces, 0, "MeshTracer")
+        self.G, self.lo, self.hi, self.inv, self.h = _grid_box(G, lo, hi, "MeshTracer")
+        self.device = vertices.device
+        L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces")
+        self.faces = faces
+        self.count, self.cell_off, self.cell_tri = kal.mesh_cell_lists(vertices, faces, self.G, self.lo, self.inv)
+        self.cells = (self.count > 0).to(torch.uint8).reshape(self.G, self.G, self.G).contiguous()
+        self.tri = kal.mesh_tri_records(vertices, faces)
+
+    def _hit(self, who, rays_o, rays_d, near, far, own_face, any_hit):
+        from . import kal
+        near, far = float(near), float(far)
+        if not (near < far and np.isfinite(near) and np.isfinite(far)):
+            raise L.CtxError(f"MeshTracer.{who}: want finite near < far, got {near}, {far}")
+        return kal.mesh_ray_hit(rays_o, rays_d, near, far, self.cells, self.G, self.lo, self.hi, self.inv, self.h, self.cell_off, self.cell_tri,
+                                self.tri, self.faces, own_face=own_face, any_hit=any_hit)
+
+    def trace(self, rays_o, rays_d, near, far, own_face=None):
+        """-> (hit u8 [R], t f32 [R], face i64 [R], bary f32 [R,3]): the nearest triangle the ray o + d*t meets within [near, far], ties
+        to the lower face id; bary weighs the face's three vertices (1 - u - v, u, v).  A miss: hit = 0, t = far, face = -1, bary = 0.
+        Two-sided.  own_face int64 [R] (optional): per ray a face to leave out together with the faces that share a vertex id with it
+        (a ray that starts on the surface).  rays_o, rays_d float32 [R,3] device tensors.  No host sync."""
+        hit, t, face, uv = self._hit("trace", rays_o, rays_d, near, far, own_face, False)
+        bary = torch.stack([1.0 - uv[:, 0] - uv[:, 1], uv[:, 0], uv[:, 1]], dim=1) * hit[:, None]
+        return hit, t, face.to(torch.int64), bary
+
+    def occluded(self, rays_o, rays_d, near, far, own_face=None):
+        """-> u8 [R]: 1 where the ray meets any triangle within [near, far]: trace's hit, stopping at the first triangle found."""
+        return self._hit("occluded", rays_o, rays_d, near, far, own_face, True)
+
+    def occupancy(self, dilate=1):
+        """-> an OccupancyGrid whose cells equal OccupancyGrid.from_mesh(vertices, faces, G, lo, hi, dilate) bit for bit: the cells that
+        hold a list, grown by `dilate` cells."""
+        if int(dilate) != dilate or dilate < 0:
+            raise L.CtxError(f"MeshTracer.occupancy: dilate={dilate}: want a whole number of cells >= 0")
+        grid = OccupancyGrid(self.G, self.lo, self.hi, self.device)
+        grid.cells = self.cells.clone()
+        if dilate > 0:
+            grid.dilate(int(dilate))
+        return grid
+
+    def stats(self):
+        """-> dict(entries, mean_list, max_list): the length of cell_tri, and the mean and the largest list over the cells that hold one
+        (host numbers: this syncs)."""
+        occupied = self.count[self.count > 0]
+        return dict(entries=int(self.cell_tri.numel()), mean_list=float(occupied.float().mean()) if occupied.numel() else 0.0,
+                    max_list=int(occupied.max()) if occupied.numel() else 0)
+
+
+def _mesh_targets(who, mesh, mask_weight, depth_weight, rays_o, rays_d, near, far):
+    """The (hit, t) pair the mask and depth terms are measured against, or None when neither term is on: from a MeshTracer (traced here,
+    without gradients) or a pair traced beforehand for the same rays."""
+    for name, w in (("mask_weight", mask_weight), ("depth_weight", depth_weight)):
+        if not w >= 0.:
+            raise L.CtxError(f"{who}: {name}={w}: want a weight >= 0")
+        if w > 0. and mesh is None:
+            raise L.CtxError(f"{who}: {name}={w} needs mesh=: a MeshTracer of the mesh the views show")
+    if mesh is None or (mask_weight == 0. and depth_weight == 0.):
+        return None
+    if isinstance(mesh, (tuple, list)):
+        hit, t = mesh
+    else:
+        with torch.no_grad():
+            hit, t = mesh.trace(rays_o, rays_d, near, far)[:2]
+    R = rays_o.shape[0]
+    if tuple(hit.shape) != (R,) or tuple(t.shape) != (R,):
+        raise L.CtxError(f"{who}: mesh= wants hit [{R}] and t [{R}] for these rays, got {tuple(hit.shape)} and {tuple(t.shape)}")
+    return hit, t
+
+
 @torch.no_grad()
 def render_image(field, H, W, K, c2w, near, far, N_samples, white_bkgd=False, rows=None, N_importance=0, occupancy=None, clip=False,
                  march=None, resample=0):
@@ -378,7 +462,8 @@ def render_and_refine(field, sd, text_z, H, W, c2w, near=0.5, far=2.5, N_samples
 
 
 def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_samples, N_importance=0, perturb=1., raw_noise_std=0.,
-               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0., resample=0, view_residual=0.):
+               white_bkgd=False, generator=None, occupancy=None, clip=False, march=None, distortion=0., resample=0, view_residual=0.,
+               mesh=None, mask_weight=0., depth_weight=0.):
     """nerf-pytorch's training step on one ray batch: render (one field for the coarse and the fine pass, as render_image),
     loss = img2mse(rgb_fine, target) (+ img2mse(rgb_coarse, target) when hierarchical), backward, optimizer.step().
     rays_o, rays_d, target_rgb: [R,3].  -> dict(loss, psnr) of device scalars (psnr of the fine image); no host sync.
@@ -397,7 +482,14 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
     A view-dependent field (hashgrid.ViewDependentField) trains on the marched lists only: without march= it is refused.
     view_residual > 0 (such a field only) adds view_residual * mean(res^2) over the samples of every pass, res being the field's colour
     residual: the term pulls colour into the base term, which is what the grid refresh, the normals and a 'diffuse' bake read.  The dict
-    then gains 'view_residual', the unweighted mean, detached.  0 (the default) runs nothing new."""
+    then gains 'view_residual', the unweighted mean, detached.  0 (the default) runs nothing new.
+    mesh: a MeshTracer of the mesh the target views show, for the two geometry terms: mask_weight > 0 adds mask_weight * mean((acc - hit)^2)
+    and depth_weight > 0 adds depth_weight * sum over the rays that hit of (depth - t_mesh)^2 / max(1, n_hit), with (hit, t_mesh) the
+    tracer's answer for these rays within [near, far] and acc, depth those of the pass that carries the image loss (the fine pass when
+    hierarchical or resampled); on the dense path and on the march path alike.  The dict then gains 'mask' and 'depth', the unweighted
+    means, detached.  mesh may also be the pair (hit u8 [R], t [R]) traced beforehand for these rays (fit_views traces once).  With both
+    weights 0 (the default) nothing new runs, with or without a tracer; a weight > 0 without mesh= is refused."""
+    targets = _mesh_targets("train_step", mesh, mask_weight, depth_weight, rays_o, rays_d, near, far)
     if not distortion >= 0.:
         raise L.CtxError(f"train_step: distortion={distortion}: want a weight >= 0")
     if not view_residual >= 0.:
@@ -429,6 +521,15 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
         count = sum(p.numel() for p in parts)
         vloss = sum((p * p).sum() for p in parts) / count if count else torch.zeros((), device=loss.device)
         loss = loss + view_residual * vloss
+    mloss = zloss = None
+    if targets is not None:
+        hit = targets[0].to(out[2].dtype)
+        mloss = ((out[2] - hit) ** 2).mean()
+        zloss = (hit * (out[4] - targets[1]) ** 2).sum() / hit.sum().clamp(min=1.)
+        if mask_weight > 0.:
+            loss = loss + mask_weight * mloss
+        if depth_weight > 0.:
+            loss = loss + depth_weight * zloss
     if occupancy is None or loss.requires_grad:
         loss.backward()
         optimizer.step()
@@ -437,12 +538,15 @@ def train_step(field, optimizer, rays_o, rays_d, target_rgb, near, far, N_sample
         res['distortion'] = dloss.detach()
     if vloss is not None:
         res['view_residual'] = vloss.detach()
+    if mloss is not None:
+        res['mask'], res['depth'] = mloss.detach(), zloss.detach()
     return res
 
 
 def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5e-4, seed=0, N_samples=64, N_importance=0,
               perturb=1., raw_noise_std=0., white_bkgd=False, occupancy=None, occupancy_every=16, occupancy_warmup=32,
-              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0, optimizer='torch', table_lr=None, view_residual=0.):
+              occupancy_thresh=0.01, clip=False, march=None, distortion=0., resample=0, optimizer='torch', table_lr=None, view_residual=0.,
+              mesh=None, mask_weight=0., depth_weight=0.):
     """Distil posed views into the 3-D field: images [V,H,W,3] in [0,1], c2ws [V,3,4], K the pinhole matrix of get_rays.
     Every iteration draws rays_per_iter pixels over all views with a generator seeded by `seed` (which also drives the jitter
     and the noise, so a run repeats exactly) and runs train_step with torch.optim.Adam(lr).  -> the loss history (floats).
@@ -462,7 +566,10 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     optimizer: 'torch' (torch.optim.Adam) or 'fused' (optim.FieldAdam: the step is HIP, the tables of the field's hash-grid encodings are
     in a group of their own with sparse=True and take their step straight from the backward's integer sums; a field without a table
     simply gets the HIP step).  table_lr: with either optimizer, the rate of that group of tables (None: lr).  The defaults build
-    torch.optim.Adam(field.parameters(), lr) as before."""
+    torch.optim.Adam(field.parameters(), lr) as before.
+    mesh, mask_weight, depth_weight: a MeshTracer of the mesh the views show and the weights of train_step's mask and depth terms.  With a
+    weight > 0 all V*H*W rays are traced once before the loop and every iteration hands its rays' (hit, t) down; with both 0 (the
+    default) nothing is traced and nothing new is handed down."""
     if optimizer not in ('torch', 'fused'):
         raise L.CtxError(f"fit_views: optimizer={optimizer!r}: want 'torch' or 'fused'")
     if table_lr is not None and not table_lr > 0:
@@ -475,6 +582,7 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
     rd = torch.stack([r[1] for r in rays]).reshape(-1, 3)
     target = images.reshape(-1, 3)
     gen = torch.Generator(device=dev).manual_seed(seed)
+    traced = _mesh_targets("fit_views", mesh, mask_weight, depth_weight, ro, rd, near, far)
     opt = field_optimizer(field, lr, optimizer, table_lr)
     hist = []
     try:
@@ -485,7 +593,9 @@ def fit_views(field, images, c2ws, K, near, far, iters, rays_per_iter=4096, lr=5
             step = train_step(field, opt, ro[idx], rd[idx], target[idx], near, far, N_samples, N_importance=N_importance,
                               perturb=perturb, raw_noise_std=raw_noise_std, white_bkgd=white_bkgd, generator=gen,
                               occupancy=occupancy, clip=clip, march=march, distortion=distortion, resample=resample,
-                              view_residual=view_residual)
+                              view_residual=view_residual,
+                              **({} if traced is None else dict(mesh=(traced[0][idx], traced[1][idx]), mask_weight=mask_weight,
+                                                               depth_weight=depth_weight)))
             hist.append(step['loss'])
     finally:
         if optimizer == 'fused':
@@ -534,7 +644,7 @@ def _checked_bake_texels(texels, T):
 
 @torch.no_grad()
 def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupancy, step=None, shell=None, supersample=1, min_alpha=0.5,
-               texels=None, rays_per_chunk=1 << 20, acc=None, colour='view'):
+               texels=None, rays_per_chunk=1 << 20, acc=None, colour='view', visibility=None):
     """Bakes a 3-D field into the mesh's UV atlas -> acc int64 [4,T,T] in units of 2^-32 (added to when given), what the painting side
     accumulates: kal.fixed_to_float(acc)[:3] / [3] is the colour, [3] > 0 the coverage, so dist.merge_atlas' conversion, complete_atlas,
     _painted_texture and export apply unchanged.
@@ -548,8 +658,14 @@ def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupanc
     OccupancyGrid.from_mesh(dilate=1) of the same mesh.  shell=None: 1.5 x the grid's largest cell edge, what such a grid holds on either
     side of the surface; step=None: shell / 8, sixteen samples per ray.  texels=None: the chart texels (kal.chart_texels: one more sync);
     a given list must hold distinct texels (checked: a sync).
-    A known limit: the rays start `shell` outside the surface, so where another wall of the mesh lies within `shell` of a texel (thin
-    fins, tight concavities) that wall composites first.  The answer is a smaller shell with a finer grid; there is no visibility test.
+    The rays start `shell` outside the surface, so where another wall of the mesh lies within `shell` of a texel (thin fins, tight
+    concavities) that wall composites first unless visibility= is given.  visibility: a MeshTracer of the same mesh.  Per chunk every
+    ray is tested against the mesh between its start and its own surface point, tracer.occluded(ro, rd, 0, shell, own_face = the
+    texel's face, repeated per sub-sample): the texel's face and the faces that share a vertex id with it do not count (a face adjacent
+    across a concave crease must not blind the texels next to the crease); a blocked sub-sample is dropped (valid &= ~blocked) before
+    the resolve.  A texel whose every sub-sample is blocked gets nothing: complete_atlas fills it from its neighbours.  What stays: a
+    wall BEHIND the surface within `shell` still lies in the march's second half; that is the field's to keep empty.
+    visibility=None (the default) runs nothing new.
     colour: what a view-dependent field (hashgrid.ViewDependentField) bakes.  'view': what it shows along each texel's ray, whose
     direction is minus the face normal; 'diffuse': its base term alone (render_rays_marched(view_dirs=False)).  For any other field the
     two are the same bake."""
@@ -578,6 +694,9 @@ def bake_atlas(field, vertices, faces, face_uv, texel_face, texel_bary, occupanc
     for j0 in range(0, texels.numel(), per):
         part = texels[j0:j0 + per].contiguous()
         ro, rd, valid = kal.texel_rays(texel_face, texel_bary, face_uv, vertices, faces, part, s, shell)
+        if visibility is not None:
+            own = texel_face.reshape(-1)[part.long()].repeat_interleave(s * s)
+            valid = valid & (visibility.occluded(ro, rd, 0., shell, own_face=own) == 0).to(valid.dtype)
         rgb, _, alpha, _, _ = rnh.render_rays_marched(field, ro, rd, 0., 2.0 * shell, occupancy, step, **base_only)
         kal.bake_resolve(rgb, alpha, valid, part, s, acc, min_alpha=min_alpha)
     return acc

@@ -387,6 +387,48 @@ int32_t ctx_occ_ray_spans(const float *rays_o, const float *rays_d, int64_t R, f
                           float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
                           float h_x, float h_y, float h_z, float *span, uint8_t *hit, ctx_stream_t stream);
 
+/* ---- where a ray meets the mesh: cell triangle lists on the grid, and the hit kernel (definition: tests/meshhit_rule.py) ---- */
+/* count int32 [G^3] (index (cz*G + cy)*G + cx): how many faces list themselves in each cell.  (cell, face) is listed if and only if
+   ctx_occ_voxelize would store a 1 in that cell for that face alone (one predicate, one device function), so count > 0 is the voxeliser's
+   grid.  The call zeroes count, then adds with integer atomics: the counts do not depend on scheduling.  Arguments as ctx_occ_voxelize. */
+int32_t ctx_mesh_cells_count(const float *vertices, const int64_t *faces, int64_t V, int64_t F, int32_t G, float lo_x, float lo_y, float lo_z,
+                             float inv_x, float inv_y, float inv_z, int32_t *count, ctx_stream_t stream);
+/* cell_off int32 [ncell + 1]: the exclusive scan of count [ncell]; total[0] (int64) = the sum, which the caller reads back and refuses at
+   2^31 or more (an offset beyond int32 is stored as INT32_MAX).  1 <= ncell <= 256^3. */
+int32_t ctx_mesh_cells_scan(const int32_t *count, int64_t ncell, int32_t *cell_off, int64_t *total, ctx_stream_t stream);
+/* cell_tri int32 [n], n = cell_off[G^3]: cell c owns cell_off[c] .. cell_off[c+1], the faces listed in it, ASCENDING by face id: the array
+   has one value whatever the arrival order (an atomic cursor per cell into `slots`, then a rank sort of every segment into cell_tri; any
+   segment length).  cursor int32 [G^3] and slots int32 [n] are workspaces (cursor is zeroed here); nothing is stored outside a cell's
+   segment or outside [0, n).  n = 0 launches nothing.  The mesh and the grid must be those of the count. */
+int32_t ctx_mesh_cells_fill(const float *vertices, const int64_t *faces, int64_t V, int64_t F, int32_t G, float lo_x, float lo_y, float lo_z,
+                            float inv_x, float inv_y, float inv_z, const int32_t *cell_off, int64_t n, int32_t *cursor, int32_t *slots,
+                            int32_t *cell_tri, ctx_stream_t stream);
+/* tri float32 [F,12], 16-byte aligned: per face v0, e1 = v1 - v0, e2 = v2 - v0, each padded with a 0 to four floats, so the hit kernel
+   loads three whole vectors and never chases faces -> vertices.  A face with an index outside [0, V) or a non-finite vertex gets twelve
+   NaN (and is in no list: it marks nothing in the voxeliser either). */
+int32_t ctx_mesh_tri_setup(const float *vertices, const int64_t *faces, int64_t V, int64_t F, float *tri, ctx_stream_t stream);
+/* hit u8 [R], t [R], face int32 [R], uv [R,2]: where the ray o + d*t first meets the mesh within [near, far].  One lane per ray, binary32
+   in the order written.  The walk is that of ctx_occ_ray_spans on cells = (count > 0) (one device function); in every occupied cell the
+   triangles cell_tri[cell_off[c] .. cell_off[c+1]) are tested in list order.
+   Test of a triangle (v0, e1, e2), dots summed (ax*bx + ay*by) + az*bz: p = d x e2, det = e1.p, inv = 1/det, s = o - v0, u = (s.p)*inv,
+   q = s x e1, v = (d.q)*inv, t = (e2.q)*inv.  Miss if det == 0, or if inv or t is not finite.  Accepted if and only if u >= -EPS,
+   v >= -EPS, u + v <= 1 + EPS and near <= t <= far, with EPS = 2^-18.  Two-sided: back faces count.
+   mode 0 (nearest): the best (t, face) is the lowest t, ties to the lower face id; a triangle seen in any cell counts with its t wherever
+   that t lies; after every cell the walk stops when best.t <= t_out of that cell (the lists are conservative, so no later cell holds a
+   nearer hit).  A miss stores hit = 0, t = far, face = -1, uv = 0.  mode 1 (any): stops at the first accepted triangle; only hit is
+   stored (t, face, uv may be null) and it equals mode 0's.
+   own_face int64 [R] (nullable): for an entry in [0, F) the triangles that are that face or share a vertex id with it in faces [F,3] are
+   skipped (the integer "related" rule of ctx_uv_gather_fixed): a ray leaving a surface point is blinded neither by its own face nor by
+   one adjacent across a crease.  Non-finite rays, a zero direction and rays that miss the box are misses.  R = 0 launches nothing.
+   Finite near < far; 0 <= R < 2^31; 1 <= F < 2^31; 0 <= n < 2^31; tri 16-byte and uv 8-byte aligned.  Entries of cell_off and cell_tri
+   that point outside [0, n) or [0, F) are skipped. */
+int32_t ctx_mesh_ray_hit(const float *rays_o, const float *rays_d, int64_t R, float near, float far, const uint8_t *cells, int32_t G,
+                         float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float inv_x, float inv_y, float inv_z,
+                         float h_x, float h_y, float h_z, const int32_t *cell_off, const int32_t *cell_tri, int64_t n, const float *tri,
+                         const int64_t *faces, int64_t F, const int64_t *own_face /*nullable*/, int32_t mode, uint8_t *hit,
+                         float *t /*nullable for mode 1*/, int32_t *face /*nullable for mode 1*/, float *uv /*nullable for mode 1*/,
+                         ctx_stream_t stream);
+
 /* ---- marching the grid into ragged per-ray sample lists, and the compositing on them (definition: tests/march_rule.py) ---- */
 /* count [R]: how many samples the march places on each ray.  The finite check, the clip, the start cell and the walk are those of
    ctx_occ_ray_spans, expression for expression (one device function).  A run is a maximal sequence of consecutive occupied cells of the
