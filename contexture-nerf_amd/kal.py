@@ -367,6 +367,25 @@ def mesh_ray_hit(rays_o, rays_d, near, far, cells, G, lo, hi, inv, h, cell_off, 
     return hit if any_hit else (hit, *out)
 
 
+def mesh_closest_point(pts, r, G, lo, inv, cell_off, cell_tri, tri):
+    """ctx_mesh_closest_point -> (found u8 [n], dist f32 [n], face i32 [n], uv f32 [n,2]): the nearest point of the mesh within r of each of
+    pts float32 [n,3] (csrc/meshdist.hip; the rule is written out at the entry point).  A miss: found = 0, dist = r, face = -1, uv = 0.
+    n = 0 gives empty tensors.  No host sync."""
+    p_p = L.ptr(pts, torch.float32, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise L.CtxError(f"mesh_closest_point: want pts [n,3]; got {tuple(pts.shape)}")
+    n, dev = pts.shape[0], pts.device
+    found = torch.empty(n, dtype=torch.uint8, device=dev)
+    dist, face = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    uv = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    if n:
+        L.check(L.load().ctx_mesh_closest_point(p_p, n, float(r), int(G), *map(float, lo), *map(float, inv), L.ptr(cell_off, torch.int32, "cell_off"),
+                                                L.ptr(cell_tri, torch.int32, "cell_tri") if cell_tri.numel() else None, cell_tri.numel(),
+                                                L.ptr(tri, torch.float32, "tri"), tri.shape[0], L.ptr(found), L.ptr(dist), L.ptr(face), L.ptr(uv),
+                                                L.stream()))
+    return found, dist, face, uv
+
+
 def _fill_ws(lib, T, device):
     n = lib.ctx_atlas_fill_ws_bytes(T)
     if n < 0:

@@ -319,6 +319,33 @@ class MeshTracer:
         """-> u8 [R]: 1 where the ray meets any triangle within [near, far]: trace's hit, stopping at the first triangle found."""
         return self._hit("occluded", rays_o, rays_d, near, far, own_face, True)
 
+    def _radius(self, who, name, value):
+        """A query radius of `closest` as the float32 the kernel takes: finite, > 0 and at most 3 min(h) (a block of at most 7^3 cells)."""
+        with np.errstate(all='ignore'):
+            r = np.float32(value)
+        limit = np.float32(3) * np.min(self.h)
+        if not (np.isfinite(r) and r > 0 and r <= limit):
+            raise L.CtxError(f"{who}: {name}={value!r} outside (0, 3 min(h)] = (0, {float(limit):g}]: the query looks at the cells within "
+                             f"{name} of the point, at most 7^3 of them; use a coarser grid for a longer reach")
+        return r
+
+    def closest(self, pts, max_dist):
+        """-> (found u8 [n], dist f32 [n], face i64 [n], bary f32 [n,3]): the nearest point of the mesh within max_dist of each of pts
+        float32 [n,3] (a device tensor in the tracer's frame): how far it is, on which face it lies (ties to the lower face id) and its
+        barycentrics (1 - u - v, u, v) on that face (`ctx_mesh_closest_point`; the rule is written out there, its numpy definition is
+        tests/meshdist_rule.py).  A miss: found = 0, dist = max_dist, face = -1, bary = 0.  The distance is unsigned.  max_dist must lie in
+        (0, 3 min(h)].  The answer is for the mesh inside the tracer's box: a nearest point outside the box lies in no cell.
+        There is no gradient to the positions: a pts that requires grad is refused.  No host sync."""
+        from . import kal
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+            raise L.CtxError(f"MeshTracer.closest: want pts [n,3], got {tuple(getattr(pts, 'shape', ()))}")
+        if pts.requires_grad:
+            raise L.CtxError("MeshTracer.closest: pts requires grad, and the query has no gradient with respect to the positions; detach pts")
+        r = self._radius("MeshTracer.closest", "max_dist", max_dist)
+        found, dist, face, uv = kal.mesh_closest_point(pts, r, self.G, self.lo, self.inv, self.cell_off, self.cell_tri, self.tri)
+        bary = torch.stack([1.0 - uv[:, 0] - uv[:, 1], uv[:, 0], uv[:, 1]], dim=1) * found[:, None]
+        return found, dist, face.to(torch.int64), bary
+
     def occupancy(self, dilate=1):
         """-> an OccupancyGrid whose cells equal OccupancyGrid.from_mesh(vertices, faces, G, lo, hi, dilate) bit for bit: the cells that
         hold a list, grown by `dilate` cells."""
@@ -336,6 +363,121 @@ class MeshTracer:
         occupied = self.count[self.count > 0]
         return dict(entries=int(self.cell_tri.numel()), mean_list=float(occupied.float().mean()) if occupied.numel() else 0.0,
                     max_list=int(occupied.max()) if occupied.numel() else 0)
+
+
+class _MeshTent:
+    """The density both mesh-anchored fields share: a tent around the surface, peak * max(0, 1 - dist / width) in float32 with dist the
+    tracer's unsigned distance to the mesh (MeshTracer.closest with the query radius width, so dist = width and the density is exactly 0
+    on a miss).  width=None: the tracer's largest cell edge; peak=None: 16 / width, so a perpendicular crossing has the optical thickness
+    peak * width = 16 and, e^-16 being below 2^-23, the wall is opaque in float32.  The march step must be at most width / 2: a longer
+    step can put a single sample, or none, inside the tent, and the quadrature of a crossing then no longer sees the peak."""
+
+    def _init_tent(self, who, tracer, width, peak):
+        if not isinstance(tracer, MeshTracer):
+            raise L.CtxError(f"{who}: tracer must be a MeshTracer, got {type(tracer).__name__}")
+        self.tracer = tracer
+        self.width = tracer._radius(who, "width", np.max(tracer.h) if width is None else width)
+        with np.errstate(all='ignore'):
+            self.peak = np.float32(16) / self.width if peak is None else np.float32(peak)
+        if not (np.isfinite(self.peak) and self.peak > 0):
+            raise L.CtxError(f"{who}: peak={peak!r}: want a finite density > 0")
+
+    @torch.no_grad()
+    def _tent(self, pts):
+        """pts [n,3] float32 contiguous -> (density [n], found, face, bary): d = dist / width; peak * max(0, 1 - d), each operation rounding
+        on its own (the divisor is a device scalar: a true division, not a product with a host reciprocal)."""
+        found, dist, face, bary = self.tracer.closest(pts, self.width)
+        d = dist / dist.new_full((), float(self.width))
+        return float(self.peak) * (1.0 - d).clamp_min(0.0), found, face, bary
+
+
+class MeshDensityField(torch.nn.Module, _MeshTent):
+    """A field whose geometry is the mesh's: `inner`'s colour with the density channel replaced by a fixed function of the distance to the
+    mesh (the tent of _MeshTent), so only colour is trained: no floaters, no mask or depth weight to tune, and a bake reads the colour at
+    the surface.  inner: any field the marched path takes (forward_pts), e.g. a HashGridField; tracer: a MeshTracer of the mesh, in the
+    frame of the points.  width=None: the tracer's largest cell edge; peak=None: 16 / width.  THE MARCH STEP MUST BE AT MOST width / 2.
+    forward_pts(pts [..., 3]) -> inner.forward_pts(pts) with channel 3 replaced; the density carries no gradient (inner's output row for
+    channel 3 gets a gradient of exactly zero), the colour channels carry theirs through inner unchanged.  view_dependent and forward_dirs
+    pass through to an inner that has them, with the same replacement.  modules() / parameters() expose inner, so field_optimizer,
+    FieldAdam, fit_views, OccupancyGrid.update and bake_atlas take it as they take any field.  It has no density_gradient:
+    render_normals refuses it (the normals of this field are the mesh's)."""
+
+    def __init__(self, inner, tracer, width=None, peak=None):
+        super().__init__()
+        if not callable(getattr(inner, 'forward_pts', None)):
+            raise L.CtxError(f"MeshDensityField: inner ({type(inner).__name__}) has no forward_pts")
+        self.inner = inner
+        self._init_tent("MeshDensityField", tracer, width, peak)
+
+    @property
+    def view_dependent(self):
+        return bool(getattr(self.inner, 'view_dependent', False))
+
+    def _replace(self, raw, pts):
+        if raw.shape[-1] != 4:
+            raise L.CtxError(f"MeshDensityField: inner returned {tuple(raw.shape)}, expected [..., 4] (colour and density)")
+        x = L.f32c(pts.detach()).reshape(-1, 3)
+        if x.shape[0] == 0:
+            return raw
+        dens = self._tent(x)[0].reshape(*raw.shape[:-1], 1)
+        return torch.cat([raw[..., :3], dens.to(raw.dtype)], dim=-1)
+
+    def forward_pts(self, pts):
+        """pts [..., 3] -> raw [..., 4]: inner's colour logits, the tent's density."""
+        return self._replace(self.inner.forward_pts(pts), pts)
+
+    forward = forward_pts
+
+    def forward_dirs(self, pts, rays_d, ray_id, return_residual=False):
+        """inner.forward_dirs with channel 3 replaced (an inner without forward_dirs is refused)."""
+        if not callable(getattr(self.inner, 'forward_dirs', None)):
+            raise L.CtxError(f"MeshDensityField.forward_dirs: inner ({type(self.inner).__name__}) has no forward_dirs")
+        raw, res = self.inner.forward_dirs(pts, rays_d, ray_id, return_residual=True)
+        raw = self._replace(raw, pts)
+        return (raw, res) if return_residual else raw
+
+
+class AtlasField(torch.nn.Module, _MeshTent):
+    """The atlas-to-field direction: a painted atlas read at each point's nearest surface point, a field the ray path can render
+    (render_image(march=)) and fit_views can distil from.  No parameters.  tracer: a MeshTracer of the mesh; face_uv float32 [F,3,2]
+    (vt[ft]); atlas float32 [3,T,T] in [0,1]; all on the tracer's device.
+    forward_pts(pts [..., 3]) -> raw [..., 4]: with (found, dist, face, bary) = tracer.closest(pts, width), the colour is the atlas
+    sampled bilinearly (kal.render.mesh.texture_mapping) at uv = (bary_0 face_uv[face,0] + bary_1 face_uv[face,1]) + bary_2
+    face_uv[face,2], clamped to [2^-12, 1 - 2^-12] and returned as its logit, since compositing applies a sigmoid; the density is the
+    tent of _MeshTent.  A miss gives colour logit 0 and density 0.  THE MARCH STEP MUST BE AT MOST width / 2.  Marched path only."""
+    CLAMP = 2.0 ** -12
+
+    def __init__(self, tracer, face_uv, atlas, width=None, peak=None):
+        super().__init__()
+        self._init_tent("AtlasField", tracer, width, peak)
+        F = tracer.faces.shape[0]
+        if not isinstance(face_uv, torch.Tensor) or tuple(face_uv.shape) != (F, 3, 2) or face_uv.dtype != torch.float32:
+            raise L.CtxError(f"AtlasField: want face_uv float32 [{F},3,2], got {getattr(face_uv, 'dtype', type(face_uv).__name__)} "
+                             f"{tuple(getattr(face_uv, 'shape', ()))}")
+        if not isinstance(atlas, torch.Tensor) or atlas.dim() != 3 or atlas.shape[0] != 3 or atlas.shape[1] != atlas.shape[2] \
+                or atlas.dtype != torch.float32:
+            raise L.CtxError(f"AtlasField: want atlas float32 [3,T,T], got {getattr(atlas, 'dtype', type(atlas).__name__)} "
+                             f"{tuple(getattr(atlas, 'shape', ()))}")
+        L.ptr(face_uv, torch.float32, "face_uv"), L.ptr(atlas, torch.float32, "atlas")
+        self.face_uv, self.atlas = face_uv, atlas
+
+    @torch.no_grad()
+    def forward_pts(self, pts):
+        from . import kal
+        if not isinstance(pts, torch.Tensor) or pts.dim() < 1 or pts.shape[-1] != 3:
+            raise L.CtxError(f"AtlasField: want pts [..., 3], got {tuple(getattr(pts, 'shape', ()))}")
+        x = L.f32c(pts.detach()).reshape(-1, 3)
+        if x.shape[0] == 0:
+            return torch.zeros(*pts.shape[:-1], 4, device=x.device)
+        dens, found, face, bary = self._tent(x)
+        fuv = self.face_uv[face.clamp_min(0)]
+        uv = (bary[:, 0:1] * fuv[:, 0] + bary[:, 1:2] * fuv[:, 1]) + bary[:, 2:3] * fuv[:, 2]
+        col = kal.render.mesh.texture_mapping(uv[None].contiguous(), self.atlas[None])[0]
+        logit = torch.logit(col.clamp(self.CLAMP, 1.0 - self.CLAMP))
+        logit = torch.where(found[:, None] != 0, logit, torch.zeros_like(logit))
+        return torch.cat([logit, dens[:, None]], dim=1).reshape(*pts.shape[:-1], 4)
+
+    forward = forward_pts
 
 
 def _mesh_targets(who, mesh, mask_weight, depth_weight, rays_o, rays_d, near, far):

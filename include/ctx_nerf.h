@@ -428,6 +428,29 @@ int32_t ctx_mesh_ray_hit(const float *rays_o, const float *rays_d, int64_t R, fl
                          const int64_t *faces, int64_t F, const int64_t *own_face /*nullable*/, int32_t mode, uint8_t *hit,
                          float *t /*nullable for mode 1*/, int32_t *face /*nullable for mode 1*/, float *uv /*nullable for mode 1*/,
                          ctx_stream_t stream);
+/* found u8 [n], dist [n], face int32 [n], uv [n,2]: the nearest point of the mesh to each of pts [n,3] within the radius r (definition:
+   tests/meshdist_rule.py).  One lane per point, binary32 in the order written; cell_off, cell_tri and tri are those of the calls above.
+   Block: per axis a = floorf(((p - r) - lo)*inv), b = floorf(((p + r) - lo)*inv).  A miss if p is not finite, or if on any axis b < 0 or
+   a > G - 1; otherwise both are clamped to [0, G - 1] and every triangle listed in any cell of [a, b]^3 is looked at (no cell is left
+   out; a triangle listed in several cells gives the same numbers each time).
+   Point against a triangle (v0, e1, e2), Ericson's closest point region by region, dots summed (ax*bx + ay*by) + az*bz:
+     ap = p - v0, d1 = e1.ap, d2 = e2.ap;   d1 <= 0 and d2 <= 0 -> (u, v) = (0, 0)
+     bp = ap - e1, d3 = e1.bp, d4 = e2.bp;  d3 >= 0 and d4 <= d3 -> (1, 0)
+     vc = d1*d4 - d3*d2;                    vc <= 0 and d1 >= 0 and d3 <= 0 -> (d1/(d1 - d3), 0)
+     cp = ap - e2, d5 = e1.cp, d6 = e2.cp;  d6 >= 0 and d5 <= d6 -> (0, 1)
+     vb = d5*d2 - d1*d6;                    vb <= 0 and d2 >= 0 and d6 <= 0 -> (0, d2/(d2 - d6))
+     va = d3*d6 - d5*d4;                    va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0 -> w = (d4 - d3)/((d4 - d3) + (d5 - d6)), (1 - w, w)
+     otherwise den = 1/((va + vb) + vc) -> (vb*den, vc*den)
+   then q = v0 + (e1*u + e2*v) per component, s = p - q, d2 = (sx*sx + sy*sy) + sz*sz.  A record with a NaN, or a non-finite d2, u or v,
+   is skipped.  The answer is the minimum over (d2, face) in lexicographic order (the lower face id on equal d2), accepted only if
+   d2 <= r*r: found = 1, dist = sqrtf(d2), face, uv; the nearest point is v0 + u e1 + v e2 of that face.  A miss stores found = 0,
+   dist = r, face = -1, uv = 0.  The nearest point of a triangle that lies outside the box is in no cell: the answer is for the mesh
+   inside the box.  n = 0 launches nothing.
+   0 <= n < 2^31; 0 <= n_list < 2^31; 1 <= G <= 256; 1 <= F < 2^31; r finite, > 0 and at most 3 min(h) (a block of at most 7^3 cells);
+   tri 16-byte and uv 8-byte aligned.  Entries of cell_off and cell_tri that point outside [0, n_list) or [0, F) are skipped. */
+int32_t ctx_mesh_closest_point(const float *pts, int64_t n, float r, int32_t G, float lo_x, float lo_y, float lo_z, float inv_x, float inv_y,
+                               float inv_z, const int32_t *cell_off, const int32_t *cell_tri, int64_t n_list, const float *tri, int64_t F,
+                               uint8_t *found, float *dist, int32_t *face, float *uv, ctx_stream_t stream);
 
 /* ---- marching the grid into ragged per-ray sample lists, and the compositing on them (definition: tests/march_rule.py) ---- */
 /* count [R]: how many samples the march places on each ray.  The finite check, the clip, the start cell and the walk are those of
