@@ -87,6 +87,11 @@ SIGNATURES = {
     "ctx_mesh_ray_hit": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 12 + [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp,
                                 _vp]),
     "ctx_mesh_closest_point": (_i32, [_vp, _i64, _f32, _i32] + [_f32] * 6 + [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_mesh_vertex_faces_count": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "ctx_mesh_vertex_faces_fill": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ctx_mesh_pseudonormals": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ctx_mesh_signed_distance": (_i32, [_vp, _i64, _f32, _i32] + [_f32] * 6 + [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
     "ctx_occ_march_count": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 13 + [_vp, _vp]),
     "ctx_occ_march_write": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp, _i32] + [_f32] * 13 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctx_raymarch_packed_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

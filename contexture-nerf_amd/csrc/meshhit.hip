@@ -142,6 +142,63 @@ extern "C" int32_t ctx_mesh_cells_fill(const float *vertices, const int64_t *fac
     return CTX_OK;
 }
 
+// ---- vertex -> face incidence lists (for the pseudonormal tables of meshpn.hip): count, the scan above, fill ----------------------------
+// One lane per face.  A face whose three ids lie in [0, V) lists itself once per corner under that corner's vertex id; any other face is
+// in no list.  FILL as for the cells: an atomic cursor into `slots`, and k_mesh_cells_sort puts every segment in ascending face id.
+template <bool FILL>
+__global__ __launch_bounds__(MH_BLK) void k_mesh_vertex_faces(const int64_t *__restrict__ faces, int64_t V, int64_t F, int32_t *__restrict__ count,
+                                                              const int32_t *__restrict__ vf_off, int64_t n, int32_t *__restrict__ slots)
+{
+    for (int64_t f = (int64_t)blockIdx.x * MH_BLK + threadIdx.x; f < F; f += (int64_t)gridDim.x * MH_BLK) {
+        const int64_t iv[3] = {faces[f * 3 + 0], faces[f * 3 + 1], faces[f * 3 + 2]};
+        if (iv[0] < 0 || iv[0] >= V || iv[1] < 0 || iv[1] >= V || iv[2] < 0 || iv[2] >= V) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int k = atomicAdd(&count[iv[c]], 1);
+            if (FILL) {
+                const int64_t off = vf_off[iv[c]], end = vf_off[iv[c] + 1];
+                if (off >= 0 && off + k < end && end <= n) slots[off + k] = (int32_t)f;
+            }
+        }
+    }
+}
+
+static int32_t mesh_vertex_faces_args(const char *who, const void *faces, int64_t V, int64_t F)
+{
+    CTX_REQUIRE(faces, "%s: null pointer", who);
+    CTX_REQUIRE(V >= 1 && V <= (int64_t)256 * 256 * 256, "%s: V=%lld outside [1, 256^3] (the scan's reach)", who, (long long)V);
+    CTX_REQUIRE(F >= 1 && F <= INT32_MAX / 3, "%s: F=%lld outside [1, 2^31 / 3)", who, (long long)F);
+    return CTX_OK;
+}
+
+extern "C" int32_t ctx_mesh_vertex_faces_count(const int64_t *faces, int64_t V, int64_t F, int32_t *count, ctx_stream_t stream)
+{
+    if (int32_t rc = mesh_vertex_faces_args("mesh_vertex_faces_count", faces, V, F)) return rc;
+    CTX_REQUIRE(count, "mesh_vertex_faces_count: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(count, 0, V * sizeof(int32_t), s) != hipSuccess) { ctx_set_error("mesh_vertex_faces_count: memset failed"); return CTX_E_LAUNCH; }
+    hipLaunchKernelGGL(k_mesh_vertex_faces<false>, dim3(capped_blocks(F, MH_BLK, MH_CAP)), dim3(MH_BLK), 0, s, faces, V, F, count,
+                       (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr);
+    CTX_CHECK_LAUNCH("mesh_vertex_faces_count");
+    return CTX_OK;
+}
+
+extern "C" int32_t ctx_mesh_vertex_faces_fill(const int64_t *faces, int64_t V, int64_t F, const int32_t *vf_off, int64_t n, int32_t *cursor,
+                                              int32_t *slots, int32_t *vf_face, ctx_stream_t stream)
+{
+    if (int32_t rc = mesh_vertex_faces_args("mesh_vertex_faces_fill", faces, V, F)) return rc;
+    CTX_REQUIRE(n >= 0 && n <= 3 * F, "mesh_vertex_faces_fill: n=%lld outside [0, 3 F]", (long long)n);
+    if (n == 0) return CTX_OK;
+    CTX_REQUIRE(vf_off && cursor && slots && vf_face, "mesh_vertex_faces_fill: null pointer");
+    CTX_REQUIRE(slots != vf_face, "mesh_vertex_faces_fill: the workspace slots must not be vf_face");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(cursor, 0, V * sizeof(int32_t), s) != hipSuccess) { ctx_set_error("mesh_vertex_faces_fill: memset failed"); return CTX_E_LAUNCH; }
+    hipLaunchKernelGGL(k_mesh_vertex_faces<true>, dim3(capped_blocks(F, MH_BLK, MH_CAP)), dim3(MH_BLK), 0, s, faces, V, F, cursor, vf_off, n, slots);
+    hipLaunchKernelGGL(k_mesh_cells_sort, dim3(capped_blocks(V, MH_BLK / 64, MH_CAP)), dim3(MH_BLK), 0, s, vf_off, V, n, (const int32_t *)slots, vf_face);
+    CTX_CHECK_LAUNCH("mesh_vertex_faces_fill");
+    return CTX_OK;
+}
+
 // ---- triangle records: v0, e1 = v1 - v0, e2 = v2 - v0, each padded to four floats; NaN for a face the voxeliser would not take ----------
 __global__ __launch_bounds__(MH_BLK) void k_mesh_tri_setup(const float *__restrict__ vtx, const int64_t *__restrict__ faces, int64_t V, int64_t F,
                                                            float4 *__restrict__ tri)

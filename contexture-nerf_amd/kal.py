@@ -386,6 +386,68 @@ def mesh_closest_point(pts, r, G, lo, inv, cell_off, cell_tri, tri):
     return found, dist, face, uv
 
 
+def mesh_vertex_faces(faces, V):
+    """-> (vf_off int32 [V + 1], vf_face int32 [n]): per vertex id the faces of faces int64 [F,3] that name it at a corner, ascending by
+    face id (ctx_mesh_vertex_faces_count, the exclusive scan ctx_mesh_cells_scan, ctx_mesh_vertex_faces_fill); a face with an id outside
+    [0, V) is in no list.  A set-up call: it reads n back, which SYNCS the host, once."""
+    lib = L.load()
+    p_f = L.ptr(faces, torch.int64, "faces")
+    V, F = int(V), faces.shape[0]
+    if faces.dim() != 2 or faces.shape[1] != 3 or F < 1:
+        raise L.CtxError(f"mesh_vertex_faces: want faces [F,3] with F >= 1; got {tuple(faces.shape)}")
+    if not 1 <= V <= 256 ** 3 or F >= 2 ** 31 // 3:
+        raise L.CtxError(f"mesh_vertex_faces: V={V}, F={F}: want 1 <= V <= 256^3 and F < 2^31 / 3")
+    dev = faces.device
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    L.check(lib.ctx_mesh_vertex_faces_count(p_f, V, F, L.ptr(count), L.stream()))
+    vf_off = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    L.check(lib.ctx_mesh_cells_scan(L.ptr(count), V, L.ptr(vf_off), L.ptr(total), L.stream()))
+    n = int(total.item())                                                                  # the one host sync
+    vf_face = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        cursor, slots = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        L.check(lib.ctx_mesh_vertex_faces_fill(p_f, V, F, L.ptr(vf_off), n, L.ptr(cursor), L.ptr(slots), L.ptr(vf_face), L.stream()))
+    return vf_off, vf_face
+
+
+def mesh_pseudonormals(faces, V, tri, vf_off, vf_face):
+    """ctx_mesh_pseudonormals -> pn float32 [F,7,3]: per face its unit normal (row 0), the angle-weighted pseudonormals of its three
+    vertices (rows 1-3) and the pseudonormals of its edges (v0,v1), (v0,v2), (v1,v2) (rows 4-6), not normalised (csrc/meshpn.hip; the
+    rule is written out at the entry point).  tri: mesh_tri_records; vf_off, vf_face: mesh_vertex_faces.  No host sync."""
+    p_f = L.ptr(faces, torch.int64, "faces")
+    V, F = int(V), faces.shape[0]
+    if tuple(tri.shape) != (F, 12) or tuple(vf_off.shape) != (V + 1,):
+        raise L.CtxError(f"mesh_pseudonormals: want tri [{F},12] and vf_off [{V + 1}]; got {tuple(tri.shape)}, {tuple(vf_off.shape)}")
+    pn = torch.empty(F, 7, 3, dtype=torch.float32, device=faces.device)
+    L.check(L.load().ctx_mesh_pseudonormals(p_f, V, F, L.ptr(tri, torch.float32, "tri"), L.ptr(vf_off, torch.int32, "vf_off"),
+                                            L.ptr(vf_face, torch.int32, "vf_face") if vf_face.numel() else None, vf_face.numel(), L.ptr(pn),
+                                            L.stream()))
+    return pn
+
+
+def mesh_signed_distance(pts, r, G, lo, inv, cell_off, cell_tri, tri, pn):
+    """ctx_mesh_signed_distance -> (found u8 [n], sdist f32 [n], face i32 [n], uv f32 [n,2], feature u8 [n], grad f32 [n,3]):
+    mesh_closest_point with the sign of (p - q) . pn[face, feature] on the distance, the feature of the winning face on which the nearest
+    point lies, and the unit direction grad = d sdist / d p (csrc/meshdist.hip; the rule is written out at the entry point).  A miss:
+    found = 0, sdist = +r, face = -1, uv = 0, feature = 0, grad = 0.  n = 0 gives empty tensors.  No host sync."""
+    p_p = L.ptr(pts, torch.float32, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise L.CtxError(f"mesh_signed_distance: want pts [n,3]; got {tuple(pts.shape)}")
+    if pn.dim() != 3 or tuple(pn.shape[1:]) != (7, 3) or pn.shape[0] < tri.shape[0]:
+        raise L.CtxError(f"mesh_signed_distance: want pn [F,7,3] with F >= {tri.shape[0]}; got {tuple(pn.shape)}")
+    n, dev = pts.shape[0], pts.device
+    found, feature = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    sdist, face = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    uv, grad = torch.empty(n, 2, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev)
+    if n:
+        L.check(L.load().ctx_mesh_signed_distance(p_p, n, float(r), int(G), *map(float, lo), *map(float, inv), L.ptr(cell_off, torch.int32, "cell_off"),
+                                                  L.ptr(cell_tri, torch.int32, "cell_tri") if cell_tri.numel() else None, cell_tri.numel(),
+                                                  L.ptr(tri, torch.float32, "tri"), tri.shape[0], L.ptr(pn, torch.float32, "pn"), pn.shape[0],
+                                                  L.ptr(found), L.ptr(sdist), L.ptr(face), L.ptr(uv), L.ptr(feature), L.ptr(grad), L.stream()))
+    return found, sdist, face, uv, feature, grad
+
+
 def _fill_ws(lib, T, device):
     n = lib.ctx_atlas_fill_ws_bytes(T)
     if n < 0:

@@ -293,7 +293,8 @@ class MeshTracer:
         self.G, self.lo, self.hi, self.inv, self.h = _grid_box(G, lo, hi, "MeshTracer")
         self.device = vertices.device
         L.ptr(vertices, torch.float32, "vertices"), L.ptr(faces, torch.int64, "faces")
-        self.faces = faces
+        self.faces, self.n_vertices = faces, vertices.shape[0]
+        self._pn = self._topology = None
         self.count, self.cell_off, self.cell_tri = kal.mesh_cell_lists(vertices, faces, self.G, self.lo, self.inv)
         self.cells = (self.count > 0).to(torch.uint8).reshape(self.G, self.G, self.G).contiguous()
         self.tri = kal.mesh_tri_records(vertices, faces)
@@ -345,6 +346,53 @@ class MeshTracer:
         found, dist, face, uv = kal.mesh_closest_point(pts, r, self.G, self.lo, self.inv, self.cell_off, self.cell_tri, self.tri)
         bary = torch.stack([1.0 - uv[:, 0] - uv[:, 1], uv[:, 0], uv[:, 1]], dim=1) * found[:, None]
         return found, dist, face.to(torch.int64), bary
+
+    def pseudonormals(self):
+        """-> pn float32 [F,7,3], built on first use and kept: per face its unit normal, the angle-weighted pseudonormals of its three
+        vertices and the pseudonormals of its three edges, in the order of signed_distance's feature code (`ctx_mesh_pseudonormals`; the
+        rule is written out there, its numpy definition is tests/meshsdf_rule.py).  Building them reads the length of the vertex -> face
+        lists back: one host sync, on the first call only."""
+        if self._pn is None:
+            from . import kal
+            vf_off, vf_face = kal.mesh_vertex_faces(self.faces, self.n_vertices)
+            self._pn = kal.mesh_pseudonormals(self.faces, self.n_vertices, self.tri, vf_off, vf_face)
+        return self._pn
+
+    def topology(self):
+        """-> dict(boundary_edges, nonmanifold_edges, inconsistent_edges): how many undirected edges have one face, more than two faces,
+        and two faces that traverse them in the same direction (host numbers: this syncs; computed once and kept).  Faces with a vertex
+        id outside [0, V) are left out.  The sign of signed_distance means inside / outside only when all three are 0 AND the faces are
+        wound outward; an inward-wound mesh inverts the sign, which is the caller's contract and is not detected."""
+        if self._topology is None:
+            V = self.n_vertices
+            f = self.faces[((self.faces >= 0) & (self.faces < V)).all(1)]
+            a, b = torch.cat([f[:, 0], f[:, 1], f[:, 2]]), torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+            und, inverse, cnt = torch.unique(torch.minimum(a, b) * V + torch.maximum(a, b), return_inverse=True, return_counts=True)
+            forward = torch.zeros_like(cnt).index_add_(0, inverse, (a < b).to(cnt.dtype))
+            self._topology = dict(boundary_edges=int((cnt == 1).sum()), nonmanifold_edges=int((cnt > 2).sum()),
+                                  inconsistent_edges=int(((cnt == 2) & (forward != 1)).sum()))
+        return dict(self._topology)
+
+    def signed_distance(self, pts, max_dist):
+        """-> (found u8 [n], sdist f32 [n], face i64 [n], bary f32 [n,3], grad f32 [n,3]): `closest` with a sign on the distance, negative
+        on the inner side of the surface, and grad = d sdist / d pts, the unit direction from the nearest surface point (times the sign;
+        on the surface itself the pseudonormal's direction).  found, |sdist|, face and bary are those of `closest`, bit for bit.  The
+        sign is that of (p - q) . N with N the angle-weighted pseudonormal of the face, edge or vertex on which the nearest point q lies
+        (`ctx_mesh_signed_distance`; numpy definition: tests/meshsdf_rule.py).  A miss: found = 0, sdist = +max_dist, face = -1,
+        bary = 0, grad = 0.  Negative means INSIDE only for a mesh whose `topology()` is all zero and whose faces are wound outward; an
+        inward-wound mesh inverts the sign (not detected).  grad is returned, not attached: there is no autograd gradient, and a pts
+        that requires grad is refused.  No host sync once the tables exist (`pseudonormals`, built on the first call)."""
+        from . import kal
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3:
+            raise L.CtxError(f"MeshTracer.signed_distance: want pts [n,3], got {tuple(getattr(pts, 'shape', ()))}")
+        if pts.requires_grad:
+            raise L.CtxError("MeshTracer.signed_distance: pts requires grad, and the query has no autograd gradient with respect to the "
+                             "positions (grad is returned beside the distance); detach pts")
+        r = self._radius("MeshTracer.signed_distance", "max_dist", max_dist)
+        found, sdist, face, uv, _, grad = kal.mesh_signed_distance(pts, r, self.G, self.lo, self.inv, self.cell_off, self.cell_tri, self.tri,
+                                                                   self.pseudonormals())
+        bary = torch.stack([1.0 - uv[:, 0] - uv[:, 1], uv[:, 0], uv[:, 1]], dim=1) * found[:, None]
+        return found, sdist, face.to(torch.int64), bary, grad
 
     def occupancy(self, dilate=1):
         """-> an OccupancyGrid whose cells equal OccupancyGrid.from_mesh(vertices, faces, G, lo, hi, dilate) bit for bit: the cells that
@@ -435,6 +483,112 @@ class MeshDensityField(torch.nn.Module, _MeshTent):
         raw, res = self.inner.forward_dirs(pts, rays_d, ray_id, return_residual=True)
         raw = self._replace(raw, pts)
         return (raw, res) if return_residual else raw
+
+
+class MeshSolidField(torch.nn.Module):
+    """MeshDensityField's sibling with a side: `inner`'s colour, and a density that is zero outside the mesh and rises only inside it, the
+    one-sided ramp peak * min(1, max(0, -sdist / width)) of the tracer's SIGNED distance (MeshTracer.signed_distance with the query
+    radius width: d = sdist / width is a true float32 division by a device scalar, then the clamp, then the product).  The density is
+    exactly 0 outside and on the surface, reaches peak at depth width, and is 0 on a miss (sdist = +width).  A ray that misses the mesh
+    composites to nothing: the silhouette is the mesh's, with no halo of half a tent outside it.  Marched path only.
+    width=None: the tracer's largest cell edge; peak=None: 32 / width.  THE MARCH STEP MUST BE AT MOST width / 2.
+    The query radius is width, so a point deeper than width inside the mesh is a miss and has the density 0 again: the solid is a wall
+    of thickness width under the surface, a ramp from 0 at the surface to peak at its inner face (the min(1, .) binds only there).
+    Why 32: a perpendicular crossing of the wall has the optical thickness peak * width / 2 = 16, the tent's (two halves of
+    peak' * width / 2 with peak' = 16 / width).  The quadrature, for intervals of length dt <= width / 2: the march's midpoint rule is
+    exact on a linear piece, so an interval loses only where it straddles an end of the ramp.  At the foot, if a part a of the interval
+    lies inside, the true integral there is (peak / width) a^2 / 2 and the midpoint gives dt (peak / width) max(0, a - dt / 2); the
+    difference is at most (peak / width) dt^2 / 8 <= peak * width / 32 = 1.  At the inner face an interval whose midpoint falls beyond
+    it loses the integral of the ramp over at most dt / 2 <= width / 4, where the ramp lies between 3/4 peak and peak: at most
+    7/32 peak * width = 7.  So one wall keeps an optical thickness >= 16 - 1 - 7 = 8 on a perpendicular crossing, and more on an oblique
+    one (the path grows with 1 / |cos|, the two losses do not); a ray that enters a closed mesh leaves it through a second wall, so it
+    keeps >= 16 and acc >= 1 - e^-16 > 1 - 2^-20.  (A single wall alone, e.g. of an open mesh under allow_open, guarantees 1 - e^-8.)
+    Why tracer.occupancy(1) holds the whole wall when width <= min(h): the density is positive only at points within width of the
+    surface; such a point is within width <= min(h) of a cell the voxeliser marks, i.e. in that cell or in one of its neighbours, which
+    occupancy(1) adds.
+    forward_pts(pts [..., 3]) -> inner.forward_pts(pts) with channel 3 replaced; the density carries no gradient (inner's output row for
+    channel 3 gets a gradient of exactly zero), the colour channels carry theirs through inner unchanged.  view_dependent and forward_dirs
+    pass through to an inner that has them.  modules() / parameters() expose inner, so field_optimizer, FieldAdam, fit_views,
+    OccupancyGrid.update and bake_atlas take it as any field.  density_gradient gives the ramp's gradient with respect to the positions,
+    so render_normals takes it too: its normals are the mesh's.
+    The sign means inside / outside only for a closed, consistently oriented mesh wound outward: a tracer whose topology() is not all
+    zero is refused unless allow_open=True (one host sync, at construction).  An inward-wound mesh gives a solid OUTSIDE; not detected."""
+
+    def __init__(self, inner, tracer, width=None, peak=None, allow_open=False):
+        super().__init__()
+        if not callable(getattr(inner, 'forward_pts', None)):
+            raise L.CtxError(f"MeshSolidField: inner ({type(inner).__name__}) has no forward_pts")
+        if not isinstance(tracer, MeshTracer):
+            raise L.CtxError(f"MeshSolidField: tracer must be a MeshTracer, got {type(tracer).__name__}")
+        self.inner, self.tracer = inner, tracer
+        self.width = tracer._radius("MeshSolidField", "width", np.max(tracer.h) if width is None else width)
+        with np.errstate(all='ignore'):
+            self.peak = np.float32(32) / self.width if peak is None else np.float32(peak)
+        if not (np.isfinite(self.peak) and self.peak > 0):
+            raise L.CtxError(f"MeshSolidField: peak={peak!r}: want a finite density > 0")
+        topo = tracer.topology()
+        if any(topo.values()) and not allow_open:
+            raise L.CtxError(f"MeshSolidField: the mesh is not closed and consistently oriented ({topo}): the signed distance has no inside; "
+                             "pass allow_open=True to take its sign as it comes")
+        tracer.pseudonormals()
+
+    @property
+    def view_dependent(self):
+        return bool(getattr(self.inner, 'view_dependent', False))
+
+    @torch.no_grad()
+    def _ramp(self, pts):
+        """pts [n,3] float32 contiguous -> (density [n], sdist [n], grad [n,3]): d = sdist / width; peak * min(1, max(0, -d))."""
+        _, sdist, _, _, grad = self.tracer.signed_distance(pts, self.width)
+        d = sdist / sdist.new_full((), float(self.width))
+        return float(self.peak) * (-d).clamp(0.0, 1.0), sdist, grad
+
+    def _replace(self, raw, pts):
+        if raw.shape[-1] != 4:
+            raise L.CtxError(f"MeshSolidField: inner returned {tuple(raw.shape)}, expected [..., 4] (colour and density)")
+        x = L.f32c(pts.detach()).reshape(-1, 3)
+        if x.shape[0] == 0:
+            return raw
+        dens = self._ramp(x)[0].reshape(*raw.shape[:-1], 1)
+        return torch.cat([raw[..., :3], dens.to(raw.dtype)], dim=-1)
+
+    def forward_pts(self, pts):
+        """pts [..., 3] -> raw [..., 4]: inner's colour logits, the ramp's density."""
+        return self._replace(self.inner.forward_pts(pts), pts)
+
+    forward = forward_pts
+
+    def forward_dirs(self, pts, rays_d, ray_id, return_residual=False):
+        """inner.forward_dirs with channel 3 replaced (an inner without forward_dirs is refused)."""
+        if not callable(getattr(self.inner, 'forward_dirs', None)):
+            raise L.CtxError(f"MeshSolidField.forward_dirs: inner ({type(self.inner).__name__}) has no forward_dirs")
+        raw, res = self.inner.forward_dirs(pts, rays_d, ray_id, return_residual=True)
+        raw = self._replace(raw, pts)
+        return (raw, res) if return_residual else raw
+
+    @torch.no_grad()
+    def density_gradient(self, pts, channel=3, return_raw=False):
+        """pts [..., 3] -> grad [..., 3] = d raw[..., 3] / d pts, and with return_raw=True (raw [..., 4], grad), HashGridField's
+        convention: (-(peak / width)) * (d sdist / d pts) where -width < sdist < 0, and 0 elsewhere (outside, on the surface, on the
+        plateau, on a miss); peak / width is rounded once, in float32.  It points inward, so render_normals' -grad / |grad| is the
+        outward unit direction from the nearest surface point.  Only the density has a closed form: any other channel is refused.  No
+        autograd is involved; the ambient grad mode plays no part."""
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or channel != 3:
+            raise L.CtxError(f"MeshSolidField.density_gradient: channel={channel!r}: only channel 3, the density, has a gradient with respect "
+                             "to the positions here (the colour is inner's)")
+        if not isinstance(pts, torch.Tensor) or pts.dim() < 1 or pts.shape[-1] != 3:
+            raise L.CtxError(f"MeshSolidField.density_gradient: want pts [..., 3], got {tuple(getattr(pts, 'shape', ()))}")
+        x = L.f32c(pts.detach()).reshape(-1, 3)
+        if x.shape[0] == 0:
+            grad = torch.zeros(*pts.shape[:-1], 3, device=x.device)
+            return (torch.zeros(*pts.shape[:-1], 4, device=x.device), grad) if return_raw else grad
+        dens, sdist, g = self._ramp(x)
+        on = (sdist > -float(self.width)) & (sdist < 0)
+        grad = torch.where(on[:, None], float(-(self.peak / self.width)) * g, torch.zeros_like(g)).reshape(*pts.shape[:-1], 3)
+        if not return_raw:
+            return grad
+        raw = self.inner.forward_pts(x).detach()
+        return torch.cat([raw[:, :3], dens[:, None]], dim=1).reshape(*pts.shape[:-1], 4), grad
 
 
 class AtlasField(torch.nn.Module, _MeshTent):

@@ -452,6 +452,46 @@ int32_t ctx_mesh_closest_point(const float *pts, int64_t n, float r, int32_t G, 
                                float inv_z, const int32_t *cell_off, const int32_t *cell_tri, int64_t n_list, const float *tri, int64_t F,
                                uint8_t *found, float *dist, int32_t *face, float *uv, ctx_stream_t stream);
 
+/* ---- on which side of the mesh a point lies: pseudonormal tables and the signed query (definition: tests/meshsdf_rule.py) ---- */
+/* count int32 [V]: how many corners of faces [F,3] name each vertex id.  Only a face whose three ids lie in [0, V) is counted, once per
+   corner.  The call zeroes count, then adds with integer atomics.  Its exclusive scan is ctx_mesh_cells_scan with ncell = V, which sets
+   the envelope: 1 <= V <= 256^3; 1 <= F < 2^31 / 3. */
+int32_t ctx_mesh_vertex_faces_count(const int64_t *faces, int64_t V, int64_t F, int32_t *count, ctx_stream_t stream);
+/* vf_face int32 [n], n = vf_off[V]: vertex w owns vf_off[w] .. vf_off[w+1], the faces that name it at a corner, ASCENDING by face id (a
+   face that names it twice is listed twice): one value whatever the arrival order, as ctx_mesh_cells_fill (the same cursor, slots and
+   rank sort).  cursor int32 [V] and slots int32 [n] are workspaces; nothing is stored outside a segment or outside [0, n).  n = 0
+   launches nothing; 0 <= n <= 3 F. */
+int32_t ctx_mesh_vertex_faces_fill(const int64_t *faces, int64_t V, int64_t F, const int32_t *vf_off, int64_t n, int32_t *cursor, int32_t *slots,
+                                   int32_t *vf_face, ctx_stream_t stream);
+/* pn float32 [F,7,3]: the angle-weighted pseudonormals (Baerentzen & Aanaes 2005) of every face's seven features, in the order of the
+   signed query's feature code.  Binary32 in the order written, dots summed (ax*bx + ay*by) + az*bz.  tri is ctx_mesh_tri_setup's.
+   Row 0, the face: n = e1 x e2 (nx = e1y*e2z - e1z*e2y, ny = e1z*e2x - e1x*e2z, nz = e1x*e2y - e1y*e2x), nn = n.n, u = n / sqrtf(nn) per
+     component if 0 < nn < inf, else 0 (a zero-area face).  A face COUNTS in the sums below if its u is finite and not (0, 0, 0).
+   Rows 1-3, the vertices faces[f,0..2]: the sum, over the counting faces g in that vertex id's list, ascending g, of alpha*u_g per
+     component (acc = acc + alpha*u from 0), alpha = atan2f(|a x b|, a.b) the angle of g at the first corner that names the id: at v0
+     a = e1, b = e2; at v1 a = -e1, b = e2 - e1; at v2 a = -e2, b = e1 - e2.
+   Rows 4-6, the edges (v0,v1), (v0,v2), (v1,v2): the sum of u_g over the counting faces g, in the list of the edge's first vertex,
+     ascending g, that name the two ids at two different corners.  A boundary edge gets its one face's normal, a non-manifold edge the sum
+     of all its faces.
+   Rows 1-6 are not normalised.  A face whose record holds a NaN (an id outside [0, V), a non-finite vertex) has seven NaN rows and
+   counts nowhere.  No atomics; every element has one writer and one value.  Entries of vf_off and vf_face that point outside
+   [0, n_vf) or [0, F) are skipped.  1 <= V < 2^31; 1 <= F < 2^31 / 21; 0 <= n_vf <= 3 F; tri 16-byte aligned. */
+int32_t ctx_mesh_pseudonormals(const int64_t *faces, int64_t V, int64_t F, const float *tri, const int32_t *vf_off, const int32_t *vf_face,
+                               int64_t n_vf, float *pn, ctx_stream_t stream);
+/* found u8 [n], sdist [n], face int32 [n], uv [n,2], feature u8 [n], grad [n,3]: ctx_mesh_closest_point's block walk, triangle arithmetic
+   and minimum over (d2, face), the same code and the same bits, and then: the winning face is evaluated once more, which gives the same
+   u, v, s = p - q and d2 as inside the loop, and feature = the region that answers: 0 the interior; 1 / 2 / 3 the vertices v0, v0 + e1,
+   v0 + e2; 4 / 5 / 6 the edges along e1, along e2 and opposite v0.  N = pn[face, feature] (pn [pn_faces,7,3] of
+   ctx_mesh_pseudonormals), dot = (sx*Nx + sy*Ny) + sz*Nz, sgn = -1 if dot < 0 else +1: zero, NaN and d2 = 0 count as outside.
+   sdist = sgn * sqrtf(d2); grad = (sgn*s) / sqrtf(d2) per component if d2 > 0, else N / sqrtf((Nx*Nx + Ny*Ny) + Nz*Nz) per component, or
+   0 where that is not finite.  A miss stores found = 0, sdist = +r, face = -1, uv = 0, feature = 0, grad = 0.
+   Negative means inside only for a closed, consistently oriented mesh wound outward; an inward-wound mesh inverts the sign, and an open
+   or non-manifold one has no inside.  Envelope, alignment and refusals as ctx_mesh_closest_point; pn_faces >= F. */
+int32_t ctx_mesh_signed_distance(const float *pts, int64_t n, float r, int32_t G, float lo_x, float lo_y, float lo_z, float inv_x, float inv_y,
+                                 float inv_z, const int32_t *cell_off, const int32_t *cell_tri, int64_t n_list, const float *tri, int64_t F,
+                                 const float *pn, int64_t pn_faces, uint8_t *found, float *sdist, int32_t *face, float *uv, uint8_t *feature,
+                                 float *grad, ctx_stream_t stream);
+
 /* ---- marching the grid into ragged per-ray sample lists, and the compositing on them (definition: tests/march_rule.py) ---- */
 /* count [R]: how many samples the march places on each ray.  The finite check, the clip, the start cell and the walk are those of
    ctx_occ_ray_spans, expression for expression (one device function).  A run is a maximal sequence of consecutive occupied cells of the
