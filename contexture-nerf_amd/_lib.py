@@ -45,6 +45,7 @@ SIGNATURES = {
     "ctx_view_consistency_ws_bytes":(_i64, [_i32, _i32]),
     "ctx_view_consistency_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctx_view_consistency_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ctx_view_pair_stats": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "ctx_texture_pack4": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "ctx_texture_mapping_packed_fwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ctx_view_weights_max": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -8,7 +8,9 @@ Exchange steps, both over RCCL, one of each per mesh:
   phase A  all-reduce(MAX) of the per-face view-weight maxima [F]    (before painting: the masks gate the scatter)
   phase B  each rank paints its items wave by wave (stable_diffusion_depth.plan_waves; items of different meshes may share a group)
   phase C  all-reduce(SUM) of the atlas contribution [3+1, T, T] as int64 fixed-point sums (bit-identical for any world size)
-Every rank calls the collectives of every mesh in mesh order, whether or not it holds views of that mesh."""
+Every rank calls the collectives of every mesh in mesh order, whether or not it holds views of that mesh.
+guide.exposure_compensation adds one exchange per mesh between B and C: phase B keeps its painted views and fills its views' slices of
+the mesh's statistics tensor [V, 4, Tc, Tc] (int64), which is all-reduced (SUM) before the gains are solved and the views projected."""
 import torch
 from . import dist as D
 from .config import validate
@@ -35,6 +37,34 @@ class MeshBatchPainter:
         self.rank, self.world, self.device = t0.rank, t0.world, t0.device
         self.plan = schedule(len(self.trainers), len(self.view_ids), self.world)
 
+    # ---- guide.exposure_compensation: one gain per view and colour channel before the merge ------------------------------
+    def _exposure_begin(self):
+        """Per mesh: the statistics tensor [V,4,Tc,Tc] int64 (this rank fills its own views' slices) and the list of kept views."""
+        g = validate(self.trainers[0].cfg).guide
+        Tc, V = int(g.exposure_resolution), len(self.view_ids)
+        return [dict(stats=torch.zeros(V, 4, Tc, Tc, dtype=torch.int64, device=self.device), views=[]) for _ in self.trainers]
+
+    def _exposure_keep(self, kept, m, v, k, ctx, rgb_output, obj_mask):
+        tr, e = self.trainers[m], kept[m]
+        tr.exposure_atlas(ctx['render_cache'], rgb_output, obj_mask, ctx['z_normals'], e['stats'].shape[-1], acc=e['stats'][v])
+        e['views'].append((v, k, ctx['render_cache'], rgb_output, obj_mask))
+
+    def _exposure_finish(self, kept, project, contrib):
+        """After the last wave, per mesh and in mesh order on every rank (an idle rank joins the collective): all-reduce(SUM) of the
+        statistics tensor, the pair statistics, the gains (the one host sync), then the kept views are projected with their gains
+        through the view-weight masks, as the plain loop projects them ungained."""
+        from . import kal
+        for m, tr in enumerate(self.trainers):
+            g, e = tr.cfg.guide, kept[m]
+            D.all_reduce_sum_(e['stats'], self.group)
+            count, colour_sum = kal.view_pair_stats(e['stats'])
+            gains = kal.solve_view_gains(count, colour_sum, ridge=g.exposure_ridge, max_gain=g.exposure_max_gain)
+            tr.view_gains, tr.view_gain_stats = gains, (count, colour_sum)
+            dev_gains = gains.to(device=self.device, dtype=torch.float32)
+            for v, k, render_cache, rgb_output, obj_mask in e['views']:
+                gained = (rgb_output * dev_gains[v][None, :, None, None]).clamp(0, 1)
+                project[m](render_cache, gained, tr.view_weights[k:k + 1] & (obj_mask > 0), acc=contrib[m])
+
     def paint_all(self, image_size=None, num_inference_steps=None):
         """-> [(atlas [3,T,T], coverage [T,T])] per mesh (identical on every rank)."""
         mine = self.plan[self.rank]
@@ -52,6 +82,8 @@ class MeshBatchPainter:
         optim = self.trainers[0].cfg.optim
         vpe, infl = int(optim.views_per_eval), int(optim.views_in_flight)
         project = {m: tr.projector() for m, tr in enumerate(self.trainers)}       # guide.projection: scatter | gather
+        compensate = self.trainers[0].cfg.guide.exposure_compensation
+        kept = self._exposure_begin() if compensate else None
         for wave in plan_waves(len(mine), vpe, infl):
             items = [mine[k] for grp in wave for k in grp]
             preps = [self.trainers[m]._paint_prepare(self.trainers[m].train_views[self.view_ids[v]], image_size, num_inference_steps)
@@ -61,7 +93,12 @@ class MeshBatchPainter:
                 tr = self.trainers[m]
                 rgb_output, obj_mask = tr._paint_finish(ctx, rgb)
                 k = slot[(m, self.view_ids[v])]
+                if compensate:          # guide.exposure_compensation: the view waits for its gain (_exposure_finish projects it)
+                    self._exposure_keep(kept, m, v, k, ctx, rgb_output, obj_mask)
+                    continue
                 project[m](ctx['render_cache'], rgb_output, tr.view_weights[k:k + 1] & (obj_mask > 0), acc=contrib[m])
+        if compensate:
+            self._exposure_finish(kept, project, contrib)
         # phase C: one all-reduce(SUM) per mesh
         res = []
         for m, tr in enumerate(self.trainers):

@@ -71,6 +71,16 @@ class GuideConfig:
                                      # the views are painted one after another, each conditioned on what the earlier ones painted, through a
                                      # generate / refine / keep trimap, masked latent blending and a meta-texture of the z-normal every texel
                                      # was painted at (csrc/maskops.hip).  One rank; optim.views_per_eval and optim.views_in_flight are not read
+    exposure_compensation: bool = False   # true: the per-view paint loop (paint_mode = 'independent', MeshBatchPainter.paint_all) keeps its painted
+                                     # views, solves one gain per view and colour channel from where the views overlap on the surface
+                                     # (kal.view_pair_stats, csrc/viewgain.hip; kal.solve_view_gains) and projects the gained views: no step in
+                                     # tone at the borders of the view-weight partition.  false: no new kernel is called, every output, launch
+                                     # and random draw as before.  Refused with paint_mode = 'progressive' (its views are consistent by
+                                     # construction); not read by the SDS loop or by project_back's running atlas
+    exposure_resolution: int = 256   # exposure_compensation: side Tc of the low-resolution atlases the statistics are taken on (1..4096)
+    exposure_ridge: float = 0.01     # weight of the pull of every log gain towards 0, per valid texel of the view (>= 0)
+    exposure_max_gain: float = 2.0   # gains are clipped to [1 / max_gain, max_gain] (>= 1)
+    exposure_z_min: float = 0.25     # a pixel enters the statistics when it shows the object and its z-normal is at least this
     texture_field: str = 'mlp'       # the field behind the atlas.  'mlp': the 8 x 256 MLP on the Fourier embedding of uv (the outputs of earlier
                                      # builds, bit for bit); 'hashgrid': a multiresolution hash table over the UV square and a 2 x 64 MLP
                                      # (hashgrid.HashGridTexture, csrc/hashtex.hip; its finest level is texture_resolution)
@@ -184,6 +194,15 @@ def validate(cfg):
             raise ValueError(f"guide.texture_field={guide.texture_field!r}: expected one of {TEXTURE_FIELDS}")
         if guide.paint_mode not in PAINT_MODES:
             raise ValueError(f"guide.paint_mode={guide.paint_mode!r}: expected one of {PAINT_MODES}")
+        if guide.exposure_compensation:
+            if guide.paint_mode == 'progressive':
+                raise ValueError("guide.exposure_compensation with guide.paint_mode='progressive': the progressive views are consistent by "
+                                 "construction; the switch belongs to paint_mode='independent'")
+            if not 1 <= guide.exposure_resolution <= 4096:
+                raise ValueError(f"guide.exposure_resolution={guide.exposure_resolution}: expected 1..4096")
+            if not (guide.exposure_ridge >= 0 and guide.exposure_max_gain >= 1):
+                raise ValueError(f"guide.exposure_ridge={guide.exposure_ridge}, guide.exposure_max_gain={guide.exposure_max_gain}: "
+                                 f"expected >= 0 and >= 1")
     optim = getattr(cfg, 'optim', None)
     if optim is not None and not (optim.hashgrid_lr > 0 and optim.hashgrid_mlp_lr > 0):
         raise ValueError(f"optim.hashgrid_lr={optim.hashgrid_lr}, optim.hashgrid_mlp_lr={optim.hashgrid_mlp_lr}: expected > 0")

@@ -642,6 +642,69 @@ def view_consistency(views, faces, face_idx, face_vertices_image, rows='image', 
     return mean
 
 
+# ---- exposure compensation across painted views (gain compensation, Brown & Lowe 2007) ----------------------------------
+VIEW_GAIN_MAX_VIEWS, VIEW_GAIN_MAX_RES = 16, 4096
+
+
+def view_pair_stats(atlases, lo=0.02, hi=0.98):
+    """-> (count [V,V] i64, colour_sum [V,V,3] i64): the pair statistics the per-view gains are solved from (csrc/viewgain.hip; the
+    rule is written out at ctx_view_pair_stats and in tests/exposure_rule.py).  atlases [V,4,Tc,Tc] int64: per view the weighted
+    colour sums and the weight sum of a low-resolution back-projection, in units of 2^-32 as scatter_fixed leaves them.  View v is
+    valid at a texel when its weight is positive and its colour lies in [lo, hi] on all three channels; count[i,j] is the number of
+    texels where i and j are both valid, colour_sum[i,j] view i's colour (units of 2^-24) summed over them.  Integer sums: every
+    rank computes the same bits.  1 <= V <= 16, 1 <= Tc <= 4096, 0 < lo < hi <= 1.  No host sync."""
+    if not isinstance(atlases, torch.Tensor) or atlases.dim() != 4 or atlases.shape[1] != 4 or atlases.shape[2] != atlases.shape[3]:
+        raise L.CtxError(f"view_pair_stats: want atlases [V,4,Tc,Tc], got {tuple(getattr(atlases, 'shape', ()))}")
+    V, Tc = int(atlases.shape[0]), int(atlases.shape[2])
+    if not 1 <= V <= VIEW_GAIN_MAX_VIEWS:
+        raise L.CtxError(f"view_pair_stats: V={V} outside [1, {VIEW_GAIN_MAX_VIEWS}]")
+    if not 1 <= Tc <= VIEW_GAIN_MAX_RES:
+        raise L.CtxError(f"view_pair_stats: Tc={Tc} outside [1, {VIEW_GAIN_MAX_RES}]")
+    lo, hi = float(lo), float(hi)
+    if not 0 < lo < hi <= 1:
+        raise L.CtxError(f"view_pair_stats: lo={lo} hi={hi}, expected 0 < lo < hi <= 1")
+    p = L.ptr(atlases, torch.int64, "atlases")
+    count = torch.empty(V, V, dtype=torch.int64, device=atlases.device)
+    colour_sum = torch.empty(V, V, 3, dtype=torch.int64, device=atlases.device)
+    L.check(L.load().ctx_view_pair_stats(p, V, Tc, lo, hi, L.ptr(count), L.ptr(colour_sum), L.stream()))
+    return count, colour_sum
+
+
+def solve_view_gains(count, colour_sum, ridge=0.01, max_gain=2.0):
+    """-> gains float64 [V,3] (a CPU tensor): one gain per view and colour channel from view_pair_stats' sums, so that gained views
+    agree in mean colour where they overlap.  Per channel, N = count, S = colour_sum[..., ch]: d_ij = log(S_ij / N_ij) - log(S_ji /
+    N_ij) for i < j with N_ij > 0 (d_ji = -d_ij); the log gains l minimise sum_{i<j} N_ij (l_i + d_ij - l_j)^2 + ridge sum_i N_ii l_i^2,
+    solved from the V x V normal equations by numpy.linalg.lstsq in float64 (minimum norm where they are singular: ridge = 0 is legal,
+    and a view that overlaps no other keeps gain exactly 1); gains = clip(exp(l), 1 / max_gain, max_gain).  The one host sync of the
+    feature: count and colour_sum (device or CPU tensors, or arrays) are brought to the host."""
+    import numpy as np
+    ridge, max_gain = float(ridge), float(max_gain)
+    if not ridge >= 0:
+        raise L.CtxError(f"solve_view_gains: ridge={ridge}, expected >= 0")
+    if not max_gain >= 1:
+        raise L.CtxError(f"solve_view_gains: max_gain={max_gain}, expected >= 1")
+    host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    N, S = host(count).astype(np.float64), host(colour_sum).astype(np.float64)
+    if N.ndim != 2 or N.shape[0] != N.shape[1] or S.shape != N.shape + (3,):
+        raise L.CtxError(f"solve_view_gains: want count [V,V] and colour_sum [V,V,3], got {N.shape} and {S.shape}")
+    V = N.shape[0]
+    gains = np.ones((V, 3), np.float64)
+    for ch in range(3):
+        M, b = np.zeros((V, V), np.float64), np.zeros(V, np.float64)
+        for i in range(V):
+            M[i, i] = ridge * N[i, i]
+            for j in range(V):
+                if j == i or not N[i, j] > 0:
+                    continue
+                a, c = min(i, j), max(i, j)
+                d = np.log(S[a, c, ch] / N[a, c]) - np.log(S[c, a, ch] / N[a, c])
+                M[i, i] += N[i, j]
+                M[i, j] = -N[i, j]
+                b[i] -= N[i, j] * (d if i < j else -d)
+        gains[:, ch] = np.clip(np.exp(np.linalg.lstsq(M, b, rcond=None)[0]), 1.0 / max_gain, max_gain)
+    return torch.from_numpy(gains)
+
+
 class _TextureMapping(torch.autograd.Function):
     @staticmethod
     def forward(ctx, uv, tex, mode, mask_idx):

@@ -62,6 +62,7 @@ class ConTEXTure:
         self.train_views = list(ds(self.cfg.render, self.device))
         self.view_weights = None
         self.atlas_filled = self.atlas_fill_src = None                                  # set by complete_atlas (guide.atlas_fill = 'nearest')
+        self.view_gains = self.view_gain_stats = None                                   # set by the paint loop under guide.exposure_compensation
         self.back_im = torch.full((3, 64, 64), 0.5, device=self.device)
         self.view_dirs = ['front', 'left', 'back', 'right', 'overhead', 'bottom']       # trainer.py:138
         self.text_string = None
@@ -213,6 +214,23 @@ class ConTEXTure:
         fvi = render_cache['face_vertices_image']
         fvi = fvi if (fvi.dtype == torch.float32 and fvi.is_contiguous()) else L.f32c(fvi)
         kal.gather_fixed(values, w, face_idx.contiguous(), fvi, self.mesh_model.mesh.faces.to(torch.int64).contiguous(), texel_face, texel_bary, acc)
+        return acc
+
+    @torch.no_grad()
+    def exposure_atlas(self, render_cache, rgb_output, object_mask, z_normals, Tc, acc=None):
+        """A painted view's low-resolution back-projection for the exposure statistics (guide.exposure_compensation): acc [4,Tc,Tc]
+        int64 += the UV scatter of (w * rgb_output, w) in units of 2^-32, w = (object_mask > 0) * (z_normals >= guide.exposure_z_min).
+        The weight is binary and is NOT the view-weight mask: those masks are a partition of the surface, so views weighted by them
+        share no texel, while gains are estimated from where views overlap.  Always kal.scatter_fixed at Tc, whatever guide.projection
+        says: the statistics do not depend on the projection mode.  -> acc (what kal.view_pair_stats reads, one slice per view)."""
+        from . import kal
+        uv, face_idx = render_cache['uv_features'], render_cache['face_idx']
+        w = ((object_mask > 0) & (z_normals >= self.cfg.guide.exposure_z_min)).to(torch.float32).permute(0, 2, 3, 1)
+        go = torch.cat([rgb_output.permute(0, 2, 3, 1) * w, w], dim=-1).contiguous()
+        if acc is None:
+            acc = torch.zeros(4, int(Tc), int(Tc), dtype=torch.int64, device=uv.device)
+        uvc = uv if (uv.dtype == torch.float32 and uv.is_contiguous()) else L.f32c(uv)
+        kal.scatter_fixed(go, uvc, face_idx.contiguous(), acc)
         return acc
 
     def projector(self):
@@ -721,11 +739,16 @@ class ConTEXTure:
     def export(self, path=None):
         """The outputs the reference writes after painting (src/training/trainer.py:954-968 -> export_mesh): mesh.obj / mesh.mtl /
         albedo.png with the painted atlas (rank 0 only; uncovered texels keep the texture field's colour, unless complete_atlas
-        has filled them)."""
+        has filled them).  Under guide.exposure_compensation also view_gains.json: the gains of the last paint and their statistics."""
         if D.dist.is_initialized() and D.dist.get_rank(self.group) != 0:
             return None
         path = str(self.cfg.log.exp_dir / 'mesh') if path is None else str(path)
         with torch.no_grad():
             tex = self._painted_texture(self.mesh_model.get_texture_map()[0])
         self.mesh_model.export_mesh(path, texture=tex)
+        if self.cfg.guide.exposure_compensation and self.view_gains is not None:
+            import json
+            count, colour_sum = self.view_gain_stats
+            with open(os.path.join(path, 'view_gains.json'), 'w') as fh:
+                json.dump(dict(gains=self.view_gains.tolist(), count=count.cpu().tolist(), colour_sum=colour_sum.cpu().tolist()), fh)
         return path

@@ -191,6 +191,16 @@ int32_t ctx_view_consistency_bwd(const float *views, const int64_t *faces, const
                                  const uint8_t *seen, int32_t V, int32_t C, int32_t h, int32_t w, int32_t F, int32_t n_vertices, int32_t rows,
                                  const int64_t *pair_count, const float *grad_mean, int32_t *sign_count, float *grad_views, ctx_stream_t stream);
 
+/* ---- exposure compensation across painted views: the pair statistics the per-view gains are solved from ------- */
+/* atlases [V,4,Tc,Tc] i64: per view the weighted colour sums and the weight sum of a low-resolution back-projection in units of 2^-32
+   (ctx_uv_scatter_fixed).  Per texel p, view v, channel ch: w = A[v,3,p], c = float32(float64(A[v,ch,p]) / float64(w)); v is valid at p
+   when w > 0 and lo <= c <= hi on all three channels; q = int64(rintf(c * 2^24)).  For every ordered pair (i, j), i == j included, with
+   both views valid at p: count[i,j] += 1 and colour_sum[i,j,ch] += q_i[ch] (count [V,V] i64, colour_sum [V,V,3] i64; written, not
+   accumulated).  Integer sums: the results do not depend on the launch geometry or the texel order.  1 <= V <= 16, 1 <= Tc <= 4096,
+   0 < lo < hi <= 1.  No host sync. */
+int32_t ctx_view_pair_stats(const int64_t *atlases, int32_t V, int32_t Tc, float lo, float hi, int64_t *count, int64_t *colour_sum,
+                            ctx_stream_t stream);
+
 /* Texel-interleaved forward for C <= 4 and one texture shared by the batch (the reference's texture_img.expand(B, ...),
    render.py:133-135): ctx_texture_pack4 repacks [C,T,T] into [T,T,4] once, ctx_texture_mapping_packed_fwd then gathers one
    16-byte texel per bilinear tap.  Results are bit-identical to ctx_texture_mapping_fwd. */
