@@ -110,7 +110,15 @@ SIGNATURES = {
     "ctx_hashtex_bwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ctx_texture_head_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texture_head_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    "ctx_adam_multi": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "ctx_mip_levels_bytes": (_i64, [_i32, _i32, _i32]),
+    "ctx_mip_cov_bytes": (_i64, [_i32, _i32]),
+    "ctx_mip_build": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_mip_status": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "ctx_face_uv_lod": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_texture_mapping_mip_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ctx_texture_mapping_mip_bwd_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "ctx_texture_mapping_mip_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ctx_adam_multi":(_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
     "ctx_table_adam": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
     "ctx_weighted_sum_packed": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "ctx_texel_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),

@@ -41,7 +41,10 @@ class GuideConfig:
     shape_scale: float = 0.6
     dy: float = 0.25
     texture_resolution: int = 1024
-    texture_interpolation_mode: str = 'bilinear'
+    texture_interpolation_mode: str = 'bilinear'    # 'nearest' | 'bilinear' (the reference's) | 'mipmap': trilinear lookup in the atlas's mip
+                                                    # pyramid at a per-face level of detail (csrc/texmip.hip)
+    mip_levels: int = 4              # read under texture_interpolation_mode = 'mipmap' only: levels of the pyramid, level 0 = the atlas;
+                                     # texture_resolution must be a multiple of 2^(mip_levels-1) and the last level at least 2 x 2
     guidance_scale: float = 7.5
     use_inpainting: bool = True
     reference_texture: Optional[Path] = None
@@ -178,6 +181,7 @@ PROJECTION_MODES = ('scatter', 'gather')
 FIELD_TEXELS_MODES = ('all', 'active')
 TEXTURE_FIELDS = ('mlp', 'hashgrid')
 PAINT_MODES = ('independent', 'progressive')
+INTERPOLATION_MODES = ('nearest', 'bilinear', 'bicubic', 'mipmap')     # 'bicubic' passes as it did: the sampler itself refuses it
 
 
 def validate(cfg):
@@ -194,6 +198,17 @@ def validate(cfg):
             raise ValueError(f"guide.texture_field={guide.texture_field!r}: expected one of {TEXTURE_FIELDS}")
         if guide.paint_mode not in PAINT_MODES:
             raise ValueError(f"guide.paint_mode={guide.paint_mode!r}: expected one of {PAINT_MODES}")
+        if guide.texture_interpolation_mode not in INTERPOLATION_MODES:
+            raise ValueError(f"guide.texture_interpolation_mode={guide.texture_interpolation_mode!r}: expected one of {INTERPOLATION_MODES}")
+        if guide.texture_interpolation_mode == 'mipmap':
+            T, Lm = int(guide.texture_resolution), int(guide.mip_levels)
+            if not (1 <= Lm <= 16 and T % (1 << (Lm - 1)) == 0 and (T >> (Lm - 1)) >= 2):
+                raise ValueError(f"guide.mip_levels={guide.mip_levels} does not fit guide.texture_resolution={T}: the resolution must be a "
+                                 f"multiple of 2^(mip_levels-1) and the last level at least 2 x 2")
+            optim_ = getattr(cfg, 'optim', None)
+            if optim_ is not None and optim_.field_texels == 'active':
+                raise ValueError("guide.texture_interpolation_mode='mipmap' with optim.field_texels='active': the active set holds the "
+                                 "texels under the bilinear taps, not those under the coarse levels' taps")
         if guide.exposure_compensation:
             if guide.paint_mode == 'progressive':
                 raise ValueError("guide.exposure_compensation with guide.paint_mode='progressive': the progressive views are consistent by "

@@ -192,6 +192,38 @@ __device__ __forceinline__ void hg_accumulate(const HgCell<DIM> &c, const float 
     }
 }
 
+// Every lane of the wave calls this.  Lanes lane .. end-1 form the run this lane belongs to (adjacent lanes with one key); returns the sum
+// of q over lane .. end-1, which in the run's first lane is the run's total: a segmented suffix scan in six shuffle steps.
+__device__ __forceinline__ long long hg_run_sum(long long q, int lane, int end)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long other = __shfl_down(q, d, 64);
+        if (lane + d < end) q += other;
+    }
+    return q;
+}
+
+// The pre-sum of a wave's terms (hashtex.hip, texmip.hip): every lane of the wave calls this with the entry it addresses and its F terms.
+// The terms of every run of adjacent live lanes that address one entry are added into the run's first lane (integers: the sum does not
+// depend on its order); returns whether this lane issues the atomics.  A lane that is not live keeps a key of its own (no entry has the
+// index 2^32 - 1) and issues nothing.
+template <int F>
+__device__ __forceinline__ bool hg_presum_runs(uint32_t entry, bool live, int lane, long long (&q)[F])
+{
+    const uint32_t key = live ? entry : 0xffffffffu;
+    const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
+    const bool first = lane == 0 || prev != key || !live;
+    const unsigned long long heads = __ballot(first);
+    if (heads != ~0ull) {                                                   // uniform: some run is longer than one lane
+        const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+        const int end = after ? lane + 1 + __ffsll((long long)after) - 1 : 64;
+#pragma unroll
+        for (int f = 0; f < F; ++f) q[f] = hg_run_sum(q[f], lane, end);
+    }
+    return live && first;
+}
+
 static __global__ __launch_bounds__(HG_BLOCK) void k_hashgrid_convert(const long long *__restrict__ acc, int64_t count, int E, const HgCtl *__restrict__ ctl,
                                                                float *__restrict__ g_table)
 {

@@ -101,18 +101,6 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashtex_absmax_list(const float *_
     hg_absmax_commit(m, ctl);
 }
 
-// Every lane of the wave calls this.  Lanes lane .. end-1 form the run this lane belongs to (adjacent lanes with one key); returns the sum
-// of q over lane .. end-1, which in the run's first lane is the run's total: a segmented suffix scan in six shuffle steps.
-__device__ __forceinline__ long long ht_run_sum(long long q, int lane, int end)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long other = __shfl_down(q, d, 64);
-        if (lane + d < end) q += other;
-    }
-    return q;
-}
-
 template <int F>
 __global__ __launch_bounds__(HG_BLOCK) void k_hashtex_bwd(HtRows rows, int64_t n, const float *__restrict__ g_emb, HgTable g, int E, int presum,
                                                           const HgCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
@@ -130,18 +118,7 @@ __global__ __launch_bounds__(HG_BLOCK) void k_hashtex_bwd(HtRows rows, int64_t n
     const int lane = threadIdx.x & 63;
     hg_accumulate<2, F>(hg_cell(hg_axes<2>(x, g.res[l]), g.res[l], g.log2T), ge, hg_pow2(E - ctl->x), acc + ((int64_t)l << g.log2T) * F,
                         [&](uint32_t entry, long long (&q)[F]) {
-        if (!presum) return live;
-        const uint32_t key = live ? entry : 0xffffffffu;                        // no entry has this index: T <= 2^22
-        const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
-        const bool first = lane == 0 || prev != key || !live;
-        const unsigned long long heads = __ballot(first);
-        if (heads != ~0ull) {                                                   // uniform: some run is longer than one lane
-            const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-            const int end = after ? lane + 1 + __ffsll((long long)after) - 1 : 64;
-#pragma unroll
-            for (int f = 0; f < F; ++f) q[f] = ht_run_sum(q[f], lane, end);
-        }
-        return live && first;
+        return presum ? hg_presum_runs<F>(entry, live, lane, q) : live;          // the segmented wave scan of hashgrid_common.h
     });
 }
 

@@ -763,11 +763,129 @@ class _TextureMapping(torch.autograd.Function):
         return None, g, None, None
 
 
-def texture_mapping(texture_coordinates, texture_maps, mode='bilinear', mask_idx=None):
+# ---- mip-mapped sampling (csrc/texmip.hip; the rule is tests/mipmap_rule.py) ------------------------------
+def _mip_build(tex, levels, coverage=None):
+    """-> (pyr uint8 buffer, cov_count uint8 | None, [level tensors]) of the atlas tex [C,T,T] f32 contiguous; level 0 is tex itself,
+    the others are views of pyr.  The counts are kept whenever a coverage plane is given or a later pass needs them."""
+    lib = L.load()
+    if tex.dim() != 3 or tex.shape[1] != tex.shape[2]:
+        raise L.CtxError(f"mip_pyramid: want a square atlas [C,T,T]; got {tuple(tex.shape)}")
+    Cc, T, levels = int(tex.shape[0]), int(tex.shape[1]), int(levels)
+    if Cc > 4:
+        raise L.CtxError(f"mip_pyramid: C={Cc} channels; the mipmap path takes 1 to 4")
+    nbytes = lib.ctx_mip_levels_bytes(Cc, T, levels)
+    if nbytes < 0:
+        raise L.CtxError(f"mip_pyramid: mip levels L={levels} do not fit T={T}: {lib.ctx_last_error().decode()}")
+    if coverage is not None and (coverage.dtype != torch.uint8 or tuple(coverage.shape) != (T, T)):
+        raise L.CtxError(f"mip_pyramid: coverage must be uint8 [{T},{T}]; got {coverage.dtype} {tuple(coverage.shape)}")
+    pyr = torch.empty(nbytes, dtype=torch.uint8, device=tex.device)
+    cov_count = None
+    if coverage is not None or levels > 6:
+        cov_count = torch.empty(lib.ctx_mip_cov_bytes(T, levels), dtype=torch.uint8, device=tex.device)
+    L.check(lib.ctx_mip_build(L.ptr(tex, torch.float32, "texture_maps"), L.ptr(coverage), Cc, T, levels, L.ptr(pyr), L.ptr(cov_count), L.stream()))
+    views, flt, off = [tex], pyr.view(torch.float32), 0
+    for l in range(1, levels):
+        n = Cc * (T >> l) ** 2
+        views.append(flt[off:off + n].view(Cc, T >> l, T >> l))
+        off += n
+    return pyr, cov_count, views
+
+
+def mip_pyramid(tex, levels, coverage=None):
+    """The mip pyramid of the atlas tex [C,T,T] (C <= 4): a list of `levels` tensors, level l of side T >> l; level 0 is tex, the others
+    are views of one buffer.  A coarse texel is the mean of its covered children; coverage uint8 [T,T] (None: everything) says which
+    level-0 texels count, so that a chart's coarse texels do not average gutter colour."""
+    return _mip_build(L.f32c(tex), levels, coverage)[2]
+
+
+def face_uv_lod(face_vertices_image, uv_face_attr, H, W, T, levels, scale=None):
+    """lod [B,F] f32 of every (view, face): integer part = mip level, fraction = blend towards the next.  The raster interpolates uv
+    affinely on the screen, so a face's uv Jacobian is constant; the lod follows the longer of its two pixel-step lengths in texels.
+    scale [B] (None: 1) widens a view's pixel footprint, for an image that is shrunk after the render."""
+    lib = L.load()
+    fvi, uva = L.f32c(face_vertices_image), L.f32c(uv_face_attr)
+    B, F = int(fvi.shape[0]), int(fvi.shape[1])
+    if tuple(fvi.shape[1:]) != (F, 3, 2) or tuple(uva.shape[1:]) != (F, 3, 2) or uva.shape[0] not in (1, B):
+        raise L.CtxError(f"face_uv_lod: want face_vertices_image [B,F,3,2] and uv_face_attr [1|B,F,3,2]; got {tuple(fvi.shape)}, {tuple(uva.shape)}")
+    if scale is not None:
+        scale = L.f32c(torch.as_tensor(scale, dtype=torch.float32), fvi.device).reshape(-1)
+        if scale.numel() != B:
+            raise L.CtxError(f"face_uv_lod: scale has {scale.numel()} entries for {B} views")
+    lod = torch.empty(B, F, device=fvi.device)
+    L.check(lib.ctx_face_uv_lod(L.ptr(fvi), L.ptr(uva), int(uva.shape[0]), B, F, int(H), int(W), int(T), int(levels), L.ptr(scale), L.ptr(lod),
+                                L.stream()))
+    return lod
+
+
+def mip_scatter_texture(go, uv, lod, face_idx, cov_count, C, T, levels):
+    """-> grad_tex [C,T,T]: the backward of the mipmap lookup (bit-reproducible; see ctx_texture_mapping_mip_bwd)."""
+    lib = L.load()
+    B, HW, F = uv.shape[0], uv[0].numel() // 2, lod.shape[1]
+    ws = torch.empty(lib.ctx_texture_mapping_mip_bwd_ws_bytes(C, T, levels), dtype=torch.uint8, device=uv.device)
+    g = torch.empty(C, T, T, device=uv.device)
+    L.check(lib.ctx_texture_mapping_mip_bwd(L.ptr(go, torch.float32, "grad_out"), L.ptr(uv, torch.float32, "uv"), L.ptr(lod, torch.float32, "lod"),
+                                            L.ptr(face_idx, torch.int64, "mask_idx"), L.ptr(cov_count), B, HW, F, C, T, levels, L.ptr(ws), L.ptr(g),
+                                            L.stream()))
+    return g
+
+
+class _TextureMappingMip(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, uv, tex, mask_idx, lod, levels, coverage):
+        lib = L.load()
+        B, H, W, _ = uv.shape
+        Bt, Cc, T, T2 = tex.shape
+        if T != T2:
+            raise L.CtxError("texture_mapping: square texture expected")
+        if Cc > 4:
+            raise L.CtxError(f"texture_mapping: mode 'mipmap' takes 1 to 4 channels; got C={Cc}")
+        if Bt not in (1, B):
+            raise L.CtxError(f"texture_mapping: {Bt} textures for {B} views")
+        if Bt > 1 and tex.stride(0) != 0 and not bool((tex == tex[:1]).all()):
+            raise L.CtxError("texture_mapping: mode 'mipmap' samples one shared atlas; the textures of this batch differ")
+        shared = Bt == 1 or tex.stride(0) == 0              # a materialised batch of equal textures: one pyramid, a gradient per slice
+        if tuple(lod.shape) != (B, lod.shape[-1]) or tuple(mask_idx.shape) != (B, H, W):
+            raise L.CtxError(f"texture_mapping: mode 'mipmap' wants lod [B,F] and mask_idx [B,H,W]; got {tuple(lod.shape)}, {tuple(mask_idx.shape)}")
+        tex_c, uvc, lodc, idx = L.f32c(tex[0]), L.f32c(uv), L.f32c(lod), mask_idx.contiguous()
+        pyr, cov_count, _ = _mip_build(tex_c, levels, coverage)
+        out = torch.empty(B, H, W, Cc, device=uv.device)
+        L.check(lib.ctx_texture_mapping_mip_fwd(L.ptr(uvc, torch.float32, "texture_coordinates"), L.ptr(tex_c), L.ptr(pyr), L.ptr(lodc),
+                                                L.ptr(idx, torch.int64, "mask_idx"), B, H * W, int(lodc.shape[1]), Cc, T, int(levels), L.ptr(out),
+                                                L.stream()))
+        ctx.save_for_backward(uvc, lodc, idx, cov_count if cov_count is not None else torch.empty(0))
+        ctx.meta = (Cc, T, int(levels), shared, tex.shape, cov_count is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        uvc, lodc, idx, cov_count = ctx.saved_tensors
+        Cc, T, levels, shared, tshape, has_cov = ctx.meta
+        cov_count = cov_count if has_cov else None
+        go = L.f32c(grad_out)
+        g = torch.zeros(tshape, device=go.device)
+        if shared:          # one atlas (or its expand()): autograd sums the batch slices, so the whole sum goes into slice 0
+            g[0] = mip_scatter_texture(go, uvc, lodc, idx, cov_count, Cc, T, levels)
+        else:
+            for b in range(tshape[0]):
+                g[b] = mip_scatter_texture(go[b:b + 1].contiguous(), uvc[b:b + 1].contiguous(), lodc[b:b + 1].contiguous(), idx[b:b + 1].contiguous(),
+                                           cov_count, Cc, T, levels)
+        return None, g, None, None, None, None
+
+
+def texture_mapping(texture_coordinates, texture_maps, mode='bilinear', mask_idx=None, lod=None, levels=4, coverage=None):
     """grid_sample(tex, (u, 1-v)*2-1, align_corners=False, padding_mode='border') -> [B,H,W,C].
-    Differentiable w.r.t. texture_maps (bilinear).  mask_idx: optional face_idx to fuse `* mask`."""
+    Differentiable w.r.t. texture_maps (bilinear, mipmap).  mask_idx: optional face_idx to fuse `* mask`.
+    mode='mipmap': trilinear lookup in the `levels`-level pyramid of one shared atlas (C <= 4); mask_idx (the raster's face_idx) and
+    lod (`face_uv_lod`'s table [B,F]) are required, coverage (uint8 [T,T]) is `mip_pyramid`'s.  Where the lod is 0 the result is the
+    bilinear one.  The other modes do not look at lod, levels or coverage."""
+    if mode == 'mipmap':
+        if mask_idx is None or lod is None:
+            raise L.CtxError("texture_mapping: mode 'mipmap' needs mask_idx (the raster's face_idx) and lod (kal.face_uv_lod)")
+        if texture_coordinates.dim() != 4:
+            raise L.CtxError("texture_mapping: mode 'mipmap' wants texture_coordinates [B,H,W,2]")
+        return _TextureMappingMip.apply(texture_coordinates, texture_maps, mask_idx, lod, int(levels), coverage)
     if mode not in ('bilinear', 'nearest'):
-        raise L.CtxError(f"texture_mapping: mode {mode!r} not implemented on the HIP path (bilinear/nearest)")
+        raise L.CtxError(f"texture_mapping: mode {mode!r} not implemented on the HIP path (bilinear/nearest/mipmap)")
     if texture_coordinates.dim() == 3:
         return _TextureMapping.apply(texture_coordinates[:, :, None, :], texture_maps, mode, mask_idx)[:, :, 0]
     return _TextureMapping.apply(texture_coordinates, texture_maps, mode, mask_idx)

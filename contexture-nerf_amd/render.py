@@ -12,10 +12,11 @@ from . import kal
 
 
 class Renderer:
-    def __init__(self, device, dim=(224, 224), interpolation_mode='nearest', fovyangle=np.pi / 3):
-        assert interpolation_mode in ['nearest', 'bilinear', 'bicubic'], f'no interpolation mode {interpolation_mode}'
+    def __init__(self, device, dim=(224, 224), interpolation_mode='nearest', fovyangle=np.pi / 3, mip_levels=4):
+        assert interpolation_mode in ['nearest', 'bilinear', 'bicubic', 'mipmap'], f'no interpolation mode {interpolation_mode}'
         self.device = device
         self.interpolation_mode = interpolation_mode
+        self.mip_levels = int(mip_levels)               # read in the 'mipmap' mode only
         self.fovyangle = float(fovyangle)
         self.camera_projection = kal.render.camera.generate_perspective_projection(fovyangle).to(device)
         self.dim = dim
@@ -59,8 +60,12 @@ class Renderer:
         return out
 
     def render_multiple_view_texture(self, verts, faces, uv_face_attr, texture_map, elev, azim, radius,
-                                     look_at_height=0.0, dims=None, background_type='none', render_cache=None):
+                                     look_at_height=0.0, dims=None, background_type='none', render_cache=None,
+                                     mip_scale=None, mip_coverage=None):
+        """mip_scale ([B] or None) and mip_coverage (uint8 [T,T] or None) are read in the 'mipmap' mode only: the per-view footprint
+        scale of kal.face_uv_lod and the coverage plane of kal.mip_pyramid."""
         dims = self.dim if dims is None else dims
+        face_lod = None if render_cache is None else render_cache.get('face_lod')
         if render_cache is None:
             camera_transform = self.get_camera_from_multiple_view(elev, azim, r=radius, look_at_height=look_at_height)
             face_vertices_camera, face_vertices_image, face_normals = kal.render.mesh.prepare_vertices(
@@ -82,8 +87,20 @@ class Renderer:
                 normals_image = face_normals[b, face_idx]
 
         mask = (face_idx > -1).float()[..., None]
-        image_features = kal.render.mesh.texture_mapping(uv_features, texture_map, mode=self.interpolation_mode,
-                                                         mask_idx=face_idx)          # == texture_mapping(...) * mask
+        if self.interpolation_mode == 'mipmap':
+            # the lod table depends on the raster's size, the atlas's and the footprint scale: kept with the raster, rebuilt when they change
+            H, W, T = int(uv_features.shape[1]), int(uv_features.shape[2]), int(texture_map.shape[-1])
+            scale_key = None if mip_scale is None else tuple(float(x) for x in torch.as_tensor(mip_scale).reshape(-1).tolist())
+            key = (H, W, T, self.mip_levels, scale_key)
+            if face_lod is None or face_lod[0] != key:
+                face_lod = (key, kal.face_uv_lod(face_vertices_image, uv_face_attr, H, W, T, self.mip_levels, scale=mip_scale))
+                if render_cache is not None:
+                    render_cache['face_lod'] = face_lod       # a loop that keeps passing the cache it was given finds the table there
+            image_features = kal.render.mesh.texture_mapping(uv_features, texture_map, mode='mipmap', mask_idx=face_idx, lod=face_lod[1],
+                                                             levels=self.mip_levels, coverage=mip_coverage)
+        else:
+            image_features = kal.render.mesh.texture_mapping(uv_features, texture_map, mode=self.interpolation_mode,
+                                                             mask_idx=face_idx)          # == texture_mapping(...) * mask
         if background_type == 'white':
             image_features = image_features + 1 * (1 - mask)
         elif background_type == 'random':
@@ -92,5 +109,7 @@ class Renderer:
         render_cache = {'camera_transform': camera_transform, 'uv_features': uv_features, 'face_normals': face_normals,
                         'face_idx': face_idx, 'depth_map': depth_map, 'raw_depth_map': raw_depth_map,
                         'face_vertices_image': face_vertices_image, 'normals_image': normals_image}
+        if self.interpolation_mode == 'mipmap':
+            render_cache['face_lod'] = face_lod           # (key (H, W, T, L, scale), lod [B,F])
         return image_features.permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2), depth_map.permute(0, 3, 1, 2), \
             normals_image.permute(0, 3, 1, 2), render_cache

@@ -90,7 +90,7 @@ class TexturedMeshModel(torch.nn.Module):
         self.num_features = 3
         self.dim = (render_grid_size, render_grid_size)
         self.renderer = Renderer(device=self.device, dim=self.dim, interpolation_mode=self.opt.texture_interpolation_mode,
-                                 fovyangle=fovyangle)
+                                 fovyangle=fovyangle, mip_levels=getattr(self.opt, 'mip_levels', 4))
         self.mesh = self.init_meshes(mesh_arrays)
         self.texture_mlp = texture_mlp
         self.uv_embedder = uv_embedder
@@ -202,8 +202,15 @@ class TexturedMeshModel(torch.nn.Module):
         return mask.permute(0, 3, 1, 2), depth.permute(0, 3, 1, 2), normals_image.permute(0, 3, 1, 2), \
             fn.permute(0, 2, 1), face_idx[:, None, :, :]
 
+    def _mip_args(self, mip_scale):
+        """what the 'mipmap' mode adds to a render: the per-view footprint scale, and the chart mask as the pyramid's coverage, so that a
+        coarse texel averages chart texels only, not gutter colour.  Nothing in the other modes."""
+        if getattr(self.renderer, 'interpolation_mode', None) != 'mipmap':
+            return {}
+        return dict(mip_scale=mip_scale, mip_coverage=self.chart_mask())
+
     def render(self, theta=None, phi=None, radius=None, background=None, use_meta_texture=False, render_cache=None,
-               use_median=False, dims=None):
+               use_median=False, dims=None, mip_scale=None):
         theta, phi, radius = self._angles(theta), self._angles(phi), self._angles(radius)
         if render_cache is None:
             assert theta is not None and phi is not None and radius is not None
@@ -219,7 +226,7 @@ class TexturedMeshModel(torch.nn.Module):
         pred_features, mask, depth, normals, render_cache = self.renderer.render_multiple_view_texture(
             self.mesh.vertices[None].repeat(batch_size, 1, 1), self.mesh.faces, self.face_attributes,
             texture_img.expand(batch_size, -1, -1, -1), elev=theta, azim=phi, radius=radius, look_at_height=self.dy,
-            render_cache=render_cache, dims=dims, background_type=background_type)
+            render_cache=render_cache, dims=dims, background_type=background_type, **self._mip_args(mip_scale))
         if texels is not None:
             render_cache['active_texels'] = texels          # the list stays with the raster it was built from
         mask = mask.detach()

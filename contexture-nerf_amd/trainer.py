@@ -482,7 +482,9 @@ class ConTEXTure:
         Host syncs of the reference's loop body that are hoisted out of it: the six crop boxes (the masks do not change) and the
         DreamTime table (rebuilt every iteration there).  -> list of per-iteration dicts (loss, t, fisher, grad_norm).
         optim.consistency_weight > 0 adds the term upstream wrote and switched off (:856-863): the loss that is back-propagated is
-        `loss - weight * kal.view_consistency(six views)`; the record's `loss` stays the SDS term and gains `consistency`."""
+        `loss - weight * kal.view_consistency(six views)`; the record's `loss` stays the SDS term and gains `consistency`.
+        guide.texture_interpolation_mode = 'mipmap': the six views are rendered at the footprint of the tile pixel the resize keeps
+        (mip_scale = box / tile per view); nothing else in the loop changes."""
         from . import sds
         from .scheduler import DDPMScheduler
         if getattr(self, 'zero123plus', None) is None:
@@ -524,6 +526,11 @@ class ConTEXTure:
             if n_active > 0:
                 render_cache['active_texels'] = texels
                 self._sds_setup['field_texels'] = 'active'
+        mip_args = {}
+        if self.cfg.guide.texture_interpolation_mode == 'mipmap':
+            # a tile pixel covers max(box_h, box_w) / tile render pixels: the render is pre-filtered to the footprint of the pixel the resize
+            # below keeps (the front view is not resized: 1)
+            mip_args = dict(mip_scale=[1.0] + [max(b[2] - b[0], b[3] - b[1]) / float(tile) for b in boxes])
         params = [p for p in self.texture_mlp.parameters()]
         if self.cfg.guide.texture_field == 'hashgrid':
             # the table and its MLP at their own rates (optim.hashgrid_lr, optim.hashgrid_mlp_lr)
@@ -554,7 +561,7 @@ class ConTEXTure:
             for i in range(iterations):
                 t = dream.get_t(i)
                 optimizer.zero_grad()
-                out = self.mesh_model.render(render_cache=render_cache, background=gray)
+                out = self.mesh_model.render(render_cache=render_cache, background=gray, **mip_args)
                 six = out['image'][1:]
                 tiles = [F.interpolate(six[j:j + 1, :, b[0]:b[2], b[1]:b[3]], (tile, tile), mode='bilinear', align_corners=False)
                          for j, b in enumerate(boxes)]

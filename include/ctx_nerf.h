@@ -631,6 +631,47 @@ int32_t ctx_texture_head_fwd(const float *raw, const int32_t *idx /*nullable*/, 
 int32_t ctx_texture_head_bwd(const float *grad_tex, const float *g_raw_in /*nullable*/, const float *raw, const int32_t *idx /*nullable*/,
                              int64_t n, int64_t plane, int32_t C, float *grad_raw, ctx_stream_t stream);
 
+/* ---- mip-mapped texture_mapping (texmip.hip; definition: tests/mipmap_rule.py; the call site is
+   src/models/render.py:135, where the reference samples the atlas with four texels whatever the pixel's footprint) ----
+   The atlas tex [C, T, T], 1 <= C <= 4, is level 0; level l has side T >> l; L levels need T % 2^(L-1) == 0 and T >> (L-1) >= 2
+   (1 <= L <= 16, 2 <= T <= 16384; anything else is refused).  Everything is binary32, every operation rounding on its own.
+   pyr: ctx_mip_levels_bytes(C, T, L) bytes (-1: refused): levels 1 .. L-1, planar [C, T_l, T_l] one after the other, and a 256-byte
+   trailer with the pyramid's sticky status.  cov_count: ctx_mip_cov_bytes(T, L) bytes = sum of T_l^2: cov_0 (0 / 1), then n_l.
+   ctx_mip_build writes levels 1 .. L-1 (level 0 stays the caller's atlas) and, where cov_count is given, the counts: the children of
+   texel (y, x) are a = (2y, 2x), b = (2y, 2x+1), c = (2y+1, 2x), d = (2y+1, 2x+1); cov_0 = coverage != 0 (coverage uint8 [T, T], null:
+   everything); n = the covered children, cov_l = n > 0, value = s / (float)n with s = 0 then s = s + child over the covered children in
+   that order, 0 where n = 0.  A 32 x 32 tile of a level gives the next five in one launch.  cov_count is required with a coverage plane
+   and for L > 6.  ctx_mip_status: 1 after a forward on this pyramid met a face_idx outside its lod table (synchronises the stream). */
+int64_t ctx_mip_levels_bytes(int32_t C, int32_t T, int32_t L);
+int64_t ctx_mip_cov_bytes(int32_t T, int32_t L);
+int32_t ctx_mip_build(const float *tex, const uint8_t *coverage /*nullable*/, int32_t C, int32_t T, int32_t L, float *pyr,
+                      uint8_t *cov_count /*nullable*/, ctx_stream_t stream);
+int32_t ctx_mip_status(const float *pyr, int32_t C, int32_t T, int32_t L, ctx_stream_t stream);
+/* lod [B, F] of the faces fvi [B, F, 3, 2] (NDC, prepare_vertices' face_vertices_image) with uv uva [Bu, F, 3, 2], Bu in {1, B}:
+   e = p1 - p0, p2 - p0, d = t1 - t0, t2 - t0; det = e1x*e2y - e2x*e1y (0 or not finite: lod 0); ux = (d1u*e2y - d2u*e1y)/det,
+   uy = (d2u*e1x - d1u*e2x)/det, vx, vy likewise; ax = ((2/W)*T)*s_b, ay = ((2/H)*T)*s_b (scale float [B], null: 1);
+   r2 = fmaxf((ax*ax)*((ux*ux)+(vx*vx)), (ay*ay)*((uy*uy)+(vy*vy))); !(r2 > 1): 0; infinite: L-1; rho = sqrtf(r2), l0 = ilogbf(rho);
+   l0 >= L-1: L-1; else (float)l0 + (ldexpf(rho, -l0) - 1.0f): the blend is linear in the footprint's width. */
+int32_t ctx_face_uv_lod(const float *fvi, const float *uva, int32_t Bu, int32_t B, int32_t F, int32_t H, int32_t W, int32_t T, int32_t L,
+                        const float *scale /*nullable*/, float *lod, ctx_stream_t stream);
+/* out [B, HW, C]: 0 where face_idx [B, HW] (int64) < 0; else lod = fminf(fmaxf(table[b, face_idx], 0), L-1), l0 = (int)lod,
+   f = lod - (float)l0, s0 = the bilinear tap of ctx_texture_mapping_fwd at level l0 (side T >> l0, same clamp, same order); f > 0:
+   out = s0*(1.0f - f) + s1*f with s1 the tap at level l0 + 1, else out = s0.  One shared atlas.  A face_idx >= F reads nothing: its
+   pixel is NaN and the pyramid's status becomes 1 (ctx_mip_status). */
+int32_t ctx_texture_mapping_mip_fwd(const float *uv, const float *tex, float *pyr, const float *lod, const int64_t *face_idx, int32_t B, int32_t HW,
+                                    int32_t F, int32_t C, int32_t T, int32_t L, float *out, ctx_stream_t stream);
+/* grad_tex [C, T, T], every element written.  Stage A: per foreground pixel and channel g = grad_out; f > 0: gl = g*(1.0f - f),
+   gh = g*f, else gl = g; the terms w_k*gl (level l0) and w'_k*gh (level l0 + 1) of the taps inside the level go into a 64-bit integer
+   pyramid by ctx_hashtex_bwd's scheme (x from max|grad_out| over all of it, E = 62 - ceil(log2(4*B*HW))).  Stage B, one launch:
+   A_l = (float)((double)acc_l * 2^(x-E)); an uncovered texel gets 0, else g0 = A_0[y, x], Wt = 1.0f, and for l = 1 .. L-1:
+   Wt = Wt / (float)n_l(y >> l, x >> l), g0 = g0 + A_l[y >> l, x >> l]*Wt (cov_count null: everything covered, n = 4).
+   An all-zero grad_out gives zeros; a non-finite one, or a face_idx >= F, NaN.  Adjacent lanes that address one texel add their
+   integers before one atomic (CTX_TEXMIP_PRESUM=0, read per call, turns that off; same bits).  ws: ..._ws_bytes(C, T, L) bytes. */
+int64_t ctx_texture_mapping_mip_bwd_ws_bytes(int32_t C, int32_t T, int32_t L);
+int32_t ctx_texture_mapping_mip_bwd(const float *grad_out, const float *uv, const float *lod, const int64_t *face_idx,
+                                    const uint8_t *cov_count /*nullable*/, int32_t B, int32_t HW, int32_t F, int32_t C, int32_t T, int32_t L,
+                                    void *ws, float *grad_tex, ctx_stream_t stream);
+
 /* ---- the field optimizer: Adam in place (adam.hip; definition: tests/adam_rule.py) ---- */
 /* Per element, in binary32, every operation rounding once, in this order (b1, b2, o1 = 1 - b1, o2 = 1 - b2, c1 = lr / (1 - b1^t),
    c2 = 1 / sqrt(1 - b2^t), eps: computed by the caller in float64 and rounded to float; t = 1, 2, ... counts the steps):
